@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: scenes/sec of the eval-mode SegDINO3D forward on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One process per GPU (N > 1: launched by torch.distributed.run, backend "nccl" = RCCL).  A *step* is one
 SCENE through the eval-mode `Baseline3D.forward` (backbone + superpoint pooling + 6-layer decoder + post-processing):
@@ -26,13 +26,10 @@ Prints ONE JSON line (rank 0) with the contract fields plus
   single_scene : the same forward with ONE scene in flight (SURVEY 8(d) defines the metric at batch = 1 scene per GPU):
                  latency and scenes/s, next to `value` = scenes/s with `--streams` scenes in flight per GPU
   cpu_baseline : the oracle's whole forward timed on the host cores (rank 0, N = 1 only)
+`--dump-outputs DIR` writes what the last of the K timed steps returned (rank 0) as DIR/<name>.npy; the inputs and weights are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
-
-import os as _os
-# HIP maps streams onto 4 hardware queues by default; scenes in flight on streams that share a queue block each
-# other head-of-line (measured: 4 streams 85 -> 102 scenes/s with 8 queues).  Must be set before the runtime starts.
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import argparse
 import json
@@ -78,6 +75,55 @@ def algorithmic_bytes(meta, pair_count):
     K, Cin, Cout, M = meta["K"], meta["Cin"], meta["Cout"], meta["M"]
     P = pair_count
     return 4 * P * Cin + 4 * M * Cout + 8 * P + 4 * K * Cin * Cout, 2 * P * Cin * Cout
+
+
+DUMP_MASK_POINTS = 8192        # point columns of the [n, N] instance masks kept by dump_outputs (n <= topk_insts = 600: <= 20 MB)
+
+
+def dump_outputs(pd, out_dir):
+    """The PointData one evaluation forward returns, as DIR/<name>.npy: integer and boolean fields as float64 / float32, scores and
+    boxes in float32.  The [n, N] instance masks go as the columns of a fixed, seeded sample of DUMP_MASK_POINTS points (their indices
+    in `instance_masks_sample_points`) next to each mask's point count over all N points.  `instance_count` holds n; an array with no
+    elements (every per-instance field when the selection kept nothing, `npoint_mask` when no candidate was scored) is not written.
+    Returns {name: shape} of the files written."""
+    import numpy as np
+
+    def host(t):
+        return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+    masks = host(pd.pts_instance_mask[0]).astype(bool)
+    n_inst, n_points = masks.shape
+    sort_idx, score_mask, npoint_mask = pd.sort_and_mask
+    arrays = {
+        "semantic_mask": host(pd.pts_semantic_mask[0]).astype(np.float64),
+        "panoptic_semantic_mask": host(pd.pts_semantic_mask[1]).astype(np.float64),
+        "panoptic_instance_mask": host(pd.pts_instance_mask[1]).astype(np.float64),
+        "instance_count": np.array([n_inst], dtype=np.float64),
+        "instance_labels": host(pd.instance_labels).astype(np.float64),
+        "instance_scores": host(pd.instance_scores).astype(np.float32),
+        "instance_mask_points": masks.sum(axis=1).astype(np.float64),
+        "sort_idx": host(sort_idx).astype(np.float64),
+        "score_mask": host(score_mask).astype(np.float32),
+        "npoint_mask": host(npoint_mask).astype(np.float32),
+    }
+    if n_inst:
+        cols = np.sort(np.random.default_rng(0).choice(n_points, size=min(n_points, DUMP_MASK_POINTS), replace=False))
+        arrays["instance_masks_sample"] = masks[:, cols].astype(np.float32)
+        arrays["instance_masks_sample_points"] = cols.astype(np.float64)
+    if pd.instance_boxes is not None:                             # None: a decoder without the box head
+        arrays["instance_boxes"] = host(pd.instance_boxes).astype(np.float32)
+    names = set(arrays) | {"instance_masks_sample", "instance_masks_sample_points", "instance_boxes"}
+    arrays = {name: a for name, a in arrays.items() if a.size}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"dump_outputs: {total} bytes exceed 64 MB"
+    os.makedirs(out_dir, exist_ok=True)
+    for name in names - set(arrays):                              # an earlier dump's file this step has no elements for
+        path = os.path.join(out_dir, name + ".npy")
+        if os.path.exists(path):
+            os.remove(path)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.shape for name, a in arrays.items()}
 
 
 def build_model(query_num, device, decoder_dtype="fp32"):
@@ -285,7 +331,11 @@ def main():
     ap.add_argument("--preroll-seconds", type=float, default=2.0, help="untimed pipelined pre-roll before the timed K steps")
     ap.add_argument("--sustain-seconds", type=float, default=1.0,
                     help="after the timed K steps the same K-step list is repeated for this long: `sustained` (never `value`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (rank 0's scene K-1) as DIR/<name>.npy, float32 / float64 (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:            # started without a launcher: be the launcher
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -369,11 +419,14 @@ def main():
         plan = runner.plan_batches(args.steps)                    # [[scene ids of a forward, ...] per stream]: what the timed region runs
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        runner.run(work)                                          # EXACTLY K steps, args.streams forwards in flight
+        results = runner.run(work)                                # EXACTLY K steps, args.streams forwards in flight
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(results[-1][0].pred_pts_seg, args.dump_outputs)
+        del results
         # sustained rate: the same K-step list repeated until >= 1 s has been timed (the K = 20 region of the driver is 0.2 s, a
         # sixth of it pipeline ramp and drain); reported next to `value`, never instead of it
         sus_n, t1 = 0, time.perf_counter()

@@ -3,7 +3,7 @@ oracle (numpy) on the host, full-size scene
 (600 predictions x 150 k points, ~60 ground-truth instances of a 198-class label set)."""
 import os, sys, time, json
 import numpy as np, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import eval_ap, _lib, ops
 from oracle import eval_ref as E
 d = torch.device("cuda:0")

@@ -2,7 +2,7 @@
 distortion forced on, device (segdino3d_amd.augment) vs the oracle (numpy + scipy, the reference's own arithmetic) on the host."""
 import json, os, sys, time
 import numpy as np, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import augment as A
 from segdino3d_amd.gtypes import GD3DTarget
 from segdino3d_amd.synth import make_scene

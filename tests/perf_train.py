@@ -5,7 +5,7 @@ backward at training size, next to the oracle / a torch CPU model on the host co
   conv backward: the U-Net's layer shapes on a 150 k-point scene: forward, input gradient, weight gradient."""
 import json, os, sys, time
 import torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import ops, train_ops
 from segdino3d_amd.sparse import SceneMaps
 from segdino3d_amd.synth import make_scene

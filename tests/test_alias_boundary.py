@@ -5,13 +5,11 @@ They import more than the registries (`segdino3d.utils`, `segdino3d.datasets.dat
 (segdino3d_amd/install.py).  The first test replays the callers' exact import lines against a stub tree laid out like the
 reference (its files are written here: a few lines each, no reference source), in fresh interpreters, for both ways in -
 this repository first on PYTHONPATH, and a script started from the reference checkout through `python -m segdino3d_amd.run`.
-The second does the same against the real checkout where it exists (the build container only)."""
+The last one checks that the fall-through submodules are the checkout's own files, found from another directory."""
 import os
 import subprocess
 import sys
 import textwrap
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -134,30 +132,28 @@ def test_repository_first_on_sys_path(tmp_path):
     assert r.returncode == 0 and "MODEL-ONLY-OK" in r.stdout, r.stdout + r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/segdino3d"), reason="reference checkout only exists in the build container")
-def test_real_reference_submodules_fall_through():
-    """Against the real checkout: `segdino3d.utils` and `segdino3d.models.module` are the reference's own files (torchvision,
-    plyfile and trimesh - host libraries absent from this image - are stubbed for `nested_tensor.py:2`, `pc_util.py:24-27`); the registries they would register into are the AMD ones."""
-    code = textwrap.dedent("""
-        import sys, types
-        tv = types.ModuleType("torchvision"); tv.__version__ = "0.20.0"; sys.modules["torchvision"] = tv
-        ply = types.ModuleType("plyfile"); ply.PlyData = ply.PlyElement = object; sys.modules["plyfile"] = ply
-        sys.modules["trimesh"] = types.ModuleType("trimesh")
+def test_checkout_submodules_fall_through(tmp_path):
+    """The checkout found through SEGDINO3D_REFERENCE_ROOT from an unrelated working directory: `segdino3d.utils` and
+    `segdino3d.models.module` are the checkout's own files, executed in place; the registries they would register into and
+    `build_architecture` are the AMD ones."""
+    ref = _stub_reference(str(tmp_path / "SegDINO3D"))
+    code = "REF = %r\n" % ref + textwrap.dedent("""
+        import os
         from segdino3d import build_architecture
         from segdino3d.utils import get_rank, init_distributed_mode, is_main_process
         from segdino3d.utils import get_world_size, is_dist_avail_and_initialized
         from segdino3d.models.module import NestedTensor, nested_tensor_from_tensor_list
         import segdino3d, segdino3d.utils, segdino3d.models.module as mm
-        assert segdino3d.utils.__file__.startswith("/root/reference/"), segdino3d.utils.__file__
-        assert mm.__file__.startswith("/root/reference/")
-        assert get_rank() == 0 and is_main_process() and get_world_size() == 1
-        import torch
-        nt = nested_tensor_from_tensor_list([torch.zeros(3, 4, 5), torch.zeros(3, 2, 6)])
-        assert tuple(nt.tensors.shape) == (2, 3, 4, 6)
+        assert segdino3d.utils.__file__.startswith(REF + os.sep), segdino3d.utils.__file__
+        assert mm.__file__.startswith(REF + os.sep), mm.__file__
+        assert get_rank() == 0 and is_main_process() and get_world_size() == 1 and not is_dist_avail_and_initialized()
+        assert isinstance(nested_tensor_from_tensor_list([]), NestedTensor)
         from segdino3d_amd.configs import scannet200_model_cfg
         import segdino3d_amd
         assert type(build_architecture(scannet200_model_cfg())) is segdino3d_amd.Baseline3D
-        print("REAL-OK")
+        print("FALLTHROUGH-OK")
         """)
-    r = _run([sys.executable, "-c", code], cwd="/tmp", extra_env={"SEGDINO3D_REFERENCE_ROOT": "/root/reference"})
-    assert r.returncode == 0 and "REAL-OK" in r.stdout, r.stdout + r.stderr
+    elsewhere = tmp_path / "elsewhere"
+    elsewhere.mkdir()
+    r = _run([sys.executable, "-c", code], cwd=str(elsewhere), extra_env={"SEGDINO3D_REFERENCE_ROOT": ref})
+    assert r.returncode == 0 and "FALLTHROUGH-OK" in r.stdout, r.stdout + r.stderr

@@ -49,15 +49,24 @@ def test_record_gathers_over_rccl_at_world_size_one(fresh_process):
     print("RCCL world size 1:", out)
 
 
-def test_bench_runs_as_a_rank_on_the_nccl_backend(fresh_process):
+def test_bench_runs_as_a_rank_on_the_nccl_backend(fresh_process, tmp_path):
     """`bench.py --gpus 1` under a launcher's environment: process group on nccl, both barriers, the max-over-ranks all-reduce and the
-    closing all-gather of the per-rank records execute (the `dist is not None` branches)."""
+    closing all-gather of the per-rank records execute (the `dist is not None` branches); rank 0 dumps its last timed step's outputs."""
+    import numpy as np
+    dump = tmp_path / "outputs"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
-           "--no-end-to-end", "--preroll-seconds", "0.3", "--sustain-seconds", "0.2"]
+           "--no-end-to-end", "--preroll-seconds", "0.3", "--sustain-seconds", "0.2", "--dump-outputs", str(dump)]
     r = fresh_process(cmd, env=_rank_env(), timeout=900)
     assert r["rc"] == 0, r["stderr"][-4000:]
     line = _last_json(r["stdout"])
-    assert line["n_gpus"] == 1 and line["steps"] == 4 and line["value"] > 0
+    assert line["n_gpus"] == 1 and line["steps"] == 4 and line["value"] > 0 and line["ms_per_step"] > 0
+    sem = np.load(dump / "semantic_mask.npy")
+    assert sem.dtype == np.float64 and sem.shape == (line["config"]["points"],)
+    n_inst = int(np.load(dump / "instance_count.npy")[0])
+    if n_inst:
+        assert np.load(dump / "instance_labels.npy").shape[0] == np.load(dump / "instance_masks_sample.npy").shape[0] == n_inst
+    assert all(np.load(f).size for f in dump.iterdir())
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 << 20
     pg = line["process_group"]
     assert pg is not None and pg["backend"] == "nccl" and pg["world_size"] == 1
     assert len(line["per_rank_records"]) == 1 and line["per_rank_records"][0][0] == 0.0

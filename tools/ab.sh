@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of two environment settings: ab.sh "ENV_A=.." "ENV_B=.." [bench args]
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 A="$1"; B="$2"; shift 2
 for rep in 1 2 3; do
   for v in "$A" "$B"; do

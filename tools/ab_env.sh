@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of environment settings over bench.py: ab_env.sh "<bench args>" "ENV1=a ENV2=b" "ENV1=c" ...   (each setting run twice, interleaved)
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 ARGS=$1; shift
 for rep in 1 2; do
   for E in "$@"; do

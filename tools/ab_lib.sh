@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of two builds of the library (SD3D_LIB): ab_lib.sh <libA.so> <libB.so> [bench args]   (paths relative to the repo root)
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 A=$1; B=$2; shift 2
 for rep in 1 2; do
   for L in "$A" "$B"; do

@@ -3,7 +3,7 @@
 # them over the dense-identity ceiling (tools/dense_ceiling.py) and the real rulebooks (tools/pair_quick.py).  The product library carries
 # none of it.  usage: tools/ablate.sh build   (in the build container)   |   tools/ablate.sh run [out.md]   (on the GPU box)
 set -e
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd "$ROOT"
 if [ "$1" = "build" ]; then
     mkdir -p _ab

@@ -1,7 +1,7 @@
 """Which torch (ATen) operators does one eval forward still launch, and from which line of the package?
 torch.profiler with Python stacks over one single-stream forward at the benchmark shape."""
 import os, sys, collections, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import segdino3d_amd as seg
 from segdino3d_amd.configs import scannet200_model_cfg
 from segdino3d_amd.synth import make_scene
@@ -25,7 +25,7 @@ for ev in prof.events():
     if not ev.kernels:
         continue
     frame = next((f for f in ev.stack if "segdino3d_amd" in f), ev.stack[0] if ev.stack else "?")
-    agg[(ev.name, frame.split("/root/repo/")[-1] if "/root/repo/" in frame else frame[-80:])] += len(ev.kernels)
+    agg[(ev.name, frame.split(sys.path[0] + "/")[-1] if sys.path[0] + "/" in frame else frame[-80:])] += len(ev.kernels)
 total = 0
 for (name, frame), n in sorted(agg.items(), key=lambda kv: -kv[1]):
     total += n

@@ -1,7 +1,7 @@
 """Attention backward at the training shapes (2441 queries x 3000 keys cross-attention with two score sources, 2441 x 2441 self-attention):
 us per backward call (both kernels), HIP events.   python tools/attn_bwd_quick.py"""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import train_dec as T
 d = torch.device("cuda:0")
 g = torch.Generator().manual_seed(0)

@@ -2,7 +2,7 @@
 (Q x 3000 keys, 8 heads, [content | positional] 64-channel scores, bit mask) at Q = 200 (headline) and Q = 3000 (query_num = -1),
 fp32 and bf16 contractions, and the self-attention at Q = 200.  Prints the HIP-event time per call for the same launches."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import ops
 
 d = torch.device("cuda:0")

@@ -2,8 +2,7 @@
 phase times (HIP events) of one batch of B scenes next to B sequential scenes, then scenes/s of the pipelined runner for a
 few (streams, batch) settings.   python tools/batch_quick.py [B]"""
 import copy, os, sys, time, torch
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 import segdino3d_amd as seg
 from segdino3d_amd import plan, sparse

@@ -2,9 +2,8 @@
 (disk/page cache -> pinned host -> H2D on a copy stream, overlapped with the forward) next to the device-resident
 number of bench.py, and the raw H2D rate of one scene."""
 import os, sys, time, json, copy, tempfile
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd import io_scene
 from segdino3d_amd.dist_eval import PipelinedRunner

@@ -7,7 +7,7 @@ device); on a multi-GPU node export SD3D_DDP_BACKEND=nccl and each rank takes it
 import json, os, sys, time
 import torch
 import torch.distributed as dist
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import segdino3d_amd as seg
 from segdino3d_amd.configs import scannet200_model_cfg
 from segdino3d_amd.synth import add_training_targets, make_scene

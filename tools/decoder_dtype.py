@@ -2,7 +2,7 @@
 200 queries (headline) and one query per superpoint (query_num = -1, the parity configuration): whole-decoder time and
 the superpoint cross-attention alone (Q x 3000 keys, 8 heads, [content | positional] 64-channel scores)."""
 import json, os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import segdino3d_amd as seg
 from segdino3d_amd import ops
 from segdino3d_amd.configs import scannet200_model_cfg

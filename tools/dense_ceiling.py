@@ -12,7 +12,7 @@ import sys
 
 import torch
 
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import ops  # noqa: E402
 
 PEAK = 157.3

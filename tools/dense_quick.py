@@ -1,6 +1,6 @@
 """Dense Linear launch shapes of the decoder: time per tiling code of sd3d_gather_gemm (0 = heuristic)."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import ops
 d = torch.device("cuda:0")
 g = torch.Generator().manual_seed(0)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # the driver's command line, N times on one box: value / single_scene / conv fraction of every run (the 20-step line is noisy)
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd "$ROOT"; mkdir -p gpurun_out
 N=${1:-6}
 : > gpurun_out/r05_driverline_repeats.txt

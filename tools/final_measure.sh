@@ -2,7 +2,7 @@
 # The round's committed measurements in one go (GPU box): bench lines of every configuration, single-stream kernel trace, the two PMC
 # traffic passes (keyed to the workload), parity prints.   usage: [ONLY_BENCH=1] tools/final_measure.sh [prefix, default r06]   (ONLY_BENCH: the bench lines, no traces / counter passes / parity prints)
 P=${1:-r06}
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd "$ROOT"; mkdir -p gpurun_out
 python bench.py > gpurun_out/${P}_bench.json 2> gpurun_out/${P}_bench.err
 python bench.py --no-cpu-baseline --no-end-to-end --decoder-dtype bf16 > gpurun_out/${P}_bench_bf16.json 2>> gpurun_out/${P}_bench.err

@@ -1,7 +1,7 @@
 """Per-launch table of the gather-GEMM family over one ScanNet200 forward (HIP events, single stream):
 shape, rulebook density, time, active TFLOP/s and algorithmic GB/s, grouped by identical shape."""
 import os, sys, collections, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd import ops
 from segdino3d_amd.synth import make_scene

@@ -1,7 +1,7 @@
 """Host (Python + launch) cost of one forward: a scene so small that every kernel is launch-bound,
 timed section by section on one stream with perf_counter (no profiler overhead)."""
 import os, sys, time, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd import ops, sparse, architecture, decoder, backbone_mink
 from segdino3d_amd.synth import make_scene

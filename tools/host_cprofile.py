@@ -1,6 +1,6 @@
 """cProfile of the host side of one forward (tiny scene, launch-bound): where the Python time goes."""
 import cProfile, os, pstats, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd.synth import make_scene
 d = torch.device("cuda:0")

@@ -2,7 +2,7 @@
 events around it (no profiler), both relative to the forward's start.  A phase whose GPU start trails its host entry by more than
 the queue depth is GPU-bound there; one whose GPU start follows its host entry closely is host-bound (the GPU waits for launches)."""
 import os, sys, time, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd import sparse, plan
 from segdino3d_amd.synth import make_scene

@@ -1,7 +1,6 @@
 """Host-sensitivity probe: busy-wait D microseconds (holding the baton / GIL) before the decoder is issued, in every forward."""
 import os, sys, time, torch
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd import architecture
 from segdino3d_amd.dist_eval import PipelinedRunner

@@ -1,6 +1,6 @@
 """Where does the host time of one forward go?  cProfile over single-stream forwards (GPU box)."""
 import os, sys, cProfile, pstats, time, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd.synth import make_scene
 d = torch.device("cuda:0")

@@ -1,7 +1,7 @@
 """Decoder projection products at training shapes (2441 rows = the query subset of a 3000-superpoint scene): fp32 kernels vs the
 bf16-operand kernel, for the forward / input-gradient product (rows x Cin x Cout) and the weight-gradient product."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import ops, train_ops
 from segdino3d_amd.train_dec import _identity_pairs
 

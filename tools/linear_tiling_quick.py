@@ -2,7 +2,7 @@
 knows: auto (0), split contraction (-1), lock-step LDS with 1-4 column tiles (-11..-14), private fragments with 1-4 column tiles.
     python tools/linear_tiling_quick.py [rows ...]"""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import ops
 
 d = torch.device("cuda:0")

@@ -1,7 +1,7 @@
 """Weight gradient of a Linear at the decoder's training shapes: the one-launch kernel (sd3d_linear_wgrad) against the pair-list kernel +
 reduce on identity lists (train_ops.pair_wgrad), us per call."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import _lib, ops, train_ops
 lib = _lib.load()
 d = torch.device("cuda:0")

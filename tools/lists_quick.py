@@ -2,7 +2,7 @@
 they do not share the chip with the convolutions (in the forward they run on the side stream, and a kernel trace reports their durations
 inflated by whatever runs beside them)."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import ops, sparse
 from segdino3d_amd.sparse import SceneMaps
 from segdino3d_amd.synth import make_scene

@@ -1,7 +1,7 @@
 """Does the pair-major convolution get cheaper per pair when its partial products fit the 256 MB Infinity Cache?  The same layer
 on the first 1/2, 1/4 of the output rows (own pair lists): us per 1000 pairs."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import ops
 from segdino3d_amd.sparse import SceneMaps
 from segdino3d_amd.synth import make_scene

@@ -1,7 +1,7 @@
 """LAB BUILD (tools/ablate.sh build; run with SD3D_LIB=_ab/libsegdino3d_hip_ablate.so): producer / consumer pass 1 against the lock-step / weight-stationary kernels on the benchmark scene's rulebooks: same bits?  us per
 convolution (incl. pass 2) with each, alone on the GPU and with the several-scenes-in-flight hint.  usage: python tools/pc_check.py"""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import _lib, ops
 from segdino3d_amd.sparse import SceneMaps
 from segdino3d_amd.synth import make_scene

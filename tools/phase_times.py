@@ -1,8 +1,7 @@
 """Where does a scene's time go when four scenes are in flight?  HIP events (no serialisation) around the phases of every forward -
 map building, the U-Net (one C call), pooling + decoder, post-processing - in the pipelined runner and alone."""
 import os, sys, time, torch
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd import architecture, backbone_mink, sparse, plan
 from segdino3d_amd.dist_eval import PipelinedRunner

@@ -1,7 +1,6 @@
 """Only the pipelined runner (for profiling its steady state): pipe_only.py <streams> <scenes>"""
 import os, sys, time, copy, torch
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd.dist_eval import PipelinedRunner
 from segdino3d_amd.synth import make_scene

@@ -1,7 +1,6 @@
 """Pipelined throughput of parts of the forward (what would trimming the non-GEMM work buy?): pipe_parts.py <streams> <scenes>"""
 import os, sys, time, copy, torch
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd import ops
 from segdino3d_amd.dist_eval import PipelinedRunner

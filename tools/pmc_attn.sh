@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ / GRBM counter passes over the attention kernels of the tree (tools/attn_pmc.py, one query count per process so that a kernel
 # name maps to one launch shape).  The program goes directly after `--`.  -> gpurun_out/pmc_attn_q<Q>_p<pass>.json
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 mkdir -p "$ROOT/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
 P1="SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAVES GRBM_GUI_ACTIVE"

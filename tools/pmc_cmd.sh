@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 PMC pass (counters in $PMC) of a python tool, condensed.  usage: PMC="A B C" pmc_cmd.sh <name> <script.py> [args...]
 NAME=$1; shift
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 mkdir -p "$ROOT/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$NAME

@@ -2,7 +2,7 @@
 # SQ / TCC / GRBM counter passes over the pair-major convolution of single U-Net layers (tools/pair_quick.py, one layer shape per
 # process so that a kernel name maps to one launch shape).  The program goes directly after `--`.
 #   usage: tools/pmc_pair.sh "<case indices of pair_quick.py>"      -> gpurun_out/pmc_pair_c<case>_p<pass>.json
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 mkdir -p "$ROOT/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
 P1="SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAVES GRBM_GUI_ACTIVE"

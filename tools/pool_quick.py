@@ -1,7 +1,7 @@
 """Superpoint pooling alone on the benchmark scene (and a 500 k-point one): us per launch and a checksum of the pooled rows (same-bits
 check between two builds of the library: SD3D_LIB=...).  usage: python tools/pool_quick.py"""
 import hashlib, os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd.sparse import SceneMaps
 from segdino3d_amd.synth import make_scene
 

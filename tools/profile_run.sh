@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 kernel trace of bench.py, condensed to gpurun_out/<name>.md.   usage: profile_run.sh <name> [bench args...]
 NAME=$1; shift
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 mkdir -p "$ROOT/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$NAME

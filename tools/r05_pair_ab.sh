@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 5: lock-step pass 1, first form vs second form (SD3D_PAIR_V2) and time-sliced priority (SD3D_PAIR_FAIR), layer by layer
 # (tools/pair_quick.py, one process per setting: the library reads its switches once) and in the whole bench.
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/gpurun_out/r05_pair_ab.txt"
 : > "$OUT"
 run() {   # label, env...

@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel timeline of one single-scene forward (all launches, start offsets, queue)
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 mkdir -p $ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_tl

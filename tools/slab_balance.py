@@ -1,6 +1,6 @@
 """How evenly do output-row slabs split a convolution's work?  pairs / padded 16-row MFMA slots per slab: mean, max."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd.sparse import SceneMaps
 from segdino3d_amd.synth import make_scene
 d = torch.device("cuda:0")

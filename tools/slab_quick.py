@@ -1,6 +1,6 @@
 """Slab (output-stationary) vs pair-major sparse convolution on the benchmark scene's rulebooks: us per conv, active TFLOP/s."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import experimental, ops
 from segdino3d_amd.sparse import SceneMaps
 from segdino3d_amd.synth import make_scene

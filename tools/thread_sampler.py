@@ -1,6 +1,6 @@
 """Where are the worker threads of the pipelined runner?  Samples their Python stacks every 0.5 ms."""
 import os, sys, time, copy, threading, collections, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from segdino3d_amd.dist_eval import PipelinedRunner
 from segdino3d_amd.synth import make_scene

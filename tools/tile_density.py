@@ -2,7 +2,7 @@
 output rows runs one MFMA row block per offset k that has at least one neighbour among the tile's rows (empty (tile, k)
 blocks are skipped).  Efficiency = pairs / (T * non-empty blocks)."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd.sparse import SceneMaps
 from segdino3d_amd.synth import make_scene
 d = torch.device("cuda:0")

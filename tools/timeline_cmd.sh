@@ -1,7 +1,7 @@
 #!/bin/bash
 # timeline_cmd.sh <name> <script.py> [args]: rocprofv3 kernel trace + tools/timeline.py
 NAME=$1; shift
-ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$NAME
 SCRIPT=$1; shift

@@ -1,6 +1,6 @@
 """top-k of the post-processing: radix select (one launch) against the full radix sort, us per call (HIP events, 200 calls)."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segdino3d_amd import ops
 d = torch.device("cuda:0")
 g = torch.Generator().manual_seed(0)

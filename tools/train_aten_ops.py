@@ -1,7 +1,7 @@
 """Which torch (ATen) operators does one training step (forward + loss + backward) launch, and from where?  torch.profiler with Python
 stacks over one step at the benchmark shape; backward-pass operators are attributed to the autograd node that ran them."""
 import os, sys, collections, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import segdino3d_amd as seg
 from segdino3d_amd.configs import scannet200_model_cfg
 from segdino3d_amd.synth import add_training_targets, make_scene
@@ -35,7 +35,7 @@ for ev in prof.events():
     frame = next((f for f in ev.stack if "segdino3d_amd" in f), None)
     if frame is None:
         frame = next((f for f in ev.stack if "autograd" in f or "Backward" in f), ev.stack[0] if ev.stack else "?")
-    agg[(ev.name, frame.split("/root/repo/")[-1] if "/root/repo/" in frame else frame[-90:])] += len(ev.kernels)
+    agg[(ev.name, frame.split(sys.path[0] + "/")[-1] if sys.path[0] + "/" in frame else frame[-90:])] += len(ev.kernels)
 total = 0
 for (name, frame), n in sorted(agg.items(), key=lambda kv: -kv[1])[:60]:
     print(f"{n:4d}  {name:28s} {frame}")

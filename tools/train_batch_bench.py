@@ -1,6 +1,6 @@
 """Training step on a batch of scenes (the reference trains 4 scenes per rank, train_engine_3d.py:88): python tools/train_batch_bench.py [scenes] [points]"""
 import json, os, sys, time, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import segdino3d_amd as seg
 from segdino3d_amd.configs import scannet200_model_cfg
 from segdino3d_amd.synth import add_training_targets, make_scene

@@ -1,6 +1,6 @@
 """ATen operators of the training FORWARD + loss by calling line (TorchDispatchMode: every aten call with the innermost segdino3d_amd frame)."""
 import os, sys, collections, traceback, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import segdino3d_amd as seg
 from segdino3d_amd.configs import scannet200_model_cfg
 from segdino3d_amd.synth import add_training_targets, make_scene

@@ -5,7 +5,7 @@ import pstats
 import sys
 import time
 
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 import segdino3d_amd as seg

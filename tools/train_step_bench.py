@@ -1,6 +1,6 @@
 """One-scene training step (forward + loss + backward) at the benchmark shape, for profiling: python tools/train_step_bench.py [points] [steps]"""
 import os, sys, time, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import segdino3d_amd as seg
 from segdino3d_amd.configs import scannet200_model_cfg
 from segdino3d_amd.synth import add_training_targets, make_scene

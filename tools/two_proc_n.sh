@@ -1,6 +1,6 @@
 #!/bin/bash
 # two_proc_n.sh <procs> <streams>: P independent bench processes on one GPU, S streams each
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 P=$1; S=$2
 pids=()
 for i in $(seq 1 $P); do
