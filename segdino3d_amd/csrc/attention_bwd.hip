@@ -17,6 +17,7 @@
 #include "../../include/segdino3d_hip.h"
 #include <math.h>
 #include <stdlib.h>
+#include <atomic>
 
 struct AttnBwdParams {
     const float* q[2]; int ldq[2];
@@ -265,11 +266,13 @@ int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1
     // budget (302 us; 324 / 362 with the kv kernel's settings).
     const int nwq = kt >= 8 ? 4 : (kt >= 2 ? 2 : 1), nwk = qt >= 32 ? 8 : (qt >= 8 ? 4 : (qt >= 2 ? 2 : 1));
     const dim3 gq((unsigned)qt, (unsigned)H), gk((unsigned)kt, (unsigned)H);
-    static bool attr_done = false;
-    if (!attr_done) {
+    static std::atomic<bool> attr_set[64];                    // per device: a function attribute belongs to the current device
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return sd3d_set_error(SD3D_ERR_LAUNCH, "attention_backward: no device");
+    if (!attr_set[dev].load(std::memory_order_relaxed)) {
         (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 2 * 4096);
         (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 3 * 4096);
-        attr_done = true;
+        attr_set[dev].store(true, std::memory_order_relaxed);
     }
     if (nsrc == 1) {
         attn_bwd_q_kernel<1><<<gq, 64 * nwq, (size_t)nwq * 1 * 4096, ST>>>(p);

@@ -1,6 +1,6 @@
 // extern "C" entry points declared in include/segdino3d_hip.h.  Thin argument checking + launch.
 #include "gg_common.h"
-#include "../../include/segdino3d_hip.h"
+#include "pair_conv.h"
 #include <string.h>
 #include <stdio.h>
 
@@ -47,16 +47,8 @@ int launch_voxel_keys(const float*, int, int64_t, float, const float*, int, int,
 int launch_gather_gemm(const GGParams&, int, void*, size_t, hipStream_t);
 int dense_plan_code(int64_t, int, int);
 int launch_gather_gemm_split(const GGParams&, int, int, const void*, void*, size_t, hipStream_t);
-size_t pair_lists_ws_bytes(int K, int64_t M);
-int launch_pair_lists(const int32_t*, int, int64_t, int64_t, int32_t*, int32_t*, int32_t*, void*, size_t, hipStream_t);
 int launch_linear_group(int, const GGParams*, hipStream_t);
 int launch_fourier_pe(const float*, int, int64_t, const float*, const float*, int, int, float*, int, const int32_t*, hipStream_t);
-int launch_pair_lists_batch(int, const int32_t* const*, const int*, const int64_t*, const int64_t*, int32_t* const*, int32_t* const*,
-                            int32_t* const*, void*, size_t, hipStream_t);
-int launch_pair_conv(const float*, int, int, const float*, int, const int32_t*, const int32_t*, int64_t, const int32_t*, const int32_t*, int,
-                     int, const int32_t*, const float*, int, int, int, int64_t, const float*, const float*, const float*, int, float*, int,
-                     int, float*, size_t, hipStream_t);
-int launch_pair_lists_desc(int, const sd3d_pair_table_desc*, void*, size_t, hipStream_t);
 size_t kernel_maps_hier_ws_bytes(int, const int64_t*);
 int launch_kernel_maps_hier(int, const uint64_t* const*, const int32_t* const*, const int64_t*, int32_t* const*, int32_t*, const int8_t*,
                             const int8_t*, const int8_t*, int32_t*, const int32_t*, int32_t* const*, int32_t* const*, void*, size_t, hipStream_t);

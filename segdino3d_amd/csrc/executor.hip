@@ -5,12 +5,9 @@
 // per scene the caller provides the neighbour tables and ONE arena carved into the activation
 // buffers (sd3d_buf[]), so this call neither allocates nor synchronises: it only enqueues.
 #include "gg_common.h"
-#include "../../include/segdino3d_hip.h"
+#include "pair_conv.h"
 
 int launch_gather_gemm(const GGParams&, int, void*, size_t, hipStream_t);
-int launch_pair_conv(const float*, int, int, const float*, int, const int32_t*, const int32_t*, int64_t, const int32_t*, const int32_t*, int,
-                     int, const int32_t*, const float*, int, int, int, int64_t, const float*, const float*, const float*, int, float*, int,
-                     int, float*, size_t, hipStream_t);
 int launch_scale_shift_act(const float*, int, int, const float*, int, const float*, const float*, int, int64_t, int, const float*, int,
                            float*, int, hipStream_t);
 

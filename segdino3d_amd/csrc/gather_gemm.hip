@@ -20,7 +20,7 @@
 // as long as A and B agree, so half h takes channels h*16 + kk: 16 contiguous floats per lane,
 // loaded as 4 x dwordx4.
 #include "gg_common.h"
-#include <stdlib.h>
+#include "pair_conv.h"
 
 template <int NT>
 struct Frag {
@@ -426,7 +426,6 @@ static int lds_column_tiles(int sub, int64_t tiles, bool gathered) {
     return nt;
 }
 
-int launch_pair_dense(const GGParams&, hipStream_t);             // pair_gemm.hip
 #define GG_PAIR_DENSE_MIN_ROWS 16384
 
 int launch_gather_gemm(const GGParams& p_in, int nt, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -443,8 +442,7 @@ int launch_gather_gemm(const GGParams& p_in, int nt, void* ws, size_t ws_bytes, 
     if (!p.nbr && p.K != 1) return sd3d_set_error(SD3D_ERR_ARG, "gather_gemm: identity gather needs K == 1");
     // dense products on tens of thousands of rows (the U-Net's 1x1 convolutions; no decoder Linear reaches this many rows per scene, and
     // the batched decoder passes its tiling code explicitly): the persistent pass-1 kernel with the identity rulebook
-    static const int pd_env = [] { const char* e = getenv("SD3D_PAIR_DENSE"); return e ? atoi(e) : 1; }();
-    if (pd_env && nt == 0 && !p.nbr && p.K == 1 && p.M >= GG_PAIR_DENSE_MIN_ROWS && !(p.Cout & 3) && !(p.ld_out & 3) && (!p.res || !(p.ld_res & 3)))
+    if (nt == 0 && !p.nbr && p.K == 1 && p.M >= GG_PAIR_DENSE_MIN_ROWS && !(p.Cout & 3) && !(p.ld_out & 3) && (!p.res || !(p.ld_res & 3)))
         return launch_pair_dense(p, st);
     const int sub = (p.Cout + 31) / 32;
     const int64_t tiles = cdiv(p.M, 32);

@@ -13,7 +13,6 @@
 // of one offset are contiguous and pass 2 adds them up in a fixed order: bit-reproducible, no atomics.
 #include "common.h"
 #include "../../include/segdino3d_hip.h"
-#include <stdlib.h>
 
 #define PT 128                       // pairs per tile of the pair lists
 #define WG_STEP 64                   // pairs staged per step (32: same speed within 3 %)
@@ -363,11 +362,9 @@ static int wgrad_ranges(int K, int Cin, int Cout, int64_t p_cap) {
     // workgroups in total: one per CU for the wide layers (every extra range is another Cout x Cin partial block to write and to
     // re-read in pass 2, and counts between whole multiples of the CU count run a half-empty last round: level-3 256 -> 256
     // 604 us with 768, 553 with 512, 533 with 256, 710 with 384), three per CU for the narrow ones (64 -> 64: 124 / 140 / 188 us
-    // with 768 / 512 / 256).  SD3D_WGRAD_WGS overrides (tuning).
-    static int total_env = -1;
-    if (total_env < 0) { const char* e = getenv("SD3D_WGRAD_WGS"); total_env = e ? atoi(e) : 0; }
+    // with 768 / 512 / 256).
     // (the 5^3 stem, 288 -> 32 with 125 offsets: 868 / 517 / 659 us with 256 / 512 / 768)
-    const int total = total_env > 0 ? total_env : ((int64_t)Cin * Cout > 96 * 96 || (Cin >= 96 && Cout >= 96) ? 256 : (K > 27 ? 512 : 768));
+    const int total = (int64_t)Cin * Cout > 96 * 96 || (Cin >= 96 && Cout >= 96) ? 256 : (K > 27 ? 512 : 768);
     int r = total / blocks;
     r = r < 32 ? 32 : r;
     const int64_t tiles = p_cap / PT;
@@ -414,22 +411,12 @@ int sd3d_pair_wgrad(const float* dy, int ld_dy, const float* x, int ld_x, const 
     const dim3 grid(ranges, (unsigned)cdiv(Cout, nco * 32), (unsigned)cdiv(Cin, nci * 32));
     // waves per workgroup: one 32 x 32 output tile per wave where the block has >= 8 tiles (16 waves share one staged step of the
     // 128 x 128 block: level-3 256 -> 256 530 -> 354 us, level-2 128 -> 128 415 -> 277 us against 4 waves x 4 tiles), 4 waves otherwise.
-    // SD3D_WGRAD_NW=4 forces the 4-wave kernel (cross-check).
-    static int nw_env = -1;
-    if (nw_env < 0) { const char* e = getenv("SD3D_WGRAD_NW"); nw_env = e ? atoi(e) : 0; }
-#define WG_LAUNCH(a, b, nw) pair_wgrad_kernel<a, b, nw><<<grid, (nw) * 64, 0, ST>>>(p)
-#define WG_CASE(a, b) if (nco == a && nci == b) {                                                   \
-        if (nw_env == 4 || a * b < 8) WG_LAUNCH(a, b, 4);                                           \
-        else if (a * b == 16) WG_LAUNCH(a, b, 16);                                                  \
-        else if (a * b == 12) WG_LAUNCH(a, b, 12);                                                  \
-        else if (a * b == 9) WG_LAUNCH(a, b, 9);                                                    \
-        else WG_LAUNCH(a, b, 8); }
+#define WG_CASE(a, b) if (nco == a && nci == b) pair_wgrad_kernel<a, b, (a * b < 8 ? 4 : a * b)><<<grid, (a * b < 8 ? 4 : a * b) * 64, 0, ST>>>(p);
     WG_CASE(1, 1) WG_CASE(1, 2) WG_CASE(1, 3) WG_CASE(1, 4)
     WG_CASE(2, 1) WG_CASE(2, 2) WG_CASE(2, 3) WG_CASE(2, 4)
     WG_CASE(3, 1) WG_CASE(3, 2) WG_CASE(3, 3) WG_CASE(3, 4)
     WG_CASE(4, 1) WG_CASE(4, 2) WG_CASE(4, 3) WG_CASE(4, 4)
 #undef WG_CASE
-#undef WG_LAUNCH
     const int64_t elems = (int64_t)Cin * Cout + (p.bias ? Cout : 0);
     int64_t gx = cdiv(elems, 256);                           // ~2048 workgroups over all offsets: a K = 1 Linear gets as many as a 27-offset convolution
     const int64_t cap = 2048 / K > 64 ? 2048 / K : 64;

@@ -14,12 +14,7 @@
 //   * the weight gradient is written in the parameter's own [K, Cin, Cout] layout and the input gradient reads the parameter as it lies
 //     (mirrored offsets, SD3D_PAIR_MIRROR_W), so no transposed / flipped copy exists in the backward pass.
 // Same kernels, same order per tensor as the autograd-node path: the two are compared at 1e-6 in tests/test_gpu_train_ops.py.
-#include "common.h"
-#include "../../include/segdino3d_hip.h"
-
-int launch_pair_conv(const float*, int, int, const float*, int, const int32_t*, const int32_t*, int64_t, const int32_t*, const int32_t*, int,
-                     int, const int32_t*, const float*, int, int, int, int64_t, const float*, const float*, const float*, int, float*, int,
-                     int, float*, size_t, hipStream_t);
+#include "pair_conv.h"
 
 #define ST ((hipStream_t)stream)
 
