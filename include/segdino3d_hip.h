@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 1
+#define SD3D_ABI_VERSION 2
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -34,7 +34,7 @@ const char* sd3d_last_error(void);
 int sd3d_selftest_host(void);
 /* Scheduling hint (process-wide, default 1): how many independent scenes the caller keeps in flight on this GPU, each on its
  * own stream (dist_eval.PipelinedRunner).  With more than one, launchers prefer kernel variants with a small LDS footprint
- * that co-schedule with the other scenes' kernels over the ones that are fastest alone on an idle GPU (sd3d_pair_conv: the
+ * that co-schedule with the other scenes' kernels over the ones that are fastest alone on an idle GPU (sd3d_pair_conv_ex: the
  * weight-stationary pass 1 for >= 96 output columns).  Results are bit-identical either way.  Returns the previous value. */
 int sd3d_set_scenes_in_flight(int n);
 
@@ -56,13 +56,9 @@ int sd3d_pair_pool_poison(int64_t word);
  * ------------------------------------------------------------------------------------------- */
 size_t sd3d_sort_ws_bytes(int64_t n);
 /* Stable LSD radix sort of (key, value) pairs on bits [begin_bit, end_bit).  keys_in / vals_in are
- * clobbered.  vals_in may be NULL (value = element index); then vals_scratch [n] must be given. */
-int sd3d_sort_pairs_u64(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out,
-                        uint32_t* vals_scratch, int64_t n, int begin_bit, int end_bit, void* ws, size_t ws_bytes,
-                        void* stream);
-/* The same without the padding pass: the radix passes ping-pong between (keys_in, vals_in | vals_scratch) and (keys_out, vals_out); an
- * EVEN number of 8-bit passes leaves the result in the former and sets *landed_in_input = 1 (sd3d_sort_pairs_u64 adds a pass over zero
- * bits instead, so that its result is always in *_out). */
+ * clobbered.  vals_in may be NULL (value = element index); then vals_scratch [n] must be given.  The radix passes ping-pong
+ * between (keys_in, vals_in | vals_scratch) and (keys_out, vals_out); an EVEN number of 8-bit passes leaves the result in the
+ * former and sets *landed_in_input = 1, otherwise the result is in *_out and *landed_in_input = 0. */
 int sd3d_sort_pairs_u64_ex(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, uint32_t* vals_scratch,
                            int64_t n, int begin_bit, int end_bit, void* ws, size_t ws_bytes, int* landed_in_input, void* stream);
 size_t sd3d_scan_ws_bytes(int64_t n);
@@ -251,7 +247,7 @@ int sd3d_linear_group(int n, const sd3d_linear_job* jobs, void* stream);
  * terms = 3 (two terms per operand, error ~2^-16 per product) or 6 (three terms, ~2^-24: fp32-grade), or
  * terms = 1: plain bf16 operands with fp32 accumulation ([1][K][Cout][Cin]) - the "bf16 decoder" of BASELINE
  * config #3 (autocast(bf16) around the decoder's nn.Linear calls in the reference, train_engine_3d.py:88-100).
- * Not used unless the host asks for it (SD3D_GEMM_MODE / decoder compute_dtype); the default is exact fp32 MFMA. */
+ * Not used unless the host asks for it (decoder compute_dtype, or split weights passed explicitly); the default is exact fp32 MFMA. */
 int sd3d_gather_gemm_split(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* nbr,
                            const uint16_t* wt_split, int terms, int K, int Cin, int Cout, int64_t M, const float* scale,
                            const float* shift, const float* res, int ld_res, float* out, int ld_out, int act, int nt,
@@ -260,30 +256,21 @@ int sd3d_gather_gemm_split(const float* in0, int ld0, int C0, const float* in1, 
 /* Pair-major sparse convolution (csrc/pair_gemm.hip) - the same contract as sd3d_gather_gemm with a
  * neighbour table (MinkowskiConvolution / SubMConv3d + folded BN + residual + activation), evaluated
  * over the rulebook laid out offset-major so that every MFMA row is a real (in, out) pair.
- * sd3d_pair_lists builds, once per neighbour table nbr [K, M]:
+ * sd3d_pair_lists_desc builds, for n <= 16 neighbour tables nbr [K, M] in ONE launch set:
  *   pos [K, M]      position of pair (k, r) in the list, -1 where nbr[k][r] < 0
  *   in_idx [p_cap]  gathered input row of each list entry; every offset's segment is padded to a
  *                   multiple of 128 entries with -1
  *   tile_k [p_cap/128 + 1]  offset of each 128-entry tile, -1 past the end of the list; the last entry
  *                   receives the number of real tiles
  * p_cap: multiple of 128, >= (number of pairs) + 127 * K (pairs beyond the capacity are dropped:
- * size it from the pair count sd3d_kernel_map returns).
- * sd3d_pair_conv: part = caller scratch of >= p_cap * Cout floats.  Cin % 32 == 0, Cout % 4 == 0. */
+ * size it from the pair count sd3d_kernel_map returns).  ws holds the tables' scratch back to back, each rounded up to
+ * 256 bytes (sum of align256(sd3d_pair_lists_ws_bytes(K_i, M_i))).
+ * sd3d_pair_conv_ex: part = caller scratch of >= p_cap * Cout floats.  Cin % 32 == 0, Cout % 4 == 0.  With plain lists
+ * (rlist and out_idx NULL, center -1) pass 2 sums each output row's partial products through pos. */
 size_t sd3d_pair_lists_ws_bytes(int K, int64_t M);
-int sd3d_pair_lists(const int32_t* nbr, int K, int64_t M, int64_t p_cap, int32_t* pos, int32_t* in_idx, int32_t* tile_k,
-                    void* ws, size_t ws_bytes, void* stream);
-/* The same for n <= 16 tables in ONE launch set (three kernels, no memsets): arrays of n host-side entries; ws holds the
- * tables' scratch back to back, each rounded up to 256 bytes (sum of align256(sd3d_pair_lists_ws_bytes(K_i, M_i))). */
-int sd3d_pair_lists_batch(int n, const int32_t* const* nbr, const int* K, const int64_t* M, const int64_t* p_cap,
-                          int32_t* const* pos, int32_t* const* in_idx, int32_t* const* tile_k, void* ws, size_t ws_bytes,
-                          void* stream);
-int sd3d_pair_conv(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* in_idx,
-                   const int32_t* tile_k, int64_t p_cap, const int32_t* pos, const float* wt, int K, int Cin, int Cout,
-                   int64_t M, const float* scale, const float* shift, const float* res, int ld_res, float* out,
-                   int ld_out, int act, float* part, size_t part_bytes, void* stream);
 
-/* Round-3 products of the list builder, all optional, and the convolution entry that uses them (same contract as sd3d_pair_conv,
- * same fixed per-row summation order for a given table description, results reproducible bit for bit):
+/* Round-3 products of the list builder, all optional, and what the convolution does with them (same fixed per-row summation
+ * order for a given table description, results reproducible bit for bit):
  *   rlist [M, rl_stride]   per output row {count, list positions of its pairs in offset order}; rl_stride a multiple of 4,
  *                          >= K + 4.  Pass 2 walks a row's own partial products instead of the K slots of pos[k][r].
  *   center                 -1 (plain lists) or SD3D_PAIR_CHAINED (below).  (Round 3 also took an offset number here - a dense
@@ -313,7 +300,7 @@ int sd3d_pair_conv(const float* in0, int ld0, int C0, const float* in1, int ld1,
 #define SD3D_PAIR_MIRROR_W(center) ((center) - 2)
 typedef struct sd3d_pair_table_desc {
     const int32_t* nbr;                  /* [K, M] */
-    int32_t *pos, *in_idx, *tile_k;      /* as sd3d_pair_lists */
+    int32_t *pos, *in_idx, *tile_k;      /* see sd3d_pair_lists_desc above */
     int32_t *rlist, *out_idx;            /* optional (NULL) */
     int64_t M, p_cap;
     int32_t K, center, rl_stride, meta;
@@ -329,7 +316,7 @@ int sd3d_pair_conv_ex(const float* in0, int ld0, int C0, const float* in1, int l
  * Python-level module loop of Res16UNetBase.forward (minkunet.py:531-601) / UBlock.forward
  * (spconvunet.py:156-201): the plan is built once per model, per scene the caller supplies the
  * neighbour tables and the activation buffers (one arena, carved by the caller); the call only enqueues.
- *   SD3D_LAYER_PAIR_CONV        out = act(scale * conv(cat[src0, src1]; table) + shift + res)   (sd3d_pair_conv)
+ *   SD3D_LAYER_PAIR_CONV        out = act(scale * conv(cat[src0, src1]; table) + shift + res)   (sd3d_pair_conv_ex)
  *   SD3D_LAYER_DENSE            the same with identity rows, K = 1                                 (sd3d_gather_gemm)
  *   SD3D_LAYER_SCALE_SHIFT_ACT  out = act(cat[src0, src1] * scale + shift) + res, Cin = total channels; res (optional) is
  *                               added AFTER the activation here                                  (sd3d_scale_shift_act_add) */
@@ -342,7 +329,7 @@ typedef struct sd3d_layer {
     const float *wt, *scale, *shift;   /* wt [K, Cout, Cin]; scale / shift per output channel or NULL */
 } sd3d_layer;
 typedef struct sd3d_table {
-    const int32_t *in_idx, *tile_k, *pos;   /* from sd3d_pair_lists */
+    const int32_t *in_idx, *tile_k, *pos;   /* from sd3d_pair_lists_desc */
     int64_t p_cap, M;                        /* M = output rows of the table */
     int32_t K, pad_;
     const int32_t *rlist, *out_idx;          /* optional products of sd3d_pair_lists_desc (NULL) */
@@ -500,12 +487,10 @@ int sd3d_dinox_mask_bits_batch(int n, const uint32_t* const* blocked, const uint
 int sd3d_box_refine(const float* ref_points, const float* d_center, const float* size_prev, int ld_size_prev,
                     const float* d_size, const float* range, int normalize, int64_t Q, float* center, float* size,
                     float* size_metric, void* stream);
-/* out = act(x * scale + shift), x = [x0 (C0 channels) | x1] : pre-activation BatchNorm1d + ReLU of the
- * spconv residual blocks (spconvunet.py:48-51, 154-156, 184-187, 227-229).  x1 may be NULL. */
-int sd3d_scale_shift_act(const float* x0, int ld0, int C0, const float* x1, int ld1, const float* scale,
-                         const float* shift, int act, int64_t M, int C, float* out, int ld_out, void* stream);
-/* out = act(x * scale + shift) + add : the tail of a normalize_before=False residual block - conv -> BatchNorm1d -> ReLU,
- * then the identity branch summed in AFTER the activation (spconvunet.py:66-81, 95-97).  add may be NULL. */
+/* out = act(x * scale + shift) + add, x = [x0 (C0 channels) | x1] (x1 may be NULL).  add NULL: the pre-activation
+ * BatchNorm1d + ReLU of the spconv residual blocks (spconvunet.py:48-51, 154-156, 184-187, 227-229); with add: the tail of a
+ * normalize_before=False residual block - conv -> BatchNorm1d -> ReLU, then the identity branch summed in AFTER the
+ * activation (spconvunet.py:66-81, 95-97). */
 int sd3d_scale_shift_act_add(const float* x0, int ld0, int C0, const float* x1, int ld1, const float* scale,
                              const float* shift, int act, int64_t M, int C, const float* add, int ld_add, float* out,
                              int ld_out, void* stream);
@@ -524,7 +509,7 @@ int sd3d_mask_scores(const float* masks, int ld, int S, const uint32_t* flat_idx
  *   boxes[i] = [centers | sizes][qidx[record[i]]] ([n, 6], baseline3d.py:447-452; centers / sizes [Q, 3] contiguous). */
 int sd3d_take_f32(const float* src, const uint32_t* idx, int n, float* out, void* stream);
 /* idx[0..k) = the first k entries of the STABLE descending sort of x[0..n) (ties: lower index first) - what
- * sd3d_keys_from_f32(descending) + sd3d_sort_pairs_u64 give, from one launch of one workgroup (radix select + rank of the k survivors).
+ * sd3d_keys_from_f32(descending) + sd3d_sort_pairs_u64_ex give, from one launch of one workgroup (radix select + rank of the k survivors).
  * `scores.flatten(0, 1).topk(topk_insts)` of predict_by_feat_instance (baseline3d.py:434).  1 <= k <= 1024, k <= n <= 40 960 (forty scores per thread of the one workgroup, in registers). */
 int sd3d_topk_desc_f32(const float* x, int64_t n, int k, uint32_t* idx, void* stream);
 /* The data-dependent selections of predict_by_feat_instance (:470-476) for two score thresholds on the device (all outputs sized k):
@@ -637,10 +622,10 @@ int sd3d_semantic_loss(const float* sem, int ld, int Q, int n_rows, int n_logits
 
 /* ---------------------------------------------------------------------------------------------
  * Backward of the pair-major sparse convolution (MinkowskiEngine / spconv autograd in the reference,
- * reached through train_engine_3d.py:88-122).  The input gradient is sd3d_pair_conv on the transposed rulebook with
+ * reached through train_engine_3d.py:88-122).  The input gradient is sd3d_pair_conv_ex on the transposed rulebook with
  * transposed weights; the weight gradient is
  *     dw[k][co][ci] (+)= sum over pairs p of offset k of dy[out_idx[p]][co] * x[in_idx[p]][ci]
- * with in_idx / tile_k from sd3d_pair_lists and out_idx from sd3d_pair_out_rows (out_idx[pos[k][r]] = r, -1 on
+ * with in_idx / tile_k from sd3d_pair_lists_desc and out_idx from sd3d_pair_out_rows (out_idx[pos[k][r]] = r, -1 on
  * padding).  dw is [K, Cout, Cin] like the forward weights; exact fp32 MFMA, fixed summation order.
  * flags: bit 0 = accumulate into dw, bit 1 = round both operands to bf16 (nearest even) before multiplying - the numbers
  * of a bf16-operand product with fp32 accumulation, for the bf16 training mode of the decoder; bit 2 (K = 1: a Linear) =
@@ -667,16 +652,14 @@ int sd3d_linear_wgrad(const float* g, int ld_g, const float* x, int ld_x, int64_
  * Training-mode BatchNorm over voxel rows (ME.MinkowskiBatchNorm = nn.BatchNorm1d, minkunet.py:302-304) with the
  * BasicBlock's residual add and ReLU folded in (:234-250), and the backward of sd3d_pool_superpoints (:668-676).
  * x, y, dy, dx, res, dres are [M, C] fp32 with row strides in floats; act: 0 none, 1 relu.
- *   sd3d_bn_stats:    mean[c], var[c] (biased), rstd[c] = 1 / sqrt(var + eps) over the M rows
- *   sd3d_bn_apply:    y = act((x - mean) * rstd * gamma + beta + res)            (res nullable)
- *   sd3d_bn_backward: g = dy masked by y > 0 when act == relu; dbeta = sum g; dgamma = sum g * xhat;
- *                     dx = gamma * rstd * (g - dbeta / M - xhat * dgamma / M); dres = g (nullable)
+ *   sd3d_bn_stats_running: mean[c], var[c] (biased), rstd[c] = 1 / sqrt(var + eps) over the M rows
+ *   sd3d_bn_apply:         y = act((x - mean) * rstd * gamma + beta + res)            (res nullable)
+ *   sd3d_bn_backward:      g = dy masked by y > 0 when act == relu; dbeta = sum g; dgamma = sum g * xhat;
+ *                          dx = gamma * rstd * (g - dbeta / M - xhat * dgamma / M); dres = g (nullable)
  * Reductions run in a fixed order (bit-reproducible).  ws: sd3d_bn_ws_bytes(M, C). */
 size_t sd3d_bn_ws_bytes(int64_t M, int C);
-int sd3d_bn_stats(const float* x, int ld, int64_t M, int C, float eps, float* mean, float* var, float* rstd, void* ws, size_t ws_bytes,
-                  void* stream);
-/* sd3d_bn_stats that also advances nn.BatchNorm1d's buffers in place (any of the three may be NULL):
- * running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with the UNBIASED batch variance
+/* sd3d_bn_stats_running also advances nn.BatchNorm1d's buffers in place (any of the three may be NULL: then it only computes
+ * the statistics): running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with the UNBIASED batch variance
  * (var * M / (M - 1)), num_batches_tracked += 1 (torch/nn/modules/batchnorm.py semantics behind minkunet.py:302-304). */
 int sd3d_bn_stats_running(const float* x, int ld, int64_t M, int C, float eps, float* mean, float* var, float* rstd,
                           float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, void* ws,

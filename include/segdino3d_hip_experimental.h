@@ -16,7 +16,7 @@ extern "C" {
  * while it walks the offsets in ascending order, and writes every output row once - no partial products in HBM, no
  * second pass, no pair lists.  n_pairs (number of entries >= 0, from sd3d_kernel_map) only guides the launch geometry.
  * Cin % 32 == 0, Cout % 16 == 0, K <= 128; sd3d_slab_conv_ws_bytes returns 0 for shapes it does not handle (the caller
- * keeps sd3d_pair_conv for those).  ws: per-workgroup rulebook scratch (+ partial slabs when the offsets are split). */
+ * keeps sd3d_pair_conv_ex for those).  ws: per-workgroup rulebook scratch (+ partial slabs when the offsets are split). */
 size_t sd3d_slab_conv_ws_bytes(int K, int Cin, int Cout, int64_t M, int64_t n_pairs);
 int sd3d_slab_conv(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* nbr, int64_t n_pairs,
                    const float* wt, int K, int Cin, int Cout, int64_t M, const float* scale, const float* shift,

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 _lib = None
 
@@ -33,7 +33,6 @@ SIGNATURES = {
     "sd3d_pair_pool_poison": (_i, [_l]),
     "sd3d_selftest_host": (_i, []),
     "sd3d_sort_ws_bytes": (_z, [_l]),
-    "sd3d_sort_pairs_u64": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _z, _p]),
     "sd3d_sort_pairs_u64_ex": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _z, _p, _p]),
     "sd3d_scan_ws_bytes": (_z, [_l]),
     "sd3d_scan_exclusive_i32": (_i, [_p, _p, _l, _p, _p, _z, _p]),
@@ -68,9 +67,6 @@ SIGNATURES = {
     "sd3d_linear_group": (_i, [_i, _p, _p]),
     "sd3d_gather_gemm_split": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _l, _p, _p, _p, _i, _p, _i, _i, _i, _p, _z, _p]),
     "sd3d_pair_lists_ws_bytes": (_z, [_i, _l]),
-    "sd3d_pair_lists": (_i, [_p, _i, _l, _l, _p, _p, _p, _p, _z, _p]),
-    "sd3d_pair_lists_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "sd3d_pair_conv": (_i, [_p, _i, _i, _p, _i, _p, _p, _l, _p, _p, _i, _i, _i, _l, _p, _p, _p, _i, _p, _i, _i, _p, _z, _p]),
     "sd3d_pair_lists_desc": (_i, [_i, _p, _p, _z, _p]),
     "sd3d_pair_conv_ex": (_i, [_p, _i, _i, _p, _i, _p, _p, _l, _p, _p, _i, _i, _p, _p, _i, _i, _i, _l, _p, _p, _p, _i, _p, _i, _i, _p, _z, _p]),
     "sd3d_run_layers": (_i, [_p, _i, _p, _i, _p, _i, _p, _z, _p, _z, _p]),
@@ -92,7 +88,6 @@ SIGNATURES = {
     "sd3d_near_bits": (_i, [_p, _l, _p, _l, _f, _p, _i, _p]),
     "sd3d_dinox_mask_bits": (_i, [_p, _p, _i, _l, _l, _p, _i, _p]),
     "sd3d_box_refine": (_i, [_p, _p, _p, _i, _p, _p, _i, _l, _p, _p, _p, _p]),
-    "sd3d_scale_shift_act": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _l, _i, _p, _i, _p]),
     "sd3d_scale_shift_act_add": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _l, _i, _p, _i, _p, _i, _p]),
     "sd3d_class_scores": (_i, [_p, _i, _l, _i, _p, _p, _p]),
     "sd3d_mask_scores": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
@@ -130,7 +125,6 @@ SIGNATURES = {
     "sd3d_pair_wgrad": (_i, [_p, _i, _p, _i, _p, _p, _p, _l, _i, _i, _i, _p, _i, _p, _z, _p]),
     "sd3d_linear_wgrad": (_i, [_p, _i, _p, _i, _l, _i, _i, _p, _p, _i, _p]),
     "sd3d_bn_ws_bytes": (_z, [_l, _i]),
-    "sd3d_bn_stats": (_i, [_p, _i, _l, _i, _f, _p, _p, _p, _p, _z, _p]),
     "sd3d_transpose_batch": (_i, [_i, _p, _p]),
     "sd3d_unet_train_forward": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _z, _p, _z, _p]),
     "sd3d_unet_train_backward": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _i, _p, _p, _z, _p, _z, _p, _z, _p]),
@@ -176,8 +170,8 @@ def load():
     # PyDLL = the calls keep the GIL.  Every entry point only enqueues work (a few microseconds), and with
     # several host threads each driving a stream (dist_eval.PipelinedRunner) releasing and re-taking the GIL
     # around ~600 such calls per forward costs more than the calls themselves (lock convoy: 73.6 -> 87.8 scenes/s
-    # in a same-box A/B).  SD3D_RELEASE_GIL=1 restores ctypes.CDLL behaviour.
-    lib = (C.CDLL if os.environ.get("SD3D_RELEASE_GIL") == "1" else C.PyDLL)(LIB_PATH)
+    # in a same-box A/B).
+    lib = C.PyDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)       # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res

@@ -44,11 +44,6 @@ except Exception:  # noqa: BLE001
 from . import criterion as _criterion  # noqa: E402,F401 - registers ScanNetUnifiedCriterion
 
 import os as _os  # noqa: E402
-# SD3D_FAN_OUT=1: the scenes of a batched evaluation forward run their decoders / post-processing side by side on one side
-# stream each.  Bit-identical, but MEASURED SLOWER than one after the other on the forward's stream (3 streams x batch 4:
-# 91.8 vs 109.1 scenes/s; more hardware queues make it worse): many concurrent chains of tiny launches take workgroup slots away
-# from the persistent convolution kernels of the other batches, whose static tile partition then waits for its slowest workgroup.
-FAN_OUT = _os.environ.get("SD3D_FAN_OUT", "0") == "1"
 
 
 def _cfg_get(cfg, key, default=None):
@@ -184,8 +179,6 @@ class Baseline3D(nn.Module):
         queries, queries_pos, targets = self._select_queries(sp_features_3d, sp_pos, targets)
         self.decoder.return_hidden_states = not self.training
         self.decoder.return_aux_outputs = True
-        if not self.training and len(samples) > 1 and FAN_OUT:
-            return self._forward_eval_fanned(samples, targets, sp_features_3d, sp_pos, sp_pos_wo_elastic, queries, queries_pos, scene_range)
         outputs = self.forward_decoder(sp_features_3d, sp_pos, sp_pos_wo_elastic, queries, queries_pos, targets, scene_range)
         cap = _trace.active()
         if cap is not None:                                      # per-call, per-thread (segdino3d_amd/_trace.py)
@@ -197,43 +190,6 @@ class Baseline3D(nn.Module):
         for b in range(len(targets)):
             pred = self.predict_by_feat(samples, outputs, targets[b]["extra_features"]["super_point_masks"], b)
             targets[b].pred_pts_seg = pred[0]
-        return targets
-
-    def _forward_eval_fanned(self, samples, targets, sp_feats, sp_pos, sp_pos_wo, queries, queries_pos, scene_range):
-        """Decoder + post-processing of the B scenes of a batched evaluation forward, each scene on its own side stream: per
-        scene these are ~300 dependent launches of a few microseconds that fill a handful of CUs, so B of them side by side
-        take about as long as one.  Issue order: all decoders, then all threshold-independent post-processing (ending in each
-        scene's host read), then the data-dependent selections as their reads arrive.  Same kernels, same per-scene launch
-        sequence as the single-scene forward: results are bit-identical to it."""
-        B = len(samples)
-        main = torch.cuda.current_stream()
-        sides = ops.side_streams(B, samples[0].device)
-        outs, coms, reads, sems = [None] * B, [None] * B, [None] * B, [None] * B
-        pick = lambda lst, b: None if lst is None else [lst[b]]      # noqa: E731
-        for b, st in enumerate(sides):
-            st.wait_stream(main)
-            with ops.use_stream(st):
-                outs[b] = self.forward_decoder([sp_feats[b]], pick(sp_pos, b), pick(sp_pos_wo, b), [queries[b]], pick(queries_pos, b),
-                                               [targets[b]], pick(scene_range, b))
-        ops.baton_yield()
-        for b, st in enumerate(sides):
-            with ops.use_stream(st):
-                coms[b] = self._instances_common([samples[b]], outs[b], targets[b]["extra_features"]["super_point_masks"])
-                reads[b] = self._select_begin(coms[b])
-                sems[b] = self._semantic(outs[b], targets[b]["extra_features"]["super_point_masks"])
-        for b, st in enumerate(sides):
-            with ops.use_stream(st):
-                pred = self._predict_finish([samples[b]], outs[b], targets[b]["extra_features"]["super_point_masks"], coms[b], reads[b],
-                                            sem_pre=sems[b])
-            targets[b].pred_pts_seg = pred[0]
-            main.wait_stream(st)
-        cap = _trace.active()
-        if cap is not None:                                      # the per-scene dicts merged back into the decoder's list-of-scenes form
-            merged = {k: [o[k][0] for o in outs] for k in outs[0] if k != "aux_outputs"}
-            if "aux_outputs" in outs[0]:
-                merged["aux_outputs"] = [{k: (None if a[0][k] is None else [x[k][0] for x in a]) for k in a[0]}
-                                         for a in zip(*[o["aux_outputs"] for o in outs])]
-            cap.outputs, cap.sp_feats, cap.sp_pos = merged, sp_feats, sp_pos
         return targets
 
     # ---- post-processing -------------------------------------------------------------------------------------

@@ -18,7 +18,6 @@ autograd nodes over HIP kernels).
 from __future__ import annotations
 
 import math
-import os
 from typing import List
 
 import torch
@@ -30,14 +29,6 @@ from .builder import BACKBONES
 from .sparse import SceneMaps
 
 BN_EPS = 1e-5      # MinkowskiBatchNorm wraps nn.BatchNorm1d with the default eps
-# SD3D_BATCH_EVAL=0: an evaluation forward of several scenes runs them one after the other (A/B switch; default = one
-# block-diagonal sparse tensor, sparse.BatchSceneMaps)
-import os as _os
-BATCH_EVAL = _os.environ.get("SD3D_BATCH_EVAL", "1") != "0"
-
-
-# SD3D_NATIVE_TRAIN_WEIGHTS=0: the round-2 training path (a permuted autograd copy per convolution and step, flipped / transposed copies in backward)
-NATIVE_TRAIN_WEIGHTS = os.environ.get("SD3D_NATIVE_TRAIN_WEIGHTS", "1") != "0"
 
 
 class MinkConv(nn.Module):
@@ -186,16 +177,8 @@ class Res16UNetBase(DerivedWeights):
                     pad[n] = _round32(self.in_channels)
             elif isinstance(m, MinkBN):
                 pk[n] = m.bn
-        if NATIVE_TRAIN_WEIGHTS:
-            # every [K, Cin, Cout] parameter -> the [K, Cout, Cin] copy the forward kernels read, in ONE launch; the backward reads the parameters as they lie
-            pk.update(train_ops.transpose_all(kernels, pad))
-        else:
-            for n, k in kernels.items():
-                w = k if k.dim() == 3 else k.unsqueeze(0)
-                w = w.permute(0, 2, 1)
-                if n in pad:
-                    w = torch.nn.functional.pad(w, (0, pad[n] - w.shape[2]))
-                pk[n] = w.contiguous()
+        # every [K, Cin, Cout] parameter -> the [K, Cout, Cin] copy the forward kernels read, in ONE launch; the backward reads the parameters as they lie
+        pk.update(train_ops.transpose_all(kernels, pad))
         return pk
 
     # ---- network ---------------------------------------------------------------------------------
@@ -244,13 +227,12 @@ class Res16UNetBase(DerivedWeights):
         """`Res16UNetBase.forward` (`minkunet.py:531-601`): [V0, Cin_padded] -> [V0, 96].  pk: `self.packed()` of this forward when
         the caller already has it (`_scene_inputs` validates the derived weights while the scene's read-back travels)."""
         k1 = self.conv1_kernel_size
-        use_plan = (not self.training and plan.USE_PLAN and ops.PAIR_CONV and ops.GEMM_MODE is None and ops.GG_FORCE_NT is None
-                    and ops.GG_HOOK is None)
+        use_plan = not self.training and plan.USE_PLAN and ops.PAIR_CONV and ops.GG_HOOK is None
         maps.prepare(same=[(0, k1)] + [(l, 3) for l in range(5)], strides=[0, 1, 2, 3], chained=not self.training, fork=use_plan)
         if self.training:                                        # batch-statistics BatchNorm; backward through HIP kernels
             from . import train_ops, train_plan
             pk = self.packed_train()
-            if (train_plan.USE_TRAIN_PLAN and NATIVE_TRAIN_WEIGHTS and torch.is_grad_enabled() and not train_ops.TrainBackend.IGNORE_ACT
+            if (train_plan.USE_TRAIN_PLAN and torch.is_grad_enabled() and not train_ops.TrainBackend.IGNORE_ACT
                     and train_plan.supported([v for v in pk.values() if isinstance(v, nn.BatchNorm1d)])):
                 # the whole U-Net as ONE autograd node over two C calls (csrc/train_plan.hip)
                 if self._train_plan is None:
@@ -326,7 +308,7 @@ class Res16UNetBase(DerivedWeights):
 
     @ops.bound_stream
     def forward_wrapper(self, samples: List[torch.Tensor], targets, return_sp_mean_pos=False):
-        if (not self.training and 1 < len(samples) <= 16 and BATCH_EVAL
+        if (not self.training and 1 < len(samples) <= 16
                 and not any("elastic_coords" in t for t in targets)):
             return self._forward_wrapper_batched(samples, targets, return_sp_mean_pos)
         feats, pos, pos_wo = [], [], []

@@ -130,11 +130,6 @@ int sd3d_selftest_host(void) {
 }
 
 size_t sd3d_sort_ws_bytes(int64_t n) { return sort_ws_bytes(n); }
-int sd3d_sort_pairs_u64(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, uint32_t* vals_scratch,
-                        int64_t n, int begin_bit, int end_bit, void* ws, size_t ws_bytes, void* stream) {
-    if (n < 0 || begin_bit < 0 || end_bit > 64 || end_bit <= begin_bit) return sd3d_set_error(SD3D_ERR_ARG, "sort: bad arguments");
-    return sort_pairs_u64(keys_in, vals_in, keys_out, vals_out, n, begin_bit, end_bit, ws, ws_bytes, ST, vals_scratch, nullptr);
-}
 int sd3d_sort_pairs_u64_ex(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, uint32_t* vals_scratch,
                            int64_t n, int begin_bit, int end_bit, void* ws, size_t ws_bytes, int* landed_in_input, void* stream) {
     if (n < 0 || begin_bit < 0 || end_bit > 64 || end_bit <= begin_bit || !landed_in_input) return sd3d_set_error(SD3D_ERR_ARG, "sort: bad arguments");
@@ -320,21 +315,6 @@ int sd3d_linear_group(int n, const sd3d_linear_job* jobs, void* stream) {
 }
 
 size_t sd3d_pair_lists_ws_bytes(int K, int64_t M) { return pair_lists_ws_bytes(K, M); }
-int sd3d_pair_lists(const int32_t* nbr, int K, int64_t M, int64_t p_cap, int32_t* pos, int32_t* in_idx, int32_t* tile_k, void* ws,
-                    size_t ws_bytes, void* stream) {
-    return launch_pair_lists(nbr, K, M, p_cap, pos, in_idx, tile_k, ws, ws_bytes, ST);
-}
-int sd3d_pair_lists_batch(int n, const int32_t* const* nbr, const int* K, const int64_t* M, const int64_t* p_cap, int32_t* const* pos,
-                          int32_t* const* in_idx, int32_t* const* tile_k, void* ws, size_t ws_bytes, void* stream) {
-    return launch_pair_lists_batch(n, nbr, K, M, p_cap, pos, in_idx, tile_k, ws, ws_bytes, ST);
-}
-int sd3d_pair_conv(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* in_idx, const int32_t* tile_k,
-                   int64_t p_cap, const int32_t* pos, const float* wt, int K, int Cin, int Cout, int64_t M, const float* scale,
-                   const float* shift, const float* res, int ld_res, float* out, int ld_out, int act, float* part,
-                   size_t part_bytes, void* stream) {
-    return launch_pair_conv(in0, ld0, C0, in1, ld1, in_idx, tile_k, p_cap, pos, nullptr, 0, -1, nullptr, wt, K, Cin, Cout, M, scale, shift,
-                            res, ld_res, out, ld_out, act, part, part_bytes, ST);
-}
 int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* tables, void* ws, size_t ws_bytes, void* stream) {
     if (n > 0 && !tables) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_desc: tables is NULL");
     return launch_pair_lists_desc(n, tables, ws, ws_bytes, ST);
@@ -556,10 +536,6 @@ size_t sd3d_instance_boxes_ws_bytes(int n_inst) { return (size_t)(n_inst > 0 ? n
 int sd3d_instance_boxes(const float* points, int ld, int64_t N, const uint8_t* masks, int64_t mask_stride, int n_inst, int mode,
                         float* centers, float* sizes, void* ws, size_t ws_bytes, void* stream) {
     return launch_instance_boxes(points, ld, N, masks, mask_stride, n_inst, mode, centers, sizes, ws, ws_bytes, ST);
-}
-int sd3d_scale_shift_act(const float* x0, int ld0, int C0, const float* x1, int ld1, const float* scale, const float* shift, int act,
-                         int64_t M, int C, float* out, int ld_out, void* stream) {
-    return launch_scale_shift_act(x0, ld0, C0, x1, ld1, scale, shift, act, M, C, nullptr, 0, out, ld_out, ST);
 }
 int sd3d_scale_shift_act_add(const float* x0, int ld0, int C0, const float* x1, int ld1, const float* scale, const float* shift, int act,
                              int64_t M, int C, const float* add, int ld_add, float* out, int ld_out, void* stream) {

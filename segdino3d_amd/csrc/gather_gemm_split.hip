@@ -1,4 +1,4 @@
-// Gather-GEMM with fp32 products evaluated as split-bf16 MFMA sums (opt-in, SD3D_GEMM_MODE=bf16x3|bf16x6).
+// Gather-GEMM with fp32 products evaluated as split-bf16 MFMA sums (opt-in: the caller passes split weights; the bf16 decoder uses 1 term).
 //
 // On gfx950 the fp32-input MFMA runs at the fp32 VECTOR rate (157 TFLOP/s) while the bf16 MFMA is 16x
 // faster.  An fp32 number is the exact sum of three bf16 numbers (8 + 8 + 8 mantissa bits), and a

@@ -13,11 +13,7 @@ struct GGParams;
 // list building (pair_lists.hip)
 size_t pair_lists_ws_bytes(int K, int64_t M);
 size_t chain_lists_ws_bytes(int K, int64_t M);
-int launch_pair_lists(const int32_t* nbr, int K, int64_t M, int64_t p_cap, int32_t* pos, int32_t* in_idx, int32_t* tile_k,
-                      void* ws, size_t ws_bytes, hipStream_t st);
 int launch_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_t ws_bytes, hipStream_t st);
-int launch_pair_lists_batch(int n, const int32_t* const* nbr, const int* K, const int64_t* M, const int64_t* p_cap, int32_t* const* pos,
-                            int32_t* const* in_idx, int32_t* const* tile_k, void* ws, size_t ws_bytes, hipStream_t st);
 
 // pass 1 + pass 2 (pair_gemm.hip)
 int launch_pair_conv(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* in_idx, const int32_t* tile_k,

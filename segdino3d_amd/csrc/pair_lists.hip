@@ -22,81 +22,7 @@ __device__ static inline int block_excl_scan_256p(int v, int* total, int* smem4)
     return base + inc - v;
 }
 
-// ---- list building ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pair_count_kernel(const int32_t* __restrict__ nbr, int64_t M, int nblk,
-                                                         int32_t* __restrict__ blk_cnt) {
-    __shared__ int sm[4];
-    const int k = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
-    int c = 0;
-#pragma unroll
-    for (int i = 0; i < PL_ROWS / 256; ++i) {
-        const int64_t row = (int64_t)blk * PL_ROWS + i * 256 + tid;
-        const bool v = row < M && nbr[(int64_t)k * M + row] >= 0;
-        c += __popcll(__ballot(v));
-    }
-    if ((tid & 63) == 0) sm[tid >> 6] = c;
-    __syncthreads();
-    if (tid == 0) blk_cnt[(int64_t)k * nblk + blk] = sm[0] + sm[1] + sm[2] + sm[3];
-}
-
-// one workgroup per offset k: exclusive scan of its block counts (in place) and its total
-__global__ __launch_bounds__(256) void pair_scan_kernel(int32_t* __restrict__ blk_cnt, int nblk, int32_t* __restrict__ totals) {
-    __shared__ int sm[4];
-    const int k = blockIdx.x, tid = threadIdx.x;
-    int running = 0;
-    for (int base = 0; base < nblk; base += 256) {
-        const int i = base + tid;
-        const int v = i < nblk ? blk_cnt[(int64_t)k * nblk + i] : 0;
-        int total;
-        const int ex = block_excl_scan_256p(v, &total, sm);
-        if (i < nblk) blk_cnt[(int64_t)k * nblk + i] = running + ex;
-        running += total;
-    }
-    if (tid == 0) totals[k] = running;
-}
-
-__global__ __launch_bounds__(256) void pair_fill_kernel(const int32_t* __restrict__ nbr, int K, int64_t M, int nblk,
-                                                        const int32_t* __restrict__ blk_off, const int32_t* __restrict__ totals,
-                                                        int64_t p_cap, int32_t* __restrict__ pos, int32_t* __restrict__ in_idx,
-                                                        int32_t* __restrict__ tile_k) {
-    __shared__ int sm[4];
-    __shared__ int wcnt[4];
-    const int k = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // segment start of offset k = sum of the padded totals before it
-    int s = 0;
-    for (int kk = tid; kk < k; kk += 256) s += (totals[kk] + PT - 1) / PT * PT;
-    int seg;
-    block_excl_scan_256p(s, &seg, sm);
-    const int seg_len = (totals[k] + PT - 1) / PT * PT;
-    if (blk == 0) {
-        for (int t = tid; t < seg_len / PT; t += 256)
-            if ((int64_t)(seg / PT + t) * PT < p_cap) tile_k[seg / PT + t] = k;
-        if (k == K - 1 && tid == 0) {                          // number of real tiles, after the last slot
-            const int64_t end = (int64_t)seg + seg_len;
-            tile_k[p_cap / PT] = (int)((end < p_cap ? end : p_cap) / PT);
-        }
-    }
-    int base = seg + blk_off[(int64_t)k * nblk + blk];
-    const uint64_t lt = (1ull << lane) - 1ull;
-#pragma unroll 1
-    for (int i = 0; i < PL_ROWS / 256; ++i) {
-        const int64_t row = (int64_t)blk * PL_ROWS + i * 256 + tid;
-        const int id = row < M ? nbr[(int64_t)k * M + row] : -1;
-        const uint64_t bal = __ballot(id >= 0);
-        if (lane == 0) wcnt[wv] = __popcll(bal);
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wv; ++w) before += wcnt[w];
-        const int all = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
-        const int p = base + before + __popcll(bal & lt);
-        if (row < M) pos[(int64_t)k * M + row] = (id >= 0 && p < p_cap) ? p : -1;
-        if (id >= 0 && p < p_cap) in_idx[p] = id;
-        base += all;
-    }
-}
-
-// ---- the same three steps for SEVERAL tables in one launch set ---------------------------------------------------------------
+// ---- list building: count, scan, fill for SEVERAL tables in one launch set ----------------------------------------------------
 // A U-Net forward needs the lists of ~14 tables (one 5^3, five 3^3, four down, four up); built one by one that was 14 x (2
 // memsets + count + scan + fill) = 70 launches of a few microseconds each on the critical path of every scene.  Here a launch
 // covers all tables: a workgroup finds its (table, offset, row block) from the tables' cumulative block counts, and the fill
@@ -611,28 +537,9 @@ size_t pair_lists_ws_bytes(int K, int64_t M) {
     return m > rows ? m : rows;
 }
 
-// p_cap: capacity of in_idx in pairs (multiple of 128, >= pairs + K * 127); tile_k has p_cap / 128 + 1 entries
-// (the last one receives the number of real tiles).
-int launch_pair_lists(const int32_t* nbr, int K, int64_t M, int64_t p_cap, int32_t* pos, int32_t* in_idx, int32_t* tile_k,
-                      void* ws, size_t ws_bytes, hipStream_t st) {
-    if (K <= 0 || M <= 0) return SD3D_OK;
-    if (p_cap <= 0 || (p_cap % PT)) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists: p_cap must be a positive multiple of 128");
-    if (ws_bytes < pair_lists_ws_bytes(K, M)) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists: workspace too small");
-    const int nblk = (int)cdiv(M, PL_ROWS);
-    int32_t* blk_cnt = (int32_t*)ws;
-    int32_t* totals = blk_cnt + (int64_t)K * nblk;
-    if (hipMemsetAsync(in_idx, 0xFF, (size_t)p_cap * sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(tile_k, 0xFF, (size_t)(p_cap / PT + 1) * sizeof(int32_t), st) != hipSuccess)
-        return sd3d_set_error(SD3D_ERR_LAUNCH, "pair_lists: memset failed");
-    hipLaunchKernelGGL(pair_count_kernel, dim3(nblk, K), dim3(256), 0, st, nbr, M, nblk, blk_cnt);
-    hipLaunchKernelGGL(pair_scan_kernel, dim3(K), dim3(256), 0, st, blk_cnt, nblk, totals);
-    hipLaunchKernelGGL(pair_fill_kernel, dim3(nblk, K), dim3(256), 0, st, nbr, K, M, nblk, blk_cnt, totals, p_cap, pos, in_idx, tile_k);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
-}
-
 // n tables at once (n <= PL_MAX_TABLES); the tables' scratch sits back to back in ws (pair_lists_ws_bytes(K_i, M_i) bytes each,
-// rounded up to 256).  rlist / out_idx / the two centre slots of tile_k are optional products (see sd3d_pair_table_desc).
+// rounded up to 256).  p_cap: capacity of in_idx in pairs (multiple of 128, >= pairs + K * 127); tile_k has p_cap / 128 + 1 entries
+// (the last one receives the number of real tiles).  rlist / out_idx / the two centre slots of tile_k are optional products (see sd3d_pair_table_desc).
 int launch_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_t ws_bytes, hipStream_t st) {
     if (n <= 0) return SD3D_OK;
     if (n > PL_MAX_TABLES) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_batch: at most 16 tables per call");
@@ -723,15 +630,4 @@ int launch_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_
     if (rb > 0) hipLaunchKernelGGL(pair_rowlist_batch_kernel, dim3(rb), dim3(RL_ROWS), 0, st, b);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
-}
-
-int launch_pair_lists_batch(int n, const int32_t* const* nbr, const int* K, const int64_t* M, const int64_t* p_cap, int32_t* const* pos,
-                            int32_t* const* in_idx, int32_t* const* tile_k, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (n > PL_MAX_TABLES) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_batch: at most 16 tables per call");
-    sd3d_pair_table_desc d[PL_MAX_TABLES];
-    for (int i = 0; i < n; ++i) {
-        d[i].nbr = nbr[i]; d[i].pos = pos[i]; d[i].in_idx = in_idx[i]; d[i].tile_k = tile_k[i]; d[i].rlist = nullptr; d[i].out_idx = nullptr;
-        d[i].M = M[i]; d[i].p_cap = p_cap[i]; d[i].K = K[i]; d[i].center = -1; d[i].rl_stride = 0; d[i].meta = 0;
-    }
-    return launch_pair_lists_desc(n, d, ws, ws_bytes, st);
 }

@@ -181,11 +181,6 @@ int sd3d_bn_stats_running(const float* x, int ld, int64_t M, int C, float eps, f
     return SD3D_OK;
 }
 
-int sd3d_bn_stats(const float* x, int ld, int64_t M, int C, float eps, float* mean, float* var, float* rstd, void* ws, size_t ws_bytes,
-                  void* stream) {
-    return sd3d_bn_stats_running(x, ld, M, C, eps, mean, var, rstd, nullptr, nullptr, nullptr, 0.f, ws, ws_bytes, stream);
-}
-
 int sd3d_bn_apply(const float* x, int ld_x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* res,
                   int ld_res, int64_t M, int C, int act, float* y, int ld_y, void* stream) {
     if (M <= 0) return SD3D_OK;

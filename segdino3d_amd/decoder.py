@@ -197,9 +197,6 @@ class _TrainF:
 
 
 _F_TLS = threading.local()
-# SD3D_BATCH_DECODER=0: the decoder of a multi-scene evaluation forward runs scene by scene (A/B switch; default: the row-wise work of
-# all scenes in one pass, `ScanNetQueryDecoder._forward_batch`)
-BATCH_DECODER = os.environ.get("SD3D_BATCH_DECODER", "1") != "0"
 # SD3D_FUSED_DECODER=0: evaluation runs the op-by-op decoder of rounds 1-3 (`_forward_scene` / `_forward_batch`) instead of the
 # row-chain launches (`_forward_fused`); training always runs op by op (autograd nodes)
 # "auto" (default): a scene takes the row-chain path when it has more than FUSED_MIN_ROWS query rows (one query per superpoint,
@@ -628,12 +625,12 @@ class ScanNetQueryDecoder(DerivedWeights):
     def _batchable(self, x, queries, dinox_queries):
         """The batched path keeps every row on the kernel its scene's own forward would use (bit-identical outputs): it is taken when
         every scene gets the same tiling code (ops.dense_code) for every Linear of its three row families, the query tensors have few
-        hundred rows (grouped launches, fused Linear + LayerNorm) and no instrumentation / opt-in arithmetic mode is active;
-        anything else runs scene by scene."""
-        if self.training or not self.add_positional_embedding or not 2 <= len(x) <= 16 or not BATCH_DECODER or ops.GG_HOOK is not None:
+        hundred rows (grouped launches, fused Linear + LayerNorm) and no instrumentation is active; anything else runs scene by
+        scene."""
+        if self.training or not self.add_positional_embedding or not 2 <= len(x) <= 16 or ops.GG_HOOK is not None:
             return False                                        # (the batched launches hold at most SD3D_MAX_BATCH = 16 scenes)
         lim = ops.LINEAR_LN_MAX_ROWS
-        if lim <= 0 or ops.GEMM_MODE is not None or ops.GG_FORCE_NT is not None:
+        if lim <= 0:
             return False
         if not all(0 < q.shape[0] <= min(512, lim) for q in queries):
             return False
@@ -834,7 +831,7 @@ class ScanNetQueryDecoder(DerivedWeights):
         if FUSED_NARROW and rows <= FUSED_MIN_ROWS and FUSED_DECODER is not False:
             want, tile = True, 4
         return tile if (want and not self.training and self.add_positional_embedding and self.pos_type == "sine" and self.d_model == 256
-                and self.num_heads == 8 and self.num_queries == 0 and ops.GEMM_MODE is None and ops.GG_FORCE_NT is None
+                and self.num_heads == 8 and self.num_queries == 0
                 and self.in_channels % 16 == 0 and self.ffn_layers[0].net[0].out_features <= 1024
                 and self.ffn_layers[0].net[0].out_features % 16 == 0) else 0
 

@@ -264,6 +264,9 @@ def cores_for_rank(local_rank: int, gpu_nodes: Sequence[int], allowed: Sequence[
     return rest[i * per:(i + 1) * per] or rest
 
 
+SWITCH_INTERVAL = 2e-4      # seconds: the GIL slice of the pipelined runner's worker threads (Python's default is 5 ms)
+
+
 class PipelinedRunner:
     """Keeps `n_streams` scenes in flight on ONE GPU: each worker thread owns a HIP stream and runs whole
     eval forwards on it.  A single forward is a chain of ~500 dependent launches, many of them far too
@@ -282,9 +285,6 @@ class PipelinedRunner:
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.n)]
         self._threading = threading
-        self.switch_interval = float(os.environ.get("SD3D_SWITCH_INTERVAL", "2e-4"))
-        # one issuing thread at a time, handed over while a thread waits for the GPU (ops.wait_event)
-        self.use_baton = os.environ.get("SD3D_BATON", "1") != "0"
         self._keep = True
 
     def plan_batches(self, n_scenes: int):
@@ -325,7 +325,8 @@ class PipelinedRunner:
         results = [None] * len(scenes)
         errors = []
 
-        baton = self._threading.Lock() if (self.n > 1 and self.use_baton) else None
+        # one issuing thread at a time, handed over while a thread waits for the GPU (ops.wait_event)
+        baton = self._threading.Lock() if self.n > 1 else None
 
         def work(wid):
             from . import ops
@@ -362,7 +363,7 @@ class PipelinedRunner:
             threads = [self._threading.Thread(target=work, args=(w,)) for w in range(self.n)]
             # a worker that wakes from a host sync must not wait a whole 5 ms GIL slice behind its siblings
             prev_switch = sys.getswitchinterval()
-            sys.setswitchinterval(self.switch_interval)
+            sys.setswitchinterval(SWITCH_INTERVAL)
             try:
                 for t in threads:
                     t.start()
@@ -410,7 +411,7 @@ def _pipelined_run_stream(self, it, on_result=None):
     it = iter(it)
     take = self._threading.Lock()
     counter = [0]
-    baton = self._threading.Lock() if (self.n > 1 and self.use_baton) else None
+    baton = self._threading.Lock() if self.n > 1 else None
 
     def work(wid):
         from . import ops

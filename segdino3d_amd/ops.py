@@ -20,9 +20,7 @@ ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2, "sigmoid": 3}
 # Optional instrumentation for bench.py: an object with before(meta: dict) / after() called around
 # every gather_gemm launch on the current stream (meta: K, Cin, Cout, M, nbr tensor or None).
 GG_HOOK = None
-# Debug / tuning override of the gather_gemm tiling heuristic (see csrc/gather_gemm.hip launch codes).
 import os as _os
-GG_FORCE_NT = int(_os.environ["SD3D_GG_NT"]) if _os.environ.get("SD3D_GG_NT") else None
 
 
 _STREAM_TLS = threading.local()
@@ -122,24 +120,13 @@ class HostRead:
     __slots__ = ("buf", "event")
 
     def __init__(self, dev_tensor: torch.Tensor):
-        if BLOCKING_SYNC:
-            self.buf, self.event = dev_tensor.cpu(), None
-            return
         self.buf = torch.empty(dev_tensor.shape, dtype=dev_tensor.dtype, pin_memory=True)
         self.buf.copy_(dev_tensor, non_blocking=True)
-        self.event = torch.cuda.Event(blocking=BLOCKING_EVENTS)
-        self.event.record()
+        self.event = stream_event()
 
     def wait(self):
-        if self.event is not None:
-            wait_event(self.event)
+        wait_event(self.event)
         return self.buf
-
-
-# hipEventBlockingSync: a thread waiting for its scene sleeps instead of spinning on a core (8 ranks x 4 scene threads
-# share one host in the multi-GPU runs).  SD3D_SPIN_EVENTS=1 restores spinning waits.
-BLOCKING_EVENTS = _os.environ.get("SD3D_SPIN_EVENTS") != "1"
-BLOCKING_SYNC = _os.environ.get("SD3D_BLOCKING_SYNC") == "1"      # A/B switch: blocking .cpu() / event.synchronize()
 
 
 _BATON_TLS = threading.local()
@@ -153,7 +140,6 @@ def set_baton(lock):
 
 import collections as _collections
 _BATON_WAITERS = _collections.deque()                          # append / pop are atomic: threads that want the baton back
-BATON_YIELD = _os.environ.get("SD3D_BATON_YIELD", "1") != "0"
 
 
 def baton_yield():
@@ -161,7 +147,7 @@ def baton_yield():
     thread has finished waiting for the GPU and wants to issue its next (short) phase, let it go first - its
     stream is empty, ours still has milliseconds of queued work."""
     baton = getattr(_BATON_TLS, "lock", None)
-    if baton is not None and BATON_YIELD and _BATON_WAITERS:
+    if baton is not None and _BATON_WAITERS:
         import time
         baton.release()
         time.sleep(0)
@@ -183,9 +169,6 @@ def wait_event(ev):
             baton.acquire()
             _BATON_WAITERS.pop()
         return
-    if BLOCKING_SYNC:
-        ev.synchronize()
-        return
     spins = 0
     while not ev.query():
         spins += 1
@@ -193,7 +176,9 @@ def wait_event(ev):
 
 
 def stream_event():
-    ev = torch.cuda.Event(blocking=BLOCKING_EVENTS)
+    # hipEventBlockingSync: a thread waiting for its scene sleeps instead of spinning on a core (8 ranks x 4 scene threads
+    # share one host in the multi-GPU runs)
+    ev = torch.cuda.Event(blocking=True)
     ev.record()
     return ev
 
@@ -213,7 +198,7 @@ class Workspace:
 
 class _PerThread:
     """One scratch buffer per (host thread, HIP stream): each worker thread of the pipelined runner drives its own stream, a
-    batched forward additionally fans its scenes' decoders out over side streams (`use_stream`), and scratch must never be
+    scene's sparse maps additionally build some of their tables on a side stream (`use_stream`), and scratch must never be
     shared between streams."""
 
     def __init__(self):
@@ -590,13 +575,8 @@ def pool_superpoints(feat, C, inverse, icoords, voxel_size, sorted_idx, start, S
 # --------------------------------------------------------------------------------------------
 # gather-GEMM
 # --------------------------------------------------------------------------------------------
-# Opt-in arithmetic mode of the lock-step gather-GEMM (csrc/gather_gemm_split.hip): None = exact fp32 MFMA
-# (default, the mode every parity claim and the bench headline are made in), "bf16x3" / "bf16x6" = fp32
-# products evaluated as 3 / 6 bf16 MFMA products with fp32 accumulation.
-GEMM_MODE = _os.environ.get("SD3D_GEMM_MODE") or None
-if GEMM_MODE not in (None, "bf16x3", "bf16x6"):
-    raise ValueError(f"SD3D_GEMM_MODE must be bf16x3 or bf16x6, got {GEMM_MODE!r}")
-SPLIT_MIN_ROWS = 2048          # below this the launch is latency-bound and stays on the fp32 kernel
+# The gather-GEMM is exact fp32 MFMA unless the bf16 decoder scope or an explicit `wt_split` asks for the split-bf16 kernel
+# (csrc/gather_gemm_split.hip: fp32 products evaluated as 1 / 3 / 6 bf16 MFMA products with fp32 accumulation).
 _SPLIT_CACHE = _collections_od()
 _BF16_TLS = threading.local()
 # projections of fewer rows are launch-latency bound and measured FASTER on the exact fp32 small-M kernel (200-query decoder:
@@ -841,7 +821,7 @@ def linear_group(jobs, force_small=False):
     force_small: the rows are several scenes' few-hundred-row tensors back to back - always the group kernel."""
     global _LINEAR_JOB_DT
     import numpy as np
-    if GG_HOOK is not None or GEMM_MODE is not None or GG_FORCE_NT is not None:
+    if GG_HOOK is not None:
         if force_small:
             return [gather_gemm(x, w, x2=x2, shift=b, act=act, res=res, nt=-1, exact=True) for (x, w, b, act, res, x2) in jobs]
         return [gather_gemm(x, w, x2=x2, shift=b, act=act, res=res) for (x, w, b, act, res, x2) in jobs]
@@ -934,13 +914,12 @@ def gather_gemm(x, wt, nbr=None, x2=None, scale=None, shift=None, res=None, act=
     PairLists) a sparse convolution runs pair-major (pair_conv); `density` is informational (kept for callers that
     pass SceneMaps.conv_table(...) as keyword arguments)."""
     if nbr is None and pairs is None and GG_HOOK is None and scale is None and out is None and wt_split is None and nt == 0 \
-            and M is None and GEMM_MODE is None and GG_FORCE_NT is None and wt.dim() == 2 and not getattr(_BF16_TLS, "on", False):
+            and M is None and wt.dim() == 2 and not getattr(_BF16_TLS, "on", False):
         return _dense_linear(x, wt, x2, shift, res, act)
     lib = _lib.load()
     if wt.dim() == 2:
         wt = wt.unsqueeze(0)
-    if pairs is not None and PAIR_CONV and nt == 0 and wt_split is None and GEMM_MODE is None and GG_FORCE_NT is None \
-            and wt.shape[1] % 4 == 0:
+    if pairs is not None and PAIR_CONV and nt == 0 and wt_split is None and wt.shape[1] % 4 == 0:
         return pair_conv(x, wt, pairs, x2=x2, scale=scale, shift=shift, res=res, act=act, out=out)
     K, Cout, Cin = wt.shape
     p0, ld0 = _rows(x, "x")
@@ -967,15 +946,7 @@ def gather_gemm(x, wt, nbr=None, x2=None, scale=None, shift=None, res=None, act=
         terms = {1: 1, 2: 3, 3: 6}[wt_split.shape[0]]
     elif nbr is None and not exact and bf16_decoder_active() and M >= BF16_MIN_ROWS and Cin % 32 == 0 and (x2 is None or C0 % 32 == 0):
         terms = 1                                  # bf16 decoder: plain bf16 operands (weights rounded once, cached)
-    elif GEMM_MODE is not None and nt == 0 and M >= SPLIT_MIN_ROWS and Cin % 32 == 0:
-        terms = 3 if GEMM_MODE == "bf16x3" else 6
-    if terms and wt_split is None:
         wt_split = _cached_split(wt, terms)
-    if GG_FORCE_NT is not None and nt == 0:
-        sub = (Cout + 31) // 32
-        eff = GG_FORCE_NT if GG_FORCE_NT > 0 else (-GG_FORCE_NT - 10 if GG_FORCE_NT <= -11 else 1)
-        if sub % eff == 0:
-            nt = GG_FORCE_NT
     hook = GG_HOOK
     if hook is not None:
         hook.before(dict(K=K, Cin=Cin, Cout=Cout, M=M, nbr=nbr))
@@ -1027,14 +998,14 @@ LINEAR_LN_MAX_ROWS = int(_os.environ.get("SD3D_LINEAR_LN_MAX_ROWS", "512"))     
 
 def linear_layernorm(x, weight, bias, ln_weight, ln_bias, res=None, act=None, eps=1e-5, max_rows=None):
     """act(LayerNorm(x @ weight^T + bias + res) * ln_weight + ln_bias).  Few rows and a 256-wide output (the decoder's query tensors):
-    one fused launch (sd3d_linear_layernorm); anything else - or an instrumented / split-precision run - is the projection followed
+    one fused launch (sd3d_linear_layernorm); anything else - or an instrumented run - is the projection followed
     by the LayerNorm kernel."""
     M, Cin = x.shape
     # (measured at 200 rows: Cin = 256 14.5 us fused vs 21.9 us in two launches; Cin = 1024 39.9 vs 22.2 - a 16-row workgroup walks
     # the whole contraction alone - so long contractions keep the two launches)
     # max_rows: the rows of several scenes of <= LINEAR_LN_MAX_ROWS rows each take the fused launch too (16-row workgroups:
     # per row the same arithmetic whatever M is - the batched decoder must not switch kernels with the batch size)
-    if (M > (LINEAR_LN_MAX_ROWS if max_rows is None else max_rows) or Cin > 512 or weight.shape[0] != 256 or Cin % 16 or GG_HOOK is not None or GEMM_MODE is not None or GG_FORCE_NT is not None
+    if (M > (LINEAR_LN_MAX_ROWS if max_rows is None else max_rows) or Cin > 512 or weight.shape[0] != 256 or Cin % 16 or GG_HOOK is not None
             or not weight.is_contiguous() or (res is not None and res.stride(1) != 1)):
         return layernorm(gather_gemm(x, weight, shift=bias, res=res), ln_weight, ln_bias, act=act, eps=eps)
     lib = _lib.load()

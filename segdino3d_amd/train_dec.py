@@ -30,9 +30,8 @@ _IDENTITY = {}
 # precise fp32 backward is the default and the autocast-faithful one is the opt-in.
 import os as _os
 BF16_BACKWARD = _os.environ.get("SD3D_BF16_BACKWARD", "0") == "1"
-BATCH_WT = _os.environ.get("SD3D_BATCH_WT", "1") != "0"
-# rows up to which a Linear's weight gradient takes the one-launch kernel (sd3d_linear_wgrad); 0: always the pair-list kernel + reduce (rounds 2 - 5)
-LINEAR_WGRAD_ROWS = int(_os.environ.get("SD3D_LINEAR_WGRAD_ROWS", "8192"))
+# rows up to which a Linear's weight gradient takes the one-launch kernel (sd3d_linear_wgrad); more rows: the pair-list kernel + reduce
+LINEAR_WGRAD_ROWS = 8192
 
 
 def _identity_pairs(n_rows: int, device):
@@ -179,13 +178,7 @@ class _Linear(torch.autograd.Function):
         g = act_backward(dy.contiguous(), ref, ctx.act, c_pad)                  # [M, c_pad], zero beyond cout
         dx = dx2 = dw = db = dres = None
         if ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[5]):
-            if BATCH_WT:
-                wt = _WT.get(w)                                 # [cin, c_pad], zero beyond cout
-            elif c_pad == cout:
-                wt = w.detach().t().contiguous()
-            else:
-                wt = torch.zeros(cin, c_pad, dtype=torch.float32, device=w.device)
-                wt[:, :cout] = w.detach().t()
+            wt = _WT.get(w)                                     # [cin, c_pad], zero beyond cout
             if ctx.bf16_bwd and c_pad % 32 == 0:
                 dxa = ops.gather_gemm(g, wt, wt_split=ops.split_weights(wt.unsqueeze(0), 1))     # bf16 operands, fp32 accumulation
             else:
