@@ -776,6 +776,46 @@ int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1
                             const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0, float* dq1, int ld_dq1, float* dk0,
                             int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Parameter update of a training iteration (csrc/optim.hip; segdino3d_amd/optim.py builds the tables): gradient-norm clipping, the AdamW
+ * step and the weight EMA of train_engine_3d.py:99-120 / ema_utils.py:34-38, each one launch over ALL parameter tensors.
+ *
+ * Tensor table: one sd3d_mt_tensor per parameter that has a gradient this step.  fp32, contiguous; p / m / v / ema / g must be 4-byte aligned,
+ * 16-byte aligned ones take the 16-byte path (an unaligned g alone only makes its loads scalar).  The scalars are this tensor's own (torch
+ * keeps `step` per parameter, the groups have their own lr), folded by the caller in double precision and rounded once to float:
+ *   decay = 1 - lr * weight_decay, step_size = lr / (1 - beta1^t), rsqrt_bc2 = 1 / sqrt(1 - beta2^t), t = this tensor's step AFTER the increment.
+ * Chunk list: chunk c covers elements [index * SD3D_MT_CHUNK, min(n, (index + 1) * SD3D_MT_CHUNK)) of tensors[tensor]; every element of
+ * every tensor must be in exactly one chunk (the entry points check that chunks lie inside their tensors, not that they cover them).
+ *
+ * Both tables are HOST arrays.  A call copies them into ws with hipMemcpyAsync on `stream` and returns without waiting: keep them unchanged
+ * until the stream has passed the copy, and keep them in pinned memory if the call is not to block.  table_resident = 1 skips the copy: ws
+ * still holds this very table from the previous sd3d_mt_* call (same ws, same stream).  ws: sd3d_mt_ws_bytes, 16-byte aligned, device.
+ *
+ *   sd3d_mt_grad_norm: norm_out[0] = total_norm = ||all g||_2, norm_out[1] = clip_coef = min(1, max_norm / (total_norm + 1e-6)) (device floats).
+ *                      One partial sum per chunk, added in chunk order in double precision: no atomics, the same bits in every run.
+ *   sd3d_mt_adamw:     g' = g * *clip_coef (clip_coef = null: g' = g; g itself is never written);  p *= decay;  m += (1 - beta1) (g' - m);
+ *                      v = beta2 v + (1 - beta2) g'^2;  p -= step_size * m / (sqrt(v) * rsqrt_bc2 + eps);  and where ema is not null
+ *                      ema = (1 - ema_decay) p + ema_decay ema with the new p, in the same pass.
+ *   sd3d_mt_ema:       ema = (1 - ema_decay) p + ema_decay ema alone (tensors whose ema is null are skipped; g, m, v are not read).
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_MT_CHUNK 4096
+typedef struct sd3d_mt_tensor {
+    float *p, *m, *v, *ema;                         /* parameter, exp_avg, exp_avg_sq, EMA shadow (null: none) */
+    const float* g;                                 /* gradient */
+    int64_t n;                                      /* elements */
+    float decay, step_size, rsqrt_bc2;
+    float one_minus_beta1, beta2, one_minus_beta2, eps;
+    float ema_decay, one_minus_ema_decay, pad_;
+} sd3d_mt_tensor;
+typedef struct sd3d_mt_chunk { int32_t tensor, index; } sd3d_mt_chunk;
+size_t sd3d_mt_ws_bytes(int n_tensors, int64_t n_chunks);
+int sd3d_mt_grad_norm(const sd3d_mt_tensor* tensors, int n_tensors, const sd3d_mt_chunk* chunks, int64_t n_chunks, float max_norm,
+                      float* norm_out, void* ws, size_t ws_bytes, void* stream);
+int sd3d_mt_adamw(const sd3d_mt_tensor* tensors, int n_tensors, const sd3d_mt_chunk* chunks, int64_t n_chunks, const float* clip_coef,
+                  int table_resident, void* ws, size_t ws_bytes, void* stream);
+int sd3d_mt_ema(const sd3d_mt_tensor* tensors, int n_tensors, const sd3d_mt_chunk* chunks, int64_t n_chunks, int table_resident, void* ws,
+                size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,10 @@ SIGNATURES = {
                                      _p, _i, _p, _z, _p]),
     "sd3d_semantic_loss_ws_bytes": (_z, [_i]),
     "sd3d_semantic_loss": (_i, [_p, _i, _i, _i, _i, _p, _i, _f, _p, _i, _p, _p, _z, _p]),
+    "sd3d_mt_ws_bytes": (_z, [_i, _l]),
+    "sd3d_mt_grad_norm": (_i, [_p, _i, _p, _l, _f, _p, _p, _z, _p]),
+    "sd3d_mt_adamw": (_i, [_p, _i, _p, _l, _p, _i, _p, _z, _p]),
+    "sd3d_mt_ema": (_i, [_p, _i, _p, _l, _i, _p, _z, _p]),
 }
 
 
