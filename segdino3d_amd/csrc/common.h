@@ -66,3 +66,17 @@ __device__ static inline uint32_t hash_u64(uint64_t k) {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------ internal launchers called across translation units
+// Declared here once, with names; the defining file includes this header too, so a call and its definition cannot drift apart.
+// sort_scan.hip
+size_t sort_ws_bytes(int64_t n);
+int sort_pairs_u64(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n, int begin_bit, int end_bit,
+                   void* ws, size_t ws_bytes, hipStream_t st, uint32_t* vals_scratch, int* landed_in_input);
+size_t scan_ws_bytes(int64_t n);
+int scan_exclusive_i32(const int* in, int* out, int64_t n_cap, const int* n_dev, int* total_dev, void* ws, size_t ws_bytes, hipStream_t st);
+int launch_i64_to_sortkey_checked_max(const int64_t* x, int64_t n, uint64_t* keys, int bits, int32_t* flag, int value, int32_t* max_out,
+                                      hipStream_t st, uint64_t add);
+// dense.hip
+int launch_scale_shift_act(const float* x0, int ld0, int C0, const float* x1, int ld1, const float* scale, const float* shift, int act,
+                           int64_t M, int C, const float* add, int ld_add, float* out, int ld_out, hipStream_t st);

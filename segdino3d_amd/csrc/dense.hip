@@ -64,8 +64,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
 }
 
-int launch_layernorm(const float* x, int ld_x, const float* res, int ld_res, const float* w, const float* b, float eps,
-                     int64_t M, int D, float* out, int ld_out, int act, hipStream_t st) {
+extern "C" int sd3d_layernorm(const float* x, int ld_x, const float* res, int ld_res, const float* w, const float* b, float eps, int64_t M, int D,
+                              float* out, int ld_out, int act, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (M <= 0) return SD3D_OK;
     if ((D & 3) || D > 1024 || (ld_x & 3) || (ld_out & 3) || (res && (ld_res & 3)))
         return sd3d_set_error(SD3D_ERR_ARG, "layernorm: D must be a multiple of 4 and <= 1024, strides multiples of 4");
@@ -216,8 +217,9 @@ __global__ __launch_bounds__(256) void linear_layernorm_kernel(const float* __re
     }
 }
 
-int launch_linear_layernorm(const float* x, int ld_x, int64_t M, int Cin, const float* wt, int Cout, const float* bias, const float* res,
-                            int ld_res, const float* g, const float* b, float eps, int act, float* out, int ld_out, hipStream_t st) {
+extern "C" int sd3d_linear_layernorm(const float* x, int ld_x, int64_t M, int Cin, const float* wt, int Cout, const float* bias, const float* res,
+                                     int ld_res, const float* g, const float* b, float eps, int act, float* out, int ld_out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (M <= 0) return SD3D_OK;
     if (Cout != 256 || Cin <= 0 || (Cin & 15) || (ld_x & 3) || act < 0 || act > 1)
         return sd3d_set_error(SD3D_ERR_ARG, "linear_layernorm: Cout must be 256, Cin a multiple of 16, ld_x a multiple of 4, act 0 / 1");
@@ -259,14 +261,25 @@ __global__ __launch_bounds__(256) void sine_pe_kernel(const float* __restrict__ 
     out[r * ld_out + c] = y;
 }
 
-int launch_sine_pe(const float* xyz, int ld_xyz, int64_t n, const float* rng, const float* dim_t, const int8_t* axis, int d_pos,
-                   const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out, int ld_out, const int32_t* row_scene,
-                   hipStream_t st) {
+static int launch_sine_pe(const float* xyz, int ld_xyz, int64_t n, const float* rng, const float* dim_t, const int8_t* axis, int d_pos,
+                          const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out, int ld_out, const int32_t* row_scene,
+                          hipStream_t st) {
     if (n <= 0) return SD3D_OK;
     hipLaunchKernelGGL(sine_pe_kernel, dim3((unsigned)cdiv(n * d_pos, 256)), dim3(256), 0, st, xyz, ld_xyz, n, rng, dim_t, axis,
                        d_pos, mod_num, ld_num, mod_den, ld_den, out, ld_out, row_scene);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_sine_pe(const float* xyz, int ld_xyz, int64_t n, const float* range, const float* dim_t, const int8_t* axis, int d_pos,
+                            const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out, int ld_out, void* stream) {
+    if (mod_num && !mod_den) return sd3d_set_error(SD3D_ERR_ARG, "sine_pe: mod_den missing");
+    return launch_sine_pe(xyz, ld_xyz, n, range, dim_t, axis, d_pos, mod_num, ld_num, mod_den, ld_den, out, ld_out, nullptr, (hipStream_t)stream);
+}
+extern "C" int sd3d_sine_pe_rows(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* dim_t,
+                                 const int8_t* axis, int d_pos, const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out,
+                                 int ld_out, void* stream) {
+    if (mod_num && !mod_den) return sd3d_set_error(SD3D_ERR_ARG, "sine_pe_rows: mod_den missing");
+    return launch_sine_pe(xyz, ld_xyz, n, ranges, dim_t, axis, d_pos, mod_num, ld_num, mod_den, ld_den, out, ld_out, row_scene, (hipStream_t)stream);
 }
 
 // PositionEmbeddingCoordsSine.get_fourier_embeddings (utils.py:107-142, pos_type = "fourier"): the normalised coordinates
@@ -293,14 +306,22 @@ __global__ __launch_bounds__(256) void fourier_pe_kernel(const float* __restrict
     out[r * ld_out + dh + c] = cosf(acc);
 }
 
-int launch_fourier_pe(const float* xyz, int ld_xyz, int64_t n, const float* rng, const float* gauss_b, int ld_b, int d_pos, float* out,
-                      int ld_out, const int32_t* row_scene, hipStream_t st) {
+static int launch_fourier_pe(const float* xyz, int ld_xyz, int64_t n, const float* rng, const float* gauss_b, int ld_b, int d_pos, float* out,
+                             int ld_out, const int32_t* row_scene, hipStream_t st) {
     if (n <= 0) return SD3D_OK;
     if (d_pos <= 0 || (d_pos & 1)) return sd3d_set_error(SD3D_ERR_ARG, "fourier_pe: d_pos must be even");
     hipLaunchKernelGGL(fourier_pe_kernel, dim3((unsigned)cdiv(n * (d_pos / 2), 256)), dim3(256), 0, st, xyz, ld_xyz, n, rng, gauss_b, ld_b,
                        d_pos, out, ld_out, row_scene);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_fourier_pe(const float* xyz, int ld_xyz, int64_t n, const float* range, const float* gauss_b, int ld_b, int d_pos, float* out,
+                               int ld_out, void* stream) {
+    return launch_fourier_pe(xyz, ld_xyz, n, range, gauss_b, ld_b, d_pos, out, ld_out, nullptr, (hipStream_t)stream);
+}
+extern "C" int sd3d_fourier_pe_rows(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* gauss_b,
+                                    int ld_b, int d_pos, float* out, int ld_out, void* stream) {
+    return launch_fourier_pe(xyz, ld_xyz, n, ranges, gauss_b, ld_b, d_pos, out, ld_out, row_scene, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -587,7 +608,7 @@ __global__ __launch_bounds__(256) void attention_merge_batch_kernel(const AttnBa
     attention_merge_body(b.s[si], blockIdx.x - b.tile0[si]);
 }
 
-size_t attention_ws_bytes(int Lq, int H) { return (size_t)cdiv(Lq, 32) * H * 8 * (64 + 1024) * sizeof(float); }
+extern "C" size_t sd3d_attention_ws_bytes(int Lq, int H) { return (size_t)cdiv(Lq, 32) * H * 8 * (64 + 1024) * sizeof(float); }
 
 // waves per workgroup and key split of one attention (Lq queries, Lk keys, H heads) given `ws_bytes` of split workspace
 static void attention_config(int Lq, int Lk, int H, bool have_ws, size_t ws_bytes, int* nw_out, int* ks_out) {
@@ -611,7 +632,7 @@ static void attention_config(int Lq, int Lk, int H, bool have_ws, size_t ws_byte
     *nw_out = nw; *ks_out = ks;
 }
 
-int launch_attention(const AttnParams& p_in, int nsrc, void* ws, size_t ws_bytes, hipStream_t st, bool merge = true) {
+static int launch_attention(const AttnParams& p_in, int nsrc, void* ws, size_t ws_bytes, hipStream_t st, bool merge = true) {
     AttnParams p = p_in;
     if (p.Lq <= 0 || p.Lk <= 0) return sd3d_set_error(SD3D_ERR_ARG, "attention: empty query or key set");
     for (int s = 0; s < nsrc; ++s)
@@ -634,12 +655,12 @@ int launch_attention(const AttnParams& p_in, int nsrc, void* ws, size_t ws_bytes
 
 // n <= SD3D_MAX_BATCH independent attentions (same heads, scale, sources, arithmetic type) in one launch - when every scene's own launch
 // would use the same number of waves per workgroup; otherwise one launch per scene.  Scene i's split workspace is
-// attention_ws_bytes(Lq_i, H) bytes, back to back in ws.
+// sd3d_attention_ws_bytes(Lq_i, H) bytes, back to back in ws.
 // ksplit_out / part_off_out (host arrays of n entries, optional): the launch then STOPS after the key-split pass - scene i's rows are
 // final in its `out` where ksplit_out[i] == 1 and otherwise wait as partial softmax states at ws + part_off_out[i] floats for the
 // consumer that combines them (rowchain.hip MERGE: the expression of attention_merge_body).
-int launch_attention_batch(int n, const AttnParams* jobs, int nsrc, void* ws, size_t ws_bytes, hipStream_t st, int32_t* ksplit_out = nullptr,
-                           int64_t* part_off_out = nullptr) {
+static int launch_attention_batch(int n, const AttnParams* jobs, int nsrc, void* ws, size_t ws_bytes, hipStream_t st, int32_t* ksplit_out = nullptr,
+                                  int64_t* part_off_out = nullptr) {
     if (n <= 0) return SD3D_OK;
     const bool merge = ksplit_out == nullptr;
     if (n > SD3D_MAX_BATCH) return sd3d_set_error(SD3D_ERR_ARG, "attention_batch: at most 16 scenes per call");
@@ -653,7 +674,7 @@ int launch_attention_batch(int n, const AttnParams* jobs, int nsrc, void* ws, si
         if (p.Lq <= 0 || p.Lk <= 0) return sd3d_set_error(SD3D_ERR_ARG, "attention_batch: empty query or key set");
         for (int s = 0; s < nsrc; ++s)
             if ((p.ldq[s] & 3) || (p.ldk[s] & 3)) return sd3d_set_error(SD3D_ERR_ARG, "attention_batch: q/k strides must be multiples of 4");
-        const size_t need = attention_ws_bytes(p.Lq, p.H);
+        const size_t need = sd3d_attention_ws_bytes(p.Lq, p.H);
         const bool have = ws != nullptr && off + need <= ws_bytes;
         int nw, ks;
         attention_config(p.Lq, p.Lk, p.H, have, need, &nw, &ks);
@@ -674,7 +695,7 @@ int launch_attention_batch(int n, const AttnParams* jobs, int nsrc, void* ws, si
     b.tile0[n] = tiles;
     if (!same) {                                               // different workgroup shapes: each scene its own launch (same results)
         for (int i = 0; i < n; ++i) {
-            const int rc = launch_attention(jobs[i], nsrc, b.s[i].part, b.s[i].part ? attention_ws_bytes(jobs[i].Lq, jobs[i].H) : 0, st, merge);
+            const int rc = launch_attention(jobs[i], nsrc, b.s[i].part, b.s[i].part ? sd3d_attention_ws_bytes(jobs[i].Lq, jobs[i].H) : 0, st, merge);
             if (rc != SD3D_OK) return rc;
         }
         return SD3D_OK;
@@ -690,6 +711,67 @@ int launch_attention_batch(int n, const AttnParams* jobs, int nsrc, void* ws, si
     if (ks_max > 1 && merge) hipLaunchKernelGGL(attention_merge_batch_kernel, dim3((unsigned)tiles, (unsigned)b.s[0].H), dim3(256), 0, st, b);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+
+// The caller's part of AttnParams; ksplit and part are the launcher's to choose.
+static AttnParams attn_params(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                              const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale, float* out, int ldo,
+                              int bf16, float* lse) {
+    AttnParams p;
+    p.q[0] = q0; p.ldq[0] = ldq0; p.q[1] = q1; p.ldq[1] = ldq1;
+    p.k[0] = k0; p.ldk[0] = ldk0; p.k[1] = k1; p.ldk[1] = ldk1;
+    p.v = v; p.ldv = ldv; p.bits = mask_bits; p.nwords = (Lk + 31) / 32; p.out = out; p.ldo = ldo;
+    p.Lq = Lq; p.Lk = Lk; p.H = H; p.scale = scale; p.ksplit = 1; p.part = nullptr; p.bf16 = bf16 ? 1 : 0; p.lse = lse;
+    return p;
+}
+static int attention_one(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                         const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale, float* out, int ldo,
+                         int bf16, float* lse, void* ws, size_t ws_bytes, void* stream) {
+    if ((q1 == nullptr) != (k1 == nullptr)) return sd3d_set_error(SD3D_ERR_ARG, "attention: q1 and k1 must be given together");
+    const AttnParams p = attn_params(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, bf16, lse);
+    return launch_attention(p, q1 ? 2 : 1, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int sd3d_attention(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                              const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale, float* out, int ldo,
+                              void* ws, size_t ws_bytes, void* stream) {
+    return attention_one(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, 0, nullptr, ws, ws_bytes, stream);
+}
+extern "C" int sd3d_attention_bf16(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                                   const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale, float* out, int ldo,
+                                   void* ws, size_t ws_bytes, void* stream) {
+    return attention_one(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, 1, nullptr, ws, ws_bytes, stream);
+}
+extern "C" int sd3d_attention_lse(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                                  const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale, float* out, int ldo,
+                                  float* lse, void* ws, size_t ws_bytes, void* stream) {
+    return attention_one(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, 0, lse, ws, ws_bytes, stream);
+}
+extern "C" int sd3d_attention_lse_bf16(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                                       const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale, float* out,
+                                       int ldo, float* lse, void* ws, size_t ws_bytes, void* stream) {
+    return attention_one(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, 1, lse, ws, ws_bytes, stream);
+}
+
+static int attention_batch_impl(int n, const sd3d_attn_job* jobs, int H, float scale, int bf16, void* ws, size_t ws_bytes, void* stream,
+                                int32_t* ksplit_out, int64_t* part_off_out) {
+    if (n <= 0) return SD3D_OK;
+    if (n > SD3D_MAX_BATCH || !jobs) return sd3d_set_error(SD3D_ERR_ARG, "attention_batch: 1..16 jobs");
+    AttnParams p[SD3D_MAX_BATCH];
+    const bool two = jobs[0].q1 != nullptr;
+    for (int i = 0; i < n; ++i) {
+        const sd3d_attn_job& j = jobs[i];
+        if ((j.q1 == nullptr) != (j.k1 == nullptr) || (j.q1 != nullptr) != two) return sd3d_set_error(SD3D_ERR_ARG, "attention_batch: all jobs need the same sources");
+        p[i] = attn_params(j.q0, j.ldq0, j.q1, j.ldq1, j.k0, j.ldk0, j.k1, j.ldk1, j.v, j.ldv, j.mask_bits, j.Lq, j.Lk, H, scale, j.out, j.ldo, bf16, nullptr);
+    }
+    return launch_attention_batch(n, p, two ? 2 : 1, ws, ws_bytes, (hipStream_t)stream, ksplit_out, part_off_out);
+}
+extern "C" int sd3d_attention_batch(int n, const sd3d_attn_job* jobs, int H, float scale, int bf16, void* ws, size_t ws_bytes, void* stream) {
+    return attention_batch_impl(n, jobs, H, scale, bf16, ws, ws_bytes, stream, nullptr, nullptr);
+}
+extern "C" int sd3d_attention_batch_parts(int n, const sd3d_attn_job* jobs, int H, float scale, int bf16, void* ws, size_t ws_bytes,
+                                          int32_t* ksplit_out_host, int64_t* part_off_out_host, void* stream) {
+    if (!ksplit_out_host || !part_off_out_host) return sd3d_set_error(SD3D_ERR_ARG, "attention_batch_parts: output arrays missing");
+    return attention_batch_impl(n, jobs, H, scale, bf16, ws, ws_bytes, stream, ksplit_out_host, part_off_out_host);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -744,8 +826,9 @@ __global__ __launch_bounds__(256) void mask_bits_batch_kernel(const MaskBitsBatc
     for (int k = 1; k < b.n; ++k) if ((int)blockIdx.x >= b.row0[k]) si = k;
     mask_bits_body(b.logits[si], b.ld[si], b.S[si], thr, b.bits[si], b.nwords[si], blockIdx.x - b.row0[si], open_s);
 }
-int launch_mask_bits_batch(int n, const float* const* logits, const int* ld, const int64_t* Q, const int* S, uint32_t* const* bits,
-                           const int* nwords, float thr, hipStream_t st) {
+extern "C" int sd3d_mask_bits_batch(int n, const float* const* logits, const int* ld, const int64_t* Q, const int* S, uint32_t* const* bits,
+                                    const int* nwords, float thr, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     if (n > SD3D_MAX_BATCH) return sd3d_set_error(SD3D_ERR_ARG, "mask_bits_batch: at most 16 scenes per call");
     MaskBitsBatch b;
@@ -763,7 +846,8 @@ int launch_mask_bits_batch(int n, const float* const* logits, const int* ld, con
     return SD3D_OK;
 }
 
-int launch_mask_bits(const float* logits, int ld, int64_t Q, int S, float thr, uint32_t* bits, int nwords, hipStream_t st) {
+extern "C" int sd3d_mask_bits(const float* logits, int ld, int64_t Q, int S, float thr, uint32_t* bits, int nwords, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (Q <= 0) return SD3D_OK;
     if (nwords != (S + 31) / 32) return sd3d_set_error(SD3D_ERR_ARG, "mask_bits: nwords != ceil(S/32)");
     hipLaunchKernelGGL(mask_bits_kernel, dim3((unsigned)Q), dim3(256), 0, st, logits, ld, Q, S, thr, bits, nwords);
@@ -906,8 +990,9 @@ __global__ __launch_bounds__(512) void dinox_mask_bits_batch_kernel(const DinoxB
 }
 // queries per workgroup: 8 where that still leaves >= 256 workgroups, 2 for the few hundred queries of the default mode
 static int dinox_qb(int64_t rows) { return rows >= 2048 ? 8 : 2; }
-int launch_dinox_mask_bits_batch(int n, const uint32_t* const* blocked, const uint32_t* const* near, const int* nwords, const int64_t* Q,
-                                 const int64_t* Mq, uint32_t* const* out, const int* nwords_out, hipStream_t st) {
+extern "C" int sd3d_dinox_mask_bits_batch(int n, const uint32_t* const* blocked, const uint32_t* const* near, const int* nwords, const int64_t* Q,
+                                          const int64_t* Mq, uint32_t* const* out, const int* nwords_out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     if (n > SD3D_MAX_BATCH) return sd3d_set_error(SD3D_ERR_ARG, "dinox_mask_bits_batch: at most 16 scenes per call");
     DinoxBitsBatch b;
@@ -933,14 +1018,16 @@ int launch_dinox_mask_bits_batch(int n, const uint32_t* const* blocked, const ui
     return SD3D_OK;
 }
 
-int launch_near_bits(const float* pos, int64_t S, const float* ctr, int64_t Mq, float thr, uint32_t* near, int nwords, hipStream_t st) {
+extern "C" int sd3d_near_bits(const float* pos, int64_t S, const float* ctr, int64_t Mq, float thr, uint32_t* near, int nwords, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (Mq <= 0 || S <= 0) return SD3D_OK;
     hipLaunchKernelGGL(near_bits_kernel, dim3((unsigned)cdiv(Mq * nwords, 256)), dim3(256), 0, st, pos, S, ctr, Mq, thr, near, nwords);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_dinox_mask_bits(const uint32_t* blocked, const uint32_t* near, int nwords, int64_t Q, int64_t Mq, uint32_t* out,
-                           int nwords_out, hipStream_t st) {
+extern "C" int sd3d_dinox_mask_bits(const uint32_t* blocked, const uint32_t* near, int nwords, int64_t Q, int64_t Mq, uint32_t* out, int nwords_out,
+                                    void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (Q <= 0) return SD3D_OK;
     if (nwords_out != (int)((Mq + 1 + 31) / 32)) return sd3d_set_error(SD3D_ERR_ARG, "dinox_mask_bits: nwords_out != ceil((M+1)/32)");
     const int qb = dinox_qb(Q);
@@ -986,13 +1073,24 @@ __global__ void box_refine_kernel(const float* __restrict__ ref, const float* __
     size[t] = s;
 }
 
-int launch_box_refine(const float* ref, const float* dc, const float* sprev, int ld_sprev, const float* ds, const float* rng,
-                      int normalize, int64_t Q, float* center, float* size, float* size_out, const int32_t* row_scene, hipStream_t st) {
+static int launch_box_refine(const float* ref, const float* dc, const float* sprev, int ld_sprev, const float* ds, const float* rng,
+                             int normalize, int64_t Q, float* center, float* size, float* size_out, const int32_t* row_scene, hipStream_t st) {
     if (Q <= 0) return SD3D_OK;
     hipLaunchKernelGGL(box_refine_kernel, dim3((unsigned)cdiv(Q * 3, 256)), dim3(256), 0, st, ref, dc, sprev, ld_sprev, ds, rng,
                        normalize, Q, center, size, size_out, row_scene);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_box_refine(const float* ref_points, const float* d_center, const float* size_prev, int ld_size_prev, const float* d_size,
+                               const float* range, int normalize, int64_t Q, float* center, float* size, float* size_metric, void* stream) {
+    return launch_box_refine(ref_points, d_center, size_prev, ld_size_prev, d_size, range, normalize, Q, center, size, size_metric, nullptr,
+                             (hipStream_t)stream);
+}
+extern "C" int sd3d_box_refine_rows(const float* ref_points, const float* d_center, const float* size_prev, int ld_size_prev, const float* d_size,
+                                    const float* ranges, const int32_t* row_scene, int normalize, int64_t Q, float* center, float* size,
+                                    float* size_metric, void* stream) {
+    return launch_box_refine(ref_points, d_center, size_prev, ld_size_prev, d_size, ranges, normalize, Q, center, size, size_metric, row_scene,
+                             (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1034,4 +1132,8 @@ int launch_scale_shift_act(const float* x0, int ld0, int C0, const float* x1, in
                        shift, act, M, C, add, ld_add, out, ld_out);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_scale_shift_act_add(const float* x0, int ld0, int C0, const float* x1, int ld1, const float* scale, const float* shift, int act,
+                                        int64_t M, int C, const float* add, int ld_add, float* out, int ld_out, void* stream) {
+    return launch_scale_shift_act(x0, ld0, C0, x1, ld1, scale, shift, act, M, C, add, ld_add, out, ld_out, (hipStream_t)stream);
 }

@@ -7,10 +7,6 @@
 #include "gg_common.h"
 #include "pair_conv.h"
 
-int launch_gather_gemm(const GGParams&, int, void*, size_t, hipStream_t);
-int launch_scale_shift_act(const float*, int, int, const float*, int, const float*, const float*, int, int64_t, int, const float*, int,
-                           float*, int, hipStream_t);
-
 // table_events[t] (optional): a hipEvent_t recorded on ANOTHER stream after table t's lists were built there (fork / join inside a
 // scene: the neighbour tables of the deeper levels are built on a side stream while the stem convolves); `stream` waits for it
 // before the first layer that reads table t.  NULL entries / a NULL array: the tables are already ordered before this call.
@@ -45,10 +41,8 @@ extern "C" int sd3d_run_layers_ev(const sd3d_layer* layers, int n_layers, const 
                                   L.Cin, L.Cout, T.M, L.scale, L.shift, r ? r->ptr : nullptr, r ? r->ld : 0, o.ptr, o.ld, L.act, part,
                                   part_bytes, st);
         } else if (L.kind == SD3D_LAYER_DENSE) {
-            GGParams p;
-            p.in0 = a.ptr; p.ld0 = a.ld; p.C0 = L.C0; p.in1 = b ? b->ptr : nullptr; p.ld1 = b ? b->ld : 0; p.nbr = nullptr; p.wt = L.wt;
-            p.K = 1; p.Cin = L.Cin; p.Cout = L.Cout; p.M = o.rows; p.scale = L.scale; p.shift = L.shift; p.res = r ? r->ptr : nullptr;
-            p.ld_res = r ? r->ld : 0; p.out = o.ptr; p.ld_out = o.ld; p.act = L.act; p.col_groups = 1; p.ksplit = 1; p.ws = nullptr;
+            const GGParams p = gg_params(a.ptr, a.ld, L.C0, b ? b->ptr : nullptr, b ? b->ld : 0, nullptr, L.wt, 1, L.Cin, L.Cout, o.rows, L.scale,
+                                         L.shift, r ? r->ptr : nullptr, r ? r->ld : 0, o.ptr, o.ld, L.act);
             rc = launch_gather_gemm(p, 0, ws, ws_bytes, st);
         } else if (L.kind == SD3D_LAYER_SCALE_SHIFT_ACT) {
             rc = launch_scale_shift_act(a.ptr, a.ld, L.C0, b ? b->ptr : nullptr, b ? b->ld : 0, L.scale, L.shift, L.act, o.rows, L.Cin,

@@ -22,6 +22,7 @@
 // partial slabs (ksplit x M x Cout floats, ~1/8 of what the pair-major partial products were), summed in k order by
 // slab_reduce_kernel together with the epilogue.
 #include "../gg_common.h"
+#include "../../../include/segdino3d_hip_experimental.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -730,7 +731,7 @@ int slab_direct_plan(int K, int Cin, int Cout, int64_t M, int64_t n_pairs, int n
     return 1;
 }
 
-size_t slab_conv_ws_bytes(int K, int Cin, int Cout, int64_t M, int64_t n_pairs) {
+extern "C" size_t sd3d_slab_conv_ws_bytes(int K, int Cin, int Cout, int64_t M, int64_t n_pairs) {
     static int n_cu = 0;
     if (!n_cu) {
         int dev = 0; hipDeviceProp_t prop;
@@ -743,9 +744,10 @@ size_t slab_conv_ws_bytes(int K, int Cin, int Cout, int64_t M, int64_t n_pairs) 
     return pl.ws_bytes;
 }
 
-int launch_slab_conv(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* nbr, int64_t n_pairs, const float* wt,
-                     int K, int Cin, int Cout, int64_t M, const float* scale, const float* shift, const float* res, int ld_res,
-                     float* out, int ld_out, int act, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sd3d_slab_conv(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* nbr, int64_t n_pairs, const float* wt,
+                              int K, int Cin, int Cout, int64_t M, const float* scale, const float* shift, const float* res, int ld_res, float* out,
+                              int ld_out, int act, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (M <= 0 || Cout <= 0) return SD3D_OK;
     if (in1 && ((C0 & 31) || C0 > Cin)) return sd3d_set_error(SD3D_ERR_ARG, "slab_conv: concat split must be a multiple of 32");
     if (!in1) C0 = Cin;

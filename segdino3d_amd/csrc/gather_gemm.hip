@@ -402,7 +402,7 @@ void launch_splitk_epilogue(const GGParams& p, hipStream_t st) {
 // row count, so the heuristic stays free), -1 = one column tile per wave with the contraction split over the four waves,
 // n > 0 = n column tiles per wave without split.  The batched decoder passes it so that the rows of several scenes run on the
 // same kernel - same summation order, same bits - as one scene's rows.  Mirrors the heuristic below; keep them together.
-int dense_plan_code(int64_t rows, int Cin, int Cout) {
+extern "C" int sd3d_dense_plan_code(int64_t rows, int Cin, int Cout) {
     const int sub = (Cout + 31) / 32;
     const int64_t tiles = cdiv(rows, 32);
     const int64_t steps = Cin / 32;
@@ -511,15 +511,21 @@ int launch_gather_gemm(const GGParams& p_in, int nt, void* ws, size_t ws_bytes, 
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
+extern "C" int sd3d_gather_gemm(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* nbr, const float* wt, int K,
+                                int Cin, int Cout, int64_t M, const float* scale, const float* shift, const float* res, int ld_res,
+                                float* out, int ld_out, int act, int nt, void* ws, size_t ws_bytes, void* stream) {
+    const GGParams p = gg_params(in0, ld0, C0, in1, ld1, nbr, wt, K, Cin, Cout, M, scale, shift, res, ld_res, out, ld_out, act);
+    return launch_gather_gemm(p, nt, ws, ws_bytes, (hipStream_t)stream);
+}
 
 // n <= 8 independent plain Linears (identity rows, K = 1): out_i = act_i(x_i W_i^T + shift_i + res_i)
-int launch_linear_group(int n, const GGParams* jobs, hipStream_t st) {
+static int launch_linear_group(int n, const GGParams* jobs, hipStream_t st) {
     if (n <= 0) return SD3D_OK;
     if (n > GG_GROUP_MAX) return sd3d_set_error(SD3D_ERR_ARG, "linear_group: at most 8 jobs per launch");
-    // every job on enough rows for the lock-step kernel (dense_plan_code 0): one launch per column-tile count, each job on the
+    // every job on enough rows for the lock-step kernel (sd3d_dense_plan_code 0): one launch per column-tile count, each job on the
     // tiling its own launch would get
     bool all_lds = true;
-    for (int i = 0; i < n; ++i) all_lds = all_lds && jobs[i].Cin > 0 && !(jobs[i].Cin & 31) && dense_plan_code(jobs[i].M, jobs[i].Cin, jobs[i].Cout) == 0;
+    for (int i = 0; i < n; ++i) all_lds = all_lds && jobs[i].Cin > 0 && !(jobs[i].Cin & 31) && sd3d_dense_plan_code(jobs[i].M, jobs[i].Cin, jobs[i].Cout) == 0;
     if (all_lds) {
         for (int want = 1; want <= 4; ++want) {
             GGGroup g;
@@ -570,4 +576,13 @@ int launch_linear_group(int n, const GGParams* jobs, hipStream_t st) {
     hipLaunchKernelGGL(gather_gemm_group_kernel, dim3((unsigned)max_units, (unsigned)n), dim3(256), 0, st, g);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_linear_group(int n, const sd3d_linear_job* jobs, void* stream) {
+    GGParams g[8];
+    if (n > 8) return sd3d_set_error(SD3D_ERR_ARG, "linear_group: at most 8 jobs per launch");
+    for (int i = 0; i < n; ++i) {
+        const sd3d_linear_job& J = jobs[i];
+        g[i] = gg_params(J.in0, J.ld0, J.C0, J.in1, J.ld1, nullptr, J.wt, 1, J.Cin, J.Cout, J.M, nullptr, J.shift, J.res, J.ld_res, J.out, J.ld_out, J.act);
+    }
+    return launch_linear_group(n, g, (hipStream_t)stream);
 }

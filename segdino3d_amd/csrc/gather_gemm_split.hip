@@ -11,6 +11,7 @@
 // Weights are split once on the host into [terms][K][Cout][Cin] bf16; the gathered activations are
 // split in registers (v_cvt_pk_bf16_f32).  Structure = the lock-step LDS-shared-weights kernel.
 #include "gg_common.h"
+#include "../../include/segdino3d_hip.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -225,11 +226,8 @@ static void launch_one(const GGParams& p, const __bf16* w, dim3 grid, hipStream_
     hipLaunchKernelGGL((gather_gemm_split_kernel<NT, NS>), grid, dim3(256), sm, st, p, w);
 }
 
-void launch_splitk_epilogue(const GGParams& p, hipStream_t st);
-
 // terms: 1 (plain bf16), 3 (bf16x3) or 6 (bf16x6).  wsplit: [1, 2 or 3][K][Cout][Cin] bf16.
-int launch_gather_gemm_split(const GGParams& p_in, int nt, int terms, const void* wsplit, void* ws, size_t ws_bytes,
-                             hipStream_t st) {
+static int launch_gather_gemm_split(const GGParams& p_in, int nt, int terms, const void* wsplit, void* ws, size_t ws_bytes, hipStream_t st) {
     GGParams p = p_in;
     p.ksplit = 1;
     p.ws = nullptr;
@@ -283,4 +281,11 @@ int launch_gather_gemm_split(const GGParams& p_in, int nt, int terms, const void
     if (p.ksplit > 1) launch_splitk_epilogue(p, st);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_gather_gemm_split(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* nbr,
+                                      const uint16_t* wt_split, int terms, int K, int Cin, int Cout, int64_t M, const float* scale,
+                                      const float* shift, const float* res, int ld_res, float* out, int ld_out, int act, int nt,
+                                      void* ws, size_t ws_bytes, void* stream) {
+    const GGParams p = gg_params(in0, ld0, C0, in1, ld1, nbr, nullptr, K, Cin, Cout, M, scale, shift, res, ld_res, out, ld_out, act);
+    return launch_gather_gemm_split(p, nt, terms, wt_split, ws, ws_bytes, (hipStream_t)stream);
 }

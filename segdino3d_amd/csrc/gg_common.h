@@ -18,6 +18,23 @@ struct GGParams {
     float* ws;                                // [ksplit][M][Cout] partial sums when ksplit > 1
 };
 
+// The fields a caller sets; col_groups, ksplit and ws are the launcher's to choose.
+static inline GGParams gg_params(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* nbr, const float* wt, int K,
+                                 int Cin, int Cout, int64_t M, const float* scale, const float* shift, const float* res, int ld_res,
+                                 float* out, int ld_out, int act) {
+    GGParams p;
+    p.in0 = in0; p.ld0 = ld0; p.C0 = C0; p.in1 = in1; p.ld1 = ld1; p.nbr = nbr; p.wt = wt; p.K = K; p.Cin = Cin; p.Cout = Cout;
+    p.M = M; p.scale = scale; p.shift = shift; p.res = res; p.ld_res = ld_res; p.out = out; p.ld_out = ld_out; p.act = act;
+    p.col_groups = 1;
+    p.ksplit = 1;
+    p.ws = nullptr;
+    return p;
+}
+
+// gather_gemm.hip; called from gather_gemm_split.hip and executor.hip as well
+int launch_gather_gemm(const GGParams& p_in, int nt, void* ws, size_t ws_bytes, hipStream_t st);
+void launch_splitk_epilogue(const GGParams& p, hipStream_t st);
+
 __device__ __forceinline__ int next_active(uint64_t m0, uint64_t m1, int after) {
     // smallest set bit index > after in the 128-bit mask (m1:m0), or -1
     int s = after + 1;

@@ -1,4 +1,4 @@
-// Internal interface of the pair-major sparse convolution: the rulebook lists (pair_lists.hip) and pass 1 / pass 2 (pair_gemm.hip).
+// Internal interface of the pair-major sparse convolution: what the rulebook lists (pair_lists.hip) and pass 1 / pass 2 (pair_gemm.hip) share.
 // Every translation unit that calls one of these launchers includes this header instead of declaring them itself.
 #pragma once
 #include "common.h"
@@ -9,11 +9,6 @@
 #define PG_KMASK 0x3FFFFFFF
 
 struct GGParams;
-
-// list building (pair_lists.hip)
-size_t pair_lists_ws_bytes(int K, int64_t M);
-size_t chain_lists_ws_bytes(int K, int64_t M);
-int launch_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_t ws_bytes, hipStream_t st);
 
 // pass 1 + pass 2 (pair_gemm.hip)
 int launch_pair_conv(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* in_idx, const int32_t* tile_k,

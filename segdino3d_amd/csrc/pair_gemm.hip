@@ -816,7 +816,7 @@ static void pg_setup_pool(PGParams& g, int dev, int cgs, hipStream_t st) {
     g.pool_epoch = (unsigned int)(t / PG_POOL_SLOTS + 1);
 }
 
-// rlist / rl_stride / center / out_idx: optional products of launch_pair_lists_desc (NULL / -1: the round-1 path, pass 1 over all
+// rlist / rl_stride / center / out_idx: optional products of sd3d_pair_lists_desc (NULL / -1: the round-1 path, pass 1 over all
 // offsets + pair_reduce_kernel over pos).  out_idx != NULL promises ONE pair per output row (transposed k2s2 convolution).
 int launch_pair_conv(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* in_idx, const int32_t* tile_k,
                      int64_t p_cap, const int32_t* pos, const int32_t* rlist, int rl_stride, int center, const int32_t* out_idx,
@@ -904,6 +904,13 @@ int launch_pair_conv(const float* in0, int ld0, int C0, const float* in1, int ld
     }
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_pair_conv_ex(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* in_idx, const int32_t* tile_k,
+                                 int64_t p_cap, const int32_t* pos, const int32_t* rlist, int rl_stride, int center, const int32_t* out_idx,
+                                 const float* wt, int K, int Cin, int Cout, int64_t M, const float* scale, const float* shift, const float* res,
+                                 int ld_res, float* out, int ld_out, int act, float* part, size_t part_bytes, void* stream) {
+    return launch_pair_conv(in0, ld0, C0, in1, ld1, in_idx, tile_k, p_cap, pos, rlist, rl_stride, center, out_idx, wt, K, Cin, Cout, M,
+                            scale, shift, res, ld_res, out, ld_out, act, part, part_bytes, (hipStream_t)stream);
 }
 
 // A dense [M, Cin] x W^T product (+ scale / shift / residual / activation) on the pass-1 kernel: the 1x1 convolutions of the U-Net

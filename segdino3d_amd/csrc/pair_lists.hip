@@ -521,14 +521,14 @@ __global__ __launch_bounds__(256) void lists_fill_kernel(const CHBatch cb, const
     if ((int)blockIdx.x < n_chain) chain_fill_body(cb, (int)blockIdx.x);
     else pair_fill_rows_body(rb, (int)blockIdx.x - n_chain);
 }
-size_t chain_lists_ws_bytes(int K, int64_t M) {
+static size_t chain_lists_ws_bytes(int K, int64_t M) {
     const int64_t nblk = cdiv(M, CH_ROWS);
     const int64_t nseg = (int64_t)(K / 2) * CH_NPAT + 1;
     return (size_t)(nseg * nblk + nseg) * sizeof(int32_t) + 256;
 }
 
 // ---- launchers --------------------------------------------------------------------------------
-size_t pair_lists_ws_bytes(int K, int64_t M) {
+extern "C" size_t sd3d_pair_lists_ws_bytes(int K, int64_t M) {
     const int64_t nblk = cdiv(M, PL_ROWS);
     const size_t plain = (size_t)((int64_t)K * nblk + K) * sizeof(int32_t) + 256;
     const size_t chained = (K & 1) ? chain_lists_ws_bytes(K, M) : 0;      // (a table may be built either way: size for all)
@@ -537,10 +537,12 @@ size_t pair_lists_ws_bytes(int K, int64_t M) {
     return m > rows ? m : rows;
 }
 
-// n tables at once (n <= PL_MAX_TABLES); the tables' scratch sits back to back in ws (pair_lists_ws_bytes(K_i, M_i) bytes each,
+// n tables at once (n <= PL_MAX_TABLES); the tables' scratch sits back to back in ws (sd3d_pair_lists_ws_bytes(K_i, M_i) bytes each,
 // rounded up to 256).  p_cap: capacity of in_idx in pairs (multiple of 128, >= pairs + K * 127); tile_k has p_cap / 128 + 1 entries
 // (the last one receives the number of real tiles).  rlist / out_idx / the two centre slots of tile_k are optional products (see sd3d_pair_table_desc).
-int launch_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_t ws_bytes, void* stream) {
+    if (n > 0 && !d) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_desc: tables is NULL");
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     if (n > PL_MAX_TABLES) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_batch: at most 16 tables per call");
     PLBatch b, rbt;                                            // (offset, row block) form / row-block form (no pos table)
@@ -589,7 +591,7 @@ int launch_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_
             T.nblk = (int)cdiv(M, 256);
             T.blk_cnt = (int32_t*)((char*)ws + off);
             T.totals = T.blk_cnt + (int64_t)T.K * T.nblk;
-            off += align_up(pair_lists_ws_bytes(K, M), 256);
+            off += align_up(sd3d_pair_lists_ws_bytes(K, M), 256);
             T.wg0 = rwg; T.k0 = rkk; T.rb0 = 0;
             rwg += T.nblk; rkk += T.K;
             continue;
@@ -601,7 +603,7 @@ int launch_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_
         T.nblk = (int)cdiv(M, PL_ROWS);
         T.blk_cnt = (int32_t*)((char*)ws + off);
         T.totals = T.blk_cnt + (int64_t)T.K * T.nblk;
-        off += align_up(pair_lists_ws_bytes(K, M), 256);
+        off += align_up(sd3d_pair_lists_ws_bytes(K, M), 256);
         T.wg0 = wg; T.k0 = kk; T.rb0 = rb;
         wg += T.K * T.nblk; kk += T.K;
         rb += T.rlist ? (int)cdiv(M, RL_ROWS) : 0;

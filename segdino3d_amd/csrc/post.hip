@@ -3,6 +3,7 @@
 // SURVEY.md 2b K20, K21).  All HBM-bound; the [600, N] point masks are produced once, bit-tested and
 // written as bytes (torch.bool layout the evaluator reads), never as fp32.
 #include "common.h"
+#include "../../include/segdino3d_hip.h"
 
 __device__ static inline float wred_sum(float v) {
 #pragma unroll
@@ -329,11 +330,35 @@ __global__ __launch_bounds__(256) void pack_mask_rows_kernel(const uint8_t* __re
     }
     out[(int64_t)i * nb + b] = (uint8_t)v;
 }
-int launch_pack_mask_rows(const uint8_t* masks, int64_t N, const int32_t* rows, int n_rows, uint8_t* out, int64_t nb, hipStream_t st) {
+extern "C" int sd3d_pack_mask_rows(const uint8_t* masks, int64_t N, const int32_t* rows, int n_rows, uint8_t* out, int64_t nb, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n_rows <= 0 || N <= 0) return SD3D_OK;
     if (nb != (N + 7) / 8) return sd3d_set_error(SD3D_ERR_ARG, "pack_mask_rows: nb != ceil(N / 8)");
     hipLaunchKernelGGL(pack_mask_rows_kernel, dim3((unsigned)cdiv(nb, 256), (unsigned)n_rows), dim3(256), 0, st, masks, N, rows, n_rows, out, nb);
     SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
+}
+// Host side of sd3d_pack_mask_rows: packed_host [n_rows, nb] bits -> out_host [n_rows, N] bytes (0 / 1).  One table lookup per
+// input byte (8 output bytes at a time); plain C, no GPU, no threads - the caller's thread does it with the GIL released.
+extern "C" int sd3d_unpack_bits_host(const uint8_t* packed_host, int64_t n_rows, int64_t N, int64_t nb, uint8_t* out_host) {
+    if (n_rows < 0 || N < 0 || nb != (N + 7) / 8) return sd3d_set_error(SD3D_ERR_ARG, "unpack_bits_host: nb != ceil(N / 8)");
+    static uint64_t lut[256];
+    static bool ready = false;
+    if (!ready) {                                              // idempotent: racing callers write the same values
+        for (int v = 0; v < 256; ++v) {
+            uint64_t w = 0;
+            for (int j = 0; j < 8; ++j) if (v >> j & 1) w |= 1ull << (8 * j);
+            lut[v] = w;
+        }
+        __atomic_store_n(&ready, true, __ATOMIC_RELEASE);
+    }
+    const int64_t full = N / 8;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const uint8_t* src = packed_host + r * nb;
+        uint8_t* dst = out_host + r * N;
+        for (int64_t b = 0; b < full; ++b) { const uint64_t w = lut[src[b]]; __builtin_memcpy(dst + 8 * b, &w, 8); }
+        for (int64_t p = full * 8; p < N; ++p) dst[p] = (src[full] >> (p - full * 8)) & 1;
+    }
     return SD3D_OK;
 }
 
@@ -399,30 +424,34 @@ __global__ void pan_finalize_kernel(const int32_t* __restrict__ inst, const int3
 }
 
 // ---------------------------------------------------------------------------------------------
-int launch_class_scores(const float* cls, int ld, int64_t Q, int C, float* scores, float* rowmax, hipStream_t st) {
+extern "C" int sd3d_class_scores(const float* cls, int ld, int64_t Q, int C, float* scores, float* rowmax, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (Q <= 0) return SD3D_OK;
     hipLaunchKernelGGL(class_scores_kernel, dim3((unsigned)cdiv(Q, 4)), dim3(256), 0, st, cls, ld, Q, C, scores, rowmax);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_mask_scores(const float* masks, int ld, int S, const uint32_t* flat_idx, const float* score_in, int n, int C,
-                       int normalize, int32_t* labels, int32_t* qidx, float* score_out, hipStream_t st) {
+extern "C" int sd3d_mask_scores(const float* masks, int ld, int S, const uint32_t* flat_idx, const float* score_in, int n, int C, int normalize,
+                                int32_t* labels, int32_t* qidx, float* score_out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     hipLaunchKernelGGL(mask_scores_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, masks, ld, S, flat_idx, score_in, n, C,
                        normalize, labels, qidx, score_out);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_gather_sigmoid(const float* masks, int ld, int S, const int32_t* qidx, const uint32_t* order, int n, float* sig,
-                          int ld_out, float* area, hipStream_t st) {
+extern "C" int sd3d_gather_sigmoid(const float* masks, int ld, int S, const int32_t* qidx, const uint32_t* order, int n, float* sig, int ld_out,
+                                   float* area, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     hipLaunchKernelGGL(gather_sigmoid_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, masks, ld, S, qidx, order, n, sig, ld_out,
                        area);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_nms_decay(const float* inter, int ld, const float* area, const int32_t* labels, int n, int gaussian, float sigma,
-                     const float* score_in, float* comp_ws, float* score_out, hipStream_t st) {
+extern "C" int sd3d_nms_decay(const float* inter, int ld, const float* area, const int32_t* labels, int n, int gaussian, float sigma,
+                              const float* score_in, float* comp_ws, float* score_out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     hipLaunchKernelGGL(nms_comp_kernel, dim3((unsigned)cdiv(n, 64)), dim3(64 * NMS_RL), 0, st, inter, ld, area, labels, n, comp_ws);
     hipLaunchKernelGGL(nms_coef_kernel, dim3((unsigned)cdiv(n, 64)), dim3(64 * NMS_RL), 0, st, inter, ld, area, labels, comp_ws, n, gaussian,
@@ -431,13 +460,14 @@ int launch_nms_decay(const float* inter, int ld, const float* area, const int32_
     return SD3D_OK;
 }
 // (+ n ints behind npts: a caller that places `count` there - ops.MaskBits - gets both zeroed by ONE memset launch)
-size_t expand_masks_ws_bytes(int n, int ld_sig) { return ((size_t)ld_sig * ((n + 31) / 32 + 1) + (size_t)n) * sizeof(uint32_t) + 256; }
-// bits [ld_sig][W] words + npts [ld_sig] ints live in `ws` (expand_masks_ws_bytes): phase 1 of expand_masks, and all of it when the
-// caller expands a list of rows later (launch_expand_rows on the same ws)
-int launch_mask_rowbits(const float* sig, int ld_sig, const uint32_t* src, int n, const int64_t* superpoints, int64_t N, float sp_thr,
-                        int32_t* count, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" size_t sd3d_expand_masks_ws_bytes(int n, int ld_sig) { return ((size_t)ld_sig * ((n + 31) / 32 + 1) + (size_t)n) * sizeof(uint32_t) + 256; }
+// bits [ld_sig][W] words + npts [ld_sig] ints live in `ws` (sd3d_expand_masks_ws_bytes): phase 1 of expand_masks, and all of it when the
+// caller expands a list of rows later (sd3d_expand_rows on the same ws)
+extern "C" int sd3d_mask_rowbits(const float* sig, int ld_sig, const uint32_t* src, int n, const int64_t* superpoints, int64_t N, float sp_thr,
+                                 int32_t* count, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0 || N <= 0) return SD3D_OK;
-    if (ws_bytes < expand_masks_ws_bytes(n, ld_sig)) return sd3d_set_error(SD3D_ERR_ARG, "expand_masks: workspace too small");
+    if (ws_bytes < sd3d_expand_masks_ws_bytes(n, ld_sig)) return sd3d_set_error(SD3D_ERR_ARG, "expand_masks: workspace too small");
     const int W = (n + 31) / 32, S = ld_sig;
     uint32_t* bits = (uint32_t*)ws;
     int32_t* npts = (int32_t*)(bits + (size_t)S * W);
@@ -453,8 +483,9 @@ int launch_mask_rowbits(const float* sig, int ld_sig, const uint32_t* src, int n
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_expand_rows(const void* ws, int n, int ld_sig, const int32_t* rows, int m, const int64_t* superpoints, const float* pts, int ld_pts,
-                       int64_t N, const float* boxes, float loose, uint8_t* out, hipStream_t st) {
+extern "C" int sd3d_expand_rows(const void* ws, int n, int ld_sig, const int32_t* rows, int m, const int64_t* superpoints, const float* pts,
+                                int ld_pts, int64_t N, const float* boxes, float loose, uint8_t* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (m <= 0 || N <= 0) return SD3D_OK;
     if (!ws || !rows || !out || n <= 0) return sd3d_set_error(SD3D_ERR_ARG, "expand_rows: null pointer");
     const int W = (n + 31) / 32;
@@ -463,11 +494,12 @@ int launch_expand_rows(const void* ws, int n, int ld_sig, const int32_t* rows, i
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_expand_masks(const float* sig, int ld_sig, const uint32_t* src, int n, const int64_t* superpoints, const float* pts,
-                        int ld_pts, int64_t N, float sp_thr, const float* boxes, float loose, uint8_t* out, int32_t* count,
-                        void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sd3d_expand_masks(const float* sig, int ld_sig, const uint32_t* src, int n, const int64_t* superpoints, const float* pts, int ld_pts,
+                                 int64_t N, float sp_thr, const float* boxes, float loose, uint8_t* out, int32_t* count, void* ws, size_t ws_bytes,
+                                 void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0 || N <= 0) return SD3D_OK;
-    const int rc = launch_mask_rowbits(sig, ld_sig, src, n, superpoints, N, sp_thr, count, ws, ws_bytes, st);
+    const int rc = sd3d_mask_rowbits(sig, ld_sig, src, n, superpoints, N, sp_thr, count, ws, ws_bytes, st);
     if (rc) return rc;
     const int W = (n + 31) / 32, S = ld_sig;
     hipLaunchKernelGGL(em_expand_kernel, dim3((unsigned)cdiv(N, 1024), (unsigned)cdiv(W, EM_WORDS)), dim3(256), 0, st, (const uint32_t*)ws, W, n, S,
@@ -475,21 +507,23 @@ int launch_expand_masks(const float* sig, int ld_sig, const uint32_t* src, int n
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_row_argmax(const float* x, int ld, int64_t Q, const int32_t* cols, int ncols, int64_t* out, hipStream_t st) {
+extern "C" int sd3d_row_argmax(const float* x, int ld, int64_t Q, const int32_t* cols, int ncols, int64_t* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (Q <= 0) return SD3D_OK;
     hipLaunchKernelGGL(row_argmax_kernel, dim3((unsigned)cdiv(Q, 4)), dim3(256), 0, st, x, ld, Q, cols, ncols, out);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_gather_i64(const int64_t* table, const int64_t* idx, int64_t N, int use_index, int64_t* out, hipStream_t st) {
+extern "C" int sd3d_gather_i64(const int64_t* table, const int64_t* idx, int64_t N, int use_index, int64_t* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (N <= 0) return SD3D_OK;
     hipLaunchKernelGGL(gather_i64_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, table, idx, N, use_index, out);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_panoptic(const uint8_t* masks, int64_t N, const int32_t* rows, const int32_t* labels_desc, int n, int n_stuff,
-                    int npoint_thr, const int64_t* sem_stuff, int32_t* inst_ws, int32_t* hist_ws, int64_t* sem_map,
-                    int64_t* inst_map, hipStream_t st) {
+extern "C" int sd3d_panoptic(const uint8_t* masks, int64_t N, const int32_t* rows, const int32_t* labels_desc, int n, int n_stuff, int npoint_thr,
+                             const int64_t* sem_stuff, int32_t* inst_ws, int32_t* hist_ws, int64_t* sem_map, int64_t* inst_map, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (N <= 0) return SD3D_OK;
     (void)hipMemsetAsync(hist_ws, 0, (size_t)(n + n_stuff + 1) * sizeof(int32_t), st);
     const unsigned nb = (unsigned)cdiv(N, 256);
@@ -558,8 +592,10 @@ __global__ void instance_boxes_final(const float* __restrict__ part, int n_inst,
     centers[t] = ctr;
     sizes[t] = sz;
 }
-int launch_instance_boxes(const float* pts, int ld, int64_t N, const uint8_t* masks, int64_t mask_stride, int n_inst, int mode,
-                          float* centers, float* sizes, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" size_t sd3d_instance_boxes_ws_bytes(int n_inst) { return (size_t)(n_inst > 0 ? n_inst : 1) * IB_CHUNKS * 10 * sizeof(float); }
+extern "C" int sd3d_instance_boxes(const float* pts, int ld, int64_t N, const uint8_t* masks, int64_t mask_stride, int n_inst, int mode,
+                                   float* centers, float* sizes, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n_inst <= 0) return SD3D_OK;
     if (ws_bytes < (size_t)n_inst * IB_CHUNKS * 10 * sizeof(float)) return sd3d_set_error(SD3D_ERR_WS, "instance_boxes workspace");
     hipLaunchKernelGGL(instance_boxes_partial, dim3(IB_CHUNKS, (unsigned)n_inst), dim3(256), 0, st, pts, ld, N, masks, mask_stride,
@@ -624,8 +660,9 @@ __global__ __launch_bounds__(256) void mask_overlaps_kernel(const uint8_t* __res
     }
 }
 
-int launch_mask_overlaps(const uint8_t* masks, int64_t mask_stride, int n, const int32_t* gt_index, int64_t N, int n_cols, int32_t* counts,
-                         hipStream_t st) {
+extern "C" int sd3d_mask_overlaps(const uint8_t* masks, int64_t mask_stride, int n, const int32_t* gt_index, int64_t N, int n_cols, int32_t* counts,
+                                  void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0 || n_cols <= 0) return SD3D_OK;
     if (n_cols > 8192) return sd3d_set_error(SD3D_ERR_ARG, "mask_overlaps: at most 8192 ground-truth columns");
     if (hipMemsetAsync(counts, 0, (size_t)n * n_cols * sizeof(int32_t), st) != hipSuccess)
@@ -763,7 +800,8 @@ __global__ __launch_bounds__(TK_THREADS) void topk_desc_kernel(const float* __re
         out[rank] = (uint32_t)me;
     }
 }
-int launch_topk_desc(const float* x, int64_t n, int k, uint32_t* out, hipStream_t st) {
+extern "C" int sd3d_topk_desc_f32(const float* x, int64_t n, int k, uint32_t* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (k <= 0) return SD3D_OK;
     if (n < k || k > TK_MAX_K || n > TK_NPT * TK_THREADS) return sd3d_set_error(SD3D_ERR_ARG, "topk_desc: 1 <= k <= 1024, k <= n <= 40960");
     hipLaunchKernelGGL(topk_desc_kernel, dim3(1), dim3(TK_THREADS), 0, st, x, (int)n, k, out);
@@ -775,7 +813,8 @@ __global__ void take_f32_kernel(const float* __restrict__ src, const uint32_t* _
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = src[idx[i]];
 }
-int launch_take_f32(const float* src, const uint32_t* idx, int n, float* out, hipStream_t st) {
+extern "C" int sd3d_take_f32(const float* src, const uint32_t* idx, int n, float* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     hipLaunchKernelGGL(take_f32_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, src, idx, n, out);
     SD3D_CHECK_LAUNCH();
@@ -788,8 +827,9 @@ __global__ void take_pair_kernel(const uint32_t* __restrict__ order, const int32
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { const uint32_t o = order[i]; labels_out[i] = labels[o]; scores_out[i] = scores[o]; }
 }
-int launch_take_pair(const uint32_t* order, const int32_t* labels, const float* scores, int n, int32_t* labels_out, float* scores_out,
-                     hipStream_t st) {
+extern "C" int sd3d_take_pair(const uint32_t* order, const int32_t* labels, const float* scores, int n, int32_t* labels_out, float* scores_out,
+                              void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     hipLaunchKernelGGL(take_pair_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, order, labels, scores, n, labels_out, scores_out);
     SD3D_CHECK_LAUNCH();
@@ -815,9 +855,10 @@ __global__ void nms_finish_kernel(const uint32_t* __restrict__ order2, const flo
         for (int a = 0; a < 3; ++a) { boxes[i * 6 + a] = centers[q * 3 + a]; boxes[i * 6 + 3 + a] = sizes[q * 3 + a]; }
     }
 }
-int launch_nms_finish(const uint32_t* order2, const float* scores2, const int32_t* labels1, const uint32_t* order1, const int32_t* qidx,
-                      const float* centers, const float* sizes, int n, float* final_scores, int32_t* final_labels, int64_t* record, float* boxes,
-                      hipStream_t st) {
+extern "C" int sd3d_nms_finish(const uint32_t* order2, const float* scores2, const int32_t* labels1, const uint32_t* order1, const int32_t* qidx,
+                               const float* centers, const float* sizes, int n, float* final_scores, int32_t* final_labels, int64_t* record,
+                               float* boxes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     if (boxes && (!centers || !sizes)) return sd3d_set_error(SD3D_ERR_ARG, "nms_finish: boxes need centers and sizes");
     hipLaunchKernelGGL(nms_finish_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, order2, scores2, labels1, order1, qidx, centers, sizes, n,
@@ -840,8 +881,9 @@ __global__ void take_instances_kernel(const int32_t* __restrict__ keep, int m, c
         for (int a = 0; a < 6; ++a) boxes_out[i * 6 + a] = boxes[r * 6 + a];
     }
 }
-int launch_take_instances(const int32_t* keep, int m, const int32_t* labels, const float* scores, const float* boxes, int64_t* labels_out,
-                          float* scores_out, float* boxes_out, hipStream_t st) {
+extern "C" int sd3d_take_instances(const int32_t* keep, int m, const int32_t* labels, const float* scores, const float* boxes, int64_t* labels_out,
+                                   float* scores_out, float* boxes_out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (m <= 0) return SD3D_OK;
     if (boxes_out && !boxes) return sd3d_set_error(SD3D_ERR_ARG, "take_instances: boxes_out without boxes");
     hipLaunchKernelGGL(take_instances_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, keep, m, labels, scores, boxes, labels_out, scores_out,
@@ -906,9 +948,10 @@ __global__ __launch_bounds__(1024) void select_instances_kernel(const float* __r
     }
     if (t < 4) counts[t] = carry[t];
 }
-int launch_select_instances(const float* scores, const int32_t* count, int k, float thr0, float thr1, int npoint_thr, int32_t* keep, int32_t* pkeep,
-                            int32_t* union_, int32_t* keep_u, int32_t* pkeep_u, uint8_t* score_mask, uint8_t* npoint_mask, int32_t* counts,
-                            hipStream_t st) {
+extern "C" int sd3d_select_instances(const float* scores, const int32_t* count, int k, float thr0, float thr1, int npoint_thr, int32_t* keep,
+                                     int32_t* pkeep, int32_t* union_, int32_t* keep_u, int32_t* pkeep_u, uint8_t* score_mask, uint8_t* npoint_mask,
+                                     int32_t* counts, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (k < 0) return sd3d_set_error(SD3D_ERR_ARG, "select_instances: k < 0");
     hipLaunchKernelGGL(select_instances_kernel, dim3(1), dim3(1024), 0, st, scores, count, k, thr0, thr1, npoint_thr, keep, pkeep, union_, keep_u, pkeep_u,
                        score_mask, npoint_mask, counts);

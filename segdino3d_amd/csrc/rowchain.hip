@@ -400,9 +400,9 @@ size_t row_chain_lds_bytes(const RCProgram& P) {
     return ((size_t)P.n_slots * RC_SLOT + (size_t)RC_R * (P.nw2_max + P.nw_max)) * sizeof(float);
 }
 
-int launch_row_chain_narrow(const RCProgram* P, hipStream_t st);       // rowchain_narrow.hip
-
-int launch_row_chain(const RCProgram* P, hipStream_t st) {
+extern "C" size_t sd3d_row_chain_program_bytes(void) { return sizeof(sd3d_rc_program); }
+extern "C" int sd3d_row_chain(const sd3d_rc_program* P, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (!P) return sd3d_set_error(SD3D_ERR_ARG, "row_chain: null program");
     if (P->tile_rows == 4) return launch_row_chain_narrow(P, st);
     if (P->tile_rows != 0 && P->tile_rows != 16) return sd3d_set_error(SD3D_ERR_ARG, "row_chain: tile_rows must be 16 (or 0) or 4");

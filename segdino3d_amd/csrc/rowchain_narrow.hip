@@ -244,7 +244,6 @@ __global__ __launch_bounds__(RCN_THREADS) void row_chain_narrow_kernel(const RCP
     }
 }
 
-const char* rc_check(const RCProgram& P, int R);                 // rowchain.hip
 
 int launch_row_chain_narrow(const RCProgram* P, hipStream_t st) {
     const char* err = rc_check(*P, RC_R);

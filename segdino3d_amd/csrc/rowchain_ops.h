@@ -13,6 +13,10 @@ typedef sd3d_rc_op RCOp;
 typedef sd3d_rc_scene RCScene;
 typedef sd3d_rc_program RCProgram;
 
+// host side, shared by the two tile shapes: the program check (rowchain.hip) and the 4-row launcher (rowchain_narrow.hip)
+const char* rc_check(const RCProgram& P, int R);
+int launch_row_chain_narrow(const RCProgram* P, hipStream_t st);
+
 __device__ __forceinline__ int rc_ld(int width) { return width <= 256 ? RC_LDW : width + 4; }
 
 __device__ __forceinline__ float rc_wsum(float v) {

@@ -7,6 +7,7 @@
 // superpoint stay in ascending point order => deterministic fp32 sums downstream) comes from
 // ranking each wave's elements in chunk order with ballot-built match masks.
 #include "common.h"
+#include "../../include/segdino3d_hip.h"
 
 #define RS_TILE 2048          // elements per workgroup (4 waves x 8 chunks x 64 lanes)
 #define RS_THREADS 256
@@ -148,6 +149,7 @@ __global__ __launch_bounds__(1024) void scan_small_kernel(const int* __restrict_
 }
 
 size_t scan_ws_bytes(int64_t n) { return align_up((size_t)cdiv(n, SCAN_TILE) * sizeof(int), 256); }
+extern "C" size_t sd3d_scan_ws_bytes(int64_t n) { return scan_ws_bytes(n > 0 ? n : 1); }
 
 // out may alias in.  n_dev (optional, device) = live length; elements beyond it count as zero.
 int scan_exclusive_i32(const int* in, int* out, int64_t n_cap, const int* n_dev, int* total_dev, void* ws,
@@ -173,6 +175,9 @@ int scan_exclusive_i32(const int* in, int* out, int64_t n_cap, const int* n_dev,
     }
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_scan_exclusive_i32(const int32_t* in, int32_t* out, int64_t n, int32_t* total_dev, void* ws, size_t ws_bytes, void* stream) {
+    return scan_exclusive_i32(in, out, n, nullptr, total_dev, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -296,6 +301,7 @@ size_t sort_ws_bytes(int64_t n) {
     const int64_t nb = cdiv(n > 0 ? n : 1, RS_TILE);
     return align_up((size_t)nb * 256 * sizeof(int), 256) + scan_ws_bytes(nb * 256);
 }
+extern "C" size_t sd3d_sort_ws_bytes(int64_t n) { return sort_ws_bytes(n); }
 
 // Sorts by bits [begin_bit, end_bit).  keys_in/vals_in are clobbered (ping-pong); the result is in
 // keys_out/vals_out.  vals_in == NULL means "value = original index".
@@ -339,6 +345,11 @@ int sort_pairs_u64(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uin
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
+extern "C" int sd3d_sort_pairs_u64_ex(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, uint32_t* vals_scratch,
+                                      int64_t n, int begin_bit, int end_bit, void* ws, size_t ws_bytes, int* landed_in_input, void* stream) {
+    if (n < 0 || begin_bit < 0 || end_bit > 64 || end_bit <= begin_bit || !landed_in_input) return sd3d_set_error(SD3D_ERR_ARG, "sort: bad arguments");
+    return sort_pairs_u64(keys_in, vals_in, keys_out, vals_out, n, begin_bit, end_bit, ws, ws_bytes, (hipStream_t)stream, vals_scratch, landed_in_input);
+}
 
 // order-preserving float -> u64 key; descending order when `desc`
 __global__ void f32_to_sortkey(const float* __restrict__ x, int64_t n, int desc, uint64_t* __restrict__ keys) {
@@ -354,9 +365,10 @@ __global__ void i64_to_sortkey(const int64_t* __restrict__ x, int64_t n, uint64_
     if (i < n) keys[i] = (uint64_t)x[i];
 }
 
-int launch_f32_to_sortkey(const float* x, int64_t n, int desc, uint64_t* keys, hipStream_t st) {
+extern "C" int sd3d_keys_from_f32(const float* x, int64_t n, int descending, uint64_t* keys, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
-    hipLaunchKernelGGL(f32_to_sortkey, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, desc, keys);
+    hipLaunchKernelGGL(f32_to_sortkey, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, descending, keys);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
@@ -364,9 +376,10 @@ __global__ void i64_to_sortkey_add(const int64_t* __restrict__ x, int64_t n, uin
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) keys[i] = (uint64_t)x[i] + add;
 }
-int launch_i64_to_sortkey_add(const int64_t* x, int64_t n, uint64_t add, uint64_t* keys, hipStream_t st) {
+extern "C" int sd3d_keys_from_i64_offset(const int64_t* x, int64_t n, int64_t add, uint64_t* keys, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
-    hipLaunchKernelGGL(i64_to_sortkey_add, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, add, keys);
+    hipLaunchKernelGGL(i64_to_sortkey_add, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, (uint64_t)add, keys);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
@@ -378,10 +391,11 @@ __global__ void i64_to_sortkey_checked(const int64_t* __restrict__ x, int64_t n,
         if (k >> bits) atomicOr(flag, value);
     }
 }
-int launch_i64_to_sortkey_checked(const int64_t* x, int64_t n, uint64_t* keys, int bits, int32_t* flag, int value, hipStream_t st) {
+extern "C" int sd3d_keys_from_i64_checked(const int64_t* x, int64_t n, uint64_t* keys, int bits, int32_t* flag, int flag_value, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     if (!flag || bits < 1 || bits > 63) return sd3d_set_error(SD3D_ERR_ARG, "keys_from_i64_checked: flag pointer and 1..63 bits");
-    hipLaunchKernelGGL(i64_to_sortkey_checked, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, keys, bits, flag, value);
+    hipLaunchKernelGGL(i64_to_sortkey_checked, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, keys, bits, flag, flag_value);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
@@ -422,7 +436,16 @@ int launch_i64_to_sortkey_checked_max(const int64_t* x, int64_t n, uint64_t* key
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-int launch_i64_to_sortkey(const int64_t* x, int64_t n, uint64_t* keys, hipStream_t st) {
+extern "C" int sd3d_keys_from_i64_checked_max(const int64_t* x, int64_t n, uint64_t* keys, int bits, int32_t* flag, int flag_value, int32_t* max_out,
+                                              void* stream) {
+    return launch_i64_to_sortkey_checked_max(x, n, keys, bits, flag, flag_value, max_out, (hipStream_t)stream, 0);
+}
+extern "C" int sd3d_keys_from_i64_offset_checked_max(const int64_t* x, int64_t n, int64_t add, uint64_t* keys, int bits, int32_t* flag, int flag_value,
+                                                     int32_t* max_out, void* stream) {
+    return launch_i64_to_sortkey_checked_max(x, n, keys, bits, flag, flag_value, max_out, (hipStream_t)stream, (uint64_t)add);
+}
+extern "C" int sd3d_keys_from_i64(const int64_t* x, int64_t n, uint64_t* keys, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     hipLaunchKernelGGL(i64_to_sortkey, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, keys);
     SD3D_CHECK_LAUNCH();

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(576) void scene_stats_final(const float* __restrict
     if (lane == 0) stats[c] = r;
 }
 
-int launch_scene_stats(const float* pts, int ld, int64_t n, float* stats, void* ws, size_t ws_bytes, hipStream_t st, int32_t* zero, int n_zero) {
+static int launch_scene_stats(const float* pts, int ld, int64_t n, float* stats, void* ws, size_t ws_bytes, hipStream_t st, int32_t* zero, int n_zero) {
     if (n_zero < 0 || n_zero > 576 || (n_zero > 0 && !zero)) return sd3d_set_error(SD3D_ERR_ARG, "scene_stats: at most 576 counters to zero");
     if (n <= 0) return sd3d_set_error(SD3D_ERR_ARG, "scene_stats: empty scene");
     if (ws_bytes < STAT_BLOCKS * 9 * sizeof(float)) return sd3d_set_error(SD3D_ERR_WS, "scene_stats workspace");
@@ -85,6 +85,10 @@ int launch_scene_stats(const float* pts, int ld, int64_t n, float* stats, void* 
     hipLaunchKernelGGL(scene_stats_final, dim3(1), dim3(576), 0, st, (const float*)ws, nb, stats, zero, n_zero);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" size_t sd3d_scene_stats_ws_bytes(void) { return STAT_BLOCKS * 9 * sizeof(float); }
+extern "C" int sd3d_scene_stats(const float* points, int ld, int64_t n, float* stats, void* ws, size_t ws_bytes, void* stream) {
+    return launch_scene_stats(points, ld, n, stats, ws, ws_bytes, (hipStream_t)stream, nullptr, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -128,13 +132,17 @@ __global__ __launch_bounds__(256) void voxel_keys_kernel(const float* __restrict
     keys[i] = m | ((uint64_t)(batch & 0xFF) << SD3D_MORTON_BITS);
 }
 
-int launch_voxel_keys(const float* pts, int ld, int64_t n, float inv_voxel, const float* stats, int shift_to_min, int batch,
-                      int32_t* origin, uint64_t* keys, int32_t* icoords, int32_t* err_flag, hipStream_t st) {
+static int launch_voxel_keys(const float* pts, int ld, int64_t n, float inv_voxel, const float* stats, int shift_to_min, int batch,
+                             int32_t* origin, uint64_t* keys, int32_t* icoords, int32_t* err_flag, hipStream_t st) {
     if (n <= 0) return sd3d_set_error(SD3D_ERR_ARG, "voxel_keys: empty scene");
     hipLaunchKernelGGL(voxel_keys_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, pts, ld, n, inv_voxel, stats,
                        shift_to_min, batch, origin, keys, icoords, err_flag);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_voxel_keys(const float* points, int ld, int64_t n, float inv_voxel, const float* stats, int shift_to_min,
+                               int batch_index, int32_t* origin, uint64_t* keys, int32_t* icoords, int32_t* err_flag, void* stream) {
+    return launch_voxel_keys(points, ld, n, inv_voxel, stats, shift_to_min, batch_index, origin, keys, icoords, err_flag, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -207,18 +215,15 @@ __global__ __launch_bounds__(256) void emit_unique(const uint64_t* __restrict__ 
     if (j == n - 1 && seg_start) seg_start[excl[j] + f] = (int32_t)n;
 }
 
-int scan_exclusive_i32(const int* in, int* out, int64_t n_cap, const int* n_dev, int* total_dev, void* ws,
-                       size_t ws_bytes, hipStream_t st);
-size_t scan_ws_bytes(int64_t n);
-
-size_t unique_ws_bytes(int64_t n_cap) {
+static size_t unique_ws_bytes(int64_t n_cap) {
     return 2 * align_up((size_t)n_cap * sizeof(int), 256) + scan_ws_bytes(n_cap);
 }
+extern "C" size_t sd3d_unique_ws_bytes(int64_t n_cap) { return unique_ws_bytes(n_cap > 0 ? n_cap : 1); }
 
-int launch_unique_sorted(const uint64_t* keys, const uint32_t* src_idx, int64_t n_cap, const int* n_dev, int shift,
-                         uint64_t* ukeys, int32_t* seg_start, int32_t* map, int32_t* n_unique_dev, void* ws,
-                         size_t ws_bytes, const float* clip_stats, float clip_inv_voxel, int clip_level, int clip_min_shape,
-                         hipStream_t st) {
+extern "C" int sd3d_unique_sorted(const uint64_t* keys, const uint32_t* src_idx, int64_t n_cap, const int* n_dev, int shift, uint64_t* ukeys,
+                                  int32_t* seg_start, int32_t* map, int32_t* n_unique_dev, void* ws, size_t ws_bytes, const float* clip_stats,
+                                  float clip_inv_voxel, int clip_level, int clip_min_shape, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     ExtentClip clip;
     clip.stats = clip_stats; clip.inv_voxel = clip_inv_voxel; clip.level = clip_level; clip.min_shape = clip_min_shape;
     if (n_cap <= 0) return sd3d_set_error(SD3D_ERR_ARG, "unique_sorted: n_cap <= 0");
@@ -241,7 +246,7 @@ int launch_unique_sorted(const uint64_t* keys, const uint32_t* src_idx, int64_t 
 // All coarser levels of a scene from its sorted level-0 keys in FOUR launches (mark, the two scan launches over the levels' flag rows
 // back to back, emit) instead of four per level: level l's voxels are the runs of (Morton >> 3 l); a run boundary at level l + 1 is one at
 // level l, so id_l(i) = (number of level-l heads among rows <= i) - 1 and the parent of level-(l - 1) voxel id_{l-1}(i) is id_l(i).  The
-// keys, parents and counts are those of launch_unique_sorted called level after level (shift 3 each); no extent clip (MinkowskiEngine
+// keys, parents and counts are those of sd3d_unique_sorted called level after level (shift 3 each); no extent clip (MinkowskiEngine
 // semantics).  The chain before a scene's first host synchronisation is bound by its number of dependent launches, not by their work.
 // ---------------------------------------------------------------------------------------------
 #define UL_MAX 7
@@ -276,12 +281,16 @@ __global__ __launch_bounds__(256) void emit_levels(const ULParams P, const int* 
     }
     if (i == n - 1) P.counts[l - 1] = id + 1;
 }
-size_t unique_levels_ws_bytes(int64_t n_cap, int n_extra) {
+static size_t unique_levels_ws_bytes(int64_t n_cap, int n_extra) {
     const int64_t tot = n_cap * n_extra;
     return 2 * align_up((size_t)tot * sizeof(int), 256) + scan_ws_bytes(tot) + 256;
 }
-int launch_unique_levels(const uint64_t* keys, int64_t n_cap, const int* n_dev, int n_extra, uint64_t* const* ukeys, int32_t* const* parents,
-                         int32_t* counts, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" size_t sd3d_unique_levels_ws_bytes(int64_t n_cap, int n_extra) {
+    return unique_levels_ws_bytes(n_cap > 0 ? n_cap : 1, n_extra > 0 ? n_extra : 1);
+}
+extern "C" int sd3d_unique_levels(const uint64_t* keys, int64_t n_cap, const int* n_dev, int n_extra, uint64_t* const* ukeys, int32_t* const* parents,
+                                  int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n_cap <= 0 || n_extra < 1 || n_extra > UL_MAX) return sd3d_set_error(SD3D_ERR_ARG, "unique_levels: n_cap > 0 and 1..7 coarser levels");
     if (!keys || !ukeys || !parents || !counts) return sd3d_set_error(SD3D_ERR_ARG, "unique_levels: null pointer");
     if (ws_bytes < unique_levels_ws_bytes(n_cap, n_extra)) return sd3d_set_error(SD3D_ERR_WS, "unique_levels workspace too small");
@@ -308,7 +317,7 @@ int launch_unique_levels(const uint64_t* keys, int64_t n_cap, const int* n_dev, 
 // Round 5: EVERY level of a scene - the level-0 unique (keys, segment starts, point -> voxel map) and all coarser levels (keys, parents) -
 // from the sorted POINT keys in four launches (mark, two scan launches, emit) instead of four for level 0 plus four for the rest: a
 // run boundary of (Morton >> 3 l) over the sorted point keys is a run boundary over the unique keys of any finer level, so the
-// arrays are those of launch_unique_sorted(shift 0) followed by launch_unique_levels, entry for entry.  No extent clip.
+// arrays are those of sd3d_unique_sorted(shift 0) followed by sd3d_unique_levels, entry for entry.  No extent clip.
 // ---------------------------------------------------------------------------------------------
 struct VLParams {
     const uint64_t* keys; const uint32_t* src_idx; int64_t n; int nl;                   // sorted point keys, their points; nl levels (level 0 included)
@@ -338,8 +347,8 @@ __global__ __launch_bounds__(256) void emit_all_levels(const VLParams P, const i
     }
     if (i == P.n - 1) P.counts[l] = id + 1;
 }
-int launch_voxel_levels_all(const uint64_t* keys, const uint32_t* src_idx, int64_t n, int n_levels, uint64_t* const* ukeys, int32_t* seg_start,
-                            int32_t* map, int32_t* const* parents, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t st) {
+static int launch_voxel_levels_all(const uint64_t* keys, const uint32_t* src_idx, int64_t n, int n_levels, uint64_t* const* ukeys, int32_t* seg_start,
+                                   int32_t* map, int32_t* const* parents, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t st) {
     if (n <= 0 || n_levels < 1 || n_levels > UL_MAX + 1) return sd3d_set_error(SD3D_ERR_ARG, "voxel_levels_all: n > 0 and 1..8 levels");
     if (!keys || !ukeys || !seg_start || !map || !counts || (n_levels > 1 && !parents)) return sd3d_set_error(SD3D_ERR_ARG, "voxel_levels_all: null pointer");
     if (ws_bytes < unique_levels_ws_bytes(n, n_levels)) return sd3d_set_error(SD3D_ERR_WS, "voxel_levels_all workspace too small");
@@ -359,6 +368,53 @@ int launch_voxel_levels_all(const uint64_t* keys, const uint32_t* src_idx, int64
     if (rc) return rc;
     hipLaunchKernelGGL(emit_all_levels, grid, dim3(256), 0, st, P, (const int*)flags, (const int*)excl);
     SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
+}
+extern "C" int sd3d_voxel_levels_all(const uint64_t* sorted_keys, const uint32_t* src_idx, int64_t n, int n_levels, uint64_t* const* ukeys,
+                                     int32_t* seg_start, int32_t* map, int32_t* const* parents, int32_t* counts, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    return launch_voxel_levels_all(sorted_keys, src_idx, n, n_levels, ukeys, seg_start, map, parents, counts, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// One scene from its points to every level's voxels in one call: statistics, keys, sort, all levels, (optionally) the superpoint keys.
+extern "C" size_t sd3d_voxelise_scene_ws_bytes(int64_t n, int n_levels) {
+    n = n > 0 ? n : 1;
+    size_t b = sd3d_scene_stats_ws_bytes();
+    const size_t c[3] = {sort_ws_bytes(n), unique_ws_bytes(n), unique_levels_ws_bytes(n, n_levels > 1 ? n_levels : 1)};
+    for (size_t v : c) b = v > b ? v : b;
+    return b;
+}
+extern "C" int sd3d_voxelise_scene(const sd3d_voxelise_desc* d, int* sorted_in_a, void* stream) {
+    if (!d || !sorted_in_a || !d->points || !d->stats || !d->origin || !d->keys_a || !d->keys_b || !d->vals_a || !d->vals_b || !d->ukeys0 ||
+        !d->seg_start || !d->inverse || !d->readback || !d->ws)
+        return sd3d_set_error(SD3D_ERR_ARG, "voxelise_scene: null pointer");
+    if (d->n <= 0 || d->n_levels < 1 || d->n_levels > 8 || (d->n_levels > 1 && (!d->ukeys || !d->parents)) || d->key_bits < 8 || d->key_bits > 64)
+        return sd3d_set_error(SD3D_ERR_ARG, "voxelise_scene: n > 0, 1..8 levels, 8..64 key bits");
+    if (d->ws_bytes < sd3d_voxelise_scene_ws_bytes(d->n, d->n_levels)) return sd3d_set_error(SD3D_ERR_ARG, "voxelise_scene: workspace too small");
+    if (d->superpoints && !d->sp_keys) return sd3d_set_error(SD3D_ERR_ARG, "voxelise_scene: superpoints without sp_keys");
+    hipStream_t st = (hipStream_t)stream;
+    const int L = d->n_levels;
+    int rc = launch_scene_stats(d->points, d->ld, d->n, d->stats, d->ws, d->ws_bytes, st, d->readback, L + 2);     // (zeroes the read-back array too)
+    if (rc) return rc;
+    rc = launch_voxel_keys(d->points, d->ld, d->n, d->inv_voxel, d->stats, d->shift_to_min, 0, d->origin, d->keys_a, d->icoords, d->readback + L, st);
+    if (rc) return rc;
+    int landed = 0;
+    rc = sort_pairs_u64(d->keys_a, nullptr, d->keys_b, d->vals_b, d->n, 0, d->key_bits, d->ws, d->ws_bytes, st, d->vals_a, &landed);
+    if (rc) return rc;
+    *sorted_in_a = landed;
+    const uint64_t* skeys = landed ? d->keys_a : d->keys_b;
+    const uint32_t* sidx = landed ? d->vals_a : d->vals_b;
+    {   // every level from the sorted point keys in four launches (level 0 and the coarser levels used to be four each)
+        uint64_t* uk[9];
+        uk[0] = d->ukeys0;
+        for (int l = 1; l < L; ++l) uk[l] = d->ukeys[l - 1];
+        rc = launch_voxel_levels_all(skeys, sidx, d->n, L, uk, d->seg_start, d->inverse, d->parents, d->readback, d->ws, d->ws_bytes, st);
+        if (rc) return rc;
+    }
+    if (d->superpoints) {
+        rc = launch_i64_to_sortkey_checked_max(d->superpoints, d->n, d->sp_keys, d->sp_bits, d->readback + L, 4, d->readback + L + 1, st, 0);
+        if (rc) return rc;
+    }
     return SD3D_OK;
 }
 
@@ -392,7 +448,8 @@ __device__ static inline int hash_lookup(const uint64_t* __restrict__ tkeys, con
     return -1;
 }
 
-int launch_hash_build(const uint64_t* ukeys, int64_t n, uint64_t* tkeys, int32_t* tvals, int64_t capacity, hipStream_t st) {
+extern "C" int sd3d_hash_build(const uint64_t* ukeys, int64_t n, uint64_t* tkeys, int32_t* tvals, int64_t capacity, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (capacity <= 0 || (capacity & (capacity - 1)) || capacity < n + 1)
         return sd3d_set_error(SD3D_ERR_ARG, "hash_build: capacity must be a power of two > n");
     (void)hipMemsetAsync(tkeys, 0xFF, (size_t)capacity * sizeof(uint64_t), st);
@@ -486,8 +543,10 @@ __global__ __launch_bounds__(256) void kernel_map_mirrored_kernel(const uint64_t
     }
 }
 
-int launch_kernel_map(const uint64_t* okeys, int64_t n_out, const uint64_t* tkeys, const int32_t* tvals, int64_t capacity,
-                      const int8_t* offs_dev, int K, int mirrored, int32_t* nbr, int32_t* pair_count, hipStream_t st) {
+extern "C" int sd3d_kernel_map(const uint64_t* okeys, int64_t n_out, const uint64_t* tkeys, const int32_t* tvals, int64_t capacity,
+                               const int8_t* offs_dev, int K, int mirrored, int32_t* nbr, int32_t* pair_count, void* stream) {
+    if (capacity <= 0 || (capacity & (capacity - 1))) return sd3d_set_error(SD3D_ERR_ARG, "kernel_map: capacity must be a power of two");
+    hipStream_t st = (hipStream_t)stream;
     if (n_out <= 0 || K <= 0) return SD3D_OK;
     if (mirrored) {
         if (!(K & 1)) return sd3d_set_error(SD3D_ERR_ARG, "kernel_map: the mirrored variant needs an odd, centred kernel");
@@ -555,7 +614,7 @@ __device__ __forceinline__ void kmap_top_body(const uint64_t* __restrict__ keys,
 }
 
 // cinfo[p] = {first child row, child mask} of every coarse voxel: the thread of a parent's FIRST child walks its (<= 8) siblings.
-// The same launch writes the level pair's stride-2 maps (launch_stride_maps' tables, entry for entry) when asked to: every fine voxel
+// The same launch writes the level pair's stride-2 maps (sd3d_stride_maps' tables, entry for entry) when asked to: every fine voxel
 // its column of nbr_up [8, n_fine] (its parent in the row of its own kernel offset, -1 in the other seven), every first child the
 // column of its parent in nbr_down [8, n_coarse] - each entry written by the thread that owns it, nothing to pre-fill.
 __device__ __forceinline__ void child_info_body(const uint64_t* __restrict__ fkeys, const int32_t* __restrict__ parent, int64_t n_fine,
@@ -659,7 +718,7 @@ __global__ __launch_bounds__(256) void kmap_hier_kernel(const KHParams P) {
     }
 }
 
-size_t kernel_maps_hier_ws_bytes(int n_levels, const int64_t* n) {
+extern "C" size_t sd3d_kernel_maps_hier_ws_bytes(int n_levels, const int64_t* n) {
     size_t b = 256;
     for (int l = 1; l < n_levels; ++l) b += align_up((size_t)n[l] * sizeof(int2), 256);
     return b;
@@ -668,11 +727,14 @@ size_t kernel_maps_hier_ws_bytes(int n_levels, const int64_t* n) {
 // enumeration order for every level); inv27: HOST table (pd index as above -> row of offs3).  pair_counts: NULL or device int32
 // [(n_levels + 1) * 64], zeroed: 64 partial counters per table (levels 0 .. n_levels - 1, then the 5^3 table).
 // nbr_down[l] [8, n_{l+1}] / nbr_up[l] [8, n_l] (l < n_levels - 1): optional stride-2 maps of the level pair (NULL arrays or entries: not built).
-int launch_kernel_maps_hier(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n, int32_t* const* nbr3,
-                            int32_t* nbr5, const int8_t* offs3, const int8_t* offs5, const int8_t* inv27, int32_t* pair_counts,
-                            const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sd3d_kernel_maps_hier(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n, int32_t* const* nbr3,
+                                     int32_t* nbr5, const int8_t* offs3, const int8_t* offs5, const int8_t* inv27, int32_t* pair_counts,
+                                     const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    if (!keys || !parent || !n || !nbr3 || !offs3 || !inv27 || (nbr5 && !offs5)) return sd3d_set_error(SD3D_ERR_ARG, "kernel_maps_hier: null pointer");
+    hipStream_t st = (hipStream_t)stream;
     if (n_levels < 1 || n_levels > 8) return sd3d_set_error(SD3D_ERR_ARG, "kernel_maps_hier: 1..8 levels");
-    if (ws_bytes < kernel_maps_hier_ws_bytes(n_levels, n)) return sd3d_set_error(SD3D_ERR_WS, "kernel_maps_hier: workspace too small");
+    if (ws_bytes < sd3d_kernel_maps_hier_ws_bytes(n_levels, n)) return sd3d_set_error(SD3D_ERR_WS, "kernel_maps_hier: workspace too small");
     for (int l = 0; l < n_levels; ++l)
         if (n[l] <= 0 || !keys[l] || !nbr3[l] || (l + 1 < n_levels && !parent[l])) return sd3d_set_error(SD3D_ERR_ARG, "kernel_maps_hier: empty level or null pointer");
     int2* cinfo[8] = {};
@@ -730,8 +792,9 @@ __global__ __launch_bounds__(256) void stride_maps_kernel(const uint64_t* __rest
     if (nbr_up) nbr_up[(int64_t)k * n_fine + j] = p;
 }
 
-int launch_stride_maps(const uint64_t* fkeys, const int32_t* parent, int64_t n_fine, int64_t n_coarse, const int32_t* perm8,
-                       int32_t* nbr_down, int32_t* nbr_up, hipStream_t st) {
+extern "C" int sd3d_stride_maps(const uint64_t* fkeys, const int32_t* parent, int64_t n_fine, int64_t n_coarse, const int32_t* perm8,
+                                int32_t* nbr_down, int32_t* nbr_up, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (nbr_down) (void)hipMemsetAsync(nbr_down, 0xFF, (size_t)8 * n_coarse * sizeof(int32_t), st);
     if (nbr_up) (void)hipMemsetAsync(nbr_up, 0xFF, (size_t)8 * n_fine * sizeof(int32_t), st);
     if (n_fine > 0)
@@ -836,8 +899,9 @@ __global__ __launch_bounds__(256) void voxel_mean_batch_kernel(const VMBatch b, 
                     out, ld_out);
 }
 
-int launch_voxel_mean(const float* pts, int ld_pts, const float* f2d, int F, int mode, const float* stats, int64_t n_points,
-                      const uint32_t* sidx, const int32_t* seg_start, int64_t n_vox, float* out, int ld_out, hipStream_t st) {
+extern "C" int sd3d_voxel_mean(const float* pts, int ld_pts, const float* f2d, int F, int mode, const float* stats, int64_t n_points,
+                               const uint32_t* sidx, const int32_t* seg_start, int64_t n_vox, float* out, int ld_out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (n_vox <= 0) return SD3D_OK;
     if (mode != 1 && !f2d) return sd3d_set_error(SD3D_ERR_ARG, "voxel_mean: 2D features missing");
     hipLaunchKernelGGL(voxel_mean_kernel, dim3((unsigned)cdiv(n_vox, 4)), dim3(256), 0, st, pts, ld_pts, f2d, F, mode, stats,
@@ -846,8 +910,10 @@ int launch_voxel_mean(const float* pts, int ld_pts, const float* f2d, int F, int
     return SD3D_OK;
 }
 
-int launch_voxel_mean_batch(const sd3d_scene_src* scenes, int n_scenes, int F, int mode, const uint64_t* ukeys, const uint32_t* sidx,
-                            const int32_t* seg_start, int64_t n_vox, float* out, int ld_out, hipStream_t st) {
+extern "C" int sd3d_voxel_mean_batch(const sd3d_scene_src* scenes, int n_scenes, int F, int mode, const uint64_t* ukeys, const uint32_t* sidx,
+                                     const int32_t* seg_start, int64_t n_vox, float* out, int ld_out, void* stream) {
+    if (!scenes) return sd3d_set_error(SD3D_ERR_ARG, "voxel_mean_batch: scenes is NULL");
+    hipStream_t st = (hipStream_t)stream;
     if (n_vox <= 0) return SD3D_OK;
     if (n_scenes <= 0 || n_scenes > SD3D_MAX_BATCH) return sd3d_set_error(SD3D_ERR_ARG, "voxel_mean_batch: 1..16 scenes per call");
     VMBatch b;
@@ -974,8 +1040,10 @@ __global__ __launch_bounds__(256) void segment_starts_batch_kernel(const uint64_
     for (int64_t s = prev + 1; s <= cur; ++s) start[s] = (int32_t)j;
 }
 
-int launch_segment_starts_batch(const uint64_t* sorted_ids, int64_t n, int64_t S, const int32_t* off_host, int n_scenes, int32_t* start,
-                                hipStream_t st) {
+extern "C" int sd3d_segment_starts_batch(const uint64_t* sorted_ids, int64_t n, int64_t S, const int32_t* off_host, int n_scenes, int32_t* start,
+                                         void* stream) {
+    if (!off_host) return sd3d_set_error(SD3D_ERR_ARG, "segment_starts_batch: id_off is NULL");
+    hipStream_t st = (hipStream_t)stream;
     if (n_scenes <= 0 || n_scenes > SD3D_MAX_BATCH) return sd3d_set_error(SD3D_ERR_ARG, "segment_starts_batch: 1..16 scenes per call");
     SegOff so;
     so.n = n_scenes;
@@ -985,15 +1053,16 @@ int launch_segment_starts_batch(const uint64_t* sorted_ids, int64_t n, int64_t S
     return SD3D_OK;
 }
 
-int launch_segment_starts(const uint64_t* sorted_ids, int64_t n, int64_t S, int32_t* start, hipStream_t st) {
+extern "C" int sd3d_segment_starts(const uint64_t* sorted_ids, int64_t n, int64_t S, int32_t* start, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(segment_starts_kernel, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, st, sorted_ids, n, S, start);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
 
-int launch_pool_superpoints(const float* feat, int ld_feat, int C, const int32_t* inverse, const int32_t* icoords,
-                            float voxel_size, const uint32_t* sidx, const int32_t* start, int64_t S, float* out_feat,
-                            float* out_pos, hipStream_t st) {
+extern "C" int sd3d_pool_superpoints(const float* feat, int ld_feat, int C, const int32_t* inverse, const int32_t* icoords, float voxel_size,
+                                     const uint32_t* sidx, const int32_t* start, int64_t S, float* out_feat, float* out_pos, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (S <= 0) return SD3D_OK;
     if ((C & 3) || C > 96 || (ld_feat & 3))
         return sd3d_set_error(SD3D_ERR_ARG, "pool_superpoints: C must be a multiple of 4 and <= 96");

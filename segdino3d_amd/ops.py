@@ -11,6 +11,7 @@ import threading
 from collections import OrderedDict as _collections_od
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -373,7 +374,12 @@ def voxel_levels_all(skeys, sidx, n_levels: int, counts_out):
     return [uk[l] for l in range(L)], seg, inv, [par[l] for l in range(L - 1)]
 
 
-_VOX_DESC_DT = None
+_VOX_DESC_DT = np.dtype([("points", "<u8"), ("n", "<i8"), ("ld", "<i4"), ("shift_to_min", "<i4"), ("inv_voxel", "<f4"), ("key_bits", "<i4"),
+                         ("n_levels", "<i4"), ("sp_bits", "<i4"), ("stats", "<u8"), ("origin", "<u8"), ("icoords", "<u8"),
+                         ("keys_a", "<u8"), ("keys_b", "<u8"), ("vals_a", "<u8"), ("vals_b", "<u8"), ("ukeys0", "<u8"),
+                         ("seg_start", "<u8"), ("inverse", "<u8"), ("ukeys", "<u8"), ("parents", "<u8"), ("readback", "<u8"),
+                         ("superpoints", "<u8"), ("sp_keys", "<u8"), ("ws", "<u8"), ("ws_bytes", "<u8")], align=True)      # sd3d_voxelise_desc
+assert _VOX_DESC_DT.itemsize == 176, _VOX_DESC_DT.itemsize
 
 
 def voxelise_scene(points, inv_voxel: float, shift_to_min: bool, key_bits: int, n_levels: int, superpoints=None, sp_bits: int = 64):
@@ -381,15 +387,6 @@ def voxelise_scene(points, inv_voxel: float, shift_to_min: bool, key_bits: int, 
     (segment starts, point -> voxel map) + unique_levels + keys_from_i64(max_out) give when called one after the other - the same kernels
     in the same order, issued from C instead of from ~10 Python calls in front of everything else the scene needs.
     -> dict(stats, origin, icoords, skeys, sidx, ukeys [L x [N]], seg_start, inverse, parents [L-1 x [N]], readback int32 [L + 2], sp_keys | None)"""
-    global _VOX_DESC_DT
-    import numpy as np
-    if _VOX_DESC_DT is None:
-        _VOX_DESC_DT = np.dtype([("points", "<u8"), ("n", "<i8"), ("ld", "<i4"), ("shift_to_min", "<i4"), ("inv_voxel", "<f4"), ("key_bits", "<i4"),
-                                 ("n_levels", "<i4"), ("sp_bits", "<i4"), ("stats", "<u8"), ("origin", "<u8"), ("icoords", "<u8"),
-                                 ("keys_a", "<u8"), ("keys_b", "<u8"), ("vals_a", "<u8"), ("vals_b", "<u8"), ("ukeys0", "<u8"),
-                                 ("seg_start", "<u8"), ("inverse", "<u8"), ("ukeys", "<u8"), ("parents", "<u8"), ("readback", "<u8"),
-                                 ("superpoints", "<u8"), ("sp_keys", "<u8"), ("ws", "<u8"), ("ws_bytes", "<u8")], align=True)
-        assert _VOX_DESC_DT.itemsize == 176, _VOX_DESC_DT.itemsize
     lib = _lib.load()
     p, ld = _rows(points, "points")
     N, dev, L = points.shape[0], points.device, int(n_levels)
@@ -498,15 +495,16 @@ def voxel_mean(points, feats2d, mode, stats, sorted_idx, seg_start, n_vox, ld_ou
     return out
 
 
+_SCENE_SRC_DT = np.dtype([("points", "<u8"), ("feats2d", "<u8"), ("stats", "<u8"), ("point_off", "<i8"), ("n_points", "<i8"),
+                          ("ld_points", "<i4"), ("pad_", "<i4")], align=True)                                              # sd3d_scene_src
+assert _SCENE_SRC_DT.itemsize == 48
+
+
 def voxel_mean_batch(scenes, mode, ukeys, sorted_idx, seg_start, n_vox, ld_out):
     """scenes: [(points [N_i, >=6], feats2d [N_i, F] | None, stats [9], point_off)] of one batch (sparse.BatchSceneMaps);
     one launch over the voxels of all scenes."""
-    import numpy as np
     lib = _lib.load()
-    dt = np.dtype([("points", "<u8"), ("feats2d", "<u8"), ("stats", "<u8"), ("point_off", "<i8"), ("n_points", "<i8"),
-                   ("ld_points", "<i4"), ("pad_", "<i4")], align=True)
-    assert dt.itemsize == 48
-    tab = np.zeros(len(scenes), dtype=dt)
+    tab = np.zeros(len(scenes), dtype=_SCENE_SRC_DT)
     F = 0
     for i, (pts, f2d, stats, off) in enumerate(scenes):
         p, ld = _rows(pts, "points")
@@ -698,7 +696,10 @@ def pair_lists(nbr, n_pairs, center=-1, direct=False):
 # Sparse convolutions run pair-major (pair_conv) whenever the caller hands over the table's PairLists;
 # SD3D_PAIR_CONV=0 keeps the output-stationary gather_gemm kernels (tuning / ablation).
 PAIR_CONV = _os.environ.get("SD3D_PAIR_CONV", "1") != "0"
-_PAIR_DESC_DT = None
+_PAIR_DESC_DT = np.dtype([("nbr", "<u8"), ("pos", "<u8"), ("in_idx", "<u8"), ("tile_k", "<u8"), ("rlist", "<u8"), ("out_idx", "<u8"),
+                          ("M", "<i8"), ("p_cap", "<i8"), ("K", "<i4"), ("center", "<i4"), ("rl_stride", "<i4"), ("meta", "<i4")],
+                         align=True)                                                                                       # sd3d_pair_table_desc
+assert _PAIR_DESC_DT.itemsize == 80
 
 
 PAIR_CHAINED = -2          # SD3D_PAIR_CHAINED: `center` value of a chained table (include/segdino3d_hip.h)
@@ -708,13 +709,6 @@ def pair_lists_batch(tables):
     """tables: list of (nbr int32 [K, M], n_pairs[, center[, direct[, lean]]]) -> list of PairLists, built by ONE launch set
     (csrc/pair_gemm.hip: count, scan, fill, per-row lists).  center = PAIR_CHAINED: chained lists (a stride-1 table of a voxel set
     onto itself, odd symmetric kernel): the entries of a row's mirror groups and its centre share partial products."""
-    global _PAIR_DESC_DT
-    import numpy as np
-    if _PAIR_DESC_DT is None:
-        _PAIR_DESC_DT = np.dtype([("nbr", "<u8"), ("pos", "<u8"), ("in_idx", "<u8"), ("tile_k", "<u8"), ("rlist", "<u8"), ("out_idx", "<u8"),
-                                  ("M", "<i8"), ("p_cap", "<i8"), ("K", "<i4"), ("center", "<i4"), ("rl_stride", "<i4"), ("meta", "<i4")],
-                                 align=True)
-        assert _PAIR_DESC_DT.itemsize == 80
     lib = _lib.load()
     out = []
     for start in range(0, len(tables), 16):
@@ -795,7 +789,10 @@ def pair_conv(x, wt, pairs, x2=None, scale=None, shift=None, res=None, act=None,
     return out
 
 
-_LINEAR_JOB_DT = None
+_LINEAR_JOB_DT = np.dtype([("in0", "<u8"), ("in1", "<u8"), ("wt", "<u8"), ("shift", "<u8"), ("res", "<u8"), ("out", "<u8"),
+                           ("M", "<i8"), ("ld0", "<i4"), ("C0", "<i4"), ("ld1", "<i4"), ("Cin", "<i4"), ("Cout", "<i4"),
+                           ("ld_res", "<i4"), ("ld_out", "<i4"), ("act", "<i4")], align=True)                              # sd3d_linear_job
+assert _LINEAR_JOB_DT.itemsize == 88
 
 
 def dense_code(rows: int, cin: int, cout: int) -> int:
@@ -819,8 +816,6 @@ def linear_group(jobs, force_small=False):
     (gather_gemm_lds_group_kernel: same bits).  Mixed sizes, the bf16 decoder scope on >= BF16_MIN_ROWS rows and the
     instrumentation hook run one by one.
     force_small: the rows are several scenes' few-hundred-row tensors back to back - always the group kernel."""
-    global _LINEAR_JOB_DT
-    import numpy as np
     if GG_HOOK is not None:
         if force_small:
             return [gather_gemm(x, w, x2=x2, shift=b, act=act, res=res, nt=-1, exact=True) for (x, w, b, act, res, x2) in jobs]
@@ -837,11 +832,6 @@ def linear_group(jobs, force_small=False):
                                                    for (x, w, *_r) in jobs)
     if not all(small) and not large:
         return [gather_gemm(x, w, x2=x2, shift=b, act=act, res=res) for (x, w, b, act, res, x2) in jobs]
-    if _LINEAR_JOB_DT is None:
-        _LINEAR_JOB_DT = np.dtype([("in0", "<u8"), ("in1", "<u8"), ("wt", "<u8"), ("shift", "<u8"), ("res", "<u8"), ("out", "<u8"),
-                                   ("M", "<i8"), ("ld0", "<i4"), ("C0", "<i4"), ("ld1", "<i4"), ("Cin", "<i4"), ("Cout", "<i4"),
-                                   ("ld_res", "<i4"), ("ld_out", "<i4"), ("act", "<i4")], align=True)
-        assert _LINEAR_JOB_DT.itemsize == 88
     lib = _lib.load()
     outs = []
     for start in range(0, len(jobs), 8):
@@ -1086,20 +1076,16 @@ def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, out=N
     return out
 
 
-_ATTN_JOB_DT = None
+_ATTN_JOB_DT = np.dtype([("q0", "<u8"), ("q1", "<u8"), ("k0", "<u8"), ("k1", "<u8"), ("v", "<u8"), ("bits", "<u8"), ("out", "<u8"),
+                         ("ldq0", "<i4"), ("ldq1", "<i4"), ("ldk0", "<i4"), ("ldk1", "<i4"), ("ldv", "<i4"), ("ldo", "<i4"),
+                         ("Lq", "<i4"), ("Lk", "<i4")], align=True)                                                        # sd3d_attn_job
+assert _ATTN_JOB_DT.itemsize == 88
 
 
-def attention_batch(jobs, num_heads, scale):
-    """jobs: list of (q, k, v, mask_bits | None, q2 | None, k2 | None, out) - the same attention for several scenes in ONE launch
-    (sd3d_attention_batch): per scene the rows are the bits of `attention` on that scene alone."""
-    global _ATTN_JOB_DT
-    import numpy as np
+def _attn_job_table(jobs, num_heads, name, strided_out):
+    """Validates the jobs of `attention_batch` / `attention_parts` (`name`: the caller, for the messages) and fills their sd3d_attn_job
+    table -> (table, bytes of split workspace).  strided_out: `out` may be a view with strided rows; otherwise it must be contiguous."""
     lib = _lib.load()
-    if _ATTN_JOB_DT is None:
-        _ATTN_JOB_DT = np.dtype([("q0", "<u8"), ("q1", "<u8"), ("k0", "<u8"), ("k1", "<u8"), ("v", "<u8"), ("bits", "<u8"), ("out", "<u8"),
-                                 ("ldq0", "<i4"), ("ldq1", "<i4"), ("ldk0", "<i4"), ("ldk1", "<i4"), ("ldv", "<i4"), ("ldo", "<i4"),
-                                 ("Lq", "<i4"), ("Lk", "<i4")], align=True)
-        assert _ATTN_JOB_DT.itemsize == 88
     tab = np.zeros(len(jobs), dtype=_ATTN_JOB_DT)
     nb = 0
     for i, (q, k, v, bits, q2, k2, out) in enumerate(jobs):
@@ -1112,14 +1098,27 @@ def attention_batch(jobs, num_heads, scale):
             pk2, ldk2 = _rows(k2, "k2")
         Lq, Lk = q.shape[0], k.shape[0]
         if q.shape[1] != num_heads * 32 or v.shape[1] != num_heads * 32:
-            raise ValueError("attention_batch: head slices must be 32 channels wide")
+            raise ValueError(f"{name}: head slices must be 32 channels wide")
         if bits is not None and tuple(bits.shape) != (Lq, (Lk + 31) // 32):
-            raise ValueError("attention_batch: mask bits shape mismatch")
-        if tuple(out.shape) != (Lq, num_heads * 32) or not out.is_contiguous() or out.dtype != torch.float32:
-            raise ValueError("attention_batch: `out` must be a contiguous fp32 [Lq, H * 32] tensor")
-        tab[i] = (pq, pq2, pk, pk2, pv, 0 if bits is None else _ptr(bits, torch.int32, "mask_bits"), out.data_ptr(), ldq, ldq2, ldk, ldk2, ldv,
-                  out.stride(0), Lq, Lk)
+            raise ValueError(f"{name}: mask bits shape mismatch")
+        if strided_out:
+            po, ldo = _rows(out, "out")
+            if out.shape[0] != Lq or out.shape[1] != num_heads * 32:
+                raise ValueError(f"{name}: `out` must be fp32 [Lq, H * 32] rows")
+        else:
+            if tuple(out.shape) != (Lq, num_heads * 32) or not out.is_contiguous() or out.dtype != torch.float32:
+                raise ValueError(f"{name}: `out` must be a contiguous fp32 [Lq, H * 32] tensor")
+            po, ldo = out.data_ptr(), out.stride(0)
+        tab[i] = (pq, pq2, pk, pk2, pv, 0 if bits is None else _ptr(bits, torch.int32, "mask_bits"), po, ldq, ldq2, ldk, ldk2, ldv, ldo, Lq, Lk)
         nb += lib.sd3d_attention_ws_bytes(Lq, num_heads)
+    return tab, nb
+
+
+def attention_batch(jobs, num_heads, scale):
+    """jobs: list of (q, k, v, mask_bits | None, q2 | None, k2 | None, out) - the same attention for several scenes in ONE launch
+    (sd3d_attention_batch): per scene the rows are the bits of `attention` on that scene alone."""
+    lib = _lib.load()
+    tab, nb = _attn_job_table(jobs, num_heads, "attention_batch", strided_out=False)
     ws = _WS6.get(nb, jobs[0][0].device)
     _lib.check(lib.sd3d_attention_batch(len(jobs), tab.ctypes.data, num_heads, float(scale), 1 if bf16_decoder_active() else 0,
                                         ws.data_ptr(), ws.numel(), _stream()), "attention_batch")
@@ -1129,36 +1128,10 @@ def attention_parts(jobs, num_heads, scale):
     """`attention_batch` WITHOUT the pass that combines the key splits (sd3d_attention_batch_parts): returns (ws, [(ksplit, part_off)])
     - scene i's rows are final in its `out` where ksplit == 1, else its partial softmax states wait at ws (a uint8 tensor) + part_off
     floats for the consumer that combines them (rowchain MERGE).  jobs as in `attention_batch`."""
-    global _ATTN_JOB_DT
     import ctypes as C
-    import numpy as np
     lib = _lib.load()
-    if _ATTN_JOB_DT is None:
-        _ATTN_JOB_DT = np.dtype([("q0", "<u8"), ("q1", "<u8"), ("k0", "<u8"), ("k1", "<u8"), ("v", "<u8"), ("bits", "<u8"), ("out", "<u8"),
-                                 ("ldq0", "<i4"), ("ldq1", "<i4"), ("ldk0", "<i4"), ("ldk1", "<i4"), ("ldv", "<i4"), ("ldo", "<i4"),
-                                 ("Lq", "<i4"), ("Lk", "<i4")], align=True)
-        assert _ATTN_JOB_DT.itemsize == 88
     n = len(jobs)
-    tab = np.zeros(n, dtype=_ATTN_JOB_DT)
-    nb = 0
-    for i, (q, k, v, bits, q2, k2, out) in enumerate(jobs):
-        pq, ldq = _rows(q, "q")
-        pk, ldk = _rows(k, "k")
-        pv, ldv = _rows(v, "v")
-        pq2 = pk2 = ldq2 = ldk2 = 0
-        if q2 is not None:
-            pq2, ldq2 = _rows(q2, "q2")
-            pk2, ldk2 = _rows(k2, "k2")
-        Lq, Lk = q.shape[0], k.shape[0]
-        if q.shape[1] != num_heads * 32 or v.shape[1] != num_heads * 32:
-            raise ValueError("attention_parts: head slices must be 32 channels wide")
-        if bits is not None and tuple(bits.shape) != (Lq, (Lk + 31) // 32):
-            raise ValueError("attention_parts: mask bits shape mismatch")
-        po, ldo = _rows(out, "out")
-        if out.shape[0] != Lq or out.shape[1] != num_heads * 32:
-            raise ValueError("attention_parts: `out` must be fp32 [Lq, H * 32] rows")
-        tab[i] = (pq, pq2, pk, pk2, pv, 0 if bits is None else _ptr(bits, torch.int32, "mask_bits"), po, ldq, ldq2, ldk, ldk2, ldv, ldo, Lq, Lk)
-        nb += lib.sd3d_attention_ws_bytes(Lq, num_heads)
+    tab, nb = _attn_job_table(jobs, num_heads, "attention_parts", strided_out=True)
     ws = _WS6.get(nb, jobs[0][0].device)                 # consumed by the next launch on this stream, before the next attention refills it
     ks = (C.c_int32 * n)()
     off = (C.c_int64 * n)()
@@ -1485,7 +1458,6 @@ class _HostPool:
                 self.free.append(buf)
 
     def bool_array(self, shape):
-        import numpy as np
         need = int(np.prod(shape))
         if need < (1 << 20):                                     # small arrays: the allocator's own free lists do this already
             return np.empty(shape, dtype=np.bool_)
@@ -1506,7 +1478,6 @@ def unpack_bits_host(packed, n_points: int):
     """HOST arrays: packed uint8 [n, ceil(N / 8)] (numpy) -> bool [n, N] (pageable; large ones come from a recycling pool, `_HostPool`).
     Runs in the C library with the GIL released (sd3d_unpack_bits_host): the other scene threads keep issuing while this one expands
     its masks."""
-    import numpy as np
     packed = np.ascontiguousarray(packed, dtype=np.uint8)
     n, nb = packed.shape
     if nb != (n_points + 7) // 8:
@@ -1537,7 +1508,6 @@ _STAGING = PinnedStaging()
 def to_host_arrays(tensors):
     """Device tensors -> pageable numpy arrays through ONE pinned staging buffer: asynchronous copies, one polled wait (the issue
     baton goes to another scene's thread meanwhile), then host copies out of the staging area."""
-    import numpy as np
     offs, total = [], 0
     for t in tensors:
         total = (total + 63) // 64 * 64
