@@ -83,6 +83,50 @@ def _range6(lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
     return torch.cat([lo.reshape(3), hi.reshape(3)]).float().contiguous()
 
 
+# ---- the rows of B scenes back to back (the batched op set and the row-chain path) ----
+def _offsets(ts, extra=0):
+    """Row offsets [0, n_0, n_0 + n_1, ...] of tensors laid back to back (`extra` rows appended to each)."""
+    offs = [0]
+    for t in ts:
+        offs.append(offs[-1] + t.shape[0] + extra)
+    return offs
+
+
+def _cat(ts):
+    return ts[0].contiguous() if len(ts) == 1 else torch.cat(list(ts)).contiguous()
+
+
+def _range_table(ranges):
+    return torch.stack([_range6(lo, hi) for lo, hi in ranges]).contiguous()      # [B, 6]
+
+
+def _row_scene(offs, dev):
+    """Scene index of every row, made ON the device from host-known sizes (B fills + a concatenation): no host -> device copy and no
+    synchronising op here - a blocking call inside the issue baton stalls the other scenes' threads (measured: 114 -> 96 scenes/s)."""
+    return torch.cat([torch.full((offs[b + 1] - offs[b],), b, dtype=torch.int32, device=dev) for b in range(len(offs) - 1)])
+
+
+def _split_scenes(aux, queries, bits, q_off=None):
+    """The layers' predictions -> [(final, aux)] per scene.  q_off: the tensors hold several scenes' query rows back to back (mask logits
+    and bits: one per scene) and every scene gets its row slices; None: they are one scene's own."""
+    results = []
+    for b in range(1 if q_off is None else len(q_off) - 1):
+        if q_off is None:
+            views = list(aux)
+            hidden, mask = queries, bits
+        else:
+            q0, q1 = q_off[b], q_off[b + 1]
+            row = lambda t: None if t is None else t[q0:q1]  # noqa: E731
+            views = [dict(cls_preds=row(e["cls_preds"]), sem_preds=row(e["sem_preds"]), masks=e["masks"][b], centers=row(e["centers"]),
+                          sizes=row(e["sizes"]), scores=row(e["scores"])) for e in aux]
+            hidden, mask = queries[q0:q1], bits[b]
+        final = views.pop()
+        final["hidden_states"] = hidden
+        final["attn_mask_bits"] = mask
+        results.append((final, views))
+    return results
+
+
 class _FFNHolder(nn.Module):
     def __init__(self, d_model, hidden_dim, dropout, activation_fn):
         super().__init__()
@@ -101,10 +145,12 @@ class _FourierPE(nn.Module):
 
 
 class _EvalF:
-    """The decoder's differentiable building blocks in eval mode: straight calls into the forward kernels."""
+    """The decoder's differentiable building blocks in eval mode: straight calls into the forward kernels.  This and `_TrainF` are the
+    one-scene op sets: the rows are one scene's own, so the row family a Linear runs on (`rows`: "q" queries, "s" superpoints, "m" 2D
+    keys; `keys` of an attention) does not matter to them."""
 
     @staticmethod
-    def linear(x, w, b=None, act=None, res=None, x2=None):
+    def linear(x, w, b=None, act=None, res=None, x2=None, rows=None):
         return ops.gather_gemm(x, w, x2=x2, shift=b, act=act, res=res)
 
     @staticmethod
@@ -117,7 +163,10 @@ class _EvalF:
     def linear_ln(x, w, b, ln_w, ln_b, res=None):               # projection + residual + LayerNorm: one launch for few rows
         return ops.linear_layernorm(x, w, b, ln_w, ln_b, res=res)
 
-    attention = staticmethod(ops.attention)
+    @staticmethod
+    def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, keys=None):
+        return ops.attention(q, k, v, num_heads, scale, mask_bits=mask_bits, q2=q2, k2=k2)
+
     box_refine = staticmethod(ops.box_refine)
 
     @staticmethod
@@ -129,6 +178,10 @@ class _EvalF:
         return [t[:, c:c + width] for c in range(0, t.shape[1], width)]
 
     @staticmethod
+    def row_scene(rows):                                        # scene index of every row of a family: one scene has none
+        return None
+
+    @staticmethod
     def sine_pe_mod(xyz, rng, dim_t, axis, num, den):
         return ops.sine_pe(xyz, rng, dim_t, axis, mod_num=num, mod_den=den)
 
@@ -136,12 +189,20 @@ class _EvalF:
     def mask_logits(nq, mask_feats):                            # einsum('nd,md->nm'); fp32 in every mode: it feeds thresholds
         return ops.gather_gemm(nq, mask_feats, exact=True)
 
+    @staticmethod
+    def mask_bits(logits, S, thr):                              # attention-mask bits of the next layer: no gradient
+        return ops.mask_bits(logits.detach(), S, thr)
 
-class _TrainF:
+    @staticmethod
+    def dinox_mask_bits(bits, near):                            # `near`: per scene (ScanNetQueryDecoder._keys2d_near)
+        return ops.dinox_mask_bits(bits, near[0])
+
+
+class _TrainF(_EvalF):
     """Training mode: the same kernels as autograd nodes with HIP backward passes (segdino3d_amd/train_dec.py)."""
 
     @staticmethod
-    def linear(x, w, b=None, act=None, res=None, x2=None):
+    def linear(x, w, b=None, act=None, res=None, x2=None, rows=None):
         from . import train_dec
         return train_dec.linear(x, w, b, act=act, res=res, x2=x2)
 
@@ -173,7 +234,7 @@ class _TrainF:
         return train_dec.layernorm(_TrainF.dropout(train_dec.linear(x, w, b)), ln_w, ln_b, res=res)
 
     @staticmethod
-    def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None):
+    def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, keys=None):
         from . import train_dec
         p = getattr(_F_TLS, "p", 0.0)
         if p > 0.0:                                             # nn.MultiheadAttention(dropout=p): dropout on the probabilities
@@ -196,9 +257,70 @@ class _TrainF:
         return train_dec.linear(nq, mask_feats, exact=True)
 
 
+class _BatchF(_EvalF):
+    """The op set of B = 2..16 scenes in evaluation, their rows back to back; made per call, it holds the call's row layout.
+    Everything row-wise (every Linear, LayerNorm, positional encoding, box refinement) runs ONCE over all scenes' rows - B x fewer
+    launches per scene - on the kernel ONE scene's rows would get (`ScanNetQueryDecoder._batchable` made sure all scenes agree on it);
+    what couples the rows of a scene (the three attentions, mask bits, the 2D-query masks) runs per scene on row slices; the B
+    mask-logit products are one grouped launch.  A scene gets the bits of its own forward through `_EvalF`."""
+
+    def __init__(self, xs, q_in, q2d_feat, ranges):
+        dev = xs[0].device
+        self.off = {"s": _offsets(xs), "q": _offsets(q_in)}      # row offsets per family: superpoints, queries, 2D keys (+ the dummy key)
+        if q2d_feat is not None:
+            self.off["m"] = _offsets(q2d_feat, 1)
+        self.rng = _range_table(ranges)
+        self._row_scene = {f: _row_scene(self.off[f], dev) for f in "sq"}
+        # ops.dense_code takes one scene's row count.  In the bf16 mode the superpoint-side families take the bf16 kernel exactly
+        # when one scene's rows would (>= BF16_MIN_ROWS), query rows never do
+        self._rows = {f: o[1] for f, o in self.off.items()}
+        self._exact = {f: f == "q" or n < ops.BF16_MIN_ROWS for f, n in self._rows.items()}
+        self._slices = {f: [slice(r0, r1) for r0, r1 in zip(o, o[1:])] for f, o in self.off.items()}      # each scene's rows
+
+    def linear(self, x, w, b=None, act=None, res=None, x2=None, rows="q"):
+        return ops.gather_gemm(x, w, x2=x2, shift=b, act=act, res=res, nt=ops.dense_code(self._rows[rows], w.shape[-1], w.shape[0]),
+                               exact=self._exact[rows])
+
+    @staticmethod
+    def linear_group(jobs):                                      # query rows
+        return ops.linear_group(jobs, force_small=True)
+
+    def linear_ln(self, x, w, b, ln_w, ln_b, res=None):
+        # where ops.linear_layernorm has no fused launch it would pick the projection's kernel by ALL scenes' rows: issue the two here
+        if x.shape[1] > 512 or w.shape[0] != 256 or x.shape[1] % 16 or not w.is_contiguous() or (res is not None and res.stride(1) != 1):
+            return ops.layernorm(self.linear(x, w, b, res=res), ln_w, ln_b)
+        return ops.linear_layernorm(x, w, b, ln_w, ln_b, res=res, max_rows=x.shape[0])
+
+    def attention(self, q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, keys="s"):
+        a = torch.empty(q.shape[0], num_heads * 32, dtype=torch.float32, device=q.device)
+        at = lambda t, r: None if t is None else t[r]  # noqa: E731
+        ops.attention_batch([(q[qr], k[kr], v[kr], at(mask_bits, b), at(q2, qr), at(k2, kr), a[qr])
+                             for b, (qr, kr) in enumerate(zip(self._slices["q"], self._slices[keys]))], num_heads, scale)
+        return a
+
+    def box_refine(self, ref_points, d_center, size_prev, d_size, rng, normalize):
+        return ops.box_refine(ref_points, d_center, size_prev, d_size, rng, normalize, row_scene=self._row_scene["q"])
+
+    def row_scene(self, rows):
+        return self._row_scene[rows]
+
+    def sine_pe_mod(self, xyz, rng, dim_t, axis, num, den):
+        return ops.sine_pe(xyz, rng, dim_t, axis, mod_num=num, mod_den=den, row_scene=self._row_scene["q"])
+
+    def mask_logits(self, nq, mask_feats):                      # -> one per scene (exact fp32 in every mode: they feed thresholds)
+        return self.linear_group([(nq[qr], mask_feats[sr], None, None, None, None) for qr, sr in zip(self._slices["q"], self._slices["s"])])
+
+    def mask_bits(self, logits, S, thr):
+        return ops.mask_bits_batch(logits, [r.stop - r.start for r in self._slices["s"]], thr)
+
+    @staticmethod
+    def dinox_mask_bits(bits, near):
+        return ops.dinox_mask_bits_batch(bits, near)
+
+
 _F_TLS = threading.local()
-# SD3D_FUSED_DECODER=0: evaluation runs the op-by-op decoder of rounds 1-3 (`_forward_scene` / `_forward_batch`) instead of the
-# row-chain launches (`_forward_fused`); training always runs op by op (autograd nodes)
+# SD3D_FUSED_DECODER=0: evaluation runs the op-by-op decoder of rounds 1-3 (`_forward_ops`, one scene through `_EvalF` or a batch
+# through `_BatchF`) instead of the row-chain launches (`_forward_fused`); training always runs op by op (autograd nodes, `_TrainF`)
 # "auto" (default): a scene takes the row-chain path when it has more than FUSED_MIN_ROWS query rows (one query per superpoint,
 # the reference's evaluation mode: 15.7 -> 15.0 ms per scene); a scene with a few hundred queries stays op by op (12.6 vs 12.85 ms:
 # thirteen 16-row workgroups are bound by ONE CU's fp32 matrix rate, 3.9 us per 256 x 256 Linear, and cannot outrun ~27 small
@@ -215,15 +337,15 @@ def _F():
     return getattr(_F_TLS, "f", _EvalF)
 
 
-def _lin(x, layer: nn.Linear, act=None, res=None):
-    return _F().linear(x, layer.weight, layer.bias, act=act, res=res)
+def _lin(x, layer: nn.Linear, act=None, res=None, F=None, rows="q"):
+    return (F or _F()).linear(x, layer.weight, layer.bias, act=act, res=res, rows=rows)
 
 
-def _mlp(x, mlp: MLP, final_act=None, res=None):
+def _mlp(x, mlp: MLP, final_act=None, res=None, F=None):
     n = len(mlp.layers)
     for i, layer in enumerate(mlp.layers):
         last = i == n - 1
-        x = _lin(x, layer, act=(final_act if last else "relu"), res=(res if last else None))
+        x = _lin(x, layer, act=(final_act if last else "relu"), res=(res if last else None), F=F)
     return x
 
 
@@ -428,22 +550,23 @@ class ScanNetQueryDecoder(DerivedWeights):
         return self._pe_tables[key]
 
     # ---- prediction head (:532-577) ----------------------------------------------------------------
-    def _head(self, queries, mask_feats, last_flag, defer_cls=False):
+    def _head(self, queries, mask_feats, last_flag, defer_cls=False, F=None):
         """-> (class logits | the normalised queries when `defer_cls`, semantic logits | None, mask logits, mask bits,
-        objectness score | None).  The class
+        objectness score | None), through the op set `F` (default: the running forward's one-scene set).  The class
         MLP feeds nothing inside the decoder, so the positional variant runs it inside the NEXT layer's first launches."""
-        S = mask_feats.shape[0]
-        nq = _F().layernorm(queries, self.out_norm.weight, self.out_norm.bias)
-        cls = nq if defer_cls else _lin(_lin(nq, self.out_cls[0], act="relu"), self.out_cls[2])
+        F = F or _F()
+        lin = lambda x, layer, act=None: _lin(x, layer, act=act, F=F)  # noqa: E731
+        nq = F.layernorm(queries, self.out_norm.weight, self.out_norm.bias)
+        cls = nq if defer_cls else lin(lin(nq, self.out_cls[0], "relu"), self.out_cls[2])
         sem = None
         if last_flag:
             if isinstance(self.out_sem, nn.Linear):
-                sem = _lin(nq, self.out_sem)
+                sem = lin(nq, self.out_sem)
             else:
-                sem = _lin(_lin(nq, self.out_sem[0], act="relu"), self.out_sem[2])
-        logits = _F().mask_logits(nq, mask_feats)
-        bits = ops.mask_bits(logits.detach(), S, self.mask_attention_threshold)
-        score = _lin(_lin(nq, self.out_score[0], act="relu"), self.out_score[2]) if self.objectness_flag else None   # [Q, 1] (:548-550)
+                sem = lin(lin(nq, self.out_sem[0], "relu"), self.out_sem[2])
+        logits = F.mask_logits(nq, mask_feats)
+        bits = F.mask_bits(logits, mask_feats.shape[0], self.mask_attention_threshold)
+        score = lin(lin(nq, self.out_score[0], "relu"), self.out_score[2]) if self.objectness_flag else None   # [Q, 1] (:548-550)
         return cls, sem, logits, bits, score
 
     def select_scores(self, x):
@@ -495,46 +618,71 @@ class ScanNetQueryDecoder(DerivedWeights):
         # placeholder, :653-655, and the zip at :781-783 truncates): keep the same length
         return final, aux[:-1]
 
-    # ---- one scene -----------------------------------------------------------------------------------
-    def _forward_scene(self, x, sp_pos, sp_pos_wo, q_in, q_pos, q2d_feat, q2d_pos, lo, hi):
-        dev = x.device
+    # ---- the layout-dependent inputs of the positional variant (op by op and row chain) --------------------------------------------
+    def _keys2d_near(self, sp_pos_wo, q2d_feat, q2d_pos, dev):
+        """Per scene: the 2D object queries plus the dummy key of ones, and the bits "2D query m lies near superpoint s"."""
+        keys2d, near = [], []
+        for wo, f, qp in zip(sp_pos_wo, q2d_feat, q2d_pos):
+            if not isinstance(qp, torch.Tensor):
+                qp = qp.tensor.type(wo.dtype).to(dev)
+            keys2d.append(torch.cat([f.float(), f.new_ones(1, f.shape[1], dtype=torch.float32)]))
+            near.append(ops.near_bits(wo.float().contiguous(), qp.float().contiguous(), self.dinox_query_ca_mask_threshold))
+        return keys2d, near
+
+    def _initial_size(self, ranges, Q_b, dev, one_row=False):
+        """The box size before the first refinement, per query row; one_row: ONE scene's normalised size as a [3] row for all its queries."""
+        if not self.normalize_box_prediction:
+            return torch.full((sum(Q_b), 3), 0.5, dtype=torch.float32, device=dev)
+        # 0.5 / d == (1 / d) * 0.5 bit for bit (a power-of-two factor commutes with the rounding): one launch less
+        if one_row:
+            lo, hi = ranges[0]
+            return (0.5 / (hi - lo)).float().reshape(3).contiguous()
+        return _cat([(0.5 / (hi - lo)).float().reshape(1, 3).expand(q, 3) for q, (lo, hi) in zip(Q_b, ranges)])
+
+    # ---- op by op: one scene (evaluation and training) or a batch of scenes (evaluation) ---------------------------------------------
+    def _forward_ops(self, xs, sp_pos, sp_pos_wo, q_in, q_pos, q2d_feat, q2d_pos, ranges):
+        """The positional decoder layer by layer through an op set, for B >= 1 scenes -> [(final, aux)] per scene.  One scene runs
+        through the forward's one-scene set (`_EvalF` / `_TrainF`) on its own tensors: nothing is concatenated.  Several (`_batchable`)
+        run through a `_BatchF` over their rows back to back, the results being row slices of the batch tensors: bit-identical to
+        one call per scene."""
+        dev = xs[0].device
         d, H, L = self.d_model, self.num_heads, self.num_layers
-        F = _F()
+        B = len(xs)
+        if B == 1:
+            F, q_off = _F(), None
+            rng = _range6(*ranges[0])
+        else:
+            F = _BatchF(xs, q_in, q2d_feat if self.add_dinox_query_ca else None, ranges)
+            q_off, rng = F.off["q"], F.rng
         pk = self.packed_train() if self.training else self.packed()
         dim_t, axis = self.pe_tables(dev)
-        x, sp_pos, q_in, q_pos = x.contiguous(), sp_pos.contiguous(), q_in.contiguous(), q_pos.contiguous()
-        Q = q_in.shape[0]
-        rng = _range6(lo, hi)
-        pe = (lambda xyz: ops.fourier_pe(xyz, rng, self.position_embedding.gauss_B, d)) if self.pos_type == "fourier" \
-            else (lambda xyz: ops.sine_pe(xyz, rng, dim_t, axis))
-        memory_emb = pe(sp_pos)
-        if self.normalize_box_prediction:
-            # one row, broadcast over queries; 0.5 / d == (1 / d) * 0.5 bit for bit (a power-of-two factor commutes with the rounding): one launch less
-            size_q = (0.5 / (hi - lo)).float().reshape(3).contiguous()
+        X, SP, Qin = _cat(xs), _cat([t.float() for t in sp_pos]), _cat(q_in)
+        if self.pos_type == "fourier":
+            pe = lambda xyz, rows: ops.fourier_pe(xyz, rng, self.position_embedding.gauss_B, d, row_scene=F.row_scene(rows))  # noqa: E731
         else:
-            size_q = torch.full((Q, 3), 0.5, dtype=torch.float32, device=dev)
-        inst = F.layernorm(_lin(x, self.input_proj[0]), self.input_proj[1].weight, self.input_proj[1].bias, act="relu")
-        mask_feats = _lin(_lin(x, self.x_mask[0], act="relu"), self.x_mask[2])
-        queries = _lin(_lin(q_in, self.query_proj[0], act="relu"), self.query_proj[2])
+            pe = lambda xyz, rows: ops.sine_pe(xyz, rng, dim_t, axis, row_scene=F.row_scene(rows))  # noqa: E731
+        QL = lambda x, layer, act=None, res=None: _lin(x, layer, act, res, F)  # noqa: E731
+        SL = lambda x, layer, act=None, res=None: _lin(x, layer, act, res, F, "s")  # noqa: E731
+        memory_emb = pe(SP, "s")
+        size_q = self._initial_size(ranges, [q.shape[0] for q in q_in], dev, one_row=B == 1)
+        inst = F.layernorm(SL(X, self.input_proj[0]), self.input_proj[1].weight, self.input_proj[1].bias, act="relu")
+        mask_feats = SL(SL(X, self.x_mask[0], act="relu"), self.x_mask[2])
+        queries = QL(QL(Qin, self.query_proj[0], act="relu"), self.query_proj[2])
         # Independent Linears on the few hundred query rows go out in ONE launch each time (F.linear_group): the class MLP of
         # a prediction head rides with the next layer's first projections, the two box MLPs run side by side, projections that
         # share an input are batched.  Every Linear is still the same fp32 product; only the dispatch count changes.
         J = lambda x, layer, act=None, res=None, x2=None: (x, layer.weight, layer.bias, act, res, x2)  # noqa: E731
-        nq_pending, sem, logits, bits, score = self._head(queries, mask_feats, False, defer_cls=True)
+        nq_pending, sem, logits, bits, score = self._head(queries, mask_feats, False, defer_cls=True, F=F)
         aux = [dict(cls_preds=None, sem_preds=None, masks=logits, centers=None, sizes=None, scores=score)]
 
         # layer-invariant key side, hoisted out of the loop (the reference recomputes it per layer, :669-671)
-        kv_all = F.split_cols(F.linear(inst, pk["kv_w"], pk["kv_b"]), d)             # [S, 2*L*d]: kc_0..kc_{L-1} | v_0..v_{L-1}
-        kp_all = F.split_cols(F.linear(memory_emb, pk["kp_w"], pk["kp_b"]), d)       # [S, L*d]
+        kv_all = F.split_cols(F.linear(inst, pk["kv_w"], pk["kv_b"], rows="s"), d)             # [S, 2*L*d]: kc_0..kc_{L-1} | v_0..v_{L-1}
+        kp_all = F.split_cols(F.linear(memory_emb, pk["kp_w"], pk["kp_b"], rows="s"), d)       # [S, L*d]
         if self.add_dinox_query_ca:
-            if not isinstance(q2d_pos, torch.Tensor):
-                q2d_pos = q2d_pos.tensor.type(sp_pos_wo.dtype).to(dev)
-            keys2d = torch.cat([q2d_feat.float(), q2d_feat.new_ones(1, q2d_feat.shape[1], dtype=torch.float32)]).contiguous()
-            kv2d_all = F.split_cols(F.linear(keys2d, pk["kv2d_w"], pk["kv2d_b"]), d)     # [M+1, 2*L*d]
-            near = ops.near_bits(sp_pos_wo.float().contiguous(), q2d_pos.float().contiguous(),
-                                 self.dinox_query_ca_mask_threshold)
+            keys2d, near = self._keys2d_near(sp_pos_wo, q2d_feat, q2d_pos, dev)
+            kv2d_all = F.split_cols(F.linear(_cat(keys2d), pk["kv2d_w"], pk["kv2d_b"], rows="m"), d)     # [sum(M_b + 1), 2*L*d]
 
-        ref_points = q_pos.float().contiguous()
+        ref_points = _cat([t.float() for t in q_pos])
         ref_sizes = size_q
         for i in range(L):
             ops.baton_yield()
@@ -557,40 +705,39 @@ class ScanNetQueryDecoder(DerivedWeights):
             if self.box_modulate_ca:
                 pq_emb = F.sine_pe_mod(ref_points, rng, dim_t, axis, outs2["hwl"], ref_sizes)
             else:
-                pq_emb = pe(ref_points)
+                pq_emb = pe(ref_points, "q")
             # ---- launch C: first layer of the positional-query MLP next to the sine projection of the cross-attention
             h, qs = F.linear_group([J(pq_emb, self.ref_point_head.layers[0], "relu"), J(pq_emb, self.ca_qpos_sine_proj[i])])
-            query_pos = _lin(h, self.ref_point_head.layers[1])
+            query_pos = QL(h, self.ref_point_head.layers[1])
             # ---- masked cross-attention to the superpoints (:668-691)
             kc, v, kp = kv_all[i], kv_all[L + i], kp_all[i]
             if i == 0:
                 qc = F.linear(queries, pk["ca_q0_w"], pk["ca_q0_b"], x2=query_pos)
-                kc = _lin(inst, self.ca_kcontent_proj[0], res=kp)
+                kc = SL(inst, self.ca_kcontent_proj[0], res=kp)
             else:
                 qc = outs["qc"]
-            a = F.attention(qc, kc, v, H, (2 * d // H) ** -0.5, mask_bits=bits, q2=qs, k2=kp)
+            a = F.attention(qc, kc, v, H, (2 * d // H) ** -0.5, mask_bits=bits, q2=qs, k2=kp, keys="s")
             op = self.cross_attn_layers[i].out_proj
             queries = F.linear_ln(a, op.weight, op.bias, self.norm1[i].weight, self.norm1[i].bias, res=queries)
             # ---- self-attention (:695-709)
             qkv = F.split_cols(F.linear(queries, pk["sa_qkv_w"][i], pk["sa_qkv_b"][i], x2=query_pos), d)     # [Q, 3d]
-            a = F.attention(qkv[0], qkv[1], qkv[2], H, (d // H) ** -0.5)
+            a = F.attention(qkv[0], qkv[1], qkv[2], H, (d // H) ** -0.5, keys="q")
             op = self.self_attn_layers[i].out_proj
             queries = F.linear_ln(a, op.weight, op.bias, self.norm2[i].weight, self.norm2[i].bias, res=queries)
             # ---- cross-attention to the cached DINO-X 2D object queries (:713-731, :60-86)
             if self.add_dinox_query_ca:
                 layer = self.dinox_query_cross_attn_layers[i]
-                bits2d = ops.dinox_mask_bits(bits, near)
+                bits2d = F.dinox_mask_bits(bits, near)
                 q = F.linear(queries, pk["q2d_w"][i], pk["q2d_b"][i])
-                a = F.attention(q, kv2d_all[i], kv2d_all[L + i], H,
-                                  (d // H) ** -0.5, mask_bits=bits2d)
+                a = F.attention(q, kv2d_all[i], kv2d_all[L + i], H, (d // H) ** -0.5, mask_bits=bits2d, keys="m")
                 if layer.fix:
                     op = layer.attn.out_proj
                     queries = F.linear_ln(a, op.weight, op.bias, layer.norm.weight, layer.norm.bias, res=queries)
                 else:
-                    queries = _lin(a, layer.attn.out_proj, res=queries)
+                    queries = QL(a, layer.attn.out_proj, res=queries)
             # ---- FFN (:173-190)
             ffn = self.ffn_layers[i]
-            hdn = F.dropout(_lin(queries, ffn.net[0], act=("relu" if self.activation_fn == "relu" else "gelu")))
+            hdn = F.dropout(QL(queries, ffn.net[0], act=("relu" if self.activation_fn == "relu" else "gelu")))
             queries = F.linear_ln(hdn, ffn.net[3].weight, ffn.net[3].bias, ffn.norm.weight, ffn.norm.bias, res=queries)
             # ---- iterative box refinement (:735-759): the centre and the size MLP side by side, three launches for six Linears
             if self.add_box_size_pred:
@@ -599,21 +746,18 @@ class ScanNetQueryDecoder(DerivedWeights):
                 c2, s2 = F.linear_group([J(c1, be[1], "relu"), J(s1, se[1], "relu")])
                 dc, ds = F.linear_group([J(c2, be[2]), J(s2, se[2])])
             else:
-                dc, ds = _mlp(queries, self.bbox_embed[i]), None
+                dc, ds = _mlp(queries, self.bbox_embed[i], F=F), None
             center, size, size_metric = F.box_refine(ref_points, dc, size_q, ds, rng, self.normalize_box_prediction)
             ref_points = center.detach()                       # `:740`
             if self.add_box_size_pred:
                 ref_sizes = size_q = size.detach()             # `:753`
             last = i == L - 1
-            nq_pending, sem, logits, bits, score = self._head(queries, mask_feats, last, defer_cls=True)
+            nq_pending, sem, logits, bits, score = self._head(queries, mask_feats, last, defer_cls=True, F=F)
             aux.append(dict(cls_preds=None, sem_preds=sem, masks=logits, centers=center, sizes=size_metric, scores=score))
-        aux[-1]["cls_preds"] = _lin(_lin(nq_pending, self.out_cls[0], act="relu"), self.out_cls[2])
-        final = aux.pop()
-        final["hidden_states"] = queries
-        final["attn_mask_bits"] = bits
-        return final, aux
+        aux[-1]["cls_preds"] = QL(QL(nq_pending, self.out_cls[0], act="relu"), self.out_cls[2])
+        return _split_scenes(aux, queries, bits, q_off)
 
-    # ---- several scenes at once (evaluation, positional variant) ---------------------------------------------------------
+    # ---- several scenes at once (evaluation, positional variant): when `_BatchF` applies ----------------------------------
     def _row_shapes(self):
         """(Cin, Cout) of every plain Linear of the positional decoder, by the rows it runs on: queries / superpoints / 2D keys."""
         d, L, c = self.d_model, self.num_layers, self.in_channels
@@ -650,178 +794,6 @@ class ScanNetQueryDecoder(DerivedWeights):
                     return False
         return True
 
-    def _forward_batch(self, xs, sp_pos, sp_pos_wo, q_in, q_pos, q2d_feat, q2d_pos, ranges):
-        """`_forward_scene` for B scenes in one pass: everything row-wise (every Linear, LayerNorm, positional encoding, box
-        refinement) runs ONCE over the scenes' rows back to back - B x fewer launches per scene - with the tiling codes one scene's
-        rows would get; what couples the rows of a scene (the three attentions, mask bits, the 2D-query masks) runs per scene on
-        row slices; the B mask-logit products are one grouped launch.  Returns [(final, aux)] per scene, the tensors being row
-        slices of the batch tensors; bit-identical to B calls of `_forward_scene`."""
-        dev = xs[0].device
-        d, H, L = self.d_model, self.num_heads, self.num_layers
-        B = len(xs)
-        pk = self.packed()
-        dim_t, axis = self.pe_tables(dev)
-        s_off, q_off = [0], [0]
-        for b in range(B):
-            s_off.append(s_off[-1] + xs[b].shape[0])
-            q_off.append(q_off[-1] + q_in[b].shape[0])
-        S_tot, Q_tot = s_off[-1], q_off[-1]
-        X = torch.cat([t.contiguous() for t in xs]).contiguous()
-        SP = torch.cat([t.float() for t in sp_pos]).contiguous()
-        Qin = torch.cat(list(q_in)).contiguous()
-        rng = torch.stack([_range6(lo, hi) for lo, hi in ranges]).contiguous()      # [B, 6]
-        # scene index of every row, made ON the device from host-known sizes (B fills + a concatenation): no host -> device copy and no
-        # synchronising op here - a blocking call inside the issue baton stalls the other scenes' threads (measured: 114 -> 96 scenes/s)
-        scene_of = lambda offs: torch.cat([torch.full((offs[b + 1] - offs[b],), b, dtype=torch.int32, device=dev) for b in range(B)])  # noqa: E731
-        rs_s, rs_q = scene_of(s_off), scene_of(q_off)
-        # every Linear with the tiling code ONE scene's rows get (`_batchable` made sure all scenes agree on it); superpoint-side rows
-        # may take the bf16 kernel in the bf16 mode exactly when one scene's rows would (>= BF16_MIN_ROWS), query-side rows never do
-        rows_q, rows_s = q_in[0].shape[0], xs[0].shape[0]
-        s_exact = rows_s < ops.BF16_MIN_ROWS
-
-        def lin_rows(rows, exact):
-            def f(x, w, b=None, act=None, res=None, x2=None):
-                return ops.gather_gemm(x, w, x2=x2, shift=b, act=act, res=res, nt=ops.dense_code(rows, w.shape[-1], w.shape[0]), exact=exact)
-            return f
-        qlin, slin = lin_rows(rows_q, True), lin_rows(rows_s, s_exact)
-        QL = lambda x, layer, act=None, res=None: qlin(x, layer.weight, layer.bias, act, res)  # noqa: E731
-        SL = lambda x, layer, act=None, res=None: slin(x, layer.weight, layer.bias, act, res)  # noqa: E731
-        J = lambda x, layer, act=None, res=None, x2=None: (x, layer.weight, layer.bias, act, res, x2)  # noqa: E731
-        group = lambda jobs: ops.linear_group(jobs, force_small=True)  # noqa: E731
-        lin_ln = lambda x, w, b, ln_w, ln_b, res: ops.linear_layernorm(x, w, b, ln_w, ln_b, res=res, max_rows=Q_tot)  # noqa: E731
-        if self.pos_type == "fourier":
-            pe = lambda xyz, rs: ops.fourier_pe(xyz, rng, self.position_embedding.gauss_B, d, row_scene=rs)  # noqa: E731
-        else:
-            pe = lambda xyz, rs: ops.sine_pe(xyz, rng, dim_t, axis, row_scene=rs)  # noqa: E731
-
-        memory_emb = pe(SP, rs_s)
-        if self.normalize_box_prediction:
-            size_q = torch.cat([(0.5 / (hi - lo)).float().reshape(1, 3).expand(q_off[b + 1] - q_off[b], 3)
-                                for b, (lo, hi) in enumerate(ranges)]).contiguous()
-        else:
-            size_q = torch.full((Q_tot, 3), 0.5, dtype=torch.float32, device=dev)
-        inst = ops.layernorm(SL(X, self.input_proj[0]), self.input_proj[1].weight, self.input_proj[1].bias, act="relu")
-        mask_feats = SL(SL(X, self.x_mask[0], act="relu"), self.x_mask[2])
-        queries = QL(QL(Qin, self.query_proj[0], act="relu"), self.query_proj[2])
-
-        def head(queries, last):
-            nq = ops.layernorm(queries, self.out_norm.weight, self.out_norm.bias)
-            sem = None
-            if last:
-                sem = QL(nq, self.out_sem) if isinstance(self.out_sem, nn.Linear) else QL(QL(nq, self.out_sem[0], act="relu"), self.out_sem[2])
-            # the B mask-logit products nq_b . mask_feats_b^T: one grouped launch (exact fp32 in every mode: they feed thresholds)
-            logits = group([(nq[q_off[b]:q_off[b + 1]], mask_feats[s_off[b]:s_off[b + 1]], None, None, None, None) for b in range(B)])
-            bits = ops.mask_bits_batch(logits, [s_off[b + 1] - s_off[b] for b in range(B)], self.mask_attention_threshold)
-            score = QL(QL(nq, self.out_score[0], act="relu"), self.out_score[2]) if self.objectness_flag else None
-            return nq, sem, logits, bits, score
-
-        nq_pending, sem, logits, bits, score = head(queries, False)
-        aux = [dict(cls_preds=None, sem_preds=None, masks=logits, centers=None, sizes=None, scores=score)]
-        kv_all = slin(inst, pk["kv_w"], pk["kv_b"])                      # [S_tot, 2*L*d]
-        kp_all = slin(memory_emb, pk["kp_w"], pk["kp_b"])                # [S_tot, L*d]
-        if self.add_dinox_query_ca:
-            m_off, keys2d, near = [0], [], []
-            for b in range(B):
-                qp = q2d_pos[b]
-                if not isinstance(qp, torch.Tensor):
-                    qp = qp.tensor.type(sp_pos_wo[b].dtype).to(dev)
-                f = q2d_feat[b]
-                keys2d.append(torch.cat([f.float(), f.new_ones(1, f.shape[1], dtype=torch.float32)]))
-                m_off.append(m_off[-1] + f.shape[0] + 1)
-                near.append(ops.near_bits(sp_pos_wo[b].float().contiguous(), qp.float().contiguous(), self.dinox_query_ca_mask_threshold))
-            rows_m = q2d_feat[0].shape[0] + 1
-            kv2d_all = lin_rows(rows_m, rows_m < ops.BF16_MIN_ROWS)(torch.cat(keys2d).contiguous(), pk["kv2d_w"], pk["kv2d_b"])    # [sum(M_b + 1), 2*L*d]
-
-        ref_points = torch.cat([t.float() for t in q_pos]).contiguous()
-        ref_sizes = size_q
-        for i in range(L):
-            ops.baton_yield()
-            jobs, what = [], []
-            if self.box_modulate_ca:
-                jobs.append(J(queries, self.ref_anchor_head.layers[0], "relu")); what.append("anchor")
-            if i > 0:
-                jobs.append(J(queries, self.ca_qcontent_proj[i])); what.append("qc")
-            jobs.append(J(nq_pending, self.out_cls[0], "relu")); what.append("cls")
-            outs = dict(zip(what, group(jobs)))
-            jobs, what = [J(outs["cls"], self.out_cls[2])], ["cls"]
-            if self.box_modulate_ca:
-                jobs.append(J(outs["anchor"], self.ref_anchor_head.layers[1], "sigmoid")); what.append("hwl")
-            outs2 = dict(zip(what, group(jobs)))
-            aux[-1]["cls_preds"] = outs2["cls"]
-            if self.box_modulate_ca:
-                pq_emb = ops.sine_pe(ref_points, rng, dim_t, axis, mod_num=outs2["hwl"], mod_den=ref_sizes, row_scene=rs_q)
-            else:
-                pq_emb = pe(ref_points, rs_q)
-            h, qs = group([J(pq_emb, self.ref_point_head.layers[0], "relu"), J(pq_emb, self.ca_qpos_sine_proj[i])])
-            query_pos = QL(h, self.ref_point_head.layers[1])
-            kc = kv_all[:, i * d:(i + 1) * d]
-            v = kv_all[:, (L + i) * d:(L + i + 1) * d]
-            kp = kp_all[:, i * d:(i + 1) * d]
-            if i == 0:
-                qc = qlin(queries, pk["ca_q0_w"], pk["ca_q0_b"], x2=query_pos)
-                kc = SL(inst, self.ca_kcontent_proj[0], res=kp)
-            else:
-                qc = outs["qc"]
-            a = torch.empty(Q_tot, d, dtype=torch.float32, device=dev)
-            QS = [(q_off[b], q_off[b + 1], s_off[b], s_off[b + 1]) for b in range(B)]
-            ops.attention_batch([(qc[q0:q1], kc[k0:k1], v[k0:k1], bits[b], qs[q0:q1], kp[k0:k1], a[q0:q1]) for b, (q0, q1, k0, k1) in enumerate(QS)],
-                                H, (2 * d // H) ** -0.5)
-            op = self.cross_attn_layers[i].out_proj
-            queries = lin_ln(a, op.weight, op.bias, self.norm1[i].weight, self.norm1[i].bias, queries)
-            qkv = qlin(queries, pk["sa_qkv_w"][i], pk["sa_qkv_b"][i], x2=query_pos)
-            a = torch.empty(Q_tot, d, dtype=torch.float32, device=dev)
-            ops.attention_batch([(qkv[q0:q1, :d], qkv[q0:q1, d:2 * d], qkv[q0:q1, 2 * d:], None, None, None, a[q0:q1]) for (q0, q1, _, _) in QS],
-                                H, (d // H) ** -0.5)
-            op = self.self_attn_layers[i].out_proj
-            queries = lin_ln(a, op.weight, op.bias, self.norm2[i].weight, self.norm2[i].bias, queries)
-            if self.add_dinox_query_ca:
-                layer = self.dinox_query_cross_attn_layers[i]
-                q = qlin(queries, pk["q2d_w"][i], pk["q2d_b"][i])
-                a = torch.empty(Q_tot, d, dtype=torch.float32, device=dev)
-                bits2d = ops.dinox_mask_bits_batch(bits, near)
-                ops.attention_batch([(q[q_off[b]:q_off[b + 1]], kv2d_all[m_off[b]:m_off[b + 1], i * d:(i + 1) * d],
-                                      kv2d_all[m_off[b]:m_off[b + 1], (L + i) * d:(L + i + 1) * d], bits2d[b], None, None, a[q_off[b]:q_off[b + 1]])
-                                     for b in range(B)], H, (d // H) ** -0.5)
-                op = layer.attn.out_proj
-                if layer.fix:
-                    queries = lin_ln(a, op.weight, op.bias, layer.norm.weight, layer.norm.bias, queries)
-                else:
-                    queries = qlin(a, op.weight, op.bias, res=queries)
-            ffn = self.ffn_layers[i]
-            hdn = QL(queries, ffn.net[0], act=("relu" if self.activation_fn == "relu" else "gelu"))
-            queries = ops.layernorm(qlin(hdn, ffn.net[3].weight, ffn.net[3].bias, res=queries), ffn.norm.weight, ffn.norm.bias)
-            if self.add_box_size_pred:
-                be, se = self.bbox_embed[i].layers, self.bbox_size_embed[i].layers
-                c1, s1 = group([J(queries, be[0], "relu"), J(queries, se[0], "relu")])
-                c2, s2 = group([J(c1, be[1], "relu"), J(s1, se[1], "relu")])
-                dc, ds = group([J(c2, be[2]), J(s2, se[2])])
-            else:
-                dc, ds = queries, None
-                for li, layer_ in enumerate(self.bbox_embed[i].layers):
-                    dc = QL(dc, layer_, act=None if li == len(self.bbox_embed[i].layers) - 1 else "relu")
-            center, size, size_metric = ops.box_refine(ref_points, dc, size_q, ds, rng, self.normalize_box_prediction, row_scene=rs_q)
-            ref_points = center
-            if self.add_box_size_pred:
-                ref_sizes = size_q = size
-            last = i == L - 1
-            nq_pending, sem, logits, bits, score = head(queries, last)
-            aux.append(dict(cls_preds=None, sem_preds=sem, masks=logits, centers=center, sizes=size_metric, scores=score))
-        aux[-1]["cls_preds"] = QL(QL(nq_pending, self.out_cls[0], act="relu"), self.out_cls[2])
-
-        def scene_view(entry, b):
-            q0, q1 = q_off[b], q_off[b + 1]
-            row = lambda t: None if t is None else t[q0:q1]  # noqa: E731
-            return dict(cls_preds=row(entry["cls_preds"]), sem_preds=row(entry["sem_preds"]), masks=entry["masks"][b],
-                        centers=row(entry["centers"]), sizes=row(entry["sizes"]), scores=row(entry["scores"]))
-        results = []
-        for b in range(B):
-            views = [scene_view(e, b) for e in aux]
-            final = views.pop()
-            final["hidden_states"] = queries[q_off[b]:q_off[b + 1]]
-            final["attn_mask_bits"] = bits[b]
-            results.append((final, views))
-        return results
-
     # ---- evaluation, positional variant: the row-local work of a layer as row-chain launches (csrc/rowchain.hip) ----------------
     def _fusable(self, rows=1 << 30):
         """Tile rows (16 or 4) of the fused (row-chain) path a scene with `rows` query rows takes, 0 = op by op.  The path covers the
@@ -836,7 +808,7 @@ class ScanNetQueryDecoder(DerivedWeights):
                 and self.ffn_layers[0].net[0].out_features % 16 == 0) else 0
 
     def _forward_fused(self, xs, sp_pos, sp_pos_wo, q_in, q_pos, q2d_feat, q2d_pos, ranges, tile=16):
-        """`_forward_scene` for B >= 1 scenes with every query-row-local stretch of a layer as ONE launch (rowchain.Program):
+        """`_forward_ops` for B >= 1 scenes with every query-row-local stretch of a layer as ONE launch (rowchain.Program):
              A  positional query: anchor MLP -> box-modulated sine PE -> ref_point_head, the two cross-attention query projections
                 (+ the class head of the previous layer as a second program of the same launch)
              -  masked cross-attention to the superpoints (dense.hip attention kernel, key-split pass only)
@@ -853,16 +825,11 @@ class ScanNetQueryDecoder(DerivedWeights):
         B = len(xs)
         pk = self.packed()
         dim_t, axis = self.pe_tables(dev)
-        s_off, q_off = [0], [0]
-        for b in range(B):
-            s_off.append(s_off[-1] + xs[b].shape[0])
-            q_off.append(q_off[-1] + q_in[b].shape[0])
-        S_tot, Q_tot = s_off[-1], q_off[-1]
-        S_b = [s_off[b + 1] - s_off[b] for b in range(B)]
-        Q_b = [q_off[b + 1] - q_off[b] for b in range(B)]
-        cat = (lambda ts: ts[0].contiguous()) if B == 1 else (lambda ts: torch.cat([t.contiguous() for t in ts]).contiguous())
-        X, SP, Qin = cat(list(xs)), cat([t.float() for t in sp_pos]), cat(list(q_in))
-        rng = torch.stack([_range6(lo, hi) for lo, hi in ranges]).contiguous()      # [B, 6]
+        s_off, q_off = _offsets(xs), _offsets(q_in)
+        Q_tot = q_off[-1]
+        S_b, Q_b = [t.shape[0] for t in xs], [t.shape[0] for t in q_in]
+        X, SP, Qin = _cat(xs), _cat([t.float() for t in sp_pos]), _cat(q_in)
+        rng = _range_table(ranges)
 
         # ---- superpoint side: big Linears on the existing GEMM kernels, each scene's rows on the tiling its own call would get
         def s_linear(x, w, b=None, act=None, res=None, rows=S_b, offs=s_off, exact=False):
@@ -881,40 +848,32 @@ class ScanNetQueryDecoder(DerivedWeights):
         if B == 1:
             memory_emb = ops.sine_pe(SP, rng[0], dim_t, axis)
         else:
-            rs_s = torch.cat([torch.full((S_b[b],), b, dtype=torch.int32, device=dev) for b in range(B)])
-            memory_emb = ops.sine_pe(SP, rng, dim_t, axis, row_scene=rs_s)
+            memory_emb = ops.sine_pe(SP, rng, dim_t, axis, row_scene=_row_scene(s_off, dev))
         inst = ops.layernorm(SL(X, self.input_proj[0]), self.input_proj[1].weight, self.input_proj[1].bias, act="relu")
         mask_feats = SL(SL(X, self.x_mask[0], act="relu"), self.x_mask[2])
         kv_all = s_linear(inst, pk["kv_w"], pk["kv_b"])                      # [S_tot, 2*L*d]: kc_0..kc_{L-1} | v_0..v_{L-1}
         kp_all = s_linear(memory_emb, pk["kp_w"], pk["kp_b"])                # [S_tot, L*d]
         kc0 = SL(inst, self.ca_kcontent_proj[0], res=kp_all[:, :d])          # layer 0: content + positional key (:669-672)
-        m_off, nw_b, near_off = [0], [(s + 31) // 32 for s in S_b], [0]
+        nw_b = [(s + 31) // 32 for s in S_b]
         kv2d_all = near_all = None
         if self.add_dinox_query_ca:
-            keys2d, nears = [], []
-            for b in range(B):
-                qp = q2d_pos[b]
-                if not isinstance(qp, torch.Tensor):
-                    qp = qp.tensor.type(sp_pos_wo[b].dtype).to(dev)
-                f = q2d_feat[b]
-                keys2d.append(torch.cat([f.float(), f.new_ones(1, f.shape[1], dtype=torch.float32)]))
-                m_off.append(m_off[-1] + f.shape[0] + 1)
-                nears.append(ops.near_bits(sp_pos_wo[b].float().contiguous(), qp.float().contiguous(), self.dinox_query_ca_mask_threshold).reshape(-1))
-                near_off.append(near_off[-1] + nears[-1].numel())
-            M_b = [m_off[b + 1] - m_off[b] for b in range(B)]
-            kv2d_all = s_linear(cat(keys2d), pk["kv2d_w"], pk["kv2d_b"], rows=M_b, offs=m_off)      # [sum(M_b + 1), 2*L*d]
-            near_all = nears[0] if B == 1 else torch.cat(nears)
+            keys2d, nears = self._keys2d_near(sp_pos_wo, q2d_feat, q2d_pos, dev)
+            nears = [t.reshape(-1) for t in nears]
+            m_off, near_off = _offsets(keys2d), _offsets(nears)
+            M_b = [t.shape[0] for t in keys2d]
+            kv2d_all = s_linear(_cat(keys2d), pk["kv2d_w"], pk["kv2d_b"], rows=M_b, offs=m_off)      # [sum(M_b + 1), 2*L*d]
+            near_all = _cat(nears)
             if near_all.numel() == 0:                              # no 2D query in any scene: only the dummy keys, the table is never read
                 near_all = torch.zeros(1, dtype=torch.int32, device=dev)
         nw_max = max(nw_b)
-        nw2_max = max(((m_off[b + 1] - m_off[b]) + 31) // 32 for b in range(B)) if self.add_dinox_query_ca else 0
+        nw2_max = max((m + 31) // 32 for m in M_b) if self.add_dinox_query_ca else 0
 
         def scene_table(bits_off=None, ca=None):
             tab = []
             for b in range(B):
                 sc = dict(q0=q_off[b], nq=Q_b[b], nw=nw_b[b])
                 if self.add_dinox_query_ca:
-                    sc.update(m0=m_off[b], nm=m_off[b + 1] - m_off[b], near_off=near_off[b])
+                    sc.update(m0=m_off[b], nm=M_b[b], near_off=near_off[b])
                 if bits_off is not None:
                     sc["bits_off"] = bits_off[b]
                 if ca is not None:
@@ -965,12 +924,8 @@ class ScanNetQueryDecoder(DerivedWeights):
         logits, bits, bits_buf, bits_off = mask_head(nq)
         aux = [dict(cls_preds=None, sem_preds=None, masks=logits, centers=None, sizes=None, scores=score)]
 
-        ref_points = cat([t.float() for t in q_pos])
-        if self.normalize_box_prediction:
-            size_q = cat([(0.5 / (hi - lo)).float().reshape(1, 3).expand(Q_b[b], 3) for b, (lo, hi) in enumerate(ranges)])
-        else:
-            size_q = torch.full((Q_tot, 3), 0.5, dtype=torch.float32, device=dev)
-        ref_sizes = size_q
+        ref_points = _cat([t.float() for t in q_pos])
+        ref_sizes = size_q = self._initial_size(ranges, Q_b, dev)
         ncls = self.out_cls[2].out_features
         # self-attention inside chain C (a workgroup walks all keys of its scene for its 16 queries: 13 us at 200 keys, 194 us at 3000)
         # or as its own launch (130 us at 3000 x 3000 on the whole chip)
@@ -1089,20 +1044,7 @@ class ScanNetQueryDecoder(DerivedWeights):
         cls_program(P, nq, cls_last)
         P.launch(scene_table())
         aux[-1]["cls_preds"] = cls_last
-
-        def scene_view(entry, b):
-            q0, q1 = q_off[b], q_off[b + 1]
-            row = lambda t: None if t is None else t[q0:q1]  # noqa: E731
-            return dict(cls_preds=row(entry["cls_preds"]), sem_preds=row(entry["sem_preds"]), masks=entry["masks"][b],
-                        centers=row(entry["centers"]), sizes=row(entry["sizes"]), scores=row(entry["scores"]))
-        results = []
-        for b in range(B):
-            views = [scene_view(e, b) for e in aux]
-            final = views.pop()
-            final["hidden_states"] = queries[q_off[b]:q_off[b + 1]]
-            final["attn_mask_bits"] = bits[b]
-            results.append((final, views))
-        return results
+        return _split_scenes(aux, queries, bits, q_off)
 
     # ---- reference-shaped entry point (:417-435) --------------------------------------------------
     @ops.bound_stream
@@ -1141,16 +1083,14 @@ class ScanNetQueryDecoder(DerivedWeights):
                     for j, (f, a) in zip(ids, out):
                         finals[j], auxes[j] = f, a
             if plain_ids and self._batchable(pick(x, plain_ids), pick(queries, plain_ids), pick(dinox_queries, plain_ids)):
-                out = self._forward_batch(pick(x, plain_ids), pick(sp_pos, plain_ids), pick(wo, plain_ids), pick(queries, plain_ids),
-                                          pick(queries_pos, plain_ids), pick(dinox_queries, plain_ids), pick(dinox_query_pos, plain_ids),
-                                          pick(scene_range, plain_ids))
-                for j, (f, a) in zip(plain_ids, out):
-                    finals[j], auxes[j] = f, a
+                groups = [plain_ids]
             else:
-                for j in plain_ids:
-                    finals[j], auxes[j] = self._forward_scene(
-                        x[j], sp_pos[j], wo[j], queries[j], queries_pos[j], dinox_queries[j] if dinox_queries is not None else None,
-                        dinox_query_pos[j] if dinox_query_pos is not None else None, scene_range[j][0], scene_range[j][1])
+                groups = [[j] for j in plain_ids]
+            for ids in groups:
+                out = self._forward_ops(pick(x, ids), pick(sp_pos, ids), pick(wo, ids), pick(queries, ids), pick(queries_pos, ids),
+                                        pick(dinox_queries, ids), pick(dinox_query_pos, ids), pick(scene_range, ids))
+                for j, (f, a) in zip(ids, out):
+                    finals[j], auxes[j] = f, a
         B = len(finals)
         result = dict(cls_preds=[f["cls_preds"] for f in finals], sem_preds=[f["sem_preds"] for f in finals],
                       masks=[f["masks"] for f in finals], scores=[f.get("scores") for f in finals], centers=[f["centers"] for f in finals],

@@ -1,6 +1,6 @@
 """Batched evaluation forward: B scenes as ONE block-diagonal sparse tensor (sparse.BatchSceneMaps - the collation of the
 reference's `utils/dataset_utils.py:215-230` collate_fn_3D + `minkunet.py:624-627`), the decoder's row-wise work for all scenes
-in one pass (`ScanNetQueryDecoder._forward_batch`), post-processing per scene.  Evaluation BatchNorm is an affine map and every kernel on the path computes an output row from that row's
+in one pass (`ScanNetQueryDecoder._forward_ops` through the batched op set `_BatchF`), post-processing per scene.  Evaluation BatchNorm is an affine map and every kernel on the path computes an output row from that row's
 own pairs in a fixed order, so EVERY output of every scene must be bit-identical (`torch.equal`) to its single-scene forward
 (`baseline3d.py:308-346` runs one scene per forward, `:335-338`).  Integer work (maps, pair lists) is compared exactly."""
 import copy

@@ -155,7 +155,7 @@ def _mask_agree(a, b, thr=0.0):
     return ((a > thr) == (b > thr)).float().mean().item()
 
 
-# The three evaluation paths of the decoder (segdino3d_amd/decoder.py): op by op (`_forward_scene`), the row-chain path on 16-row
+# The three evaluation paths of the decoder (segdino3d_amd/decoder.py): op by op (`_forward_ops`), the row-chain path on 16-row
 # tiles (csrc/rowchain.hip) and on 4-row tiles (csrc/rowchain_narrow.hip).  Every reference golden runs on all three.
 DECODER_PATHS = ["op_by_op", "rowchain16", "rowchain4"]
 
