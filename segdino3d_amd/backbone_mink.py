@@ -250,15 +250,19 @@ class Res16UNetBase(DerivedWeights):
             return self._plan.run(maps, vox_feats)
         return self._network(plan.EagerBackend(maps), pk, vox_feats)
 
+    def _target_inputs(self, pts, tgt):
+        """-> (points, superpoints, 2-D features | None, voxel-feature mode) of one scene as the kernels read them."""
+        ef = tgt["extra_features"]
+        f2d = ef["points_2dfeats"].float().contiguous() if self.mode_fuse_2d_feat == "early_fusion" else None
+        return pts.float().contiguous(), ef["super_point_masks"].contiguous(), f2d, 0 if f2d is not None else 1
+
+    def _wrapper_result(self, feats, pos, pos_wo, return_sp_mean_pos):
+        sp_pos = pos if self.add_positional_embedding else None
+        return (feats, sp_pos, pos_wo) if return_sp_mean_pos else (feats, sp_pos, None)
+
     def _scene_inputs(self, pts, tgt):
         """-> (maps, voxel features, undistorted points, superpoints, elastic?, packed weights | None) of one scene (`:604-630`)."""
-        ef = tgt["extra_features"]
-        pts = pts.float().contiguous()
-        sp = ef["super_point_masks"].contiguous()
-        if self.mode_fuse_2d_feat == "early_fusion":
-            f2d, mode = ef["points_2dfeats"].float().contiguous(), 0
-        else:
-            f2d, mode = None, 1
+        pts, sp, f2d, mode = self._target_inputs(pts, tgt)
         elastic = tgt["elastic_coords"] if "elastic_coords" in tgt else None
         geo = pts
         if elastic is not None:                                  # voxelise the elastically distorted scene (:606-608), colours as they are
@@ -286,12 +290,9 @@ class Res16UNetBase(DerivedWeights):
         one set of neighbour tables, every convolution one launch over all scenes' pairs, one pooling launch.  Each scene's
         outputs are bit-identical to its single-scene forward."""
         from .sparse import BatchSceneMaps
-        pts = [p.float().contiguous() for p in samples]
-        sps = [t["extra_features"]["super_point_masks"].contiguous() for t in targets]
-        if self.mode_fuse_2d_feat == "early_fusion":
-            f2d, mode = [t["extra_features"]["points_2dfeats"].float().contiguous() for t in targets], 0
-        else:
-            f2d, mode = None, 1
+        ins = [self._target_inputs(p, t) for p, t in zip(samples, targets)]
+        pts, sps, mode = [i[0] for i in ins], [i[1] for i in ins], ins[0][3]
+        f2d = [i[2] for i in ins] if mode == 0 else None
         maps = BatchSceneMaps(pts, self.voxel_size, 5, shift_to_min=False, order=self.KERNEL_ORDER, superpoints=sps)
         cap = _trace.active()
         if cap is not None:
@@ -302,9 +303,7 @@ class Res16UNetBase(DerivedWeights):
         cuts = list(zip(maps.sp_off[:-1], maps.sp_off[1:]))
         feats = [f_all[a:b] for a, b in cuts]
         pos = [p_all[a:b] for a, b in cuts]
-        pos_wo = [p.clone() for p in pos]
-        sp_pos = pos if self.add_positional_embedding else None
-        return (feats, sp_pos, pos_wo) if return_sp_mean_pos else (feats, sp_pos, None)
+        return self._wrapper_result(feats, pos, [p.clone() for p in pos], return_sp_mean_pos)
 
     @ops.bound_stream
     def forward_wrapper(self, samples: List[torch.Tensor], targets, return_sp_mean_pos=False):
@@ -340,10 +339,7 @@ class Res16UNetBase(DerivedWeights):
                 pos_wo.append(p.clone())
             elif return_sp_mean_pos:
                 pos_wo.append(self._positions_wo_elastic(pts, sp, x))
-        sp_pos = pos if self.add_positional_embedding else None
-        if return_sp_mean_pos:
-            return feats, sp_pos, pos_wo
-        return feats, sp_pos, None
+        return self._wrapper_result(feats, pos, pos_wo, return_sp_mean_pos)
 
 
 class Res16UNet34(Res16UNetBase):

@@ -8,13 +8,16 @@ the coarser tensor strides, and hand out cached neighbour tables (`nbr[k, v]`) f
 HBM layout per scene (V_l voxels at level l, Z-order sorted, so a voxel's children/parents and
 spatial neighbours are close in memory):
     keys_l   int64 [V_l]        Z-order key of (coord - origin) >> l  (+ batch bits)
-    hash_l   int64/int32 [cap]  open-addressing table key -> voxel id (cap = pow2 >= 2 V_l)
-    nbr      int32 [K, V_out]   gather table of one convolution kernel (K-major: coalesced per offset)
+    nbr      int32 [K, V_out]   gather table of one convolution kernel (K-major: coalesced per offset), built through the
+                                level hierarchy of the sorted keys
+    hash_l   int64/int32 [cap]  open-addressing table key -> voxel id (cap = pow2 >= 2 V_l): only for spconv's clipped
+                                levels (and with SD3D_HIER_MAPS=0), whose maps are hash-probed
     parent_l int32 [V_l]        id of the parent voxel at level l+1
     inverse  int32 [N]          point -> level-0 voxel id
     sidx/seg int32 [N], [V_0+1] points sorted by voxel + segment starts (ascending point order inside)
-Exactly one host synchronisation per scene: the voxel counts of all levels (needed to size the
-launches) are read back together with the overflow flag and the superpoint count.
+Two host synchronisations per scene: the voxel counts of all levels (needed to size the
+launches) are read back together with the overflow flags and the superpoint count; then the rulebook sizes of the
+neighbour tables, which size the pair lists (`prepare`; skipped where the lists are sized for the worst case).
 """
 from __future__ import annotations
 
@@ -130,13 +133,14 @@ MIRRORED_MAPS = os.environ.get("SD3D_MIRRORED_MAPS", "1") != "0"
 # entries of an output row's mirror offsets {k, K-1-k} and its centre share ONE partial product - 27-44 % fewer partial rows written
 # by pass 1 and read by pass 2).  Training keeps the plain lists (the weight-gradient kernels walk them offset by offset).
 PAIR_CHAIN = os.environ.get("SD3D_PAIR_CHAIN", "1") != "0"
-# Which U-Net levels get chained lists is a property of the LEVEL, never of the scene or the batch (a scene's rows must see the same
+# SD3D_PAIR_CHAIN_LEVELS: which U-Net levels get chained lists.  A property of the LEVEL, never of the scene or the batch (a scene's rows must see the same
 # list format whether it runs alone or in a batch: the two formats sum in different orders).  Levels 0-2 (the tables with thousands
 # of tiles): measured same box, 4 streams x 4 scenes 118.1 -> 120.5-123 scenes/s, convolutions 7.29 -> 7.06 ms per scene in the
 # instrumented replay (0.471 -> 0.486 of the fp32 matrix peak), one scene in flight neutral (7.78 vs 7.76 ms: what the fewer partial
 # rows win, the weight-stationary pass-1 variants - which cannot chain - lose).  Levels 3-4 have few hundred to ~1800 tiles: chains
 # of three tiles on 3-4 tiles per workgroup unbalance the static ranges and the level-3 layers lose their weight-stationary variant:
 # all five levels 124.6 scenes/s with several scenes in flight but 8.27 vs 7.74 ms of convolutions with one.
+PAIR_CHAIN_LEVELS = tuple(int(v) for v in os.environ.get("SD3D_PAIR_CHAIN_LEVELS", "0,1,2").split(",") if v.strip() != "")
 # SD3D_FORK_JOIN=0: every neighbour table of a scene is built on the scene's own stream before the first convolution.  Default:
 # with ONE scene in flight (worst-case list sizes, no second read-back) only the stem's table is; the other levels' hash tables,
 # kernel maps and pair lists are built on a side stream while the stem and the first blocks convolve, each table's first layer
@@ -152,10 +156,36 @@ OPTIMISTIC_SORT = os.environ.get("SD3D_OPTIMISTIC_SORT", "1") != "0"
 LEVELS_AT_ONCE = os.environ.get("SD3D_LEVELS_AT_ONCE", "1") != "0"
 # SD3D_LEAN_LISTS=0: evaluation tables with their [K, M] position table and -1-filled unused capacity (rounds 1 - 4)
 LEAN_LISTS = os.environ.get("SD3D_LEAN_LISTS", "1") != "0"
-MORTON_BITS = 48               # SD3D_MORTON_BITS (csrc/common.h): the Z-order code of a voxel; a batch's scene index sits above it
 # SD3D_VOXELISE_ONE_CALL=0: the voxelisation chain of a scene as ~10 Python calls (the round 1 - 4 path; the clipped / per-level variants keep it)
 VOXELISE_ONE_CALL = os.environ.get("SD3D_VOXELISE_ONE_CALL", "1") != "0"
-PAIR_CHAIN_LEVELS = tuple(int(v) for v in os.environ.get("SD3D_PAIR_CHAIN_LEVELS", "0,1,2").split(",") if v.strip() != "")
+MORTON_BITS = 48               # SD3D_MORTON_BITS (csrc/common.h): the Z-order code of a voxel; a batch's scene index sits above it
+
+
+def _levels_at_once(n_levels: int, clip_min_shape: int) -> bool:
+    return LEVELS_AT_ONCE and clip_min_shape == 0 and 1 < n_levels <= 8
+
+
+def _levels_from_sorted(skeys, sidx, n_levels: int, rb, clip=None):
+    """Sorted point keys -> (keys_l, seg_start, inverse, parents) of every level; the voxel counts land in the read-back slots
+    rb[0:n_levels].  clip = (stats, inv_voxel, clip_min_shape): spconv's output-extent rule for the strided levels."""
+    N = skeys.shape[0]
+    at_once = _levels_at_once(n_levels, clip[2] if clip else 0)
+    if at_once and VOXELISE_ONE_CALL:
+        # every level from the sorted point keys in four launches (level 0 and the coarser levels were four each).  Batches only:
+        # one scene with these settings never gets here, its whole chain is `ops.voxelise_scene`
+        return ops.voxel_levels_all(skeys, sidx, n_levels, rb[0:n_levels])
+    ukeys, seg_start, inverse, n_prev = ops.unique_sorted(
+        skeys, sidx, N, None, 0, want_seg_start=True, want_map=True, map_size=N, nuniq_out=rb[0:1])
+    if at_once:
+        uks, parents, _ = ops.unique_levels(ukeys, N, n_prev, n_levels - 1, counts_out=rb[1:n_levels])   # every coarser level in four launches
+        return [ukeys] + uks, seg_start, inverse, parents
+    keys_l, parents = [ukeys], []
+    for lvl in range(1, n_levels):
+        uk, _, parent, n_prev = ops.unique_sorted(keys_l[-1], None, N, n_prev, 3, want_seg_start=False, want_map=True,
+                                                  clip=(clip[0], clip[1], lvl, clip[2]) if clip else None, nuniq_out=rb[lvl:lvl + 1])
+        keys_l.append(uk)
+        parents.append(parent)
+    return keys_l, seg_start, inverse, parents
 
 
 class SceneMaps:
@@ -169,96 +199,87 @@ class SceneMaps:
         scene (the validity check of the derived weights) costs nothing there, the host would sleep."""
         if not points.is_cuda:
             raise RuntimeError("SceneMaps needs device-resident points (no CPU fallback in the product path)")
-        self.order = order
         self.device = points.device
+        self.n_points = points.shape[0]
+        self._voxelise(points, voxel_size, n_levels, shift_to_min, order, superpoints, clip_min_shape, while_waiting)
+
+    def _voxelise(self, points, voxel_size, n_levels, shift_to_min, order, superpoints, clip_min_shape, while_waiting=None):
+        """The constructor of one scene and of a batch (`points` / `superpoints`: a tensor or a list of them; device, n_points and what
+        else `_issue` needs are set): voxelisation chain, the one read-back, retry with the full sorts, counts, caches."""
+        self.order = order
         self.voxel_size = float(voxel_size)
         self.clipped = clip_min_shape > 0
-        N = points.shape[0]
-        self.n_points = N
-        inv = float(np.float32(1.0) / np.float32(voxel_size))
         self.superpoints = superpoints                    # int64 id per point (kept for the pooling backward, train_ops)
-        # Optimistic radix passes: the voxel keys are sorted over their low 32 bits (4 passes instead of 7: any scene up to ~20 m at 2 cm)
-        # and the superpoint ids over 16 (2 instead of 4); the key kernels raise a flag when a key needs more, the flag rides in the
-        # scene's read-back, and the chain is then redone with the full sorts (tests/test_gpu_sparse.py exercises both).
-        key_bits, sp_bits = (32, 16) if OPTIMISTIC_SORT else (56, 32)
-        at_once = LEVELS_AT_ONCE and clip_min_shape == 0 and 1 < n_levels <= 8
+        inv = float(np.float32(1.0) / np.float32(voxel_size))
+        # Optimistic radix passes: the Morton part of the voxel keys is sorted over its low 32 bits (4 passes instead of 7: any scene up
+        # to ~20 m at 2 cm) and the superpoint ids over 16 (2 instead of 4); the key kernels raise a flag when a key needs more, the flag
+        # rides in the read-back, and the chain is then redone with the full sorts (tests/test_gpu_sparse.py exercises both).  Either way
+        # the arrays are those of the full sorts.
+        optimistic = OPTIMISTIC_SORT
         while True:
-            if at_once and VOXELISE_ONE_CALL:
-                # the whole chain below from one C call (same kernels, same order): ~28 launches of 4 - 13 us that a Python host issues
-                # slower than the GPU runs them, in front of everything else of the scene
-                v = ops.voxelise_scene(points, inv, shift_to_min, key_bits, n_levels, superpoints,
-                                       (sp_bits if sp_bits < 32 else 64) if superpoints is not None else 64)
-                self.stats, self.icoords, self.origin, self.sidx = v["stats"], v["icoords"], v["origin"], v["sidx"]
-                self.seg_start, self.inverse, keys_l, parents = v["seg_start"], v["inverse"], v["ukeys"], v["parents"]
-                self._rb_dev = v["readback"]
-                read = ops.HostRead(v["readback"])           # synchronisation 1 of the scene (polled)
-                if superpoints is not None:                  # sorted while the read-back travels
-                    self.sp_sorted, self.sp_sidx = ops.sort_pairs(v["sp_keys"], None, 0, sp_bits)
-                if while_waiting is not None:
-                    while_waiting(self)
-                    while_waiting = None
-                host = read.wait().tolist()
-                flags = int(host[n_levels])
-                if (flags & 2 and key_bits < 56) or (flags & 4 and sp_bits < 32):
-                    key_bits, sp_bits = 56, 32
-                    continue
-                break
-            # the scene's read-back, written in place by the kernels (no concatenation launch): [n_0 .. n_{L-1}, flags, largest superpoint id]
-            rb = torch.zeros(n_levels + 2, dtype=torch.int32, device=self.device)
-            err = rb[n_levels:n_levels + 1]
-            self.stats = ops.scene_stats(points)
-            keys, self.icoords, self.origin, _ = ops.voxel_keys(points, inv, self.stats, shift_to_min, err=err)
-            skeys, self.sidx = ops.sort_pairs(keys, None, 0, key_bits)
-            ukeys, self.seg_start, self.inverse, n0 = ops.unique_sorted(
-                skeys, self.sidx, N, None, 0, want_seg_start=True, want_map=True, map_size=N, nuniq_out=rb[0:1])
-            keys_l, parents = [ukeys], []
-            cap = N
-            if at_once:
-                uks, parents, _ = ops.unique_levels(ukeys, cap, n0, n_levels - 1, counts_out=rb[1:n_levels])   # every coarser level in four launches
-                keys_l += uks
-            else:
-                n_prev = n0
-                for lvl in range(1, n_levels):
-                    clip = (self.stats, inv, lvl, clip_min_shape) if clip_min_shape > 0 else None
-                    uk, _, parent, n_prev = ops.unique_sorted(keys_l[-1], None, cap, n_prev, 3, want_seg_start=False, want_map=True,
-                                                              clip=clip, nuniq_out=rb[lvl:lvl + 1])
-                    keys_l.append(uk)
-                    parents.append(parent)
-            sp_keys = None
-            if superpoints is not None:                  # (the ids' largest value - the superpoint count - does not wait for their sort)
-                sp_keys = ops.keys_from_i64(superpoints, check=(sp_bits if sp_bits < 32 else 64, err, 4), max_out=rb[n_levels + 1:])
-            self._rb_dev = rb
-            read = ops.HostRead(rb)                      # synchronisation 1 of the scene (polled)
-            if sp_keys is not None:                      # sorted while the read-back travels
-                self.sp_sorted, self.sp_sidx = ops.sort_pairs(sp_keys, None, 0, sp_bits)
+            # rb, written in place by the kernels: [n_0 .. n_{L-1}, flags, largest superpoint id (of every scene)]
+            rb, keys_l, parents, sp_keys = self._issue(points, inv, n_levels, shift_to_min, superpoints, clip_min_shape, optimistic)
+            read = ops.HostRead(rb)                          # synchronisation 1 (polled)
+            if sp_keys is not None:                          # sorted while the read-back travels
+                self.sp_sorted, self.sp_sidx = self._sort_superpoints(sp_keys, optimistic)
             if while_waiting is not None:
                 while_waiting(self)
                 while_waiting = None
             host = read.wait().tolist()
-            flags = int(host[n_levels])
-            if (flags & 2 and key_bits < 56) or (flags & 4 and sp_bits < 32):
-                key_bits, sp_bits = 56, 32                                   # a key did not fit: full sorts (rare: the chain runs twice)
+            flags = int(host[n_levels])                      # 1: key range, 2: Morton part > 32 bits, 4: superpoint id > 16 bits, 8: bad id
+            if optimistic and flags & 6:
+                optimistic = False                           # a key did not fit: full sorts (rare: the chain runs twice)
                 continue
             break
         self.n_vox = [int(v) for v in host[:n_levels]]
-        if int(host[n_levels]) & 1:
+        if flags & 1:
             raise RuntimeError("scene exceeds the 16-bit-per-axis voxel key range (extent > ~1.3 km at 2 cm)")
-        if int(host[n_levels]) & 8:
+        if flags & 8:
             raise RuntimeError("superpoint ids must lie in [0, 2^31 - 2] (a negative or oversized id was found)")
-        self.n_superpoints = int(host[n_levels + 1]) + 1 if superpoints is not None else 0
+        self._count_superpoints(host[n_levels + 1:])
         self.keys = [k[: self.n_vox[l]] for l, k in enumerate(keys_l)]
         self.parents = [p[: self.n_vox[l]] for l, p in enumerate(parents)]
         self.seg_start = self.seg_start[: self.n_vox[0] + 1]
         self._hash: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
         self._same: Dict[Tuple[int, int], torch.Tensor] = {}
         self._stride: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._hier_built = False                             # the maps came from ops.kernel_maps_hier (no hash tables)
         self._perm8 = perm8_device(order, self.device)
         self._sp_start = None
         self.density: Dict[Tuple, float] = {}
         self.pairs: Dict[Tuple, "ops.PairLists"] = {}       # offset-major rulebooks (prepare())
         self.events: Dict[Tuple, torch.cuda.Event] = {}     # tables built on the side stream (prepare(fork=True)) -> their event
         self._join_ev = self._late = self._stem_done = None
+        self._side_used = False
         self._fork_ev = ops.stream_event()                   # everything the tables are built from is complete here
+
+    def _issue(self, points, inv, n_levels, shift_to_min, superpoints, clip_min_shape, optimistic):
+        """Enqueue the voxelisation chain up to the read-back -> (read-back, keys per level, parents per level, superpoint keys | None)."""
+        key_bits, sp_check = (32, 16) if optimistic else (56, 64)
+        if _levels_at_once(n_levels, clip_min_shape) and VOXELISE_ONE_CALL:
+            # the whole chain below from one C call (same kernels, same order): ~28 launches of 4 - 13 us that a Python host issues
+            # slower than the GPU runs them, in front of everything else of the scene
+            v = ops.voxelise_scene(points, inv, shift_to_min, key_bits, n_levels, superpoints, sp_check if superpoints is not None else 64)
+            self.stats, self.icoords, self.origin, self.sidx = v["stats"], v["icoords"], v["origin"], v["sidx"]
+            self.seg_start, self.inverse = v["seg_start"], v["inverse"]
+            return v["readback"], v["ukeys"], v["parents"], v["sp_keys"]
+        rb = torch.zeros(n_levels + 2, dtype=torch.int32, device=self.device)
+        err = rb[n_levels:n_levels + 1]
+        self.stats = ops.scene_stats(points)
+        keys, self.icoords, self.origin, _ = ops.voxel_keys(points, inv, self.stats, shift_to_min, err=err)
+        skeys, self.sidx = ops.sort_pairs(keys, None, 0, key_bits)
+        keys_l, self.seg_start, self.inverse, parents = _levels_from_sorted(
+            skeys, self.sidx, n_levels, rb, (self.stats, inv, clip_min_shape) if clip_min_shape > 0 else None)
+        sp_keys = None
+        if superpoints is not None:                      # (the ids' largest value - the superpoint count - does not wait for their sort)
+            sp_keys = ops.keys_from_i64(superpoints, check=(sp_check, err, 4), max_out=rb[n_levels + 1:])
+        return rb, keys_l, parents, sp_keys
+
+    def _sort_superpoints(self, sp_keys, optimistic):
+        return ops.sort_pairs(sp_keys, None, 0, 16 if optimistic else 32)
+
+    def _count_superpoints(self, largest_ids):
+        self.n_superpoints = int(largest_ids[0]) + 1 if self.superpoints is not None else 0
 
     def prepare(self, same=(), strides=(), chained=False, fork=False):
         """Build the listed neighbour tables now and read their rulebook sizes back in ONE copy (the
@@ -300,7 +321,7 @@ class SceneMaps:
         self._side_used = True
         with ops.use_stream(side):
             side.wait_event(self._fork_ev)
-            if getattr(self, "_hier_built", False) or any(t[0] in self._hash for t in g_same):
+            if self._hier_built or any(t[0] in self._hash for t in g_same):
                 side.wait_event(self._stem_done)                          # maps / a hash table the stem's stream built
             keys = self._build_tables(g_same, g_strides, chained, False)
             ev = ops.stream_event()
@@ -322,7 +343,7 @@ class SceneMaps:
         scene's stream; when this SceneMaps dies their blocks return to that pool at once, and without this edge only the next
         scene's fork event - recorded on whatever stream THAT forward runs on - would keep later side-stream work from overwriting
         them under the U-Net kernels that still read them."""
-        if getattr(self, "_side_used", False):
+        if self._side_used:
             ops.side_streams(1, self.device)[0].wait_event(ops.stream_event())
             self._side_used = False
 
@@ -363,9 +384,7 @@ class SceneMaps:
                 if exact and not hier:                           # (built earlier without a counter: count the table's entries)
                     counters[i, 0] = (self._same[(lvl, k)] >= 0).sum().to(torch.int32)
                 continue
-            offs = offsets_device(k, self.order, self.device)
-            self._same[(lvl, k)] = ops.kernel_map(self.keys[lvl], self.n_vox[lvl], self.table(lvl), offs,
-                                                  counters[i] if exact else None, mirrored=MIRRORED_MAPS and k % 2 == 1)
+            self._same[(lvl, k)] = self._probe_map(lvl, k, counters[i] if exact else None)
         for lvl in strides:
             self._stride_maps(lvl)
         if exact:
@@ -407,14 +426,18 @@ class SceneMaps:
             self._hash[level] = ops.hash_build(self.keys[level], self.n_vox[level])
         return self._hash[level]
 
+    def _probe_map(self, level: int, ksize: int, pair_count=None):
+        """nbr [k^3, V_l] by hash-table probes (pair_count int32 [>= 1]: receives the table's number of entries)."""
+        offs = offsets_device(ksize, self.order, self.device)
+        return ops.kernel_map(self.keys[level], self.n_vox[level], self.table(level), offs, pair_count,
+                              mirrored=MIRRORED_MAPS and ksize % 2 == 1)
+
     def same(self, level: int, ksize: int) -> torch.Tensor:
         """nbr [k^3, V_l] of a stride-1 convolution on level `level`."""
         self.join()
         key = (level, ksize)
         if key not in self._same:
-            offs = offsets_device(ksize, self.order, self.device)
-            self._same[key] = ops.kernel_map(self.keys[level], self.n_vox[level], self.table(level), offs,
-                                             mirrored=MIRRORED_MAPS and ksize % 2 == 1)
+            self._same[key] = self._probe_map(level, ksize)
         return self._same[key]
 
     def _stride_maps(self, level: int):
@@ -484,96 +507,55 @@ class BatchSceneMaps(SceneMaps):
             raise ValueError("BatchSceneMaps: 1..16 scenes per batch (SD3D_MAX_BATCH)")
         if not all(p.is_cuda for p in points):
             raise RuntimeError("BatchSceneMaps needs device-resident points (no CPU fallback in the product path)")
-        self.order = order
-        self.device = dev = points[0].device
-        self.voxel_size = float(voxel_size)
-        self.clipped = clip_min_shape > 0
+        self.device = points[0].device
         self.n_scenes = B
         self.point_off = [0]
         for p in points:
             self.point_off.append(self.point_off[-1] + int(p.shape[0]))
-        N = self.point_off[-1]
-        self.n_points = N
-        inv = float(np.float32(1.0) / np.float32(voxel_size))
-        self.stats = torch.empty(B, 9, dtype=torch.float32, device=dev)
-        self.superpoints = superpoints
-        scene_bits = max(1, (B - 1).bit_length())
-        # Optimistic radix passes as for one scene: Morton parts that fit 32 bits are sorted over those and then over the scene bits
-        # (5 passes instead of 7), superpoint ids that fit 16 bits likewise (3 instead of 5); the key kernels raise a flag otherwise and
-        # the chain runs again with the full sorts.  Either way the arrays are those of the full sorts.
-        optimistic = OPTIMISTIC_SORT
-        while True:
-            # the batch's read-back, written in place by the kernels: [n_0 .. n_{L-1}, flags, largest superpoint id of scene 0 .. B-1]
-            rb = torch.zeros(n_levels + 1 + B, dtype=torch.int32, device=dev)
-            err = rb[n_levels:n_levels + 1]
-            keys = torch.empty(N, dtype=torch.int64, device=dev)
-            self.icoords = torch.empty(N, 3, dtype=torch.int32, device=dev)
-            for i, p in enumerate(points):
-                a, b = self.point_off[i], self.point_off[i + 1]
-                ops.scene_stats(p, out=self.stats[i])
-                ops.voxel_keys(p, inv, self.stats[i], shift_to_min, batch_index=i, out=(keys[a:b], self.icoords[a:b], err))
-            if optimistic:
-                skeys, self.sidx = ops.sort_pairs(keys, None, 0, 32)
-                skeys, self.sidx = ops.sort_pairs(skeys, self.sidx, MORTON_BITS, MORTON_BITS + scene_bits)
-            else:
-                skeys, self.sidx = ops.sort_pairs(keys, None, 0, 56)
-            if LEVELS_AT_ONCE and VOXELISE_ONE_CALL and clip_min_shape == 0 and 1 < n_levels <= 8:
-                # every level from the sorted point keys in four launches (round 5; level 0 and the coarser levels were four each)
-                keys_l, self.seg_start, self.inverse, parents = ops.voxel_levels_all(skeys, self.sidx, n_levels, rb[0:n_levels])
-            elif LEVELS_AT_ONCE and clip_min_shape == 0 and 1 < n_levels <= 8:
-                ukeys, self.seg_start, self.inverse, n0 = ops.unique_sorted(
-                    skeys, self.sidx, N, None, 0, want_seg_start=True, want_map=True, map_size=N, nuniq_out=rb[0:1])
-                uks, parents, _ = ops.unique_levels(ukeys, N, n0, n_levels - 1, counts_out=rb[1:n_levels])
-                keys_l = [ukeys] + uks
-            else:
-                ukeys, self.seg_start, self.inverse, n0 = ops.unique_sorted(
-                    skeys, self.sidx, N, None, 0, want_seg_start=True, want_map=True, map_size=N, nuniq_out=rb[0:1])
-                keys_l, parents = [ukeys], []
-                n_prev = n0
-                for lvl in range(1, n_levels):
-                    clip = (self.stats, inv, lvl, clip_min_shape) if clip_min_shape > 0 else None
-                    uk, _, parent, n_prev = ops.unique_sorted(keys_l[-1], None, N, n_prev, 3, want_seg_start=False, want_map=True, clip=clip,
-                                                              nuniq_out=rb[lvl:lvl + 1])
-                    keys_l.append(uk)
-                    parents.append(parent)
-            sp_keys = None
-            if superpoints is not None:                        # (every scene's largest id - its superpoint count - does not wait for the sort)
-                sp_keys = torch.empty(N, dtype=torch.int64, device=dev)
-                for i, sp in enumerate(superpoints):
-                    ops.keys_from_i64_offset(sp.contiguous(), i << 32, sp_keys[self.point_off[i]:self.point_off[i + 1]],
-                                             check=(16 if optimistic else 64, err, 4), max_out=rb[n_levels + 1 + i:n_levels + 2 + i])
-            read = ops.HostRead(rb)                            # synchronisation 1 of the batch (polled)
-            if sp_keys is not None:                            # sorted while the read-back travels
-                if optimistic:
-                    k1, v1 = ops.sort_pairs(sp_keys, None, 0, 16)
-                    self.sp_sorted, self.sp_sidx = ops.sort_pairs(k1, v1, 32, 32 + scene_bits)
-                else:
-                    self.sp_sorted, self.sp_sidx = ops.sort_pairs(sp_keys, None, 0, 32 + scene_bits)
-            host = read.wait().tolist()
-            flags = int(host[n_levels])
-            if optimistic and flags & 6:
-                optimistic = False                             # a key did not fit: full sorts (rare: the chain runs twice)
-                continue
-            break
-        self.n_vox = [int(v) for v in host[:n_levels]]
-        if int(host[n_levels]) & 1:                                # (bit 1 = "more than 32 Morton bits": the batch sorts all 56 key bits anyway)
-            raise RuntimeError("scene exceeds the 16-bit-per-axis voxel key range (extent > ~1.3 km at 2 cm)")
-        if int(host[n_levels]) & 8:
-            raise RuntimeError("superpoint ids must lie in [0, 2^31 - 2] (a negative or oversized id was found)")
+        self.n_points = self.point_off[-1]
+        self.stats = torch.empty(B, 9, dtype=torch.float32, device=self.device)
+        self._voxelise(points, voxel_size, n_levels, shift_to_min, order, superpoints, clip_min_shape)
+
+    def _scene_bits(self):
+        return max(1, (self.n_scenes - 1).bit_length())
+
+    def _issue(self, points, inv, n_levels, shift_to_min, superpoints, clip_min_shape, optimistic):
+        N, dev = self.n_points, self.device
+        rb = torch.zeros(n_levels + 1 + self.n_scenes, dtype=torch.int32, device=dev)
+        err = rb[n_levels:n_levels + 1]
+        keys = torch.empty(N, dtype=torch.int64, device=dev)
+        self.icoords = torch.empty(N, 3, dtype=torch.int32, device=dev)
+        for i, p in enumerate(points):
+            a, b = self.point_off[i], self.point_off[i + 1]
+            ops.scene_stats(p, out=self.stats[i])
+            ops.voxel_keys(p, inv, self.stats[i], shift_to_min, batch_index=i, out=(keys[a:b], self.icoords[a:b], err))
+        if optimistic:                                     # Morton parts that fit 32 bits, then the scene bits: 5 radix passes instead of 7
+            skeys, self.sidx = ops.sort_pairs(keys, None, 0, 32)
+            skeys, self.sidx = ops.sort_pairs(skeys, self.sidx, MORTON_BITS, MORTON_BITS + self._scene_bits())
+        else:
+            skeys, self.sidx = ops.sort_pairs(keys, None, 0, 56)
+        keys_l, self.seg_start, self.inverse, parents = _levels_from_sorted(
+            skeys, self.sidx, n_levels, rb, (self.stats, inv, clip_min_shape) if clip_min_shape > 0 else None)
+        sp_keys = None
+        if superpoints is not None:                        # (every scene's largest id - its superpoint count - does not wait for the sort)
+            sp_keys = torch.empty(N, dtype=torch.int64, device=dev)
+            for i, sp in enumerate(superpoints):
+                ops.keys_from_i64_offset(sp.contiguous(), i << 32, sp_keys[self.point_off[i]:self.point_off[i + 1]],
+                                         check=(16 if optimistic else 64, err, 4), max_out=rb[n_levels + 1 + i:n_levels + 2 + i])
+        return rb, keys_l, parents, sp_keys
+
+    def _sort_superpoints(self, sp_keys, optimistic):
+        if optimistic:                                     # ids that fit 16 bits, then the scene bits: 3 radix passes instead of 5
+            k1, v1 = ops.sort_pairs(sp_keys, None, 0, 16)
+            return ops.sort_pairs(k1, v1, 32, 32 + self._scene_bits())
+        return ops.sort_pairs(sp_keys, None, 0, 32 + self._scene_bits())
+
+    def _count_superpoints(self, largest_ids):
         self.sp_off = [0]
-        if superpoints is not None:
-            for v in host[n_levels + 1:n_levels + 1 + B]:
+        if self.superpoints is not None:
+            for v in largest_ids:
                 self.sp_off.append(self.sp_off[-1] + int(v) + 1)
         self.n_superpoints = self.sp_off[-1]
-        self.keys = [k[: self.n_vox[l]] for l, k in enumerate(keys_l)]
-        self.parents = [p[: self.n_vox[l]] for l, p in enumerate(parents)]
-        self.seg_start = self.seg_start[: self.n_vox[0] + 1]
-        self._hash, self._same, self._stride = {}, {}, {}
-        self._perm8 = perm8_device(order, self.device)
-        self._sp_start = None
-        self.density, self.pairs = {}, {}
-        self.events, self._join_ev, self._fork_ev = {}, None, ops.stream_event()
-        self._late = self._stem_done = None
 
     def voxel_features(self, points: Sequence[torch.Tensor], feats2d, mode: int, ld_out: int, stats=None) -> torch.Tensor:
         """points / feats2d: the scenes' tensors in batch order (feats2d None or a list)."""
