@@ -168,6 +168,14 @@ int sd3d_kernel_maps_hier(int n_levels, const uint64_t* const* keys, const int32
                           int32_t* const* nbr3, int32_t* nbr5, const int8_t* offsets3, const int8_t* offsets5, const int8_t* inv27,
                           int32_t* pair_counts, const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up, void* ws,
                           size_t ws_bytes, void* stream);
+/* ... and, while a workgroup holds the 256 rows of a block, the entry counts per (offset, 256-row block) of the tables it writes:
+ * blk_cnt3[l] (l < n_levels - 1; the array or any entry may be NULL) device int32 [27, ceil(n_l / 256)], blk_cnt5 (NULL or)
+ * [125, ceil(n_0 / 256)], count of offset k in rows [256 b, 256 b + 256) at [k * nblk + b] - what sd3d_pair_lists_desc_counts takes in
+ * place of its own count pass.  (The coarsest level's map is searched directly and brings no counts.) */
+int sd3d_kernel_maps_hier_counts(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n,
+                                 int32_t* const* nbr3, int32_t* nbr5, const int8_t* offsets3, const int8_t* offsets5, const int8_t* inv27,
+                                 int32_t* pair_counts, const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up,
+                                 int32_t* const* blk_cnt3, int32_t* blk_cnt5, void* ws, size_t ws_bytes, void* stream);
 /* 2x2x2 stride-2 maps from the parent array: nbr_down [8, n_coarse], nbr_up [8, n_fine]; perm8[8]
  * maps the child's Z-order position (x | y<<1 | z<<2) to the weight index. */
 int sd3d_stride_maps(const uint64_t* fine_keys, const int32_t* parent, int64_t n_fine, int64_t n_coarse,
@@ -306,6 +314,12 @@ typedef struct sd3d_pair_table_desc {
     int32_t K, center, rl_stride, meta;
 } sd3d_pair_table_desc;
 int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* tables, void* ws, size_t ws_bytes, void* stream);
+/* The same, with the count pass of some tables already done: blk_counts (NULL or) [n] pointers, each NULL or device int32
+ * [K, ceil(M / 256)] as sd3d_kernel_maps_hier_counts leaves them.  Only a table built in the row-block form (pos == NULL, K <= 128, not
+ * chained) may bring counts; it has no workgroups in the count launch, its counts are scanned in place (consumed), and its lists are
+ * those of sd3d_pair_lists_desc bit for bit. */
+int sd3d_pair_lists_desc_counts(int n, const sd3d_pair_table_desc* tables, int32_t* const* blk_counts, void* ws, size_t ws_bytes,
+                                void* stream);
 int sd3d_pair_conv_ex(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* in_idx,
                       const int32_t* tile_k, int64_t p_cap, const int32_t* pos, const int32_t* rlist, int rl_stride, int center,
                       const int32_t* out_idx, const float* wt, int K, int Cin, int Cout, int64_t M, const float* scale,

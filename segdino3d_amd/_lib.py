@@ -55,6 +55,7 @@ SIGNATURES = {
     "sd3d_kernel_map": (_i, [_p, _l, _p, _p, _l, _p, _i, _i, _p, _p, _p]),
     "sd3d_kernel_maps_hier_ws_bytes": (_z, [_i, _p]),
     "sd3d_kernel_maps_hier": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "sd3d_kernel_maps_hier_counts": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "sd3d_stride_maps": (_i, [_p, _p, _l, _l, _p, _p, _p, _p]),
     "sd3d_voxel_mean": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _p, _l, _p, _i, _p]),
     "sd3d_segment_starts": (_i, [_p, _l, _l, _p, _p]),
@@ -68,6 +69,7 @@ SIGNATURES = {
     "sd3d_gather_gemm_split": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _l, _p, _p, _p, _i, _p, _i, _i, _i, _p, _z, _p]),
     "sd3d_pair_lists_ws_bytes": (_z, [_i, _l]),
     "sd3d_pair_lists_desc": (_i, [_i, _p, _p, _z, _p]),
+    "sd3d_pair_lists_desc_counts": (_i, [_i, _p, _p, _p, _z, _p]),
     "sd3d_pair_conv_ex": (_i, [_p, _i, _i, _p, _i, _p, _p, _l, _p, _p, _i, _i, _p, _p, _i, _i, _i, _l, _p, _p, _p, _i, _p, _i, _i, _p, _z, _p]),
     "sd3d_run_layers": (_i, [_p, _i, _p, _i, _p, _i, _p, _z, _p, _z, _p]),
     "sd3d_run_layers_ev": (_i, [_p, _i, _p, _i, _p, _i, _p, _z, _p, _z, _p, _p]),

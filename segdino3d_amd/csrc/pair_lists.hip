@@ -540,15 +540,21 @@ extern "C" size_t sd3d_pair_lists_ws_bytes(int K, int64_t M) {
 // n tables at once (n <= PL_MAX_TABLES); the tables' scratch sits back to back in ws (sd3d_pair_lists_ws_bytes(K_i, M_i) bytes each,
 // rounded up to 256).  p_cap: capacity of in_idx in pairs (multiple of 128, >= pairs + K * 127); tile_k has p_cap / 128 + 1 entries
 // (the last one receives the number of real tiles).  rlist / out_idx / the two centre slots of tile_k are optional products (see sd3d_pair_table_desc).
-extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_t ws_bytes, void* stream) {
+// blk_counts: NULL, or per table NULL or device int32 [K, cdiv(M, 256)]: the entry counts per (offset, 256-row block) that the count
+// pass of the row-block form would produce (sd3d_kernel_maps_hier_counts leaves them while it writes the table).  Such a table has no
+// workgroups in the count launch; scan and fill run as ever, the scan in place over the given counts (they are consumed).  Only a
+// table that takes the row-block form (no pos, K <= 128, not chained) may bring counts.
+extern "C" int sd3d_pair_lists_desc_counts(int n, const sd3d_pair_table_desc* d, int32_t* const* blk_counts, void* ws, size_t ws_bytes,
+                                           void* stream) {
     if (n > 0 && !d) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_desc: tables is NULL");
     hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
     if (n > PL_MAX_TABLES) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_batch: at most 16 tables per call");
-    PLBatch b, rbt;                                            // (offset, row block) form / row-block form (no pos table)
+    PLBatch b, rbt, rbc;                                       // (offset, row block) form / row-block form (no pos table) / those of rbt that must count
     b.n = 0;
     rbt.n = 0;
-    int rwg = 0, rkk = 0;
+    rbc.n = 0;
+    int rwg = 0, rkk = 0, rcwg = 0;
     CHBatch cb;
     cb.n = 0;
     size_t off = 0;
@@ -557,6 +563,9 @@ extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* 
     for (int i = 0; i < n; ++i) {
         const int K = d[i].K;
         const int64_t M = d[i].M, p_cap = d[i].p_cap;
+        int32_t* const given = blk_counts ? blk_counts[i] : nullptr;
+        if (given && (d[i].center == SD3D_PAIR_CHAINED || d[i].pos || K > PR_MAX_K))
+            return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_desc_counts: only a row-block table (no pos, K <= 128, not chained) takes block counts");
         if (d[i].center == SD3D_PAIR_CHAINED && K > 0 && M > 0) {
             // chained lists (mirror groups + centre share a partial product): their own builder
             if (!(K & 1) || K < 3) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_batch: chained lists need an odd kernel (symmetric offsets)");
@@ -591,9 +600,16 @@ extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* 
             T.nblk = (int)cdiv(M, 256);
             T.blk_cnt = (int32_t*)((char*)ws + off);
             T.totals = T.blk_cnt + (int64_t)T.K * T.nblk;
+            if (given) T.blk_cnt = given;
             off += align_up(sd3d_pair_lists_ws_bytes(K, M), 256);
             T.wg0 = rwg; T.k0 = rkk; T.rb0 = 0;
             rwg += T.nblk; rkk += T.K;
+            if (!given) {                                      // the count launch numbers its workgroups over the tables that count
+                PLTable& C = rbc.t[rbc.n++];
+                C = T;
+                C.wg0 = rcwg;
+                rcwg += T.nblk;
+            }
             continue;
         }
         if (!d[i].pos && d[i].rlist) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_batch: row lists without pos take kernels up to 128 offsets");
@@ -610,7 +626,7 @@ extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* 
     }
     if (off > ws_bytes) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_batch: workspace too small");
     if (cb.n > 0 && rbt.n > 0) {
-        hipLaunchKernelGGL(lists_count_kernel, dim3(cwg + rwg), dim3(256), 0, st, cb, rbt, cwg);
+        hipLaunchKernelGGL(lists_count_kernel, dim3(cwg + rcwg), dim3(256), 0, st, cb, rbc, cwg);
         hipLaunchKernelGGL(lists_scan_kernel, dim3(csg + rkk), dim3(256), 0, st, cb, rbt, csg);
         hipLaunchKernelGGL(lists_fill_kernel, dim3(cwg + rwg), dim3(256), 0, st, cb, rbt, cwg);
         SD3D_CHECK_LAUNCH();
@@ -620,7 +636,7 @@ extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* 
         hipLaunchKernelGGL(chain_fill_kernel, dim3(cwg), dim3(256), 0, st, cb);
         SD3D_CHECK_LAUNCH();
     } else if (rbt.n > 0) {
-        hipLaunchKernelGGL(pair_count_rows_kernel, dim3(rwg), dim3(256), 0, st, rbt);
+        if (rcwg > 0) hipLaunchKernelGGL(pair_count_rows_kernel, dim3(rcwg), dim3(256), 0, st, rbc);
         hipLaunchKernelGGL(pair_scan_batch_kernel, dim3(rkk), dim3(256), 0, st, rbt);
         hipLaunchKernelGGL(pair_fill_rows_kernel, dim3(rwg), dim3(256), 0, st, rbt);
         SD3D_CHECK_LAUNCH();
@@ -632,4 +648,7 @@ extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* 
     if (rb > 0) hipLaunchKernelGGL(pair_rowlist_batch_kernel, dim3(rb), dim3(RL_ROWS), 0, st, b);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_t ws_bytes, void* stream) {
+    return sd3d_pair_lists_desc_counts(n, d, nullptr, ws, ws_bytes, stream);
 }

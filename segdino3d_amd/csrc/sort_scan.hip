@@ -2,8 +2,9 @@
 //
 // Used by: voxelisation (sort points along the Z-order curve), superpoint pooling (group points by
 // superpoint id) and post-processing (top-k / score ordering).  These are HBM-bound integer passes
-// over <= a few million elements; 8-bit digits, one histogram + one scatter kernel per digit (the
-// scatter derives its cursors from the raw [256][n_blocks] histogram itself); arrays of <= 4096 elements are ranked by one workgroup.  Stability (needed so that points inside one voxel /
+// over <= a few million elements; 8-bit digits, one histogram + one scatter kernel per digit.  Up to RS_BASES_MIN_NB tiles the
+// scatter derives its cursors from the raw [256][n_blocks] histogram itself; above, one small launch in between turns every digit's
+// row into exclusive bases once per pass (rs_bases).  Arrays of <= 4096 elements are ranked by one workgroup.  Stability (needed so that points inside one voxel /
 // superpoint stay in ascending point order => deterministic fp32 sums downstream) comes from
 // ranking each wave's elements in chunk order with ballot-built match masks.
 #include "common.h"
@@ -183,7 +184,8 @@ extern "C" int sd3d_scan_exclusive_i32(const int32_t* in, int32_t* out, int64_t 
 // ----------------------------------------------------------------------------------------------
 // radix sort
 // ----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(RS_THREADS) void rs_hist(const uint64_t* __restrict__ keys, int64_t n, int shift,
+// `dmask`: 0xFF, or the low bits of the last digit when end_bit - begin_bit is no multiple of 8 (key bits from end_bit on do not order)
+__global__ __launch_bounds__(RS_THREADS) void rs_hist(const uint64_t* __restrict__ keys, int64_t n, int shift, int dmask,
                                                       int* __restrict__ hist, int nb) {
     __shared__ int h[256];
     h[threadIdx.x] = 0;
@@ -192,17 +194,44 @@ __global__ __launch_bounds__(RS_THREADS) void rs_hist(const uint64_t* __restrict
 #pragma unroll
     for (int c = 0; c < RS_TILE / RS_THREADS; ++c) {
         const int64_t i = base + c * RS_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&h[(int)((keys[i] >> shift) & 0xFF)], 1);
+        if (i < n) atomicAdd(&h[(int)(keys[i] >> shift) & dmask], 1);
     }
     __syncthreads();
     hist[(int64_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
+}
+
+// Once per pass (nb > RS_BASES_MIN_NB): workgroup d turns row d of the digit-major histogram into exclusive prefixes over the blocks, in
+// place, and stores the row's total in tot[d].  256 workgroups, one round of 2048 blocks each (4 M keys) per loop trip.
+// Threshold, measured as back-to-back six-pass sorts on one stream (us per sort, walk in every workgroup / rs_bases): 20 tiles 79 / 88,
+// 37 tiles 91 / 88, 74 tiles (one scene) 109 / 91, 128 tiles 163 / 97, 367 tiles (five scenes) - / 134: the extra launch pays from
+// about 32 tiles on.
+#ifndef RS_BASES_MIN_NB
+#define RS_BASES_MIN_NB 32
+#endif
+__global__ __launch_bounds__(256) void rs_bases(int* __restrict__ hist, int nb, int* __restrict__ tot) {
+    __shared__ int sm[4];
+    int* hrow = hist + (int64_t)blockIdx.x * nb;
+    int carry = 0;
+    for (int start = 0; start < nb; start += 256 * 8) {
+        const int base = start + threadIdx.x * 8;
+        int v[8], s = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { v[i] = base + i < nb ? hrow[base + i] : 0; s += v[i]; }
+        int total;
+        int ex = block_excl_scan_256(s, &total, sm) + carry;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { if (base + i < nb) hrow[base + i] = ex; ex += v[i]; }
+        carry += total;
+    }
+    if (threadIdx.x == 0) tot[blockIdx.x] = carry;
 }
 
 // Each wave owns 512 consecutive elements (8 chunks of 64) of the block's 2048-element tile.
 __global__ __launch_bounds__(RS_THREADS) void rs_scatter(const uint64_t* __restrict__ keys_in,
                                                          const uint32_t* __restrict__ vals_in,
                                                          uint64_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
-                                                         int64_t n, int shift, const int* __restrict__ hist_scanned, int nb) {
+                                                         int64_t n, int shift, int dmask, const int* __restrict__ hist_scanned, int nb,
+                                                         const int* __restrict__ digit_tot) {
     __shared__ int cnt[4][256];     // per-wave digit counts, then running output cursors
     __shared__ int scan_sm[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -217,22 +246,29 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter(const uint64_t* __restr
         const bool ok = i < n;
         k[c] = ok ? keys_in[i] : 0ull;
         v[c] = ok ? (vals_in ? vals_in[i] : (uint32_t)i) : 0u;
-        if (ok) atomicAdd(&cnt[w][(int)((k[c] >> shift) & 0xFF)], 1);
+        if (ok) atomicAdd(&cnt[w][(int)(k[c] >> shift) & dmask], 1);
     }
     __syncthreads();
     {   // thread d: turn counts into starting cursors: global base of (digit, block) + earlier waves.  The global base is the
         // exclusive prefix of the digit-major [256][nb] histogram at (d, this block) = (all blocks of smaller digits) + (earlier
-        // blocks of this digit); every workgroup adds it up itself from the raw histogram (nb <= a few hundred loads per
-        // thread, L2-resident) - that replaces a separate scan of the histogram, three launches per digit pass.
+        // blocks of this digit).  Up to RS_BASES_MIN_NB blocks every workgroup adds it up itself from the raw histogram (nb / 8
+        // dependent L2 round trips per thread: at most four, cheaper than a launch in the chain); beyond, that walk grows with nb
+        // in EVERY workgroup (46 round trips and 137 MB of L2 reads per pass at the 366 tiles of five scenes: 78 us of a pass that
+        // moves 18 MB), so rs_bases has reduced each row once and two loads remain here.
         const int d = threadIdx.x;
         const int* hrow = hist_scanned + (int64_t)d * nb;
         int before = 0, all = 0;
-        for (int b0 = 0; b0 < nb; b0 += 8) {
-            int h[8];
+        if (digit_tot) {        // rs_bases ran: the row holds exclusive prefixes over the blocks already, its total sits beside it
+            before = hrow[blockIdx.x];
+            all = digit_tot[d];
+        } else {
+            for (int b0 = 0; b0 < nb; b0 += 8) {
+                int h[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) h[i] = b0 + i < nb ? hrow[b0 + i] : 0;
+                for (int i = 0; i < 8; ++i) h[i] = b0 + i < nb ? hrow[b0 + i] : 0;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) { all += h[i]; if (b0 + i < (int)blockIdx.x) before += h[i]; }
+                for (int i = 0; i < 8; ++i) { all += h[i]; if (b0 + i < (int)blockIdx.x) before += h[i]; }
+            }
         }
         int tot;
         const int smaller = block_excl_scan_256(all, &tot, scan_sm);
@@ -245,7 +281,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter(const uint64_t* __restr
     for (int c = 0; c < 8; ++c) {
         const int64_t i = wbase + c * 64 + lane;
         const bool ok = i < n;
-        const int d = (int)((k[c] >> shift) & 0xFF);
+        const int d = (int)(k[c] >> shift) & dmask;
         uint64_t same = __ballot(ok);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
@@ -299,7 +335,7 @@ __global__ __launch_bounds__(256) void rank_sort_kernel(const uint64_t* __restri
 
 size_t sort_ws_bytes(int64_t n) {
     const int64_t nb = cdiv(n > 0 ? n : 1, RS_TILE);
-    return align_up((size_t)nb * 256 * sizeof(int), 256) + scan_ws_bytes(nb * 256);
+    return align_up((size_t)nb * 256 * sizeof(int), 256) + align_up(256 * sizeof(int), 256);      // histogram + digit totals
 }
 extern "C" size_t sd3d_sort_ws_bytes(int64_t n) { return sort_ws_bytes(n); }
 
@@ -327,20 +363,24 @@ int sort_pairs_u64(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uin
     }
     const int nb = (int)cdiv(n, RS_TILE);
     int* hist = (int*)ws;
+    int* digit_tot = nb > RS_BASES_MIN_NB ? (int*)((char*)ws + align_up((size_t)nb * 256 * sizeof(int), 256)) : nullptr;
     // ping-pong: even passes read A (=*_in) and write B (=*_out), odd passes the other way round;
     // with an odd pass count the last pass writes *_out.  When vals_in is NULL pass 0 synthesises
     // value = index and the ping-pong partner of vals_out is vals_scratch.
     uint32_t* vother = vals_in ? vals_in : vals_scratch;
     if (!vother && passes > 1) return sd3d_set_error(SD3D_ERR_ARG, "sort: need vals_in or vals_scratch");
     for (int p = 0; p < passes; ++p) {
-        const int shift = begin_bit + 8 * p;
+        int shift = begin_bit + 8 * p;
+        const int dmask = end_bit - shift >= 8 ? 0xFF : (end_bit > shift ? (1 << (end_bit - shift)) - 1 : 0);     // (0: the padding pass)
+        if (!dmask) shift = 0;
         const bool even = (p & 1) == 0;
         const uint64_t* ksrc = even ? keys_in : keys_out;
         uint64_t* kdst = even ? keys_out : keys_in;
         const uint32_t* vsrc = (p == 0) ? vals_in : (even ? vother : vals_out);
         uint32_t* vdst = even ? vals_out : vother;
-        hipLaunchKernelGGL(rs_hist, dim3(nb), dim3(RS_THREADS), 0, st, ksrc, n, shift, hist, nb);
-        hipLaunchKernelGGL(rs_scatter, dim3(nb), dim3(RS_THREADS), 0, st, ksrc, vsrc, kdst, vdst, n, shift, hist, nb);
+        hipLaunchKernelGGL(rs_hist, dim3(nb), dim3(RS_THREADS), 0, st, ksrc, n, shift, dmask, hist, nb);
+        if (digit_tot) hipLaunchKernelGGL(rs_bases, dim3(256), dim3(256), 0, st, hist, nb, digit_tot);
+        hipLaunchKernelGGL(rs_scatter, dim3(nb), dim3(RS_THREADS), 0, st, ksrc, vsrc, kdst, vdst, n, shift, dmask, hist, nb, digit_tot);
     }
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;

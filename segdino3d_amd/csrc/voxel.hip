@@ -572,7 +572,7 @@ extern "C" int sd3d_kernel_map(const uint64_t* okeys, int64_t n_out, const uint6
 // (|d| <= 2 per axis) lies in the parent cell P(v) + pd with pd = floor((bit(v) + d) / 2) in {-1, 0, 1} per axis: ONE entry of the
 // parent level's 3^3 map finds that cell, and its {first child, 8-bit child mask} record finds the row:
 //     nbr[k][v] = first[Q] + popcount(mask[Q] & ((1 << cb) - 1))  if mask[Q] has bit cb,   Q = nbr3_parent[pd][P(v)],  cb = low bits of v + d
-// Two dependent, cache-friendly loads per probe (a wave's 64 consecutive rows share one or two parents) instead of a random 64-byte
+// Two dependent, cache-friendly loads per parent cell (staged once per workgroup, see kmap_hier_kernel) instead of a random 64-byte
 // line of an open-addressing table per probe and table slot - the hash probes fetched 0.5-1.1 GB per scene for ~0.1 GB of useful bytes
 // (profiles/r04_pmc_fetch.md).  No Morton arithmetic, no coordinate range checks (a cell outside the key range has no parent entry), no
 // insert pass, no table memsets, and every entry of nbr is written by its own thread: coalesced, nothing to pre-fill.  The coarsest level
@@ -658,63 +658,122 @@ __global__ __launch_bounds__(256) void kmap_roots_kernel(const KRoots R) {
     child_info_body(R.fkeys[l], R.parent[l], R.n_fine[l], R.n_coarse[l], R.cinfo[l], R.perm8, R.nbr_down[l], R.nbr_up[l], bx - R.blk0[l]);
 }
 
-#define KH_UNROLL 4                 // offsets per thread: their loads are all requested before the first is used
+// One workgroup owns 256 consecutive voxels of a level and writes ALL offsets of the level's table(s) for them.  Its voxels' parents are
+// consecutive rows of the parent level (<= 256 of them), and every offset (|d| <= 2) of every voxel lands in one of the 27 cells around
+// its parent: the workgroup stages those cells' {first child, child mask} records in LDS once - 27 per distinct parent, all of a thread's
+// map loads in flight, then all of its record loads - and derives every table entry from LDS.  (One thread per (voxel, 4 offsets) issued
+// the two dependent loads per ENTRY, 152 per level-0 voxel, and ran at an eighth of the plain-store rate.)  The 1024 threads are the 256
+// voxels times KH_PARTS slices of the offsets (a slice per four waves: a one-scene level is a few hundred workgroups, and 152 stores in
+// a row per thread left it waiting on its own chain); each offset's column of 256 rows is one coalesced store per wave.  The
+// workgroup is also a 256-row block of the pair-list builders: it can leave the per-(offset, block) entry counts in the layout
+// pair_count_rows_body produces, so that a list build need not read the table again to count.
+#define KH_PARTS 4
+#define KH_THREADS (256 * KH_PARTS)
+#define KH_STEP 7
 struct KHParams {
     const uint64_t* keys; const int32_t* parent; int64_t n;          // this level: keys, parent row of every voxel
     const int32_t* nbr3p; int64_t np;                                 // the parent level's 3^3 map [27, np]
     const int2* cinfo;                                                // per parent-level voxel: {first child, child mask}
-    const int8_t* offs; int K;                                        // this table's offsets (|d| <= 2)
+    const int8_t* offs;                                               // this level's 3^3 offsets [27, 3]
     int8_t inv27[27];                                                 // (pdx + 1) + 3 (pdy + 1) + 9 (pdz + 1) -> offset index of the parent level's 3^3 map
-    int32_t* nbr; int32_t* pair_count;
-    // a second table of the SAME level in the same launch (the finest level's 5^3 map next to its 3^3 map): y-blocks >= y_split
-    const int8_t* offs_b; int K_b; int32_t* nbr_b; int32_t* pair_count_b; int y_split;
+    int32_t* nbr; int32_t* pair_count; int32_t* blk_cnt;              // blk_cnt: NULL or [K, cdiv(n, 256)] entry counts per (offset, 256-row block)
+    // a second table of the SAME level in the same launch (the finest level's 5^3 map next to its 3^3 map)
+    const int8_t* offs_b; int32_t* nbr_b; int32_t* pair_count_b; int32_t* blk_cnt_b;
 };
-__global__ __launch_bounds__(256) void kmap_hier_kernel(const KHParams P) {
-    __shared__ int wsum[4];
-    // (the table of this y-block: selected field by field - a modified COPY of the argument struct would move inv27[] to scratch)
-    const bool second = P.nbr_b != nullptr && (int)blockIdx.y >= P.y_split;
-    const int by = second ? (int)blockIdx.y - P.y_split : (int)blockIdx.y;
-    const int8_t* __restrict__ t_offs = second ? P.offs_b : P.offs;
-    const int t_K = second ? P.K_b : P.K;
-    int32_t* __restrict__ t_nbr = second ? P.nbr_b : P.nbr;
-    int32_t* __restrict__ t_count = second ? P.pair_count_b : P.pair_count;
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int k0 = by * KH_UNROLL;
-    int found = 0;
-    if (v < P.n) {
-        const int bits = (int)(P.keys[v] & 7ull);                     // Morton bit 0 = x, 1 = y, 2 = z
-        const int par = P.parent[v];
-        int q[KH_UNROLL], cb[KH_UNROLL];
+__global__ __launch_bounds__(KH_THREADS) void kmap_hier_kernel(const KHParams P) {
+    __shared__ int2 rec[27 * 256];          // [pd][parent - first parent of the workgroup]
+    // per (offset, child position): (pd * 256) << 3 | cb - the row of `rec` and the child bit the offset lands on (3^3 offsets, then 5^3)
+    __shared__ uint16_t cell[(27 + 125) * 8];
+    __shared__ int wc[4][27 + 125];         // entries per (wave of the slice, offset)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int row = tid & 255, part = tid >> 8;                           // part: wave-uniform
+    const int64_t v0 = (int64_t)blockIdx.x * 256, v = v0 + row;
+    const bool live = v < P.n;
+    const int64_t v_last = (v0 + 256 < P.n ? v0 + 256 : P.n) - 1;
+    const int p0 = P.parent[v0];
+    int npar = P.parent[v_last] - p0 + 1;   // parents are unique(key >> 3) of sorted keys: consecutive rows, at most one per voxel
+    npar = npar < 1 ? 1 : (npar > 256 ? 256 : npar);
+    const bool two = P.nbr_b != nullptr;
+    for (int i = tid; i < (two ? 27 + 125 : 27) * 8; i += KH_THREADS) {
+        const int k = i >> 3, b = i & 7;
+        const int8_t* o = k < 27 ? P.offs + k * 3 : P.offs_b + (k - 27) * 3;
+        const int sx = (b & 1) + o[0], sy = ((b >> 1) & 1) + o[1], sz = ((b >> 2) & 1) + o[2];
+        const int pd = ((sx >> 1) + 1) + 3 * ((sy >> 1) + 1) + 9 * ((sz >> 1) + 1);         // arithmetic shift = floor
+        cell[i] = (uint16_t)(((pd * 256) << 3) | (sx & 1) | ((sy & 1) << 1) | ((sz & 1) << 2));
+    }
+    int bits = 0, pl = 0;
+    if (live) {
+        bits = (int)(P.keys[v] & 7ull);                                   // Morton bit 0 = x, 1 = y, 2 = z
+        pl = P.parent[v] - p0;
+        pl = pl < 0 ? 0 : (pl >= npar ? npar - 1 : pl);
+    }
+    {   // records (pd, parent `row`) for pd = part, part + 4, ...: seven per thread
+        constexpr int NR = (27 + KH_PARTS - 1) / KH_PARTS;
+        const bool mine = row < npar;
+        int q[NR];
 #pragma unroll
-        for (int u = 0; u < KH_UNROLL; ++u) {
-            const int k = k0 + u < t_K ? k0 + u : t_K - 1;
-            const int sx = (bits & 1) + t_offs[k * 3 + 0], sy = ((bits >> 1) & 1) + t_offs[k * 3 + 1], sz = ((bits >> 2) & 1) + t_offs[k * 3 + 2];
-            const int pd = ((sx >> 1) + 1) + 3 * ((sy >> 1) + 1) + 9 * ((sz >> 1) + 1);     // arithmetic shift = floor
-            cb[u] = (sx & 1) | ((sy & 1) << 1) | ((sz & 1) << 2);
-            q[u] = pd == 13 ? par : P.nbr3p[(int64_t)P.inv27[pd] * P.np + par];
+        for (int u = 0; u < NR; ++u) {
+            const int pd = part + u * KH_PARTS;
+            q[u] = -1;
+            if (mine && pd < 27) q[u] = pd == 13 ? p0 + row : P.nbr3p[(int64_t)P.inv27[pd] * P.np + p0 + row];
         }
-        int2 ci[KH_UNROLL];
+        int2 ci[NR];
 #pragma unroll
-        for (int u = 0; u < KH_UNROLL; ++u) ci[u] = q[u] >= 0 ? P.cinfo[q[u]] : make_int2(0, 0);
+        for (int u = 0; u < NR; ++u) ci[u] = q[u] >= 0 ? P.cinfo[q[u]] : make_int2(0, 0);
 #pragma unroll
-        for (int u = 0; u < KH_UNROLL; ++u) {
-            if (k0 + u < t_K) {
-                const int hit = (ci[u].y >> cb[u]) & 1;
-                t_nbr[(int64_t)(k0 + u) * P.n + v] = hit ? ci[u].x + __popc((unsigned)ci[u].y & ((1u << cb[u]) - 1u)) : -1;
-                found += hit;
+        for (int u = 0; u < NR; ++u) {
+            const int pd = part + u * KH_PARTS;
+            if (mine && pd < 27) rec[pd * 256 + row] = ci[u];
+        }
+    }
+    __syncthreads();
+    // this slice's offsets: with the 5^3 table, slice 0 takes the 3^3 table and the others a third of the 5^3 table each
+    int k_beg, k_end;
+    if (two) {
+        constexpr int per = (125 + KH_PARTS - 2) / (KH_PARTS - 1);
+        k_beg = part == 0 ? 0 : 27 + (part - 1) * per;
+        k_end = part == 0 ? 27 : (27 + part * per < 27 + 125 ? 27 + part * per : 27 + 125);
+    } else {
+        constexpr int per = (27 + KH_PARTS - 1) / KH_PARTS;
+        k_beg = part * per;
+        k_end = k_beg + per < 27 ? k_beg + per : 27;
+    }
+    const int wv = (tid >> 6) & 3;
+    for (int k0 = k_beg; k0 < k_end; k0 += KH_STEP) {                     // KH_STEP offsets at a time: their LDS reads are all requested first
+        int c[KH_STEP];
+#pragma unroll
+        for (int u = 0; u < KH_STEP; ++u) c[u] = cell[(k0 + u < k_end ? k0 + u : k_end - 1) * 8 + bits];
+        int2 ci[KH_STEP];
+#pragma unroll
+        for (int u = 0; u < KH_STEP; ++u) ci[u] = rec[(c[u] >> 3) + pl];
+#pragma unroll
+        for (int u = 0; u < KH_STEP; ++u) {
+            const int k = k0 + u;
+            if (k < k_end) {                                              // (wave-uniform)
+                const int cb = c[u] & 7;
+                const int hit = live ? (ci[u].y >> cb) & 1 : 0;
+                int32_t* col = k < 27 ? P.nbr + (int64_t)k * P.n : P.nbr_b + (int64_t)(k - 27) * P.n;
+                if (live) col[v] = hit ? ci[u].x + __popc((unsigned)ci[u].y & ((1u << cb) - 1u)) : -1;
+                const int cnt = __popcll(__ballot(hit));
+                if (lane == 0) wc[wv][k] = cnt;
             }
         }
     }
-    if (t_count) {
-        int c = found;
+    __syncthreads();
+    // the first 27 (+ 125) threads own an offset each: block count, and the table's partial counters (sum = number of entries)
+    int tot = 0;
+    const bool is_b = tid >= 64;                                          // (waves 0: the 3^3 table, waves 1-2: the 5^3 table)
+    const int k = is_b ? 27 + tid - 64 : tid;
+    if (is_b ? (two && tid - 64 < 125) : tid < 27) {
+        tot = wc[0][k] + wc[1][k] + wc[2][k] + wc[3][k];
+        int32_t* bc = is_b ? P.blk_cnt_b : P.blk_cnt;
+        if (bc) bc[(int64_t)(is_b ? tid - 64 : tid) * gridDim.x + blockIdx.x] = tot;
+    }
+    if (tid < 192) {
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-            if (tot) atomicAdd(&t_count[(blockIdx.x + by) & 63], tot);
-        }
+        for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
+        int32_t* pc = is_b ? P.pair_count_b : P.pair_count;
+        if (lane == 0 && tot && pc) atomicAdd(&pc[(blockIdx.x * 2 + (tid >> 7)) & 63], tot);
     }
 }
 
@@ -727,10 +786,13 @@ extern "C" size_t sd3d_kernel_maps_hier_ws_bytes(int n_levels, const int64_t* n)
 // enumeration order for every level); inv27: HOST table (pd index as above -> row of offs3).  pair_counts: NULL or device int32
 // [(n_levels + 1) * 64], zeroed: 64 partial counters per table (levels 0 .. n_levels - 1, then the 5^3 table).
 // nbr_down[l] [8, n_{l+1}] / nbr_up[l] [8, n_l] (l < n_levels - 1): optional stride-2 maps of the level pair (NULL arrays or entries: not built).
-extern "C" int sd3d_kernel_maps_hier(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n, int32_t* const* nbr3,
-                                     int32_t* nbr5, const int8_t* offs3, const int8_t* offs5, const int8_t* inv27, int32_t* pair_counts,
-                                     const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up, void* ws, size_t ws_bytes,
-                                     void* stream) {
+// blk_cnt3[l] (l < n_levels - 1) / blk_cnt5: NULL or device int32 [27, cdiv(n_l, 256)] / [125, cdiv(n_0, 256)]: the entry counts per (offset,
+// 256-row block) of that table, the form sd3d_pair_lists_desc_counts takes in place of its own count pass.  (The coarsest level's map is
+// searched, not derived: it brings none.)
+extern "C" int sd3d_kernel_maps_hier_counts(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n,
+                                            int32_t* const* nbr3, int32_t* nbr5, const int8_t* offs3, const int8_t* offs5, const int8_t* inv27,
+                                            int32_t* pair_counts, const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up,
+                                            int32_t* const* blk_cnt3, int32_t* blk_cnt5, void* ws, size_t ws_bytes, void* stream) {
     if (!keys || !parent || !n || !nbr3 || !offs3 || !inv27 || (nbr5 && !offs5)) return sd3d_set_error(SD3D_ERR_ARG, "kernel_maps_hier: null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (n_levels < 1 || n_levels > 8) return sd3d_set_error(SD3D_ERR_ARG, "kernel_maps_hier: 1..8 levels");
@@ -762,17 +824,25 @@ extern "C" int sd3d_kernel_maps_hier(int n_levels, const uint64_t* const* keys, 
         KHParams P;
         P.keys = keys[l]; P.parent = parent[l]; P.n = n[l]; P.nbr3p = nbr3[l + 1]; P.np = n[l + 1]; P.cinfo = cinfo[l + 1];
         for (int i = 0; i < 27; ++i) P.inv27[i] = inv27[i];
-        P.offs = offs3; P.K = 27; P.nbr = nbr3[l]; P.pair_count = pair_counts ? pair_counts + 64 * l : nullptr;
-        P.offs_b = nullptr; P.K_b = 0; P.nbr_b = nullptr; P.pair_count_b = nullptr; P.y_split = (int)cdiv(27, KH_UNROLL);
-        unsigned gy = (unsigned)P.y_split;
+        P.offs = offs3; P.nbr = nbr3[l]; P.pair_count = pair_counts ? pair_counts + 64 * l : nullptr;
+        P.blk_cnt = blk_cnt3 ? blk_cnt3[l] : nullptr;
+        P.offs_b = nullptr; P.nbr_b = nullptr; P.pair_count_b = nullptr; P.blk_cnt_b = nullptr;
         if (l == 0 && nbr5) {                                  // the stem's 5^3 table rides in the finest level's launch
-            P.offs_b = offs5; P.K_b = 125; P.nbr_b = nbr5; P.pair_count_b = pair_counts ? pair_counts + 64 * n_levels : nullptr;
-            gy += (unsigned)cdiv(125, KH_UNROLL);
+            P.offs_b = offs5; P.nbr_b = nbr5; P.pair_count_b = pair_counts ? pair_counts + 64 * n_levels : nullptr;
+            P.blk_cnt_b = blk_cnt5;
         }
-        hipLaunchKernelGGL(kmap_hier_kernel, dim3((unsigned)cdiv(n[l], 256), gy), dim3(256), 0, st, P);
+        hipLaunchKernelGGL(kmap_hier_kernel, dim3((unsigned)cdiv(n[l], 256)), dim3(KH_THREADS), 0, st, P);
     }
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+
+extern "C" int sd3d_kernel_maps_hier(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n, int32_t* const* nbr3,
+                                     int32_t* nbr5, const int8_t* offs3, const int8_t* offs5, const int8_t* inv27, int32_t* pair_counts,
+                                     const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    return sd3d_kernel_maps_hier_counts(n_levels, keys, parent, n, nbr3, nbr5, offs3, offs5, inv27, pair_counts, perm8, nbr_down, nbr_up, nullptr,
+                                        nullptr, ws, ws_bytes, stream);
 }
 
 // Stride-2, kernel-2 maps from the parent array.  The child's position inside its parent is the low

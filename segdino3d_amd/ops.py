@@ -440,12 +440,14 @@ def kernel_map(out_keys, n_out, table, offsets_i8, pair_count=None, mirrored=Fal
     return nbr
 
 
-def kernel_maps_hier(keys, parents, n_vox, offs3, offs5, inv27, pair_counts=None, perm8=None):
+def kernel_maps_hier(keys, parents, n_vox, offs3, offs5, inv27, pair_counts=None, perm8=None, block_counts=None):
     """The 3^3 kernel maps of every level (+ the 5^3 map of level 0 when `offs5` is given) from ONE call, through the level hierarchy of
     the sorted keys instead of hash tables (`sd3d_kernel_maps_hier`).  keys: per level int64 [n_l] (finest first); parents: per level
     but the last int32 [n_l]; offs3 / offs5: device int8 [27, 3] / [125, 3]; inv27: numpy int8 [27] ((dx+1) + 3 (dy+1) + 9 (dz+1) -> row
     of offs3).  pair_counts: zeroed int32 [(L + 1), 64] or None.  perm8 (int32 [8], as `stride_maps`): the stride-2 maps of every level
-    pair come out of the same launches.  -> ([nbr3 per level], nbr5 | None, [(nbr_down, nbr_up) per level pair] | None)"""
+    pair come out of the same launches.  block_counts: a dict that receives {(level, 3 | 5): int32 [K, ceil(n_l / 256)]}, the tables' entry
+    counts per (offset, 256-row block) for `pair_lists_batch` (every level but the coarsest, and the 5^3 table).
+    -> ([nbr3 per level], nbr5 | None, [(nbr_down, nbr_up) per level pair] | None)"""
     lib = _lib.load()
     L = len(keys)
     dev = keys[0].device
@@ -462,13 +464,22 @@ def kernel_maps_hier(keys, parents, n_vox, offs3, offs5, inv27, pair_counts=None
                    for l in range(L - 1)]
         dp = (ctypes.c_void_p * L)(*([t[0].data_ptr() for t in strides] + [None]))
         up = (ctypes.c_void_p * L)(*([t[1].data_ptr() for t in strides] + [None]))
+    c3, c5 = None, None
+    if block_counts is not None:
+        for l in range(L - 1):
+            block_counts[(l, 3)] = torch.empty(27, (int(n_vox[l]) + 255) // 256, dtype=torch.int32, device=dev)
+        c3 = (ctypes.c_void_p * L)(*([block_counts[(l, 3)].data_ptr() for l in range(L - 1)] + [None]))
+        if nbr5 is not None and L > 1:
+            block_counts[(0, 5)] = c5 = torch.empty(125, (int(n_vox[0]) + 255) // 256, dtype=torch.int32, device=dev)
     ws = _WS.get(lib.sd3d_kernel_maps_hier_ws_bytes(L, ctypes.addressof(n)), dev)
-    _lib.check(lib.sd3d_kernel_maps_hier(L, ctypes.addressof(kp), ctypes.addressof(pp), ctypes.addressof(n), ctypes.addressof(np_),
-                                         _ptr(nbr5), _ptr(offs3, torch.int8, "offs3"), _ptr(offs5, torch.int8, "offs5"),
-                                         ctypes.addressof(inv), _ptr(pair_counts, torch.int32, "pair_counts"),
-                                         _ptr(perm8, torch.int32, "perm8") if strides is not None else None,
-                                         ctypes.addressof(dp) if strides is not None else None, ctypes.addressof(up) if strides is not None else None,
-                                         ws.data_ptr(), ws.numel(), _stream()), "kernel_maps_hier")
+    _lib.check(lib.sd3d_kernel_maps_hier_counts(L, ctypes.addressof(kp), ctypes.addressof(pp), ctypes.addressof(n), ctypes.addressof(np_),
+                                                _ptr(nbr5), _ptr(offs3, torch.int8, "offs3"), _ptr(offs5, torch.int8, "offs5"),
+                                                ctypes.addressof(inv), _ptr(pair_counts, torch.int32, "pair_counts"),
+                                                _ptr(perm8, torch.int32, "perm8") if strides is not None else None,
+                                                ctypes.addressof(dp) if strides is not None else None,
+                                                ctypes.addressof(up) if strides is not None else None,
+                                                ctypes.addressof(c3) if c3 is not None else None, _ptr(c5),
+                                                ws.data_ptr(), ws.numel(), _stream()), "kernel_maps_hier")
     return nbr3, nbr5, strides
 
 
@@ -706,9 +717,11 @@ PAIR_CHAINED = -2          # SD3D_PAIR_CHAINED: `center` value of a chained tabl
 
 
 def pair_lists_batch(tables):
-    """tables: list of (nbr int32 [K, M], n_pairs[, center[, direct[, lean]]]) -> list of PairLists, built by ONE launch set
+    """tables: list of (nbr int32 [K, M], n_pairs[, center[, direct[, lean[, counts]]]]) -> list of PairLists, built by ONE launch set
     (csrc/pair_gemm.hip: count, scan, fill, per-row lists).  center = PAIR_CHAINED: chained lists (a stride-1 table of a voxel set
-    onto itself, odd symmetric kernel): the entries of a row's mirror groups and its centre share partial products."""
+    onto itself, odd symmetric kernel): the entries of a row's mirror groups and its centre share partial products.  counts (a lean
+    plain table only): int32 [K, ceil(M / 256)] from `kernel_maps_hier(block_counts=...)`; the table is not read again to count, and
+    the tensor is consumed (scanned in place)."""
     lib = _lib.load()
     out = []
     for start in range(0, len(tables), 16):
@@ -716,6 +729,7 @@ def pair_lists_batch(tables):
         dev = chunk[0][0].device
         desc = np.zeros(len(chunk), dtype=_PAIR_DESC_DT)
         res, nb = [], 0
+        given = (ctypes.c_void_p * len(chunk))()
         for i, t in enumerate(chunk):
             nbr, n_pairs = t[0], t[1]
             center = int(t[2]) if len(t) > 2 else -1
@@ -741,11 +755,17 @@ def pair_lists_batch(tables):
             desc[i] = (_ptr(nbr, torch.int32, "nbr"), 0 if pos is None else pos.data_ptr(), in_idx.data_ptr(), tile_k.data_ptr(),
                        0 if rlist is None else rlist.data_ptr(), 0 if out_idx is None else out_idx.data_ptr(), M, p_cap, K, center,
                        rl_stride, 3 if lean else 1)
+            counts = t[5] if len(t) > 5 else None
+            if counts is not None:
+                if not lean or chained or tuple(counts.shape) != (K, (M + 255) // 256):
+                    raise ValueError("pair_lists: block counts go with a lean plain table, int32 [K, ceil(M / 256)]")
+                given[i] = _ptr(counts, torch.int32, "counts")
             nb += (lib.sd3d_pair_lists_ws_bytes(K, M) + 255) // 256 * 256
             res.append(PairLists(pos, in_idx, tile_k, p_cap, K, M, rlist=rlist, rl_stride=rl_stride, center=center, out_idx=out_idx,
                                  direct=direct))
         ws = _WS4.get(nb, dev)
-        _lib.check(lib.sd3d_pair_lists_desc(len(chunk), desc.ctypes.data, ws.data_ptr(), ws.numel(), _stream()), "pair_lists_desc")
+        _lib.check(lib.sd3d_pair_lists_desc_counts(len(chunk), desc.ctypes.data, ctypes.addressof(given) if any(given) else None,
+                                                   ws.data_ptr(), ws.numel(), _stream()), "pair_lists_desc")
         out += res
     return out
 

@@ -244,6 +244,7 @@ class SceneMaps:
         self._same: Dict[Tuple[int, int], torch.Tensor] = {}
         self._stride: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
         self._hier_built = False                             # the maps came from ops.kernel_maps_hier (no hash tables)
+        self._blk_counts = None                              # {(level, k): per-(offset, row block) entry counts} the hierarchy maps left for the list build
         self._perm8 = perm8_device(order, self.device)
         self._sp_start = None
         self.density: Dict[Tuple, float] = {}
@@ -367,9 +368,12 @@ class SceneMaps:
             # finds them): the hierarchy runs coarse to fine, and the whole chain costs less than one level's hash probes did
             want5 = (0, 5) in same
             cnt_all = torch.zeros(L + 1, 64, dtype=torch.int32, device=self.device) if exact else None
+            # evaluation builds lean plain lists: the map workgroups leave their (offset, row block) counts for them
+            self._blk_counts = {} if (chained and LEAN_LISTS and ops.PAIR_CONV) else None
             nbr3, nbr5, st_maps = ops.kernel_maps_hier(self.keys, self.parents, self.n_vox, offsets_device(3, self.order, self.device),
                                                        offsets_device(5, self.order, self.device) if want5 else None, inv27_table(self.order),
-                                                       cnt_all, perm8=self._perm8 if not self._stride else None)
+                                                       cnt_all, perm8=self._perm8 if not self._stride else None,
+                                                       block_counts=self._blk_counts)
             for l, t in enumerate(st_maps or []):                # the stride-2 maps of every level pair ride in the same launches
                 self._stride[l] = t
             for l in range(L):
@@ -404,7 +408,9 @@ class SceneMaps:
                     center = ops.PAIR_CHAINED                    # mirror groups + centre share partial products (evaluation)
                 else:
                     center = -1
-                todo.append((("same", lvl, k), self._same[(lvl, k)], c, center, False, lean))
+                # (the counts are consumed by the build: popped, so that a rebuilt table counts for itself)
+                given = self._blk_counts.pop((lvl, k), None) if (self._blk_counts and lean and center == -1 and k ** 3 <= 128) else None
+                todo.append((("same", lvl, k), self._same[(lvl, k)], c, center, False, lean, given))
         for lvl in strides:
             # every fine voxel has exactly one parent: P = V_fine pairs in both directions
             self.density[("down", lvl)] = self.n_vox[lvl] / max(1, 8 * self.n_vox[lvl + 1])

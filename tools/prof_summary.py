@@ -40,6 +40,12 @@ def main():
     for name, wgs, n, avg, tot, vg, lds, gy in cur.execute(q).fetchall()[:40]:
         short = name.split("(")[0].replace("void ", "")
         lines.append(f"| `{short}` | {wgs}x{gy} | {n} | {avg / 1e3:.1f} | {tot / 1e6:.3f} | {vg} | {lds} |")
+    lines += ["", "## Prologue kernels by launch shape", "", "| kernel | workgroups | launches | avg us | total ms |", "|---|---:|---:|---:|---:|"]
+    q = ("select name, grid_x / workgroup_x, count(*), avg(duration), sum(duration), grid_y / workgroup_y from kernels "
+         "where name like 'rs_%' or name like 'kmap_%' or name like 'lists_%' or name like 'voxel_mean%' "
+         "group by name, grid_x, grid_y order by name, grid_x desc")
+    for name, wgs, n, avg, tot, gy in cur.execute(q).fetchall()[:60]:
+        lines.append(f"| `{name.split('(')[0]}` | {wgs}x{gy} | {n} | {avg / 1e3:.1f} | {tot / 1e6:.3f} |")
     try:
         pm = cur.execute("select name, counter_name, count(*), sum(counter_value) from pmc_events group by name, counter_name").fetchall()
     except sqlite3.Error:
