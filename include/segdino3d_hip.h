@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 2
+#define SD3D_ABI_VERSION 3
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -356,11 +356,6 @@ typedef struct sd3d_buf {
 } sd3d_buf;
 int sd3d_run_layers(const sd3d_layer* layers, int n_layers, const sd3d_table* tables, int n_tables, const sd3d_buf* bufs,
                     int n_bufs, float* part, size_t part_bytes, void* ws, size_t ws_bytes, void* stream);
-/* The same with table_events[n_tables] (or NULL): entry t, when not NULL, is a hipEvent_t recorded on another stream after table t's
- * lists were built there; `stream` waits for it before the first layer that reads the table (fork / join inside a scene). */
-int sd3d_run_layers_ev(const sd3d_layer* layers, int n_layers, const sd3d_table* tables, int n_tables, const sd3d_buf* bufs,
-                       int n_bufs, float* part, size_t part_bytes, void* ws, size_t ws_bytes, const void* const* table_events,
-                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Decoder kernels (segdino3d/models/decoder/instance_seg_3d_decoder.py:606-799,

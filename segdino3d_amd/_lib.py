@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _lib = None
 
@@ -72,7 +72,6 @@ SIGNATURES = {
     "sd3d_pair_lists_desc_counts": (_i, [_i, _p, _p, _p, _z, _p]),
     "sd3d_pair_conv_ex": (_i, [_p, _i, _i, _p, _i, _p, _p, _l, _p, _p, _i, _i, _p, _p, _i, _i, _i, _l, _p, _p, _p, _i, _p, _i, _i, _p, _z, _p]),
     "sd3d_run_layers": (_i, [_p, _i, _p, _i, _p, _i, _p, _z, _p, _z, _p]),
-    "sd3d_run_layers_ev": (_i, [_p, _i, _p, _i, _p, _i, _p, _z, _p, _z, _p, _p]),
     "sd3d_layernorm": (_i, [_p, _i, _p, _i, _p, _p, _f, _l, _i, _p, _i, _i, _p]),
     "sd3d_linear_layernorm": (_i, [_p, _i, _l, _i, _p, _i, _p, _p, _i, _p, _p, _f, _i, _p, _i, _p]),
     "sd3d_sine_pe": (_i, [_p, _i, _l, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p]),
@@ -198,7 +197,7 @@ def load_nogil():
     if _lib_nogil is None:
         load()
         lib = C.CDLL(LIB_PATH)
-        for name in ("sd3d_run_layers", "sd3d_run_layers_ev", "sd3d_unpack_bits_host", "sd3d_unet_train_forward", "sd3d_unet_train_backward"):
+        for name in ("sd3d_run_layers", "sd3d_unpack_bits_host", "sd3d_unet_train_forward", "sd3d_unet_train_backward"):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = SIGNATURES[name]
         _lib_nogil = lib

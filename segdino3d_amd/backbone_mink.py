@@ -228,7 +228,7 @@ class Res16UNetBase(DerivedWeights):
         the caller already has it (`_scene_inputs` validates the derived weights while the scene's read-back travels)."""
         k1 = self.conv1_kernel_size
         use_plan = not self.training and plan.USE_PLAN and ops.PAIR_CONV and ops.GG_HOOK is None
-        maps.prepare(same=[(0, k1)] + [(l, 3) for l in range(5)], strides=[0, 1, 2, 3], chained=not self.training, fork=use_plan)
+        maps.prepare(same=[(0, k1)] + [(l, 3) for l in range(5)], strides=[0, 1, 2, 3], chained=not self.training)
         if self.training:                                        # batch-statistics BatchNorm; backward through HIP kernels
             from . import train_ops, train_plan
             pk = self.packed_train()

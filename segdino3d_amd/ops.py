@@ -69,19 +69,6 @@ class use_stream:
         return self.ctx.__exit__(*exc)
 
 
-_SIDE_TLS = threading.local()
-
-
-def side_streams(n: int, device=None):
-    """`n` side streams owned by the calling host thread (created once, reused by every forward of the thread)."""
-    pool = getattr(_SIDE_TLS, "pool", None)
-    if pool is None:
-        pool = _SIDE_TLS.pool = []
-    while len(pool) < n:
-        pool.append(torch.cuda.Stream(device=device))
-    return pool[:n]
-
-
 def bound_stream(fn):
     """Decorator form of stream_scope for the public forward entry points."""
     import functools
@@ -199,8 +186,7 @@ class Workspace:
 
 class _PerThread:
     """One scratch buffer per (host thread, HIP stream): each worker thread of the pipelined runner drives its own stream, a
-    scene's sparse maps additionally build some of their tables on a side stream (`use_stream`), and scratch must never be
-    shared between streams."""
+    thread may move to another stream (`use_stream`), and scratch must never be shared between streams."""
 
     def __init__(self):
         self._tls = threading.local()

@@ -4,7 +4,8 @@ The network is written once against a small backend interface (`conv`, `dense`, 
   * `EagerBackend` issues every layer through `segdino3d_amd.ops` (one ctypes call + one tensor per layer),
   * `Recorder` records the same calls into a `LayerPlan` - an array of `sd3d_layer` structs with the packed
     weight pointers baked in - which is then replayed per scene with the scene's neighbour tables and one
-    activation arena.
+    activation arena.  `LayerPlan.run` is straight-line: size the arena, fill the buffer and table structs from the
+    pair lists `SceneMaps.prepare` built on the scene's stream, one C call.
 Both run the same kernels in the same order, so their results are bit-identical
 (`tests/test_gpu_sparse.py::test_layer_plan_matches_eager`).  Why: ~110 Python-level launches per scene held
 the GIL for ~2 ms of the ~6.5 ms a forward costs on the host, and the host - not the GPU - limits scenes/s.
@@ -140,7 +141,7 @@ class LayerPlan:
 
     def run(self, maps, x: torch.Tensor) -> torch.Tensor:
         """x [V_in_level, C] (row stride may exceed C).  Returns the output activation [V, C_out] (a view into the
-        scene's activation arena)."""
+        scene's activation arena).  Every neighbour table of the plan must have its pair lists (`maps.prepare`) on this stream."""
         lib = _lib.load_nogil()
         n_vox = np.asarray(maps.n_vox, dtype=np.int64)
         rows = n_vox[self.buf_level]
@@ -155,55 +156,22 @@ class LayerPlan:
         bufs["ptr"][0], bufs["ld"][0] = x.data_ptr(), x.stride(0)
         if x.shape[0] != rows[0] or x.shape[1] < self.buf_ch[0] or x.stride(1) != 1 or x.dtype != torch.float32:
             raise ValueError("plan input does not match the recorded network input")
+        missing = [k for k in self.table_keys if maps.pairs.get(k) is None]
+        if missing:                                              # (before anything is enqueued)
+            raise RuntimeError(f"neighbour tables {missing} have no pair lists (SceneMaps.prepare not called for them)")
         tabs = np.zeros(len(self.table_keys), dtype=TABLE_DT)
-        evs = np.zeros(len(self.table_keys), dtype=np.uint64)
+        part_floats = 0                                          # partial-product scratch: the largest table x its widest convolution
+        for i, key in enumerate(self.table_keys):
+            pl = maps.pairs[key]
+            tabs[i] = (pl.in_idx.data_ptr(), pl.tile_k.data_ptr(), 0 if pl.pos is None else pl.pos.data_ptr(), pl.p_cap, pl.M, pl.K, 0,
+                       0 if pl.rlist is None else pl.rlist.data_ptr(), pl.out_idx.data_ptr() if pl.direct else 0, pl.rl_stride, pl.center)
+            part_floats = max(part_floats, pl.p_cap * int(self.table_cout[i]))
         ws = ops._WS2.get(256, x.device)
-
-        def fill_tables():
-            """-> (floats of partial-product scratch the tables present need, do all tables exist?)"""
-            part_floats, complete = 0, True
-            pending = getattr(maps, "events", None) or {}
-            for i, key in enumerate(self.table_keys):
-                pl = maps.pairs.get(key)
-                if pl is None:
-                    complete = False
-                    continue
-                tabs[i] = (pl.in_idx.data_ptr(), pl.tile_k.data_ptr(), 0 if pl.pos is None else pl.pos.data_ptr(), pl.p_cap, pl.M, pl.K, 0,
-                           0 if pl.rlist is None else pl.rlist.data_ptr(), pl.out_idx.data_ptr() if pl.direct else 0, pl.rl_stride, pl.center)
-                ev = pending.get(key)
-                evs[i] = 0 if ev is None else ev.cuda_event
-                part_floats = max(part_floats, pl.p_cap * int(self.table_cout[i]))
-            return part_floats, complete
-
-        def run(a, b, part_floats):
-            part = ops._WS3.get(part_floats * 4, x.device)
-            rc = lib.sd3d_run_layers_ev(self.layers.ctypes.data + a * LAYER_DT.itemsize, b - a, tabs.ctypes.data, len(tabs), bufs.ctypes.data,
-                                        len(bufs), part.data_ptr(), part.numel(), ws.data_ptr(), ws.numel(),
-                                        evs.ctypes.data if evs.any() else None, ops._stream())
-            if rc:
-                _lib.check(rc, "run_layers")
-
-        # Tables built on the scene's side stream (SceneMaps.prepare(fork=True)): this stream waits for a table's event before the first
-        # layer that reads it.  Only the stem's table exists when this is called: the layers up to the first one that needs another table
-        # go first - the stem convolves while the host is still issuing table kernels - then the next group of tables, and so on.
-        n, done = len(self.layers), 0
-        while True:
-            part_floats, complete = fill_tables()
-            if complete:
-                run(done, n, part_floats)
-                break
-            have = np.array([maps.pairs.get(k) is not None for k in self.table_keys])
-            needs = (self.layers["kind"] == KIND_PAIR_CONV) & ~have[np.clip(self.layers["table"], 0, len(have) - 1)]
-            cut = int(np.argmax(needs))                          # first layer whose table does not exist yet
-            if cut > done:
-                run(done, cut, part_floats)
-                done = cut
-            if not getattr(maps, "next_fork", lambda: False)():
-                missing = [k for k in self.table_keys if maps.pairs.get(k) is None]
-                raise RuntimeError(f"neighbour tables {missing} have no pair lists (SceneMaps.prepare not called for them)")
-        if getattr(maps, "events", None):
-            maps.join()                                          # (tables no layer read: nothing of the side stream outlives this call unordered)
-        getattr(maps, "release_side", lambda: None)()            # the side stream's pool may reuse the tables' blocks only behind these layers
+        part = ops._WS3.get(part_floats * 4, x.device)
+        rc = lib.sd3d_run_layers(self.layers.ctypes.data, len(self.layers), tabs.ctypes.data, len(tabs), bufs.ctypes.data, len(bufs),
+                                 part.data_ptr(), part.numel(), ws.data_ptr(), ws.numel(), ops._stream())
+        if rc:
+            _lib.check(rc, "run_layers")
         o = int(offs[self.out_id])
         n = int(rows[self.out_id])
         cap = _trace.active()

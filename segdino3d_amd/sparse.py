@@ -125,37 +125,22 @@ def inv27_table(order: str) -> np.ndarray:
     return _INV27[order]
 
 
-# kernel offsets are enumerated symmetrically (kernel_offsets_np: off[K-1-k] == -off[k] for odd k), so a stride-1 table
-# needs only half its hash probes.  SD3D_MIRRORED_MAPS=0 probes every offset (cross-check).
-MIRRORED_MAPS = os.environ.get("SD3D_MIRRORED_MAPS", "1") != "0"
-
-# SD3D_PAIR_CHAIN=0: plain offset-major lists for the 3^3 tables too.  Default: CHAINED lists in evaluation (csrc/pair_gemm.hip: the
-# entries of an output row's mirror offsets {k, K-1-k} and its centre share ONE partial product - 27-44 % fewer partial rows written
-# by pass 1 and read by pass 2).  Training keeps the plain lists (the weight-gradient kernels walk them offset by offset).
-PAIR_CHAIN = os.environ.get("SD3D_PAIR_CHAIN", "1") != "0"
-# SD3D_PAIR_CHAIN_LEVELS: which U-Net levels get chained lists.  A property of the LEVEL, never of the scene or the batch (a scene's rows must see the same
+# Which U-Net levels get CHAINED lists for their 3^3 tables in evaluation (csrc/pair_gemm.hip: the entries of an output row's mirror offsets
+# {k, K-1-k} and its centre share ONE partial product - 27-44 % fewer partial rows written by pass 1 and read by pass 2).  Training keeps
+# the plain lists (the weight-gradient kernels walk them offset by offset).
+# A property of the LEVEL, never of the scene or the batch (a scene's rows must see the same
 # list format whether it runs alone or in a batch: the two formats sum in different orders).  Levels 0-2 (the tables with thousands
 # of tiles): measured same box, 4 streams x 4 scenes 118.1 -> 120.5-123 scenes/s, convolutions 7.29 -> 7.06 ms per scene in the
 # instrumented replay (0.471 -> 0.486 of the fp32 matrix peak), one scene in flight neutral (7.78 vs 7.76 ms: what the fewer partial
 # rows win, the weight-stationary pass-1 variants - which cannot chain - lose).  Levels 3-4 have few hundred to ~1800 tiles: chains
 # of three tiles on 3-4 tiles per workgroup unbalance the static ranges and the level-3 layers lose their weight-stationary variant:
 # all five levels 124.6 scenes/s with several scenes in flight but 8.27 vs 7.74 ms of convolutions with one.
-PAIR_CHAIN_LEVELS = tuple(int(v) for v in os.environ.get("SD3D_PAIR_CHAIN_LEVELS", "0,1,2").split(",") if v.strip() != "")
-# SD3D_FORK_JOIN=0: every neighbour table of a scene is built on the scene's own stream before the first convolution.  Default:
-# with ONE scene in flight (worst-case list sizes, no second read-back) only the stem's table is; the other levels' hash tables,
-# kernel maps and pair lists are built on a side stream while the stem and the first blocks convolve, each table's first layer
-# waits for its event (sd3d_run_layers_ev).  Same kernels on the same data: bit-identical outputs.
-# Round 5: OFF by default.  The fork bought 0.2 ms when a scene's maps and lists cost 0.96 ms of kernels; alone on the GPU they now take 0.24 ms
-# (hierarchical maps, row-block list builders, lean tables), and three cross-stream hand-offs cost the host about what the overlap still
-# wins: same-process A/B 10.565 - 10.570 ms without the fork against 10.582 - 10.584 with it (profiles/EXPERIMENTS.md).  SD3D_FORK_JOIN=1 restores it.
-FORK_JOIN = os.environ.get("SD3D_FORK_JOIN", "0") != "0"
+PAIR_CHAIN_LEVELS = (0, 1, 2)
 # SD3D_OPTIMISTIC_SORT=0: a scene's voxel keys / superpoint ids are always sorted over all their bits (7 + 4 radix passes instead of 4 + 2)
 OPTIMISTIC_SORT = os.environ.get("SD3D_OPTIMISTIC_SORT", "1") != "0"
 # SD3D_LEVELS_AT_ONCE=0: the coarser levels of a scene by one run-length unique per level (four launches each) instead of all of them
 # from the level-0 keys in four launches (`sd3d_unique_levels`; MinkowskiEngine semantics only - spconv's extent clip keeps the per-level path)
 LEVELS_AT_ONCE = os.environ.get("SD3D_LEVELS_AT_ONCE", "1") != "0"
-# SD3D_LEAN_LISTS=0: evaluation tables with their [K, M] position table and -1-filled unused capacity (rounds 1 - 4)
-LEAN_LISTS = os.environ.get("SD3D_LEAN_LISTS", "1") != "0"
 # SD3D_VOXELISE_ONE_CALL=0: the voxelisation chain of a scene as ~10 Python calls (the round 1 - 4 path; the clipped / per-level variants keep it)
 VOXELISE_ONE_CALL = os.environ.get("SD3D_VOXELISE_ONE_CALL", "1") != "0"
 MORTON_BITS = 48               # SD3D_MORTON_BITS (csrc/common.h): the Z-order code of a voxel; a batch's scene index sits above it
@@ -249,10 +234,6 @@ class SceneMaps:
         self._sp_start = None
         self.density: Dict[Tuple, float] = {}
         self.pairs: Dict[Tuple, "ops.PairLists"] = {}       # offset-major rulebooks (prepare())
-        self.events: Dict[Tuple, torch.cuda.Event] = {}     # tables built on the side stream (prepare(fork=True)) -> their event
-        self._join_ev = self._late = self._stem_done = None
-        self._side_used = False
-        self._fork_ev = ops.stream_event()                   # everything the tables are built from is complete here
 
     def _issue(self, points, inv, n_levels, shift_to_min, superpoints, clip_min_shape, optimistic):
         """Enqueue the voxelisation chain up to the read-back -> (read-back, keys per level, parents per level, superpoint keys | None)."""
@@ -282,94 +263,26 @@ class SceneMaps:
     def _count_superpoints(self, largest_ids):
         self.n_superpoints = int(largest_ids[0]) + 1 if self.superpoints is not None else 0
 
-    def prepare(self, same=(), strides=(), chained=False, fork=False):
+    def prepare(self, same=(), strides=(), chained=False):
         """Build the listed neighbour tables now and read their rulebook sizes back in ONE copy (the
         second and last synchronisation of a scene): density[key] = pairs / (K * V_out) lets the host
-        pick the pair-compacted convolution kernel for sparse maps.  same: [(level, ksize)], strides: [level].
-        fork=True (the caller runs the tables through `LayerPlan.run`, which waits per table): with worst-case list sizes (no
-        read-back) only the FIRST table of `same` - the stem's - is built on this stream; the others go to the thread's side stream
-        in the order the U-Net needs them, `self.events[key]` is recorded behind each group."""
+        pick the pair-compacted convolution kernel for sparse maps.  same: [(level, ksize)], strides: [level]."""
         same = list(dict.fromkeys((lvl, k) for (lvl, k) in same if ("same", lvl, k) not in self.density))
         exact = exact_pair_capacity(self.n_vox[0], self.device) or not ops.PAIR_CONV
-        if fork and FORK_JOIN and not exact and len(same) > 1 and not self.pairs:
-            return self._prepare_forked(same, list(strides), chained)
         self._build_tables(same, strides, chained, exact)
 
-    def _prepare_forked(self, same, strides, chained):
-        """Fork / join inside a scene.  Everything the side stream reads was finished before the scene's host
-        synchronisation (keys, parents) or is ordered by an event (the level-0 hash table, built here for the stem)."""
-        self._build_tables(same[:1], [], chained, False)                 # stem: this stream, first in line
-        stem_done = ops.stream_event()                                   # (its hash table serves the other level-0 table as well)
-        lvl0 = same[0][0]
-        rest = same[1:]
-        # need order: the levels below the stem's downwards (one group per level: the first must be ready when the stem's convolution
-        # ends), then the deepest levels together with the stem level's other tables (the last block of the U-Net)
-        groups = []
-        for d in (1, 2):
-            groups.append(([t for t in rest if t[0] == lvl0 + d], [l for l in strides if l == lvl0 + d - 1]))
-        taken_s = [t for g in groups for t in g[0]]
-        taken_l = [l for g in groups for l in g[1]]
-        groups.append(([t for t in rest if t not in taken_s], [l for l in strides if l not in taken_l]))
-        self._stem_done = stem_done
-        # LayerPlan.run issues the groups between its segments (next_fork): the stem's convolution is enqueued before the first group
-        self._late = [(g, chained) for g in groups if g[0] or g[1]]
-
-    def _fork_side(self, group, chained):
-        g_same, g_strides = group
-        if not g_same and not g_strides:
-            return
-        side = ops.side_streams(1, self.device)[0]
-        self._side_used = True
-        with ops.use_stream(side):
-            side.wait_event(self._fork_ev)
-            if self._hier_built or any(t[0] in self._hash for t in g_same):
-                side.wait_event(self._stem_done)                          # maps / a hash table the stem's stream built
-            keys = self._build_tables(g_same, g_strides, chained, False)
-            ev = ops.stream_event()
-            for key in keys:
-                self.events[key] = ev
-            self._join_ev = ev
-
-    def next_fork(self) -> bool:
-        """Enqueue the next pending table group of a forked prepare() on the side stream (LayerPlan.run calls it once the layers that
-        need no further table are enqueued).  False: nothing was pending."""
-        if not self._late:
-            return False
-        self._fork_side(*self._late.pop(0))
-        return True
-
-    def release_side(self):
-        """After the last kernel that reads a side-built table is enqueued (LayerPlan.run calls it): the side stream waits for
-        everything the scene's stream holds so far.  The tables come out of the SIDE stream's allocator pool but are read by the
-        scene's stream; when this SceneMaps dies their blocks return to that pool at once, and without this edge only the next
-        scene's fork event - recorded on whatever stream THAT forward runs on - would keep later side-stream work from overwriting
-        them under the U-Net kernels that still read them."""
-        if self._side_used:
-            ops.side_streams(1, self.device)[0].wait_event(ops.stream_event())
-            self._side_used = False
-
-    def join(self):
-        """The calling stream waits for the side stream's table building (no-op without a fork)."""
-        while self.next_fork():
-            pass
-        if self._join_ev is not None:
-            torch.cuda.current_stream().wait_event(self._join_ev)
-            self._join_ev = None
-            self.events = {}
-
     def _build_tables(self, same, strides, chained, exact):
-        """-> keys of the pair lists built (on the current stream)."""
         counters = torch.zeros(max(1, len(same)), 64, dtype=torch.int32, device=self.device) if exact else None
         L = len(self.keys)
         hier = (HIER_MAPS and same and not self.clipped and not self._same and len(self.parents) == L - 1 and min(self.n_vox) > 0
                 and all((k == 3) or (k == 5 and lvl == 0) for lvl, k in same))
         if hier:
-            # all maps of the scene now, whatever subset this call asks for (a forked prepare() calls again for the other levels and
-            # finds them): the hierarchy runs coarse to fine, and the whole chain costs less than one level's hash probes did
+            # all maps of the scene now, whatever subset this call asks for: the hierarchy runs coarse to fine, and the whole chain
+            # costs less than one level's hash probes did
             want5 = (0, 5) in same
             cnt_all = torch.zeros(L + 1, 64, dtype=torch.int32, device=self.device) if exact else None
             # evaluation builds lean plain lists: the map workgroups leave their (offset, row block) counts for them
-            self._blk_counts = {} if (chained and LEAN_LISTS and ops.PAIR_CONV) else None
+            self._blk_counts = {} if (chained and ops.PAIR_CONV) else None
             nbr3, nbr5, st_maps = ops.kernel_maps_hier(self.keys, self.parents, self.n_vox, offsets_device(3, self.order, self.device),
                                                        offsets_device(5, self.order, self.device) if want5 else None, inv27_table(self.order),
                                                        cnt_all, perm8=self._perm8 if not self._stride else None,
@@ -399,12 +312,12 @@ class SceneMaps:
             host = [k ** 3 * self.n_vox[lvl] for (lvl, k) in same]
         # evaluation (`chained`): nothing reads a [K, M] position table or the lists' unused capacity - pass 2 walks per-row lists, pass 1 the
         # real tiles (csrc/pair_gemm.hip, "plain lists without a position table"); training keeps both (pair_out_rows, the weight gradient)
-        lean = bool(chained) and LEAN_LISTS
+        lean = bool(chained)
         todo = []                                               # (key, nbr, pairs): all rulebooks of the scene in one launch set
         for (lvl, k), c in zip(same, host):
             self.density[("same", lvl, k)] = (c / max(1, k ** 3 * self.n_vox[lvl])) if exact else None
             if ops.PAIR_CONV:                                   # stride-1 table of the level onto itself: offset k^3 // 2 pairs every row with itself
-                if chained and PAIR_CHAIN and k == 3 and lvl in PAIR_CHAIN_LEVELS:
+                if chained and k == 3 and lvl in PAIR_CHAIN_LEVELS:
                     center = ops.PAIR_CHAINED                    # mirror groups + centre share partial products (evaluation)
                 else:
                     center = -1
@@ -424,7 +337,6 @@ class SceneMaps:
         if todo:
             for t, pl in zip(todo, ops.pair_lists_batch([t[1:] for t in todo])):
                 self.pairs[t[0]] = pl
-        return [t[0] for t in todo]
 
     # ------------------------------------------------------------------------------------------
     def table(self, level: int):
@@ -435,12 +347,11 @@ class SceneMaps:
     def _probe_map(self, level: int, ksize: int, pair_count=None):
         """nbr [k^3, V_l] by hash-table probes (pair_count int32 [>= 1]: receives the table's number of entries)."""
         offs = offsets_device(ksize, self.order, self.device)
-        return ops.kernel_map(self.keys[level], self.n_vox[level], self.table(level), offs, pair_count,
-                              mirrored=MIRRORED_MAPS and ksize % 2 == 1)
+        # odd kernels enumerate their offsets symmetrically (kernel_offsets_np: off[K-1-k] == -off[k]): half the probes fill the table
+        return ops.kernel_map(self.keys[level], self.n_vox[level], self.table(level), offs, pair_count, mirrored=ksize % 2 == 1)
 
     def same(self, level: int, ksize: int) -> torch.Tensor:
         """nbr [k^3, V_l] of a stride-1 convolution on level `level`."""
-        self.join()
         key = (level, ksize)
         if key not in self._same:
             self._same[key] = self._probe_map(level, ksize)
@@ -454,12 +365,10 @@ class SceneMaps:
 
     def down(self, level: int) -> torch.Tensor:
         """nbr [8, V_{l+1}] of the k=2 s=2 convolution level -> level+1."""
-        self.join()
         return self._stride_maps(level)[0]
 
     def up(self, level: int) -> torch.Tensor:
         """nbr [8, V_l] of the transposed k=2 s=2 convolution level+1 -> level."""
-        self.join()
         return self._stride_maps(level)[1]
 
     def conv_table(self, kind: str, level: int, ksize: int = 0) -> dict:
@@ -486,7 +395,6 @@ class SceneMaps:
     def rulebook_sizes(self):
         """{(kind, level[, k]): number of (in, out, offset) pairs} of the tables built so far (for the
         roofline accounting of bench.py; costs a sync)."""
-        self.join()
         out = {}
         for (lvl, k), t in self._same.items():
             out[("same", lvl, k)] = int((t >= 0).sum())
@@ -596,7 +504,7 @@ class BatchedMaps:
         self.n_vox = [self.offsets[l][-1] for l in range(n_levels)]
         self._tables: Dict[Tuple, dict] = {}
 
-    def prepare(self, same=(), strides=(), chained=False, fork=False):     # (training batches: `chained` / `fork` are False by construction)
+    def prepare(self, same=(), strides=(), chained=False):     # (training batches: `chained` is False by construction)
         for m in self.maps:
             m.prepare(same=same, strides=strides, chained=chained)
 

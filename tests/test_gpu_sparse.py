@@ -489,6 +489,42 @@ def _plan_vs_eager(bb, d):
         assert torch.equal(f_plan[0], f_eager[0]) and torch.equal(p_plan[0], p_eager[0])
 
 
+def test_layer_plan_refuses_maps_without_pair_lists(monkeypatch):
+    """`LayerPlan.run` on a scene whose `SceneMaps.prepare` was not called raises before anything is enqueued and names the tables
+    (the stem's among them); after `prepare()` with the backbone's table list the same call gives the U-Net output of a normal
+    forward of that scene bit for bit."""
+    import segdino3d_amd as seg
+    from segdino3d_amd import plan
+    from segdino3d_amd.configs import scannet200_model_cfg
+    from segdino3d_amd.synth import make_scene
+    d = dev()
+    bb = seg.build_architecture(scannet200_model_cfg(query_num=40)).eval().to(d).backbone      # Res16UNet34C
+    pts, tgt = make_scene(5, 2000, 40, 10)
+    pts, tgt = pts.to(d), tgt.to(d)
+    unet_out = []
+    run = plan.LayerPlan.run
+
+    def run_recorded(self, maps, x):
+        out = run(self, maps, x)
+        unet_out.append(out.clone())
+        return out
+    monkeypatch.setattr(plan.LayerPlan, "run", run_recorded)
+    with torch.no_grad():
+        bb.forward_wrapper([pts], [tgt], return_sp_mean_pos=True)
+    monkeypatch.setattr(plan.LayerPlan, "run", run)
+    assert bb._plan is not None and len(unet_out) == 1
+    k1 = bb.conv1_kernel_size
+    with torch.no_grad():
+        maps, vf = bb._scene_inputs(pts.float().contiguous(), tgt)[:2]
+        assert min(maps.n_vox) > 0 and len(maps.n_vox) == 5 and not maps.pairs
+        with pytest.raises(RuntimeError, match="have no pair lists") as err:
+            bb._plan.run(maps, vf)
+        assert repr(("same", 0, k1)) in str(err.value), err.value
+        maps.prepare(same=[(0, k1)] + [(l, 3) for l in range(5)], strides=[0, 1, 2, 3], chained=True)
+        got = bb._plan.run(maps, vf)
+    assert got.shape == unet_out[0].shape and torch.equal(got, unet_out[0])
+
+
 def test_mirrored_kernel_map_equals_full_probe():
     """Half-probe neighbour tables (mirror slots written from the hits) are bit-identical to probing every offset,
     pair counters included."""

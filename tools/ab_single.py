@@ -1,7 +1,7 @@
 """Same-process A/B of module switches at the `single_scene` operating point (one scene in flight, back to back): the settings
 alternate every 10 forwards for `rounds` rounds, the report is the median / min of the group means - box-to-box and process-to-process
 noise (0.3 - 0.5 ms between two bench.py runs of one build) cancels.
-usage: python tools/ab_single.py [rounds] [query_num]   (switches: sparse.FORK_JOIN, sparse.OPTIMISTIC_SORT, decoder.FUSED_NARROW)"""
+usage: python tools/ab_single.py [rounds] [query_num]   (switches: sparse.OPTIMISTIC_SORT / LEVELS_AT_ONCE / VOXELISE_ONE_CALL, decoder.FUSED_NARROW)"""
 import os
 import statistics
 import sys
@@ -20,13 +20,11 @@ d = torch.device("cuda:0")
 model = bench.build_model(qn, d)
 pool = [tuple(t.to(d) for t in make_scene(j, 150000, 3000, 300)) for j in range(2)]
 SETTINGS = {
-    "base (no fork, op-by-op decoder)": dict(fork=False, narrow=False),
-    "fork / join": dict(fork=True, narrow=False),
-    "narrow row chain": dict(fork=False, narrow=True),
-    "fork / join + narrow row chain": dict(fork=True, narrow=True),
-    "fork / join, full radix sorts": dict(fork=True, narrow=False, optimistic=False),
-    "fork / join, one unique per level": dict(fork=True, narrow=False, levels=False),
-    "fork / join, voxelisation by separate calls": dict(fork=True, narrow=False, one_call=False),
+    "base (op-by-op decoder)": dict(narrow=False),
+    "narrow row chain": dict(narrow=True),
+    "full radix sorts": dict(narrow=False, optimistic=False),
+    "one unique per level": dict(narrow=False, levels=False),
+    "voxelisation by separate calls": dict(narrow=False, one_call=False),
 }
 only = os.environ.get("AB_ONLY")
 if only:
@@ -34,7 +32,6 @@ if only:
 
 
 def apply(s):
-    sparse.FORK_JOIN = s["fork"]
     sparse.OPTIMISTIC_SORT = s.get("optimistic", True)
     sparse.LEVELS_AT_ONCE = s.get("levels", True)
     sparse.VOXELISE_ONE_CALL = s.get("one_call", True)

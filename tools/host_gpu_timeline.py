@@ -30,7 +30,7 @@ def wrap(obj, name, label):
 wrap(sparse.SceneMaps, "__init__", "1 voxelise + levels (sync 1)")
 wrap(sparse.SceneMaps, "prepare", "2 maps + stem lists")
 wrap(sparse.SceneMaps, "voxel_features", "2b voxel_mean")
-wrap(plan.LayerPlan, "run", "3 U-Net (run_layers, forks)")
+wrap(plan.LayerPlan, "run", "3 U-Net (run_layers)")
 wrap(sparse.SceneMaps, "pool", "4 pooling")
 wrap(model.decoder, "forward", "5 decoder")
 wrap(model, "predict_by_feat", "6 post-processing (sync 2)")

@@ -8,7 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 import bench
-from segdino3d_amd import ops, sparse
+from segdino3d_amd import ops
 from segdino3d_amd.sparse import SceneMaps
 from segdino3d_amd.synth import make_scene
 
@@ -17,7 +17,6 @@ model = bench.build_model(200, d)
 bb = model.backbone
 pts, tgt = make_scene(0, 150000, 3000, 300)
 pts, tgt = pts.to(d), tgt.to(d)
-sparse.FORK_JOIN = False
 with torch.no_grad():
     model([pts], [tgt])                                         # builds the plan, warms everything
     maps, vf, _, _, _, _ = bb._scene_inputs(pts.float().contiguous(), tgt)
