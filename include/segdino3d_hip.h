@@ -609,8 +609,20 @@ int sd3d_match_costs(const float* cls, int ld_cls, int n_cls1, const float* mask
 /* SparseMatcher.__call__ (loss_3d.py:360-365): match[q][g] = cost[q][g] < (topk+1)-th smallest cost of column g. */
 int sd3d_sparse_match(const float* cost, int Q, int G, int topk, uint8_t* match, void* stream);
 
+/* HungarianMatcher.__call__ (loss_3d.py:274-312, scipy.optimize.linear_sum_assignment there): the minimum-cost one-to-one
+ * assignment of n independent problems in one call (csrc/assign.hip: shortest augmenting paths in fp64, one workgroup per
+ * problem).  Problem i is cost[i] [Q[i], G[i]] fp32 row-major; match[i] [Q[i], G[i]] bytes is fully overwritten with exactly
+ * min(Q[i], G[i]) ones, at most one per row and per column (all zeros when Q[i] or G[i] is 0).  cost, Q, G, match are HOST
+ * arrays of n entries (of device pointers / sizes) copied into the launches; n is not limited (one launch per SD3D_MAX_BATCH
+ * problems).  status (device, n words, may be NULL): 0, or 1 where scipy would raise - a NaN or -inf entry, or no finite
+ * assignment; the match of such a problem is still one-to-one.  +inf entries are ordinary values.  The result is an optimum;
+ * where the optimum is not unique it need not be the one scipy picks. */
+size_t sd3d_hungarian_match_ws_bytes(int n, const int* Q, const int* G);
+int sd3d_hungarian_match_batch(int n, const float* const* cost, const int* Q, const int* G, uint8_t* const* match, int32_t* status,
+                               void* ws, size_t ws_bytes, void* stream);
+
 /* InstanceCriterion's per-scene terms of one layer (loss_3d.py:459-503 / :618-663) for a given match [Q, G] (from
- * sd3d_sparse_match, or scipy's linear_sum_assignment for the HungarianMatcher :311), and their gradients.
+ * sd3d_sparse_match or sd3d_hungarian_match_batch), and their gradients.
  * parts8 (device) = [class CE, mask BCE, mask dice, score MSE, centre L1, size L1, matched pairs, scores kept];
  * d_* = coef6[i] * d(parts[i]) / d(prediction): coef6 (HOST array) carries the loss weight and the batch-size factors
  * of :505-521 / :665-679, so the d_* buffers are the gradients of the total loss.  d_cls [Q, n_cls1], d_masks [Q, S],

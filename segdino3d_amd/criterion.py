@@ -11,12 +11,18 @@ layer and scene and lets autograd derive the gradients; here each (layer, scene)
 (`sd3d_match_costs`, `sd3d_sparse_match`, `sd3d_instance_loss`; csrc/loss.hip) that produce the loss terms AND the
 gradients with respect to every prediction in the same pass over the `[Q, S]` mask logits.  The returned losses are
 attached to those gradients through one `torch.autograd.Function`, so `loss.backward()` hands them to whatever
-produced the predictions.  Only the Hungarian assignment itself stays on the host (scipy, as in the reference `:311`).
-There is no CPU fallback: CPU tensors raise.
+produced the predictions.  There is no CPU fallback: CPU tensors raise.
+
+The HungarianMatcher (`:274-312`) runs on the device too: the costs of every (prediction set, scene) that needs its own
+assignment are computed first, ONE `sd3d_hungarian_match_batch` call (csrc/assign.hip, one workgroup per problem) solves them
+all, and the layer terms follow in the reference's order - no copy to the host, no stream drain, no scipy.
+`SD3D_HUNGARIAN=host` keeps the earlier route (`cost.cpu()`, `scipy.optimize.linear_sum_assignment`, index scatter, once per
+problem) as the cross-check; the default is `device`.
 """
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Dict, List, Sequence
 
 import torch
@@ -123,14 +129,13 @@ class InstanceCriterion:
             self._cw[key] = torch.tensor(self.class_weight, dtype=torch.float32, device=device)
         return self._cw[key]
 
-    def match(self, layer, i, truth: _SceneTruth) -> torch.Tensor:
-        """[Q, G] byte matrix of matched (query, object) pairs for scene i of a prediction set."""
+    def costs(self, layer, i, truth: _SceneTruth) -> torch.Tensor:
+        """[Q, G] matching costs of scene i of a prediction set."""
         lib = _lib.load()
         cls, masks = _f32(layer["cls_preds"][i], "cls_preds"), _f32(layer["masks"][i], "masks")
         ctr, size = _f32(layer["centers"][i], "centers"), _f32(layer["sizes"][i], "sizes")
         Q, G = masks.shape[0], truth.G
-        dev = masks.device
-        cost = torch.empty(Q, G, dtype=torch.float32, device=dev)
+        cost = torch.empty(Q, G, dtype=torch.float32, device=masks.device)
         w5 = (ctypes.c_float * 5)(*self.cost_weights)
         sparse = self.matcher_kind == "SparseMatcher"
         _lib.check(lib.sd3d_match_costs(cls.data_ptr(), cls.stride(0), cls.shape[1], masks.data_ptr(), masks.stride(0), Q, masks.shape[1],
@@ -138,14 +143,33 @@ class InstanceCriterion:
                                         truth.count.data_ptr(), G, ops._ptr(truth.centers), truth.centers.stride(0) if truth.centers is not None else 0,
                                         ops._ptr(truth.sizes), truth.sizes.stride(0) if truth.sizes is not None else 0,
                                         truth.query_masks.data_ptr() if sparse else None, w5, cost.data_ptr(), ops._stream()), "match_costs")
-        match = torch.zeros(Q, G, dtype=torch.uint8, device=dev)
-        if sparse:
-            _lib.check(lib.sd3d_sparse_match(cost.data_ptr(), Q, G, self.topk, match.data_ptr(), ops._stream()), "sparse_match")
-        else:
-            from scipy.optimize import linear_sum_assignment                      # the assignment itself: host, as loss_3d.py:311
-            q_ids, g_ids = linear_sum_assignment(cost.cpu().numpy())
-            match[torch.as_tensor(q_ids, device=dev), torch.as_tensor(g_ids, device=dev)] = 1
         self.last_cost = cost
+        return cost
+
+    def assign(self, costs: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+        """HungarianMatcher: the one-to-one [Q, G] byte match of every cost matrix (loss_3d.py:274-312)."""
+        route = os.environ.get("SD3D_HUNGARIAN", "device")
+        if route == "device":
+            return ops.hungarian_match(costs)                                     # one C call for all of them, nothing read back
+        if route != "host":
+            raise ValueError(f"SD3D_HUNGARIAN must be 'device' or 'host', got {route!r}")
+        from scipy.optimize import linear_sum_assignment                          # the cross-check: host, as loss_3d.py:311
+        out = []
+        for cost in costs:
+            match = torch.zeros(cost.shape, dtype=torch.uint8, device=cost.device)
+            q_ids, g_ids = linear_sum_assignment(cost.cpu().numpy())
+            match[torch.as_tensor(q_ids, device=cost.device), torch.as_tensor(g_ids, device=cost.device)] = 1
+            out.append(match)
+        return out
+
+    def match(self, layer, i, truth: _SceneTruth) -> torch.Tensor:
+        """[Q, G] byte matrix of matched (query, object) pairs for scene i of a prediction set."""
+        cost = self.costs(layer, i, truth)
+        if self.matcher_kind != "SparseMatcher":
+            return self.assign([cost])[0]
+        Q, G = cost.shape
+        match = torch.zeros(Q, G, dtype=torch.uint8, device=cost.device)
+        _lib.check(_lib.load().sd3d_sparse_match(cost.data_ptr(), Q, G, self.topk, match.data_ptr(), ops._stream()), "sparse_match")
         return match
 
     def layer_terms(self, layer, i, truth: _SceneTruth, match: torch.Tensor, coef: Sequence[float]):
@@ -259,12 +283,17 @@ class ScanNetUnifiedCriterion:
         self.last_parts, self.last_matches = [], []
         w = ic.loss_weight + [0.0] * (6 - len(ic.loss_weight))
         matches_last = None
-        for layer, last in layers:
+        # HungarianMatcher: the costs of every (prediction set, scene) that needs its own match, then ONE batched solve
+        hungarian, solved = ic.matcher_kind == "HungarianMatcher", {}
+        if hungarian:
+            need = [(li, i) for li, (_, last) in enumerate(layers) if last or ic.iter_matcher for i in range(n_b)]
+            solved = dict(zip(need, ic.assign([ic.costs(layers[li][0], i, truths[i]) for li, i in need])))
+        for li, (layer, last) in enumerate(layers):
             coef = ic.scene_coefficients(n_b, last)
             parts_b, matches = [], []
             for i in range(n_b):
                 if last or ic.iter_matcher:
-                    m = ic.match(layer, i, truths[i])
+                    m = solved[(li, i)] if hungarian else ic.match(layer, i, truths[i])
                 else:
                     m = matches_last[i]
                 matches.append(m)

@@ -1597,3 +1597,41 @@ def scale_shift_act(x, scale, shift, act=None, x2=None, add=None):
                                             _ptr(shift, torch.float32, "shift"), ACT[act], x.shape[0], C, pa, lda, _ptr(out), C,
                                             _stream()), "scale_shift_act")
     return out
+
+
+def hungarian_match(costs, check=False, return_status=False):
+    """Minimum-cost one-to-one assignment (scipy.optimize.linear_sum_assignment, the reference's HungarianMatcher) of every
+    [Q_i, G_i] fp32 cost matrix of `costs` in ONE C call (csrc/assign.hip: one workgroup per problem) -> list of [Q_i, G_i] byte
+    matrices with min(Q_i, G_i) ones, at most one per row and per column.  Where the optimum is not unique the pairs may differ
+    from scipy's; the total cost does not.  `check=True` reads the status words back (a synchronisation) and raises ValueError
+    where scipy would (NaN / -inf entries, no finite assignment); `check=False` never reads the device.
+    `return_status=True` -> (matches, int32 device tensor of the status words)."""
+    import ctypes as C
+    lib = _lib.load()
+    costs = list(costs)
+    n = len(costs)
+    if n == 0:
+        return ([], None) if return_status else []
+    P, I = (C.c_void_p * n), (C.c_int * n)
+    cp, mp, Q, G = P(), P(), I(), I()
+    out = []
+    dev = costs[0].device
+    for i, c in enumerate(costs):
+        if c.dim() != 2:
+            raise ValueError(f"hungarian_match: costs[{i}] must be a [Q, G] matrix, got {tuple(c.shape)}")
+        cp[i] = _ptr(c, torch.float32, f"hungarian_match: costs[{i}]")
+        if c.device != dev:
+            raise ValueError("hungarian_match: all cost matrices must live on one device")
+        Q[i], G[i] = c.shape
+        m = torch.empty(c.shape, dtype=torch.uint8, device=dev)
+        mp[i] = m.data_ptr()
+        out.append(m)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    ws_bytes = lib.sd3d_hungarian_match_ws_bytes(n, Q, G)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.sd3d_hungarian_match_batch(n, cp, Q, G, mp, status.data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "hungarian_match")
+    if check:
+        bad = torch.nonzero(status).reshape(-1).tolist()
+        if bad:
+            raise ValueError(f"hungarian_match: cost matrix {bad[0]} contains invalid numeric entries or has no finite assignment")
+    return (out, status) if return_status else out
