@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 3
+#define SD3D_ABI_VERSION 4
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -836,6 +836,40 @@ int sd3d_mt_adamw(const sd3d_mt_tensor* tensors, int n_tensors, const sd3d_mt_ch
                   int table_resident, void* ws, size_t ws_bytes, void* stream);
 int sd3d_mt_ema(const sd3d_mt_tensor* tensors, int n_tensors, const sd3d_mt_chunk* chunks, int64_t n_chunks, int table_resident, void* ws,
                 size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Dataset targets: raw per-point labels -> the fields the model and the criterion read (the label side of the reference's
+ * `Dataset.__getitem__`: scannet200.py:155-193 adjust_class_ids_ / exclude_stuffs_ / merge_stuffs_, :243-253 superpoint votes,
+ * :291-326 split_instance_gt, and instance_seg_3d_preparer.py).  Integers only; every result is a pure function of the input.
+ *
+ *   sd3d_targets_scan(instance_mask, semantic_mask, super_points [n] int64, lut [lut_len] int64, ...): pass 1.
+ *     sem = lut[swap_2_3 ? (2 <-> 3)(raw) : raw]; points whose sem is a stuff id (ascending class ids, at most 8) or n_classes get
+ *     instance -1; the distinct masked instance ids are ranked.  Writes the header, four int32 at the START of `ws`:
+ *       [0] status: OR of SD3D_TARGETS_BAD_*;  [1] G' = distinct masked ids - 1 (new id = rank - 1: with no background point the
+ *       smallest instance becomes -1, as in the reference);  [2] S = largest superpoint id + 1;  [3] bit k: stuff id k occurs.
+ *     The caller copies these 16 bytes to the host (the one read-back) and sizes the outputs from them.
+ *   sd3d_targets_rows(header, n_stuff, val_view): G, the number of mask rows: G' (train view) or G' + present stuff classes.
+ *   sd3d_targets_build(n, header (HOST copy), ...): pass 2 on the SAME `ws`.  A non-zero status returns SD3D_ERR_RANGE and names the
+ *     status in sd3d_last_error.  Outputs:
+ *       masks [G, n] bytes 0/1, labels / area [G] int64 (may be NULL when G = 0): row order = ascending id.  Train view: row g = new id g,
+ *         label = sem at the row's lowest point index - n_stuff.  Val view (merge_stuffs_): the present stuff classes first (all points
+ *         of the class, label = the class), then the instances, labels not shifted.
+ *       seg_start [S + 1], sp_inst [S], sp_sem [S] int32: start of every superpoint in the sorted order; the instance (new id, -1: none)
+ *         and class (n_classes: none) that hold MORE THAN HALF of the superpoint's points, 2 k > n.
+ *       sp_masks [G' + n_classes + 1, S] bytes 0/1: rows g < G': sp_inst == g; then sp_sem == c.  Votes are taken before the val merge.
+ *   ws: sd3d_targets_ws_bytes(n) bytes, untouched between the two calls.  1 <= n <= 0x7F000000.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_TARGETS_BAD_SEMANTIC 1      /* a raw semantic id outside [0, lut_len) */
+#define SD3D_TARGETS_BAD_INSTANCE 2      /* a raw instance id outside [-1, 2^20) */
+#define SD3D_TARGETS_BAD_SUPERPOINT 4    /* a superpoint id outside [0, 2^31 - 2] */
+size_t sd3d_targets_ws_bytes(int64_t n);
+int sd3d_targets_scan(const int64_t* instance_mask, const int64_t* semantic_mask, const int64_t* super_points, int64_t n,
+                      const int64_t* lut, int64_t lut_len, int n_classes, const int32_t* stuff_ids, int n_stuff, int swap_2_3,
+                      void* ws, size_t ws_bytes, void* stream);
+int sd3d_targets_rows(const int32_t* header, int n_stuff, int val_view);
+int sd3d_targets_build(int64_t n, const int32_t* header, int n_classes, const int32_t* stuff_ids, int n_stuff, int val_view,
+                       uint8_t* masks, int64_t* labels, int64_t* area, int32_t* seg_start, int32_t* sp_inst, int32_t* sp_sem,
+                       uint8_t* sp_masks, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,5 +15,6 @@ from .decoder import ScanNetQueryDecoder  # noqa: F401
 from .architecture import Baseline3D, PointData  # noqa: F401
 from ._trace import capture  # noqa: F401
 from .optim import FusedAdamW, ModelEma, fuse  # noqa: F401
+from .targets import LabelSpec, build_targets, drop_2d_queries  # noqa: F401
 
-__all__ = list(_builder_all) + ["GDType", "GD3DTarget", "Res16UNet34C", "SpConvUNet", "ScanNetQueryDecoder", "Baseline3D", "PointData", "capture", "FusedAdamW", "ModelEma", "fuse"]
+__all__ = list(_builder_all) + ["GDType", "GD3DTarget", "Res16UNet34C", "SpConvUNet", "ScanNetQueryDecoder", "Baseline3D", "PointData", "capture", "FusedAdamW", "ModelEma", "fuse", "LabelSpec", "build_targets", "drop_2d_queries"]

@@ -1,7 +1,8 @@
 """Input side of the path: the reference's on-disk scene formats, a packed single-file format,
 and a pinned-memory prefetcher that overlaps disk -> host -> device copies with the forward of earlier scenes.
 
-Reference behaviour restated here (validation split; training-only augmentation is out of scope):
+Reference behaviour restated here (the file formats and the val transform; the train-time augmentation is `augment.py`, the label
+side of the dataset classes - instance masks, labels, superpoint votes, 2D-query dropout - is `targets.py`, both on the device):
   * file layout and decoding: `segdino3d/datasets/dataset/scannet200.py:206-256` - `points/{id}.bin` f32 [N,6]
     (xyz + rgb 0..255), `instance_mask|semantic_mask/{id}.bin` i64 [N], `super_points/{id}.bin` i64 [N],
     `{id}.pth` = list of multi-scale [N,256] feature tensors averaged at load (`:234-235`), `{id}_query_feats.pth`
@@ -136,17 +137,29 @@ def load_packed(path: str, pin: bool = False, staging: Optional[torch.Tensor] = 
     return out
 
 
-def to_device_scene(host: Dict[str, torch.Tensor], device, non_blocking: bool = True):
-    """(points [N,6] f32, GD3DTarget) on the device, laid out like the reference dataset output."""
+def to_device_scene(host: Dict[str, torch.Tensor], device, non_blocking: bool = True, labels=None, scene_set: str = "val", scene_id=None,
+                    index: int = 0):
+    """(points [N,6] f32, GD3DTarget) on the device, laid out like the reference dataset output.
+    `labels` None: the target carries a placeholder (`masks` = ones [1, N, 1], `labels` = zeros [1]: the eval forward only needs
+    the scene range).  `labels` a `targets.LabelSpec`: the raw label arrays of the scene become the reference's target fields on
+    the device (`targets.build_targets`: `masks` [G, N, 1], `labels`, `area`, `iscrowd`, `sp_inst_sem_masks`, ... in the train or
+    val view of `scene_set`) - one 16-byte read-back on the current stream."""
     dev = {k: v.to(device, non_blocking=non_blocking) for k, v in host.items() if not k.startswith("_")}
     f2d = dev["points_2dfeats"]
     if f2d.dtype != torch.float32:
         f2d = f2d.float()
     N = dev["points"].shape[0]
-    masks = torch.ones(1, N, 1, dtype=torch.bool, device=device)          # the eval forward only needs the scene range
     extra = {"points_2dfeats": f2d, "query2d_feats": dev["query2d_feats"], "query2d_pos": dev["query2d_pos"],
              "super_point_masks": dev["super_points"]}
-    tgt = GD3DTarget(masks=masks, labels=torch.zeros(1, dtype=torch.int64, device=device), extra_features=extra)
+    if labels is None:
+        masks = torch.ones(1, N, 1, dtype=torch.bool, device=device)      # the eval forward only needs the scene range
+        tgt = GD3DTarget(masks=masks, labels=torch.zeros(1, dtype=torch.int64, device=device), extra_features=extra)
+    else:
+        if "instance_mask" not in dev:
+            raise ValueError("to_device_scene: labels given, but the scene holds no instance_mask / semantic_mask")
+        from .targets import build_targets
+        tgt = build_targets(dev["instance_mask"], dev["semantic_mask"], dev["super_points"], labels, scene_set,
+                            GD3DTarget(extra_features=extra), scene_id=scene_id, index=index)
     if "instance_mask" in dev:
         tgt["gt_instance_mask"], tgt["gt_semantic_mask"] = dev["instance_mask"], dev["semantic_mask"]
     return dev["points"], tgt
@@ -159,10 +172,21 @@ class ScenePrefetcher:
     sequential read, the GIL is released inside it) and issue the H2D copies on a dedicated stream; `__next__`
     hands scenes out IN ORDER, making the consumer's current stream wait on the scene's copy event (a device-side
     wait: the host never blocks on a transfer).  A staging buffer is recycled when the consumer asks for the scene
-    after the one that used it.  Thread-safe for several consumers (the pipelined runner's workers)."""
+    after the one that used it.  Thread-safe for several consumers (the pipelined runner's workers).
 
-    def __init__(self, paths: Iterable[str], device, depth: int = 3, readers: int = 2):
+    `labels` (a `targets.LabelSpec`): every scene's raw labels become real targets on the device in the `scene_set` view
+    (`to_device_scene`), the scene id being the file's base name.  The kernels run on the copy stream; their one 16-byte read-back
+    per scene blocks the READER thread only, `depth` scenes ahead of the consumer.  `dropout_rate_2dfeats` > 0 applies
+    `targets.drop_2d_queries` with `numpy.random` (drawn in the reader threads: with more than one reader the order of the draws
+    across scenes is not fixed, as with the reference's loader workers).  `skip_empty` (None: in the train view only): a scene
+    without any instance is not handed out but counted in `skipped` (the reference steps over such scenes, `scannet.py:173-175`)."""
+
+    def __init__(self, paths: Iterable[str], device, depth: int = 3, readers: int = 2, labels=None, scene_set: str = "val",
+                 dropout_rate_2dfeats: float = 0.0, skip_empty: Optional[bool] = None):
         self.paths = list(paths)
+        self.labels, self.scene_set, self.dropout_rate_2dfeats = labels, scene_set, float(dropout_rate_2dfeats)
+        self.skip_empty = (scene_set == "train") if skip_empty is None else bool(skip_empty)
+        self.skipped = 0
         self.device = torch.device(device)
         self.depth = max(1, depth)
         self.copy_stream = torch.cuda.Stream(device=self.device)
@@ -192,7 +216,17 @@ class ScenePrefetcher:
                 staging = self._free.get()
                 host = load_packed(self.paths[i], pin=True, staging=staging)
                 with torch.cuda.stream(self.copy_stream):
-                    pts, tgt = to_device_scene(host, self.device, non_blocking=True)
+                    if self.labels is None:
+                        pts, tgt = to_device_scene(host, self.device, non_blocking=True)
+                    else:
+                        sid = os.path.splitext(os.path.basename(self.paths[i]))[0]
+                        pts, tgt = to_device_scene(host, self.device, non_blocking=True, labels=self.labels, scene_set=self.scene_set,
+                                                   scene_id=sid, index=i)
+                        if self.skip_empty and tgt["labels"].shape[0] == 0:
+                            tgt = None
+                    if tgt is not None and self.dropout_rate_2dfeats > 0.0:
+                        from .targets import drop_2d_queries
+                        drop_2d_queries(tgt, self.dropout_rate_2dfeats)
                     ev = torch.cuda.Event()
                     ev.record(self.copy_stream)
                 with self._cv:
@@ -210,23 +244,29 @@ class ScenePrefetcher:
         return len(self.paths)
 
     def __next__(self):
-        with self._cv:
-            i = self._next_out
-            if i >= len(self.paths):
-                raise StopIteration
-            self._next_out += 1
-            self._cv.notify_all()                                         # readers may move ahead
-            while i not in self._ready and self._err is None:
-                self._cv.wait()
-            if self._err is not None:
-                raise self._err
-            pts, tgt, ev, staging = self._ready.pop(i)
+        while True:
+            with self._cv:
+                i = self._next_out
+                if i >= len(self.paths):
+                    raise StopIteration
+                self._next_out += 1
+                self._cv.notify_all()                                     # readers may move ahead
+                while i not in self._ready and self._err is None:
+                    self._cv.wait()
+                if self._err is not None:
+                    raise self._err
+                pts, tgt, ev, staging = self._ready.pop(i)
+                if tgt is None:                                           # a scene without instances (skip_empty)
+                    self.skipped += 1
+            if tgt is not None:
+                break
+            self._recycle(ev, staging)
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ev)
         # the tensors were allocated on the copy stream: tell the allocator the consumer's stream uses them
         pts.record_stream(cur)
-        for v in tgt.extra_features.values():
-            if torch.is_tensor(v):
+        for v in list(tgt.extra_features.values()) + ([tgt[k] for k in tgt.keys()] if self.labels is not None else []):
+            if torch.is_tensor(v) and v.is_cuda:
                 v.record_stream(cur)
         # the H2D copy out of `staging` is complete once `ev` has fired; recycle it when that is known on the host
         self._recycle(ev, staging)

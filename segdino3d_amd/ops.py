@@ -1635,3 +1635,53 @@ def hungarian_match(costs, check=False, return_status=False):
         if bad:
             raise ValueError(f"hungarian_match: cost matrix {bad[0]} contains invalid numeric entries or has no finite assignment")
     return (out, status) if return_status else out
+
+
+# --------------------------------------------------------------------------------------------
+# dataset targets (csrc/targets.hip)
+# --------------------------------------------------------------------------------------------
+def _stuff_array(stuff_ids):
+    return (ctypes.c_int32 * max(1, len(stuff_ids)))(*stuff_ids)
+
+
+def targets_scan(instance_mask, semantic_mask, super_points, lut, n_classes: int, stuff_ids, swap_2_3: bool):
+    """Pass 1 of `sd3d_targets_scan` on int64 [N] label arrays: returns (workspace, HostRead of the 4-word header
+    {status, G', S, present stuff bits}).  The workspace belongs to this scene until `targets_build` has run on it."""
+    lib = _lib.load()
+    n = instance_mask.numel()
+    if semantic_mask.numel() != n or super_points.numel() != n:
+        raise ValueError("targets_scan: instance_mask, semantic_mask and super_points must have one entry per point")
+    dev = instance_mask.device
+    ws = torch.empty(lib.sd3d_targets_ws_bytes(n), dtype=torch.uint8, device=dev)
+    _lib.check(lib.sd3d_targets_scan(_ptr(instance_mask, torch.int64, "instance_mask"), _ptr(semantic_mask, torch.int64, "semantic_mask"),
+                                     _ptr(super_points, torch.int64, "super_points"), n, _ptr(lut, torch.int64, "seg_label_mapping"), lut.numel(),
+                                     int(n_classes), _stuff_array(stuff_ids), len(stuff_ids), int(bool(swap_2_3)), ws.data_ptr(), ws.numel(),
+                                     _stream()), "targets_scan")
+    return ws, HostRead(ws[:16].view(torch.int32))
+
+
+def targets_build(ws, header, n: int, n_classes: int, stuff_ids, val_view: bool):
+    """Pass 2 (`sd3d_targets_build`) from the header as read back (int32 [4] on the host): allocates and fills masks [G, N] uint8,
+    labels / area [G] int64, sp_inst / sp_sem [S] int32 and sp_masks [G' + C + 1, S] uint8.  Raises on a range status."""
+    lib = _lib.load()
+    dev = ws.device
+    hdr = (ctypes.c_int32 * 4)(*[int(v) for v in header.tolist()])
+    stuff = _stuff_array(stuff_ids)
+    if hdr[0] != 0:                                          # a range status: the C call names it (outputs are not touched)
+        _lib.check(lib.sd3d_targets_build(n, hdr, int(n_classes), stuff, len(stuff_ids), int(bool(val_view)), None, None, None, None, None, None,
+                                          None, ws.data_ptr(), ws.numel(), _stream()), "targets_build")
+    G1, S = int(hdr[1]), int(hdr[2])
+    G = lib.sd3d_targets_rows(hdr, len(stuff_ids), int(bool(val_view)))
+    if G < 0:
+        _lib.check(G, "targets_rows")
+    masks = torch.empty((G, n), dtype=torch.uint8, device=dev)
+    labels = torch.empty(G, dtype=torch.int64, device=dev)
+    area = torch.empty_like(labels)
+    seg_start = torch.empty(S + 1, dtype=torch.int32, device=dev)
+    sp_inst = torch.empty(S, dtype=torch.int32, device=dev)
+    sp_sem = torch.empty(S, dtype=torch.int32, device=dev)
+    sp_masks = torch.empty((G1 + n_classes + 1, S), dtype=torch.uint8, device=dev)
+    _lib.check(lib.sd3d_targets_build(n, hdr, int(n_classes), stuff, len(stuff_ids), int(bool(val_view)), _ptr(masks), _ptr(labels), _ptr(area),
+                                      _ptr(seg_start), _ptr(sp_inst), _ptr(sp_sem), _ptr(sp_masks), ws.data_ptr(), ws.numel(), _stream()),
+               "targets_build")
+    return dict(masks=masks, labels=labels, area=area, sp_inst=sp_inst, sp_sem=sp_sem, sp_masks=sp_masks, n_instances=G1, n_superpoints=S)
