@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 4
+#define SD3D_ABI_VERSION 5
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -870,6 +870,30 @@ int sd3d_targets_rows(const int32_t* header, int n_stuff, int val_view);
 int sd3d_targets_build(int64_t n, const int32_t* header, int n_classes, const int32_t* stuff_ids, int n_stuff, int val_view,
                        uint8_t* masks, int64_t* labels, int64_t* area, int32_t* seg_start, int32_t* sp_inst, int32_t* sp_sem,
                        uint8_t* sp_masks, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Benchmark submission text (csrc/submit.hip): the bytes `np.savetxt(path, x, fmt='%d')` writes, made on the device
+ * (evaluator_3d.py:351-396 format_results_semantic / save_single_instance).  The host copies them and calls write().
+ *
+ *   sd3d_mask_text(masks [*, N] bytes, N, rows [n_rows] | NULL = rows 0..n_rows-1, n_rows, out [n_rows, pitch], pitch):
+ *     the byte table and row list of sd3d_pack_mask_rows.  out[r * pitch + 2 p] = '0' + (masks[rows[r]][p] != 0),
+ *     out[r * pitch + 2 p + 1] = '\n': the first 2 N bytes of row r are the file of mask rows[r]; the bytes behind them are not
+ *     written.  pitch >= 2 N, pitch % 16 == 0 and `out` 16-byte aligned, N >= 1, n_rows >= 0 (SD3D_ERR_ARG otherwise); n_rows == 0
+ *     does nothing.  Row indices may repeat, in any order.
+ *   sd3d_label_text(values [N] int64, N, lut [lut_len] int32 | NULL, lut_len, out [out_cap], out_cap, info [2], ws, ws_bytes):
+ *     line p = the decimal text of lut[values[p]] (of values[p] without a table) + '\n', as '%d' prints an int32 ('-', -2147483648
+ *     included); the lines stand back to back from out[0] on.  info[0] = length of the whole text in bytes, info[1] = status, OR of
+ *     SD3D_LABEL_TEXT_*: a line whose value cannot be printed is left out (no clamp, no wrap), and a text longer than out_cap is cut
+ *     at out_cap - nothing is written at or behind out + out_cap (info[0] is still the full length).  `out` 16-byte aligned.
+ *     0 <= N <= (2^31 - 1) / 12; N == 0 writes info = {0, 0} only.  ws: sd3d_label_text_ws_bytes(N) bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_LABEL_TEXT_BAD_INDEX 1      /* with a table: a value outside [0, lut_len) */
+#define SD3D_LABEL_TEXT_BAD_VALUE 2      /* without a table: a value outside int32 */
+#define SD3D_LABEL_TEXT_OVERFLOW 4       /* the text is longer than out_cap */
+int sd3d_mask_text(const uint8_t* masks, int64_t N, const int32_t* rows, int n_rows, uint8_t* out, int64_t pitch, void* stream);
+size_t sd3d_label_text_ws_bytes(int64_t N);
+int sd3d_label_text(const int64_t* values, int64_t N, const int32_t* lut, int lut_len, uint8_t* out, int64_t out_cap, int32_t* info,
+                    void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -163,6 +163,24 @@ def wait_event(ev):
         time.sleep(0 if spins < 200 else 5e-5)
 
 
+class baton_released:
+    """A host wait that is no GPU wait (a free staging buffer, a queue): this thread's issue baton goes to the other scene threads
+    for the duration of the scope, as in `wait_event`.  Take no lock inside that a baton holder may want while it is held on exit."""
+
+    def __enter__(self):
+        self.baton = getattr(_BATON_TLS, "lock", None)
+        if self.baton is not None:
+            self.baton.release()
+        return self
+
+    def __exit__(self, *exc):
+        if self.baton is not None:
+            _BATON_WAITERS.append(1)
+            self.baton.acquire()
+            _BATON_WAITERS.pop()
+        return False
+
+
 def stream_event():
     # hipEventBlockingSync: a thread waiting for its scene sleeps instead of spinning on a core (8 ranks x 4 scene threads
     # share one host in the multi-GPU runs)
@@ -1685,3 +1703,73 @@ def targets_build(ws, header, n: int, n_classes: int, stuff_ids, val_view: bool)
                                       _ptr(seg_start), _ptr(sp_inst), _ptr(sp_sem), _ptr(sp_masks), ws.data_ptr(), ws.numel(), _stream()),
                "targets_build")
     return dict(masks=masks, labels=labels, area=area, sp_inst=sp_inst, sp_sem=sp_sem, sp_masks=sp_masks, n_instances=G1, n_superpoints=S)
+
+
+# --------------------------------------------------------------------------------------------
+# benchmark submission text (csrc/submit.hip)
+# --------------------------------------------------------------------------------------------
+def mask_text(masks, rows=None):
+    """masks [n, N] uint8 / bool -> uint8 [len(rows) | n, pitch], pitch = 2 N rounded up to 16: the first 2 N bytes of row r are what
+    `np.savetxt(f, masks[rows[r]], fmt='%d')` writes ("0\\n" / "1\\n" per point); the bytes behind them are not initialised."""
+    if not masks.is_cuda:
+        raise RuntimeError(f"masks: expected a tensor on the HIP device, got {masks.device} (no CPU fallback)")
+    lib = _lib.load()
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    n, N = masks.shape
+    n_rows = n if rows is None else rows.numel()
+    pitch = (2 * N + 15) // 16 * 16
+    out = torch.empty(n_rows, pitch, dtype=torch.uint8, device=masks.device)
+    if n_rows == 0 or N == 0:
+        return out
+    _lib.check(lib.sd3d_mask_text(_ptr(masks, torch.uint8, "masks"), N, _ptr(rows, torch.int32, "rows"), n_rows, _ptr(out), pitch, _stream()),
+               "mask_text")
+    return out
+
+
+LABEL_TEXT_STATUS = ((1, "an index lies outside the label table"), (2, "a value lies outside int32"),
+                     (4, "the text does not fit the output buffer"))
+
+
+class LabelTable:
+    """An id table of `label_text` on the device: int32 entries and the bytes of its widest line."""
+
+    def __init__(self, mapping, device):
+        m = np.asarray(mapping).astype(np.int64).ravel()
+        if m.size and (m.min() < -2 ** 31 or m.max() > 2 ** 31 - 1):
+            raise ValueError("label table: entries must fit int32")
+        self.width = max((len(str(int(v))) for v in (m.min(), m.max())), default=1) + 1 if m.size else 1
+        self.dev = torch.from_numpy(m.astype(np.int32)).to(device)
+
+
+def label_text(values, lut=None, out=None):
+    """values int64 [N] -> (text uint8 [cap], info int32 [2]), both on the device: `np.savetxt(f, lut[values], fmt='%d')` as one byte
+    string of info[0] bytes; info[1] is a status the reader of `info` checks with `label_text_check` (nothing is read back here).
+    lut: None (the values themselves, which must fit int32), a `LabelTable`, or an id array (uploaded).  cap = N x the widest line
+    (12 bytes without a table); `out`: a caller's uint8 buffer to use instead - a text that does not fit it sets the status."""
+    if not values.is_cuda:
+        raise RuntimeError(f"values: expected a tensor on the HIP device, got {values.device} (no CPU fallback)")
+    lib = _lib.load()
+    dev = values.device
+    N = values.numel()
+    if lut is not None and not isinstance(lut, LabelTable):
+        lut = LabelTable(lut, dev)
+    cap = N * (12 if lut is None else lut.width)
+    if cap > 2 ** 31 - 1:
+        raise ValueError(f"label_text: {cap} bytes of text exceed 2^31 - 1; split the values")
+    if out is None:
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = _WS.get(lib.sd3d_label_text_ws_bytes(N), dev)
+    _lib.check(lib.sd3d_label_text(_ptr(values, torch.int64, "values"), N, _ptr(lut.dev, torch.int32, "lut") if lut is not None else None,
+                                   lut.dev.numel() if lut is not None else 0, _ptr(out, torch.uint8, "out"), out.numel(), _ptr(info),
+                                   ws.data_ptr(), ws.numel(), _stream()), "label_text")
+    return out, info
+
+
+def label_text_check(info_host, what="label_text"):
+    """Raises when the status word of a `label_text` info pair (read back by the caller) is set; returns the length of the text."""
+    status = int(info_host[1])
+    if status:
+        raise RuntimeError(f"{what}: status {status}: " + "; ".join(msg for bit, msg in LABEL_TEXT_STATUS if status & bit))
+    return int(info_host[0])
