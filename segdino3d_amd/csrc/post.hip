@@ -363,6 +363,14 @@ extern "C" int sd3d_unpack_bits_host(const uint8_t* packed_host, int64_t n_rows,
 }
 
 // sem_q[q] = argmax_c sem[q, classes...]: classes = first n_cls columns (n_cls = C) or an explicit list.
+// The order of torch.argmax: a NaN is above every number, the lowest position wins among equals (and among NaNs) - so the result is
+// always a position of the list (lanes without a column carry -inf at position 0x7fffffff, which loses against any real column).
+__device__ static inline bool am_better(float v, int i, float best, int bi) {
+    const bool vn = v != v, bn = best != best;
+    if (vn != bn) return vn;
+    if (vn) return i < bi;
+    return v > best || (v == best && i < bi);
+}
 __global__ __launch_bounds__(256) void row_argmax_kernel(const float* __restrict__ x, int ld, int64_t Q, const int32_t* __restrict__ cols,
                                                          int ncols, int64_t* __restrict__ out) {
     const int lane = threadIdx.x & 63;
@@ -372,13 +380,13 @@ __global__ __launch_bounds__(256) void row_argmax_kernel(const float* __restrict
     int bi = 0x7fffffff;
     for (int c = lane; c < ncols; c += 64) {
         const float v = x[q * ld + (cols ? cols[c] : c)];
-        if (v > best || (v == best && c < bi)) { best = v; bi = c; }
+        if (am_better(v, c, best, bi)) { best = v; bi = c; }
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         const float ob = __shfl_xor(best, d);
         const int oi = __shfl_xor(bi, d);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        if (am_better(ob, oi, best, bi)) { best = ob; bi = oi; }
     }
     if (lane == 0) out[q] = bi;
 }
