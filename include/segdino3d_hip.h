@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 5
+#define SD3D_ABI_VERSION 6
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -894,6 +894,40 @@ int sd3d_mask_text(const uint8_t* masks, int64_t N, const int32_t* rows, int n_r
 size_t sd3d_label_text_ws_bytes(int64_t N);
 int sd3d_label_text(const int64_t* values, int64_t N, const int32_t* lut, int lut_len, uint8_t* out, int64_t out_cap, int32_t* info,
                     void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Semantic and panoptic evaluation (csrc/segeval.hip): what mmdet3d's `seg_eval` (fast_hist) and `panoptic_seg_eval`
+ * (EvalPanoptic.add_batch_panoptic, the SemanticKITTI protocol) count per scene, added into DEVICE-RESIDENT accumulators that persist
+ * across scenes (evaluation/evaluator_3d.py:128-163 collects the inputs, :184-196 would score them).  Both calls only enqueue work.
+ * Label arrays are int64 [n] with an element stride each (any stride >= 0: views are read in place), 0 <= n <= 0x7F000000 (n == 0
+ * does nothing), 1 <= n_classes <= SD3D_SEG_EVAL_MAX_CLASSES.  `status` is one int64 word, OR of SD3D_SEG_EVAL_*; it is only ever
+ * OR-ed into.  Integer results do not depend on the order of the points; iou_sum is added in a fixed order (same bits on every run).
+ *
+ *   sd3d_semantic_confusion: confusion [n_classes, n_classes] int64, rows = ground truth, columns = prediction.  A point counts when
+ *     its ground truth is not ignore_index and lies in [0, n_classes).  A prediction outside [0, n_classes) on such a point sets
+ *     SD3D_SEG_EVAL_BAD_PRED_CLASS and the point is skipped (no clamp, no write outside the table).
+ *   sd3d_panoptic_accumulate: tp / fp / fn [n_classes] int64, iou_sum [n_classes] double.  Instance ids are shifted by +1 (-1 = no
+ *     instance); points whose ground-truth class is one of ignore_ids_host (HOST array, at most SD3D_SEG_EVAL_MAX_IGNORE) are dropped
+ *     from both sides.  Per class that is not ignored: segments = distinct positive shifted ids among the points of that class on the
+ *     ground-truth / prediction side, area = their point count; a (gt, pred) pair of one class with 2 * inter > area_gt + area_pred -
+ *     inter is a true positive and adds inter / union (float64) to iou_sum; unmatched segments of area >= min_num_points count into
+ *     fn / fp.  A shifted id outside [0, 2^16) on a kept point sets SD3D_SEG_EVAL_BAD_INSTANCE_ID and counts as "no instance".
+ *     More than SD3D_SEG_EVAL_MAX_SEGMENTS segments on one side of one scene set SD3D_SEG_EVAL_TOO_MANY_SEGMENTS; the segments past
+ *     the capacity are left out, nothing is written outside a buffer.  ws: sd3d_seg_eval_ws_bytes(n, n_classes) bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_SEG_EVAL_BAD_PRED_CLASS 1         /* a semantic prediction outside [0, n_classes) on a counted point */
+#define SD3D_SEG_EVAL_BAD_INSTANCE_ID 2        /* a shifted instance id outside [0, 2^16) */
+#define SD3D_SEG_EVAL_TOO_MANY_SEGMENTS 4      /* more than SD3D_SEG_EVAL_MAX_SEGMENTS segments on one side of a scene */
+#define SD3D_SEG_EVAL_MAX_CLASSES 1024
+#define SD3D_SEG_EVAL_MAX_IGNORE 8
+#define SD3D_SEG_EVAL_MAX_SEGMENTS 65536
+size_t sd3d_seg_eval_ws_bytes(int64_t n, int n_classes);
+int sd3d_semantic_confusion(const int64_t* pred_sem, int64_t pred_stride, const int64_t* gt_sem, int64_t gt_stride, int64_t n,
+                            int n_classes, int64_t ignore_index, int64_t* confusion, int64_t* status, void* stream);
+int sd3d_panoptic_accumulate(const int64_t* pred_sem, int64_t pred_sem_stride, const int64_t* pred_inst, int64_t pred_inst_stride,
+                             const int64_t* gt_sem, int64_t gt_sem_stride, const int64_t* gt_inst, int64_t gt_inst_stride, int64_t n,
+                             int n_classes, const int32_t* ignore_ids_host, int n_ignore, int min_num_points, int64_t* tp, int64_t* fp,
+                             int64_t* fn, double* iou_sum, int64_t* status, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

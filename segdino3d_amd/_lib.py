@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _lib = None
 
@@ -164,6 +164,9 @@ SIGNATURES = {
     "sd3d_mask_text": (_i, [_p, _l, _p, _i, _p, _l, _p]),
     "sd3d_label_text_ws_bytes": (_z, [_l]),
     "sd3d_label_text": (_i, [_p, _l, _p, _i, _p, _l, _p, _p, _z, _p]),
+    "sd3d_seg_eval_ws_bytes": (_z, [_l, _i]),
+    "sd3d_semantic_confusion": (_i, [_p, _l, _p, _l, _l, _i, _l, _p, _p, _p]),
+    "sd3d_panoptic_accumulate": (_i, [_p, _l, _p, _l, _p, _l, _p, _l, _l, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
 }
 
 

@@ -1773,3 +1773,66 @@ def label_text_check(info_host, what="label_text"):
     if status:
         raise RuntimeError(f"{what}: status {status}: " + "; ".join(msg for bit, msg in LABEL_TEXT_STATUS if status & bit))
     return int(info_host[0])
+
+
+# --------------------------------------------------------------------------------------------
+# semantic and panoptic evaluation (csrc/segeval.hip)
+# --------------------------------------------------------------------------------------------
+SEG_EVAL_STATUS = ((1, "a semantic prediction lies outside [0, n_classes) on a counted point"),
+                   (2, "a shifted instance id lies outside [0, 2^16)"),
+                   (4, "a scene has more than 65536 segments on one side"))
+_WS_SEG = _PerThread()   # panoptic_accumulate: presence bits, segment tables and per-point keys of one scene
+
+
+def _labels1d(t: torch.Tensor, name: str):
+    """int64 [N] label array, read in place whatever its element stride -> (ptr, stride)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a tensor on the HIP device, got {t.device} (no CPU fallback)")
+    if t.dtype != torch.int64 or t.dim() != 1:
+        raise TypeError(f"{name}: expected a 1-D int64 tensor, got {t.dtype} with {t.dim()} dimensions")
+    return t.data_ptr(), (t.stride(0) if t.numel() > 1 else 1)
+
+
+def _accumulator(t: torch.Tensor, dtype, numel: int, name: str):
+    p = _ptr(t, dtype, name)
+    if t.numel() != numel:
+        raise ValueError(f"{name}: expected {numel} elements, got {t.numel()}")
+    return p
+
+
+def semantic_confusion(pred_sem, gt_sem, n_classes: int, ignore_index: int, confusion, status):
+    """confusion[gt, pred] += 1 per counted point (`sd3d_semantic_confusion`): int64 [N] labels with any element stride,
+    `confusion` int64 [C, C] and `status` int64 [1] are device accumulators that persist across calls.  Enqueues only."""
+    lib = _lib.load()
+    pp, sp = _labels1d(pred_sem, "pred_sem")
+    pg, sg = _labels1d(gt_sem, "gt_sem")
+    n = gt_sem.numel()
+    if pred_sem.numel() != n:
+        raise ValueError("semantic_confusion: pred_sem and gt_sem must have one entry per point")
+    C = int(n_classes)
+    _lib.check(lib.sd3d_semantic_confusion(pp, sp, pg, sg, n, C, int(ignore_index), _accumulator(confusion, torch.int64, C * C, "confusion"),
+                                           _accumulator(status, torch.int64, 1, "status"), _stream()), "semantic_confusion")
+
+
+def panoptic_accumulate(pred_sem, pred_inst, gt_sem, gt_inst, n_classes: int, ignore_ids, min_num_points: int, tp, fp, fn, iou_sum, status):
+    """One scene of the panoptic protocol (`sd3d_panoptic_accumulate`) added into tp / fp / fn int64 [C], iou_sum float64 [C] and
+    status int64 [1] on the device.  Labels: int64 [N] with any element stride.  Enqueues only; scratch comes from a per-stream buffer."""
+    lib = _lib.load()
+    arrs = [_labels1d(t, nm) for t, nm in ((pred_sem, "pred_sem"), (pred_inst, "pred_inst"), (gt_sem, "gt_sem"), (gt_inst, "gt_inst"))]
+    n = gt_sem.numel()
+    if any(t.numel() != n for t in (pred_sem, pred_inst, gt_inst)):
+        raise ValueError("panoptic_accumulate: the four label arrays must have one entry per point")
+    C = int(n_classes)
+    ignore_ids = [int(v) for v in ignore_ids]
+    if len(ignore_ids) > 8 or any(abs(v) >= 2 ** 31 for v in ignore_ids):
+        raise ValueError("panoptic_accumulate: at most 8 ignored classes, each an int32")
+    nb = lib.sd3d_seg_eval_ws_bytes(n, C)
+    if nb == 0:
+        raise ValueError(f"panoptic_accumulate: unsupported size (n = {n}, n_classes = {C})")
+    ws = _WS_SEG.get(nb, gt_sem.device)
+    ign = (ctypes.c_int32 * max(1, len(ignore_ids)))(*ignore_ids)
+    args = [v for pair in arrs for v in pair]
+    _lib.check(lib.sd3d_panoptic_accumulate(*args, n, C, ign, len(ignore_ids), int(min_num_points), _accumulator(tp, torch.int64, C, "tp"),
+                                            _accumulator(fp, torch.int64, C, "fp"), _accumulator(fn, torch.int64, C, "fn"),
+                                            _accumulator(iou_sum, torch.float64, C, "iou_sum"), _accumulator(status, torch.int64, 1, "status"),
+                                            ws.data_ptr(), ws.numel(), _stream()), "panoptic_accumulate")
