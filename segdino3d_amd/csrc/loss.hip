@@ -79,13 +79,13 @@ __global__ __launch_bounds__(256) void loss_cost_kernel(const CostParams p) {
     __shared__ float red[4];
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float* xrow = p.masks + (int64_t)q * p.ld_masks;
-    float n_sum = 0.f, s_sum = 0.f;
+    float l_sum = 0.f, s_sum = 0.f;
     for (int s = tid; s < p.S; s += 256) {
         const float x = xrow[s], sig = sigmoid_f(x);
         xs[s] = x; sg[s] = sig;
-        n_sum += softplus_f(x); s_sum += sig;
+        l_sum += log1pf(expf(-fabsf(x))); s_sum += sig;       // softplus(+-x) = relu(+-x) + log1p(exp(-|x|)): this half does not depend on the target
     }
-    n_sum = block_sum(n_sum, red);
+    l_sum = block_sum(l_sum, red);
     s_sum = block_sum(s_sum, red);
     // softmax statistics of the class row
     const float* crow = p.cls + (int64_t)q * p.ld_cls;
@@ -104,14 +104,15 @@ __global__ __launch_bounds__(256) void loss_cost_kernel(const CostParams p) {
             float a = 0.f, b = 0.f;
             for (int s = lane; s < p.S; s += 64) {
                 const bool t = (bits[s >> 5] >> (s & 31)) & 1u;
-                a += t ? xs[s] : 0.f;
+                a += fmaxf(t ? -xs[s] : xs[s], 0.f);
                 b += t ? sg[s] : 0.f;
             }
             a = wave_sum(a); b = wave_sum(b);
             const float T = (float)p.gt_count[g];
             c = -p.w_cls * expf(crow[p.labels[g]] - mx) / se;
-            // sum_s softplus(-x) t + softplus(x) (1 - t) = sum_s softplus(x) - sum_s x t
-            c += p.w_bce * (n_sum - a) / (float)p.S;
+            // sum_s softplus(-x) t + softplus(x) (1 - t) = sum_s log1p(exp(-|x|)) + sum_s relu(t ? -x : x): two sums of non-negative terms.
+            // (sum_s softplus(x) - sum_s x t is the same number, but for a confident, correct mask it subtracts two nearly equal sums.)
+            c += p.w_bce * (l_sum + a) / (float)p.S;
             c += p.w_dice * (1.f - (2.f * b + 1.f) / (s_sum + T + 1.f));
             if (p.centers && p.w_ctr != 0.f) {
                 float l1 = 0.f;
