@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 6
+#define SD3D_ABI_VERSION 7
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -928,6 +928,68 @@ int sd3d_panoptic_accumulate(const int64_t* pred_sem, int64_t pred_sem_stride, c
                              const int64_t* gt_sem, int64_t gt_sem_stride, const int64_t* gt_inst, int64_t gt_inst_stride, int64_t n,
                              int n_classes, const int32_t* ignore_ids_host, int n_ignore, int min_num_points, int64_t* tp, int64_t* fp,
                              int64_t* fn, double* iou_sum, int64_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ScanNet instance AP, streamed (csrc/apeval.hip): the protocol of evaluation/utils_instance_seg_3d_eval.py (`evaluate_matches`
+ * :18-209) decomposed per scene.  sd3d_ap_scene enqueues, for one scene, the association (points -> ground-truth columns,
+ * sd3d_mask_overlaps on SD3D_AP_COLS columns) and the greedy matching of every (class, overlap) pair, and leaves ENTRIES in a store
+ * that stays on the device; sd3d_ap_finish sorts the entries of all scenes and evaluates the precision / recall curve of every
+ * (class, overlap) group.  Both calls only enqueue work.  `status` is one int64 word, OR of SD3D_AP_*; it is only ever OR-ed into.
+ *
+ *   Entry = one int64 code: ((class * n_overlaps + overlap) << 33) | (sortable(fp32 score) << 1) | true, sortable() the transform of
+ *     sd3d_keys_from_f32 (ascending).  The sentinel (n_classes * n_overlaps) << 33 sorts behind every entry and is no entry.
+ *   sd3d_ap_scene:
+ *     gt_sem / gt_inst: int64 [N] with an element stride each.  id_map != NULL: the reference's `map_inst_markup` is applied first
+ *       (ids shifted down by num_stuff, negative instance ids -> -1 and their semantic id -> -1, semantic id -> id_map[id] with an
+ *       index in [-map_len, 0) counted from the back; an index outside [-map_len, map_len) reads as -1).  id_map == NULL: ids as given.
+ *     class_lut: int32 [lut_len], dataset id -> class index in [0, n_classes) or -1.  A point whose semantic id has a class and whose
+ *       instance index i lies in [0, SD3D_AP_INSTANCE_COLS) belongs to ground-truth instance i (column i; instances are processed in
+ *       ascending i, the order of the reference's `get_instances`); instance index -1 or a semantic id without a class: the void
+ *       column; semantic id 0 with a class and instance index 0: no column (the reference counts such a point nowhere).  An instance
+ *       index outside [-1, SD3D_AP_INSTANCE_COLS) sets SD3D_AP_BAD_INSTANCE and the point is void; an instance whose points carry two
+ *       classes sets SD3D_AP_MIXED_SEMANTIC (the larger class index is used).
+ *       Where this differs from the host route (`rename_gt` + `assign_scene`): only with dataset id 0 among the classes.  There an
+ *       instance whose semantic id has NO class keeps an id below 1000 and is read as a ground-truth instance of the class of id 0;
+ *       here its points are void, as with every other label set.
+ *     masks: uint8 [n, N], row pitch mask_stride, non-zero = member; 0 <= n <= SD3D_AP_MAX_PREDS.  labels: int64 [n] class INDEX,
+ *       scores: float [n].  A label outside [0, n_classes) sets SD3D_AP_BAD_LABEL, a non-finite score SD3D_AP_BAD_SCORE; such a
+ *       prediction is left out, as is (silently) one with fewer than min_region points.
+ *     overlaps: DEVICE double [n_overlaps], each in (0, 1), n_overlaps <= SD3D_AP_MAX_OVERLAPS; slots_host: HOST int32 [n_overlaps],
+ *       the entries one prediction can emit at that overlap (max(1, ceil(1 / th) - 1): IoU > th needs inter > th * |pred| and ground
+ *       truths are disjoint).  zero_class: the class index of dataset id 0, or -1.
+ *     The scene owns the slots store[slot_begin .. slot_begin + n * sum(slots_host)) and writes EVERY one of them that lies below
+ *       slot_begin + slot_cap, an entry or the sentinel: slot of entry j of prediction row r at overlap o =
+ *       n * sum(slots_host[:o]) + r * slots_host[o] + j.  What does not fit (a slot past slot_cap, more entries than slots_host[o])
+ *       is dropped and sets SD3D_AP_STORE_FULL; nothing is written outside the range.
+ *     hard_fn int64 [n_classes * n_overlaps] += ground truths of >= min_region points that no prediction matched; has_gt / has_pred
+ *       int64 [n_classes] |= 1.  Comparisons are the reference's, in float64: double(inter) / double(gt + pred - inter) > th and
+ *       double(void + intersections with ground truth below min_region) / double(pred) <= th.  ws: sd3d_ap_scene_ws_bytes(N, n).
+ *   sd3d_ap_finish: codes int64 [n_slots] (clobbered: sorted in place or into the workspace).  ap double [n_classes * n_overlaps],
+ *     pr_rc double [2 * n_classes * n_overlaps] (precision, then recall, at the FIRST maximum of f1 = 2 p r / (p + r + 0.0001)).  A class
+ *     with ground truth and predictions: the curve over the distinct scores plus the closing point (1, 0), AP = sum prec[i] *
+ *     (0.5 r[i-1] - 0.5 r[i+1]) with r[-1] = r[0] and a trailing 0, summed per thread in ascending i and over threads in a fixed tree;
+ *     ground truth only: 0, 0, 0; otherwise NaN.  ws: sd3d_ap_finish_ws_bytes(n_slots).
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_AP_BAD_INSTANCE 1           /* an instance index outside [-1, SD3D_AP_INSTANCE_COLS) */
+#define SD3D_AP_MIXED_SEMANTIC 2         /* one ground-truth instance over two classes */
+#define SD3D_AP_BAD_LABEL 4              /* a prediction label outside [0, n_classes) */
+#define SD3D_AP_BAD_SCORE 8              /* a non-finite prediction score */
+#define SD3D_AP_STORE_FULL 16            /* more entries than the store (or a prediction's slots) holds */
+#define SD3D_AP_INSTANCE_COLS 1000
+#define SD3D_AP_COLS 1002                /* instances, void, "counted nowhere" */
+#define SD3D_AP_MAX_CLASSES 1024
+#define SD3D_AP_MAX_OVERLAPS 16
+#define SD3D_AP_MAX_PREDS 4096
+size_t sd3d_ap_scene_ws_bytes(int64_t N, int n);
+int sd3d_ap_scene(const int64_t* gt_sem, int64_t sem_stride, const int64_t* gt_inst, int64_t inst_stride, int64_t N,
+                  const int64_t* id_map, int map_len, int num_stuff, const uint8_t* masks, int64_t mask_stride, int n,
+                  const int64_t* labels, const float* scores, const int32_t* class_lut, int lut_len, int zero_class, int n_classes,
+                  const double* overlaps, const int32_t* slots_host, int n_overlaps, int min_region, int64_t* store,
+                  int64_t slot_begin, int64_t slot_cap, int64_t* hard_fn, int64_t* has_gt, int64_t* has_pred, int64_t* status, void* ws,
+                  size_t ws_bytes, void* stream);
+size_t sd3d_ap_finish_ws_bytes(int64_t n_slots);
+int sd3d_ap_finish(int64_t* codes, int64_t n_slots, int n_classes, int n_overlaps, const int64_t* hard_fn, const int64_t* has_gt,
+                   const int64_t* has_pred, double* ap, double* pr_rc, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,9 @@ same argument meaning, same result dictionaries - but
     label, vert_count, void_intersection, confidence; per ground truth: label, instance id, vert_count; per
     intersecting pair: prediction, ground truth, intersection) - the payload of the per-rank all-gather in
     `dist_eval` - and `evaluate_records` computes AP from those rows on the host (greedy matching in the
-    reference's order; there is nothing to parallelise in it and it is O(records));
+    reference's order, O(records), one core).  The `visited` flags of that matching never cross a (scene, label,
+    overlap) triple, so the triples are independent: `ApAccumulator` (below) matches them on the device, scene by
+    scene, and scores the sorted entries there; this host route stays as the cross-check;
   * `to_reference_dicts` rebuilds the reference's `gt2pred / pred2gt` dictionaries from a record, for callers
     that keep the reference's own `evaluate_matches`.
 
@@ -394,3 +396,260 @@ def eval_ann_info(target, bg_class_id: int) -> dict:
     sem = torch.where(covered, sem, torch.full_like(sem, int(bg_class_id)))
     return dict(pts_instance_mask=inst, pts_semantic_mask=sem, sp_pts_mask=target["extra_features"]["super_point_masks"],
                 lidar_idx=target["scene_id"])
+
+
+class ApAccumulator:
+    """ScanNet instance AP over any number of scenes with everything but the final dictionary arithmetic on the device.
+
+    `add` / `add_scene` only enqueue kernels (`ops.ap_scene`: association, greedy matching per (class, overlap), the scene's
+    ENTRIES `(class, overlap, score, true)` into a device-resident store, hard false negatives and the has_gt / has_pred flags
+    into device counters) - no device-to-host copy, no synchronisation, no torch op that hides one - so `add` can be the
+    `on_result` consumer of a `dist_eval.PipelinedRunner`.  `tables()` is the one read-back: the entries of all scenes are sorted
+    by (class, overlap, score) and every group's precision / recall curve is evaluated on the device (`ops.ap_finish`); what
+    comes back is `ap [1, C, O]` and `pr_rc [2, C, O]` as `evaluate_records` returns them, and `result()` hands them to
+    `compute_averages`.
+
+    `valid_class_ids` / `class_labels` are the thing classes, as `instance_seg_eval` takes them.  `add(eval_ann, pred)` applies
+    `map_inst_markup(.., valid_class_ids, num_stuff_cls)` inside the kernel; `add_scene` takes ids that are already mapped.
+    Ground truth needs no ranking step: after `map_inst_markup` the instance index itself identifies the instance (the host
+    route forms `1000 * semantic id + index` in `rename_gt`), so a point's column is its instance index when its semantic id is
+    a valid class and the void column otherwise (also for index -1).  What the host route asserts is reported through a status
+    word instead (`ops.AP_STATUS`); `tables()` raises when it is set.
+    One known difference from the host route, only when dataset id 0 is a valid class: there `rename_gt` leaves an instance whose
+    semantic id is NOT valid with an id below 1000, which `assign_scene` then reads as a ground-truth instance of class 0; here
+    such points are void, as for every other label set.  (With id 0 not valid - ScanNet, ScanNet200 - both routes agree.)
+    The score of an entry is kept as 32 bits of the sort key: scores are fp32 (fp16 / bf16 are widened, which is exact); float64
+    scores raise and belong to the host route (`instance_seg_eval`).  At most `ops.AP_MAX_PREDS` predictions per scene.
+    One accumulator belongs to one stream; several streams get one each and `merge` their `state()`s.
+
+    State (`state()`, float64 [R, STATE_WIDTH], the payload of `dist_eval.all_gather_records`): every row names its kind in
+    column 0 - 1: counters (column 1 = chunk index, then hard_fn [C, O], has_gt [C], has_pred [C] in chunks), 2: entry codes
+    (integers below 2^53, -1 = no entry), 3: the status word - so rows of any number of states can be concatenated in any order."""
+
+    STATE_WIDTH = 1024
+    STORE_CHUNK = 1 << 16                 # slots the store grows by at least
+    max_slots: Optional[int] = None       # a cap on the store in slots (None: it grows as needed); scenes past it set the status word
+
+    def __init__(self, valid_class_ids, class_labels, options: Optional[dict] = None, num_stuff_cls: int = 0, groups=None, device=None):
+        self.valid_class_ids = tuple(int(v) for v in valid_class_ids)
+        self.class_labels = tuple(class_labels)
+        if len(self.valid_class_ids) != len(self.class_labels):
+            raise ValueError("valid_class_ids and class_labels must have one entry per class")
+        C = len(self.valid_class_ids)
+        if not 1 <= C <= 1024 or min(self.valid_class_ids) < 0 or len(set(self.valid_class_ids)) != C:
+            raise ValueError("valid_class_ids: 1..1024 distinct ids >= 0")
+        self.options = get_options(options)
+        overlaps = np.ascontiguousarray(self.options["overlaps"], dtype=np.float64).reshape(-1)
+        if not 1 <= len(overlaps) <= 16:
+            raise ValueError("options['overlaps']: 1..16 thresholds")
+        if not np.all((overlaps > 0.0) & (overlaps < 1.0)):
+            raise ValueError("options['overlaps']: every threshold must lie in (0, 1)")
+        self.n_classes, self.n_overlaps = C, len(overlaps)
+        self.min_region = int(self.options["min_region_sizes"][0])
+        self.num_stuff_cls = int(num_stuff_cls)
+        self.groups = groups
+        self.slots = ops.ap_slots_per_prediction(overlaps)
+        self.slots_per_pred = int(sum(self.slots))
+        self.zero_class = self.valid_class_ids.index(0) if 0 in self.valid_class_ids else -1
+        # constants staged once on the host; they go to the device with the first buffers
+        lut = np.full(max(self.valid_class_ids) + 1, -1, dtype=np.int32)
+        lut[list(self.valid_class_ids)] = np.arange(C, dtype=np.int32)
+        self._host = dict(lut=torch.from_numpy(lut), overlaps=torch.from_numpy(overlaps.copy()),     # the float64 bits of the options
+                          id_map=torch.tensor(list(self.valid_class_ids) + [-1], dtype=torch.int64))
+        self.device = torch.device(device) if device is not None else None
+        self._const = None
+        self._counters = None
+        self._store = None
+        self.used = 0
+        if self.device is not None and self.device.type == "cuda":
+            self._buffers(self.device)
+
+    # ---- layout
+    @property
+    def sentinel(self) -> int:
+        return (self.n_classes * self.n_overlaps) << 33
+
+    @property
+    def n_counters(self) -> int:
+        return self.n_classes * self.n_overlaps + 2 * self.n_classes
+
+    def _views(self, buf):
+        C, O = self.n_classes, self.n_overlaps
+        return dict(hard_fn=buf[:C * O], has_gt=buf[C * O:C * O + C], has_pred=buf[C * O + C:C * O + 2 * C], status=buf[C * O + 2 * C:])
+
+    def _buffers(self, device):
+        if self._counters is None:
+            if self.device is None:
+                self.device = device
+            self._const = {k: (v.pin_memory() if torch.cuda.is_available() else v).to(self.device, non_blocking=True)
+                           for k, v in self._host.items()}
+            self._counters = torch.zeros(self.n_counters + 1, dtype=torch.int64, device=self.device)
+            self._store = torch.empty(0, dtype=torch.int64, device=self.device)
+        if device != self._counters.device:
+            raise RuntimeError(f"ApAccumulator: the accumulators live on {self._counters.device}, the scene on {device}")
+        return self._views(self._counters)
+
+    def _reserve(self, need: int) -> int:
+        """Slots of the next scene: grows the store in chunks on the host (a device copy, no read-back); returns how many of the
+        `need` slots the store can hold (all of them unless `max_slots` says otherwise)."""
+        room = need if self.max_slots is None else max(0, min(need, self.max_slots - self.used))
+        if self.used + room > self._store.numel():
+            cap = max(2 * self._store.numel(), self.used + room, self.STORE_CHUNK)
+            if self.max_slots is not None:
+                cap = min(cap, self.max_slots)
+            grown = torch.empty(cap, dtype=torch.int64, device=self.device)
+            grown[:self.used].copy_(self._store[:self.used])
+            self._store = grown
+        return room
+
+    # ---- accumulation
+    @staticmethod
+    def _on_device(t, name):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            where = t.device if torch.is_tensor(t) else type(t).__name__
+            raise RuntimeError(f"ApAccumulator: {name}: expected a tensor on the HIP device, got {where} (no CPU fallback)")
+        return t
+
+    def add(self, eval_ann, pred) -> None:
+        """One scene as the evaluator collects it: `eval_ann` = dict(pts_semantic_mask, pts_instance_mask) before
+        `map_inst_markup`, `pred` the model's `PointData` (or its dict)."""
+        if not isinstance(pred, dict):
+            pred = dict(pred.items())
+        self._add(eval_ann["pts_semantic_mask"], eval_ann["pts_instance_mask"], pred["pts_instance_mask"][0], pred["instance_labels"],
+                  pred["instance_scores"], mapped=False)
+
+    def add_scene(self, gt_sem, gt_inst, masks, labels, scores) -> None:
+        """One scene with ids that went through `map_inst_markup` already - the per-scene arguments of `instance_seg_eval`."""
+        self._add(gt_sem, gt_inst, masks, labels, scores, mapped=True)
+
+    def _add(self, gt_sem, gt_inst, masks, labels, scores, mapped: bool) -> None:
+        gt_sem, gt_inst = self._on_device(gt_sem, "gt_sem"), self._on_device(gt_inst, "gt_inst")
+        masks, labels, scores = self._on_device(masks, "masks"), self._on_device(labels, "labels"), self._on_device(scores, "scores")
+        as_ids = lambda t: (t if t.dim() == 1 else t.reshape(-1)).long()              # noqa: E731  (.long() of int64 is the tensor itself)
+        gt_sem, gt_inst = as_ids(gt_sem), as_ids(gt_inst)
+        m8 = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        if m8.dtype != torch.uint8 or m8.dim() != 2 or (m8.shape[1] > 1 and m8.stride(1) != 1):
+            raise TypeError("ApAccumulator: masks must be bool / uint8 [n, N] with contiguous rows")
+        if scores.dtype == torch.float64:
+            raise TypeError("ApAccumulator: float64 scores: the sort key holds the 32 bits of an fp32 score; use the host route "
+                            "(eval_ap.instance_seg_eval) for float64 scores")
+        if scores.dtype in (torch.float16, torch.bfloat16):
+            scores = scores.float()                                                  # exact
+        if scores.dtype != torch.float32:
+            raise TypeError(f"ApAccumulator: scores must be fp32 (fp16 / bf16 are widened), got {scores.dtype}")
+        if labels.is_floating_point() or labels.dtype == torch.bool:
+            raise TypeError(f"ApAccumulator: labels must be integer class indices, got {labels.dtype}")
+        labels, scores = labels.detach().reshape(-1).long().contiguous(), scores.detach().reshape(-1).contiguous()
+        v = self._buffers(gt_sem.device)
+        n = m8.shape[0]
+        need = n * self.slots_per_pred
+        room = self._reserve(need)
+        ops.ap_scene(gt_sem, gt_inst, m8, labels, scores, self._const["lut"], self.zero_class, self.n_classes, self._const["overlaps"],
+                     self.slots, self.min_region, self._store, self.used, room, v["hard_fn"], v["has_gt"], v["has_pred"], v["status"],
+                     id_map=None if mapped else self._const["id_map"], num_stuff=0 if mapped else self.num_stuff_cls)
+        self.used += room
+
+    # ---- state
+    def state(self) -> torch.Tensor:
+        W = self.STATE_WIDTH
+        if self._counters is None:                                                    # no scene yet: nothing lives on a device
+            dev = self.device if self.device is not None else torch.device("cpu")
+            counters = torch.zeros(self.n_counters, dtype=torch.float64, device=dev)
+            status = torch.zeros(1, dtype=torch.float64, device=dev)
+            codes = torch.zeros(0, dtype=torch.float64, device=dev)
+        else:
+            dev = self._counters.device
+            counters, status = self._counters[:-1].double(), self._counters[-1:].double()
+            codes = self._store[:self.used].double()
+        crow = self._rows(counters, W - 2, 0.0)
+        crow = torch.cat([self._kind(1, crow), torch.arange(crow.shape[0], dtype=torch.float64, device=dev)[:, None], crow], dim=1)
+        srow = self._rows(status, W - 1, 0.0)
+        erow = self._rows(codes, W - 1, -1.0)
+        return torch.cat([torch.cat([self._kind(3, srow), srow], dim=1), crow, torch.cat([self._kind(2, erow), erow], dim=1)], dim=0)
+
+    @staticmethod
+    def _rows(values, width: int, fill: float):
+        """`values` as rows of `width`, the last one filled up with `fill`."""
+        tail = torch.full(((-values.numel()) % width,), fill, dtype=torch.float64, device=values.device)
+        return torch.cat([values, tail]).reshape(-1, width)
+
+    @staticmethod
+    def _kind(kind: int, rows):
+        """The kind column in front of `rows`."""
+        return torch.full((rows.shape[0], 1), float(kind), dtype=torch.float64, device=rows.device)
+
+    @staticmethod
+    def merge(states) -> torch.Tensor:
+        """One state from several ([R, W] each, or the per-rank tensors `all_gather_records` returns): entries concatenated,
+        counters summed, status words OR-ed."""
+        states = [s for s in states if s.numel() > 0]
+        dev = next((s.device for s in states if s.is_cuda), states[0].device)      # an accumulator that saw no scene keeps its state on the host
+        rows = torch.cat([s.reshape(-1, s.shape[-1]).to(dev) for s in states])
+        W = rows.shape[1]
+        kind = rows[:, 0]
+        status = 0
+        for s in rows[kind == 3][:, 1].tolist():
+            status |= int(s)
+        srow = torch.zeros(1, W, dtype=rows.dtype, device=rows.device)
+        srow[0, 0], srow[0, 1] = 3.0, float(status)
+        c = rows[kind == 1]
+        idx = c[:, 1].long()
+        n_chunks = int(idx.max()) + 1 if idx.numel() else 0
+        crow = torch.zeros(n_chunks, W, dtype=rows.dtype, device=rows.device)
+        crow[:, 2:].index_add_(0, idx, c[:, 2:])
+        crow[:, 0] = 1.0
+        crow[:, 1] = torch.arange(n_chunks, dtype=rows.dtype, device=rows.device)
+        return torch.cat([srow, crow, rows[kind == 2]], dim=0)
+
+    def _parse(self, state):
+        """(codes int64 [n] with the sentinel where there is no entry, counters int64 [C O + 2 C], status) on the state's device."""
+        s = self.state() if state is None else state
+        if s.dim() != 2 or s.shape[1] != self.STATE_WIDTH:
+            raise ValueError(f"state: expected [R, {self.STATE_WIDTH}], got {tuple(s.shape)}")
+        s = self.merge([s])                                                            # any row order, any number of states
+        kind = s[:, 0]
+        status = int(s[0, 1])
+        counters = s[kind == 1][:, 2:].reshape(-1)
+        if counters.numel() < self.n_counters:
+            raise ValueError("state: the counter rows do not belong to an accumulator of this shape")
+        counters = counters[:self.n_counters].round().long()
+        codes = s[kind == 2][:, 1:].reshape(-1)
+        codes = torch.where(codes < 0, torch.full_like(codes, float(self.sentinel)), codes).long()
+        return codes, counters, status
+
+    def _raise_on(self, status: int):
+        if status:
+            raise RuntimeError(f"ApAccumulator: status {status}: " + "; ".join(msg for bit, msg in ops.AP_STATUS if status & bit))
+
+    def tables(self, state: Optional[torch.Tensor] = None):
+        """The read-back: `(ap [1, C, O], pr_rc [2, C, O])` as `evaluate_records` returns them, from this accumulator or a merged
+        state; raises when the status word is set and names the bits."""
+        C, O = self.n_classes, self.n_overlaps
+        codes, counters, status = self._parse(state)
+        self._raise_on(status)
+        dev = self.device if self.device is not None and self.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+        codes, counters = codes.to(dev).contiguous(), counters.to(dev)
+        ap, pr_rc = ops.ap_finish(codes, C, O, counters[:C * O].contiguous(), (counters[C * O:C * O + C] > 0).long(),
+                                  (counters[C * O + C:] > 0).long())
+        out = torch.cat([ap[None], pr_rc]).cpu().numpy()
+        return out[:1].reshape(1, C, O).copy(), out[1:].reshape(2, C, O).copy()
+
+    def result(self, state: Optional[torch.Tensor] = None) -> dict:
+        """The metrics dictionary of `instance_seg_eval` (`compute_averages` on the tables)."""
+        ap, pr_rc = self.tables(state)
+        return compute_averages(ap, pr_rc, self.options, self.class_labels, self.groups)
+
+    def entries(self, state: Optional[torch.Tensor] = None) -> dict:
+        """Read-back for tests and debugging: the entries sorted by (group, score, true) - `group` = class * O + overlap, `score`
+        float32, `true` 0 / 1 - with hard_fn [C, O], has_gt [C], has_pred [C] and the status word (no raise)."""
+        C, O = self.n_classes, self.n_overlaps
+        codes, counters, status = self._parse(state)
+        codes, counters = codes.cpu().numpy(), counters.cpu().numpy()
+        codes = codes[(codes >> 33) < C * O]
+        key = ((codes >> 1) & 0xFFFFFFFF).astype(np.uint32)
+        bits = np.where(key & np.uint32(0x80000000), key ^ np.uint32(0x80000000), ~key)
+        score = bits.astype(np.uint32).view(np.float32)
+        group, true = (codes >> 33).astype(np.int64), (codes & 1).astype(np.int64)
+        order = np.lexsort((true, score, group))
+        return dict(group=group[order], score=score[order], true=true[order], hard_fn=counters[:C * O].reshape(C, O).copy(),
+                    has_gt=counters[C * O:C * O + C] > 0, has_pred=counters[C * O + C:] > 0, status=status)

@@ -1836,3 +1836,86 @@ def panoptic_accumulate(pred_sem, pred_inst, gt_sem, gt_inst, n_classes: int, ig
                                             _accumulator(fp, torch.int64, C, "fp"), _accumulator(fn, torch.int64, C, "fn"),
                                             _accumulator(iou_sum, torch.float64, C, "iou_sum"), _accumulator(status, torch.int64, 1, "status"),
                                             ws.data_ptr(), ws.numel(), _stream()), "panoptic_accumulate")
+
+
+# --------------------------------------------------------------------------------------------
+# streamed ScanNet instance AP (csrc/apeval.hip)
+# --------------------------------------------------------------------------------------------
+AP_STATUS = ((1, "a ground-truth instance index lies outside [-1, 1000)"),
+             (2, "a ground-truth instance spans two semantic classes"),
+             (4, "a prediction label lies outside [0, n_classes)"),
+             (8, "a prediction score is not finite"),
+             (16, "the entry store is too small for the scenes it was given"))
+AP_MAX_PREDS = 4096
+_WS_AP = _PerThread()    # ap_scene: columns, count matrix and per-class lists of one scene
+_WS_AP_FIN = _PerThread()   # ap_finish: sort buffers and the curve points
+
+
+def ap_slots_per_prediction(overlaps) -> list:
+    """Entries one prediction can emit at each overlap: IoU > th needs inter > th * |pred| and ground truths are disjoint, so at
+    most ceil(1 / th) - 1 of them can pass (3 at 0.25, 1 from 0.5 up); a prediction that passes none emits at most one false positive."""
+    return [max(1, int(np.ceil(1.0 / float(th))) - 1) for th in overlaps]
+
+
+def ap_scene(gt_sem, gt_inst, masks, labels, scores, class_lut, zero_class: int, n_classes: int, overlaps, slots, min_region: int, store,
+             slot_begin: int, slot_cap: int, hard_fn, has_gt, has_pred, status, id_map=None, num_stuff: int = 0):
+    """One scene of the streamed AP protocol (`sd3d_ap_scene`): association, greedy matching per (class, overlap) and the scene's
+    entries written into its slots `store[slot_begin : slot_begin + n * sum(slots)]` (those below `slot_begin + slot_cap`).
+    gt_sem / gt_inst int64 [N] (any element stride), masks uint8 [n, N] with contiguous rows (any pitch), labels int64 [n],
+    scores fp32 [n], class_lut int32 [lut_len], overlaps float64 [O] on the device, slots the host list of
+    `ap_slots_per_prediction`; hard_fn int64 [C * O], has_gt / has_pred int64 [C] and status int64 [1] persist across calls.
+    Enqueues only; scratch comes from a per-stream buffer."""
+    lib = _lib.load()
+    ps, ss = _labels1d(gt_sem, "gt_sem")
+    pi, si = _labels1d(gt_inst, "gt_inst")
+    N = gt_sem.numel()
+    if gt_inst.numel() != N:
+        raise ValueError("ap_scene: gt_sem and gt_inst must have one entry per point")
+    if not masks.is_cuda:
+        raise RuntimeError(f"masks: expected a tensor on the HIP device, got {masks.device} (no CPU fallback)")
+    if masks.dtype != torch.uint8 or masks.dim() != 2 or (masks.shape[1] > 1 and masks.stride(1) != 1):
+        raise TypeError("masks: expected uint8 [n, N] with contiguous rows")
+    n = masks.shape[0]
+    if masks.shape[1] != N:
+        raise ValueError("ap_scene: masks must have one column per point")
+    if n > AP_MAX_PREDS:
+        raise ValueError(f"ap_scene: at most {AP_MAX_PREDS} predictions per scene, got {n}")
+    if labels.numel() != n or scores.numel() != n:
+        raise ValueError("ap_scene: labels and scores must have one entry per prediction")
+    C, O = int(n_classes), overlaps.numel()
+    slots = [int(k) for k in slots]
+    if len(slots) != O:
+        raise ValueError("ap_scene: one slot count per overlap")
+    nb = lib.sd3d_ap_scene_ws_bytes(N, n)
+    if nb == 0:
+        raise ValueError(f"ap_scene: unsupported size (N = {N}, n = {n})")
+    ws = _WS_AP.get(nb, gt_sem.device)
+    slots_c = (ctypes.c_int32 * O)(*slots)
+    pitch = masks.stride(0) if n > 1 else max(N, 1)
+    _lib.check(lib.sd3d_ap_scene(ps, ss, pi, si, N, _ptr(id_map, torch.int64, "id_map"), id_map.numel() if id_map is not None else 0,
+                                 int(num_stuff), masks.data_ptr() if n else None, pitch, n, _ptr(labels, torch.int64, "labels") if n else None,
+                                 _ptr(scores, torch.float32, "scores") if n else None, _ptr(class_lut, torch.int32, "class_lut"),
+                                 class_lut.numel(), int(zero_class), C, _ptr(overlaps, torch.float64, "overlaps"), slots_c, O, int(min_region),
+                                 _ptr(store, torch.int64, "store"), int(slot_begin), int(slot_cap),
+                                 _accumulator(hard_fn, torch.int64, C * O, "hard_fn"), _accumulator(has_gt, torch.int64, C, "has_gt"),
+                                 _accumulator(has_pred, torch.int64, C, "has_pred"), _accumulator(status, torch.int64, 1, "status"),
+                                 ws.data_ptr(), ws.numel(), _stream()), "ap_scene")
+
+
+def ap_finish(codes, n_classes: int, n_overlaps: int, hard_fn, has_gt, has_pred):
+    """AP [C * O] and best-F1 precision / recall [2, C * O] (float64, on the device) from the entry codes of all scenes
+    (`sd3d_ap_finish`; `codes` int64 is clobbered) and the counters.  Enqueues only."""
+    lib = _lib.load()
+    C, O = int(n_classes), int(n_overlaps)
+    dev = hard_fn.device
+    n = codes.numel()
+    ap = torch.empty(C * O, dtype=torch.float64, device=dev)
+    pr_rc = torch.empty(2, C * O, dtype=torch.float64, device=dev)
+    nb = lib.sd3d_ap_finish_ws_bytes(n)
+    if nb == 0:
+        raise ValueError(f"ap_finish: unsupported size (n_slots = {n})")
+    ws = _WS_AP_FIN.get(nb, dev)
+    _lib.check(lib.sd3d_ap_finish(_ptr(codes, torch.int64, "codes") if n else None, n, C, O, _accumulator(hard_fn, torch.int64, C * O, "hard_fn"),
+                                  _accumulator(has_gt, torch.int64, C, "has_gt"), _accumulator(has_pred, torch.int64, C, "has_pred"),
+                                  _ptr(ap), _ptr(pr_rc), ws.data_ptr(), ws.numel(), _stream()), "ap_finish")
+    return ap, pr_rc
