@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 7
+#define SD3D_ABI_VERSION 8
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -990,6 +990,30 @@ int sd3d_ap_scene(const int64_t* gt_sem, int64_t sem_stride, const int64_t* gt_i
 size_t sd3d_ap_finish_ws_bytes(int64_t n_slots);
 int sd3d_ap_finish(int64_t* codes, int64_t n_slots, int n_classes, int n_overlaps, const int64_t* hard_fn, const int64_t* has_gt,
                    const int64_t* has_pred, double* ap, double* pr_rc, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ScanNet instance AP per scene (csrc/apeval_scene.hip): `compute_each_sample_metrics` (evaluation/evaluator_3d.py:227-321), which
+ * scores one scene at a time.  The caller gives every scene its own counter row to sd3d_ap_scene: counters int64
+ * [n_scenes, n_classes * n_overlaps + 2 * n_classes], a row = hard_fn [C, O], has_gt [C], has_pred [C].  Both calls only enqueue work.
+ *   sd3d_ap_finish_scenes: codes int64 [n_slots], the store as sd3d_ap_scene left it (READ only; a group above the sentinel's reads as
+ *     the sentinel).  slot_offsets: DEVICE int64 [n_scenes + 1], ascending from 0 to n_slots: scene s owns the slots
+ *     [slot_offsets[s], slot_offsets[s + 1]); empty scenes are allowed.  Every slot gets the key
+ *     (s * (C O + 1) + group) << 33 | low 33 bits of its code in the workspace, the keys are sorted, and every (scene, class, overlap)
+ *     segment is scored by the curve body of sd3d_ap_finish with the scene's counters: a class without ground truth in THAT scene is
+ *     NaN, with ground truth but no prediction in that scene 0.  n_scenes * (C O + 1) must stay below 2^30 (SD3D_ERR_ARG otherwise,
+ *     nothing is launched).  ap double [n_scenes, C, O], pr_rc double [2, n_scenes, C, O], summary double [n_scenes, 5]: the means of
+ *     `compute_averages` over the scene's finite cells, NaN without one - all_ap (overlaps whose bit is NOT set in mask25), all_ap_50%
+ *     (bits of mask50), all_ap_25% (bits of mask25), all_prec_50%, all_rec_50% (mask50); bit o of a mask = overlap o.  Each mean is
+ *     summed per lane over cells lane, lane + 64, .. in class-major order and over the 64 lanes in a fixed butterfly, in float64.
+ *     ws: sd3d_ap_finish_scenes_ws_bytes(n_slots).
+ *   sd3d_ap_reduce_counters: out int64 [C O + 2 C] = the rows of counters reduced in integers, hard_fn added, has_gt / has_pred 0 / 1
+ *     (OR): the counters sd3d_ap_scene leaves when all scenes share one row.  n_scenes == 0 gives zeros.
+ * ------------------------------------------------------------------------------------------- */
+size_t sd3d_ap_finish_scenes_ws_bytes(int64_t n_slots);
+int sd3d_ap_finish_scenes(const int64_t* codes, int64_t n_slots, const int64_t* slot_offsets, int n_scenes, int n_classes, int n_overlaps,
+                          const int64_t* counters, int mask50, int mask25, double* ap, double* pr_rc, double* summary, void* ws,
+                          size_t ws_bytes, void* stream);
+int sd3d_ap_reduce_counters(const int64_t* counters, int n_scenes, int n_classes, int n_overlaps, int64_t* out, void* stream);
 
 #ifdef __cplusplus
 }

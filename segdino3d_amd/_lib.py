@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _lib = None
 
@@ -172,6 +172,9 @@ SIGNATURES = {
                            _z, _p]),
     "sd3d_ap_finish_ws_bytes": (_z, [_l]),
     "sd3d_ap_finish": (_i, [_p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "sd3d_ap_finish_scenes_ws_bytes": (_z, [_l]),
+    "sd3d_ap_finish_scenes": (_i, [_p, _l, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "sd3d_ap_reduce_counters": (_i, [_p, _i, _i, _i, _p, _p]),
 }
 
 

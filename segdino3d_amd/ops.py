@@ -1919,3 +1919,70 @@ def ap_finish(codes, n_classes: int, n_overlaps: int, hard_fn, has_gt, has_pred)
                                   _accumulator(has_gt, torch.int64, C, "has_gt"), _accumulator(has_pred, torch.int64, C, "has_pred"),
                                   _ptr(ap), _ptr(pr_rc), ws.data_ptr(), ws.numel(), _stream()), "ap_finish")
     return ap, pr_rc
+
+
+# --------------------------------------------------------------------------------------------
+# ScanNet instance AP per scene (csrc/apeval_scene.hip)
+# --------------------------------------------------------------------------------------------
+AP_SCENE_KEY_LIMIT = 1 << 30    # scenes * (classes * overlaps + 1) must stay below this: the scene prefix shares a 63-bit sort key
+_WS_AP_SCN = _PerThread()       # ap_finish_scenes: composite keys, sort buffers and the curve points
+
+
+def ap_finish_scenes(codes, slot_offsets, n_classes: int, n_overlaps: int, counters, mask50: int, mask25: int):
+    """Per-scene AP [S, C, O], best-F1 precision / recall [2, S, C, O] and the five means of `compute_averages` [S, 5] (float64, on
+    the device) from the store's entry codes (`sd3d_ap_finish_scenes`; `codes` int64 is only read), the host list `slot_offsets`
+    [S + 1] (scene s owns the slots [off[s], off[s + 1]); a device int64 tensor is taken as it is) and the per-scene counters int64
+    [S, C * O + 2 * C].  mask50 / mask25: bit o set = overlap o belongs to the 0.5 / 0.25 set.  Enqueues only."""
+    lib = _lib.load()
+    C, O = int(n_classes), int(n_overlaps)
+    for t, name in ((codes, "codes"), (counters, "counters")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: expected a tensor on the HIP device, got {t.device} (no CPU fallback)")
+    if counters.dim() != 2:
+        raise ValueError("ap_finish_scenes: counters must be [S, C * O + 2 * C]")
+    S, n = counters.shape[0], codes.numel()
+    if S < 1:
+        raise ValueError("ap_finish_scenes: at least one scene")
+    if S * (C * O + 1) >= AP_SCENE_KEY_LIMIT:
+        raise ValueError(f"ap_finish_scenes: scenes * (classes * overlaps + 1) = {S * (C * O + 1)} must stay below 2^30 (the sort key)")
+    dev = counters.device
+    if torch.is_tensor(slot_offsets):
+        off = slot_offsets
+    else:
+        host = np.ascontiguousarray(slot_offsets, dtype=np.int64).reshape(-1)
+        if len(host) != S + 1 or host[0] != 0 or host[-1] != n or np.any(np.diff(host) < 0):
+            raise ValueError("ap_finish_scenes: slot_offsets must ascend from 0 to the number of slots, one more than there are scenes")
+        off = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+    if off.numel() != S + 1:
+        raise ValueError("ap_finish_scenes: one slot offset more than there are scenes")
+    ap = torch.empty(S, C, O, dtype=torch.float64, device=dev)
+    pr_rc = torch.empty(2, S, C, O, dtype=torch.float64, device=dev)
+    summary = torch.empty(S, 5, dtype=torch.float64, device=dev)
+    nb = lib.sd3d_ap_finish_scenes_ws_bytes(n)
+    if nb == 0:
+        raise ValueError(f"ap_finish_scenes: unsupported size (n_slots = {n})")
+    ws = _WS_AP_SCN.get(nb, dev)
+    _lib.check(lib.sd3d_ap_finish_scenes(_ptr(codes, torch.int64, "codes") if n else None, n, _ptr(off, torch.int64, "slot_offsets"), S, C, O,
+                                         _accumulator(counters, torch.int64, S * (C * O + 2 * C), "counters"), int(mask50), int(mask25),
+                                         _ptr(ap), _ptr(pr_rc), _ptr(summary), ws.data_ptr(), ws.numel(), _stream()), "ap_finish_scenes")
+    return ap, pr_rc, summary
+
+
+def ap_reduce_counters(counters, n_classes: int, n_overlaps: int):
+    """Per-scene counters int64 [S, C * O + 2 * C] reduced to the [C * O + 2 * C] an `ApAccumulator` fed the same scenes holds
+    (`sd3d_ap_reduce_counters`: hard_fn added, has_gt / has_pred OR-ed, integers only).  S = 0 gives zeros.  Enqueues only."""
+    lib = _lib.load()
+    C, O = int(n_classes), int(n_overlaps)
+    n = C * O + 2 * C
+    if counters.dim() != 2 or counters.shape[1] != n:
+        raise ValueError(f"ap_reduce_counters: counters must be [S, {n}]")
+    S = counters.shape[0]
+    if S:
+        p = _accumulator(counters, torch.int64, S * n, "counters")
+    elif not counters.is_cuda:
+        raise RuntimeError(f"counters: expected a tensor on the HIP device, got {counters.device} (no CPU fallback)")
+    else:
+        p = None
+    out = torch.empty(n, dtype=torch.int64, device=counters.device)
+    _lib.check(lib.sd3d_ap_reduce_counters(p, S, C, O, _ptr(out), _stream()), "ap_reduce_counters")
+    return out
