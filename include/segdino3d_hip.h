@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 8
+#define SD3D_ABI_VERSION 9
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1014,6 +1014,53 @@ int sd3d_ap_finish_scenes(const int64_t* codes, int64_t n_slots, const int64_t* 
                           const int64_t* counters, int mask50, int mask25, double* ap, double* pr_rc, double* summary, void* ws,
                           size_t ws_bytes, void* stream);
 int sd3d_ap_reduce_counters(const int64_t* counters, int n_scenes, int n_classes, int n_overlaps, int64_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * 3D box AP / AR, streamed (csrc/boxeval.hip): the VOC-style indoor detection protocol for axis-aligned boxes, per class c and IoU
+ * threshold t.  All three calls only enqueue work; `status` is the int64 word of sd3d_ap_scene (OR of SD3D_AP_* and SD3D_BOX_*).
+ *
+ *   Protocol.  Ground truth: one box per instance of a scene.  IoU in float64 from the fp32 values, every operation rounded on its
+ *     own: prediction corners centre -+ size / 2, volumes ((dx * dy) * dz), inter = ((ox * oy) * oz) of the overlaps clamped at 0,
+ *     iou = inter / ((va + vb) - inter), 0 where that denominator is 0.  Within a scene the predictions of class c are taken in
+ *     (score descending, row ascending) order; each takes the ground truth of class c with the largest IoU (the lowest index on equal
+ *     IoU); it is a true positive when that IoU is > t and the ground truth is not yet taken at t, a false positive otherwise (also
+ *     without any ground truth of its class).  Curve of (c, t): all entries of all scenes in descending score, true before false on
+ *     equal scores; recall = tp / npos, precision = tp / max(tp + fp, eps); AP = the area under the precision envelope (recall
+ *     padded with 0 and 1, precision with 0 and 0, running maximum from the back, sum of (r[i+1] - r[i]) * p[i+1]); AR = the last
+ *     recall.  npos[c] = 0: AP = AR = NaN; ground truth but no entry: 0.
+ *   sd3d_gt_boxes: points float [N, ld] (x, y, z first, ld >= 3); gt_sem / gt_inst / id_map / num_stuff / class_lut / n_classes read by
+ *     the id rule of sd3d_ap_scene (same columns, same SD3D_AP_BAD_INSTANCE / SD3D_AP_MIXED_SEMANTIC).  corners float
+ *     [SD3D_AP_INSTANCE_COLS, 6] = min xyz, max xyz over the points of instance column i (exact, whatever the order of the points; -0
+ *     reads as +0), cls int32 [SD3D_AP_INSTANCE_COLS] = its class index, -1 = no such instance (its corners are 0).  An instance with
+ *     one point is a ground truth.  A non-finite coordinate in an instance sets SD3D_BOX_BAD_COORD and the instance is left out.
+ *     ws: sd3d_gt_boxes_ws_bytes().
+ *   sd3d_box_ap_scene: boxes float [n, 6] (centre, size), labels int64 [n] class INDEX, scores float [n], 0 <= n <= SD3D_AP_MAX_PREDS.
+ *     A label outside [0, n_classes) sets SD3D_AP_BAD_LABEL, a non-finite score SD3D_AP_BAD_SCORE, a negative or non-finite size or a
+ *     non-finite centre SD3D_BOX_BAD_BOX; such a prediction is left out.  gt_corners float [n_gt, 6], gt_cls int32 [n_gt] (-1 = no
+ *     ground truth), 0 <= n_gt <= SD3D_AP_INSTANCE_COLS: the output of sd3d_gt_boxes or the caller's own; a class outside
+ *     [-1, n_classes) sets SD3D_AP_BAD_LABEL, a non-finite corner or max < min SD3D_BOX_BAD_COORD, and the box is left out.
+ *     thresholds: DEVICE double [n_overlaps], n_overlaps <= SD3D_AP_MAX_OVERLAPS.  Prediction r emits exactly one entry per threshold
+ *     o, in the code layout of sd3d_ap_scene with group = class * n_overlaps + o, into slot slot_begin + o * n + r; a prediction that
+ *     is left out writes the sentinel.  A slot at or past slot_begin + slot_cap is not written and sets SD3D_AP_STORE_FULL.
+ *     npos int64 [n_classes] += the scene's ground-truth boxes per class; has_pred int64 [n_classes] |= 1.
+ *     ws: sd3d_box_ap_scene_ws_bytes(n, n_gt, n_overlaps).
+ *   sd3d_box_ap_finish: codes int64 [n_slots] (clobbered: sorted in place or into the workspace, the sort of sd3d_ap_finish).  ap, ar
+ *     double [n_classes * n_overlaps].  The AP sum is taken per thread in ascending index and over the threads in a fixed tree.
+ *     ws: sd3d_box_ap_finish_ws_bytes(n_slots).
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_BOX_BAD_COORD 32            /* a non-finite point coordinate in an instance, or a bad ground-truth corner */
+#define SD3D_BOX_BAD_BOX 64              /* a predicted box with a negative or non-finite size or a non-finite centre */
+size_t sd3d_gt_boxes_ws_bytes(void);
+int sd3d_gt_boxes(const float* points, int64_t ld, int64_t N, const int64_t* gt_sem, int64_t sem_stride, const int64_t* gt_inst,
+                  int64_t inst_stride, const int64_t* id_map, int map_len, int num_stuff, const int32_t* class_lut, int lut_len,
+                  int n_classes, float* corners, int32_t* cls, int64_t* status, void* ws, size_t ws_bytes, void* stream);
+size_t sd3d_box_ap_scene_ws_bytes(int n, int n_gt, int n_overlaps);
+int sd3d_box_ap_scene(const float* boxes, int n, const int64_t* labels, const float* scores, const float* gt_corners, const int32_t* gt_cls,
+                      int n_gt, int n_classes, const double* thresholds, int n_overlaps, int64_t* store, int64_t slot_begin,
+                      int64_t slot_cap, int64_t* npos, int64_t* has_pred, int64_t* status, void* ws, size_t ws_bytes, void* stream);
+size_t sd3d_box_ap_finish_ws_bytes(int64_t n_slots);
+int sd3d_box_ap_finish(int64_t* codes, int64_t n_slots, int n_classes, int n_overlaps, const int64_t* npos, double* ap, double* ar,
+                       void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

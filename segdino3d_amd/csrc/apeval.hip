@@ -22,13 +22,11 @@
 // A prediction owns fixed slots of the store, so there is no append counter and no float atomic: the same bits on every run.
 #include "common.h"
 #include "ap_curve.h"
+#include "ap_ids.h"
 #include "../../include/segdino3d_hip.h"
 
 #define AP_PER 4
 #define AP_PTS (256 * AP_PER)                           // points per workgroup of ap_points_kernel
-#define AP_NI SD3D_AP_INSTANCE_COLS
-#define AP_VOID SD3D_AP_INSTANCE_COLS                   // the void column
-#define AP_NOWHERE (SD3D_AP_INSTANCE_COLS + 1)          // id 0 of the valid semantic id 0: counted in the prediction's size only
 #define AP_TILE 8192                                    // ints of the count matrix a matcher stages in LDS
 #define AP_MAX_POINTS 0x7F000000ll
 
@@ -62,24 +60,6 @@ static ApWs ap_carve(void* ws, int64_t N, int n) {
     return w;
 }
 
-__device__ static inline void ap_raise(unsigned long long* status, int bits) {         // every lane of the wave must arrive
-    const unsigned long long any = __ballot(bits != 0);
-    if (!any) return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bits |= __shfl_xor(bits, d);
-    if ((threadIdx.x & 63) == 0) atomicOr(status, (unsigned long long)bits);
-}
-
-__device__ static inline uint32_t ap_sortable(float s) {
-    if (s == 0.0f) s = 0.0f;                            // -0 and +0 are one score
-    const uint32_t u = __float_as_uint(s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ static inline int64_t ap_code(int group, float score, int truth) {
-    return (int64_t)(((uint64_t)group << 33) | ((uint64_t)ap_sortable(score) << 1) | (uint64_t)(truth & 1));
-}
-
 // ---------------------------------------------------------------------------------------------- points -> columns
 __global__ __launch_bounds__(256) void ap_points_kernel(const int64_t* __restrict__ gt_sem, int64_t s_sem, const int64_t* __restrict__ gt_inst,
                                                         int64_t s_inst, int64_t N, const int64_t* __restrict__ id_map, int map_len, int num_stuff,
@@ -101,21 +81,8 @@ __global__ __launch_bounds__(256) void ap_points_kernel(const int64_t* __restric
     for (int j = 0; j < AP_PER; ++j) {
         const int64_t i = base + j * 256 + threadIdx.x;
         if (i >= N) continue;
-        int64_t s = sem[j], in = inst[j];
-        if (id_map) {
-            in -= num_stuff;
-            if (in < 0) in = -1;
-            s -= num_stuff;
-            if (in == -1) s = -1;
-            const int64_t idx = s < 0 ? s + map_len : s;
-            s = (idx >= 0 && idx < map_len) ? id_map[idx] : -1;
-        }
-        const int cls = (s >= 0 && s < lut_len) ? lut[s] : -1;
-        int col;
-        if (in < -1 || in >= AP_NI) { bad = SD3D_AP_BAD_INSTANCE; col = AP_VOID; }
-        else if (cls < 0 || cls >= C || in == -1) col = AP_VOID;
-        else if (s == 0 && in == 0) col = AP_NOWHERE;
-        else col = (int)in;
+        int cls;
+        const int col = ap_point_column(sem[j], inst[j], id_map, map_len, num_stuff, lut, lut_len, C, &cls, &bad);   // the id rule (ap_ids.h)
         gt_index[i] = col;
         if (col < AP_NI) {
             atomicAdd(&vert[col], 1);

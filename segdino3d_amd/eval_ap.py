@@ -644,12 +644,18 @@ class ApAccumulator:
         float32, `true` 0 / 1 - with hard_fn [C, O], has_gt [C], has_pred [C] and the status word (no raise)."""
         C, O = self.n_classes, self.n_overlaps
         codes, counters, status = self._parse(state)
-        codes, counters = codes.cpu().numpy(), counters.cpu().numpy()
-        codes = codes[(codes >> 33) < C * O]
+        counters = counters.cpu().numpy()
+        group, score, true = self._decode(codes.cpu().numpy(), C * O)
+        return dict(group=group, score=score, true=true, hard_fn=counters[:C * O].reshape(C, O).copy(),
+                    has_gt=counters[C * O:C * O + C] > 0, has_pred=counters[C * O + C:] > 0, status=status)
+
+    @staticmethod
+    def _decode(codes: np.ndarray, n_groups: int):
+        """Entry codes (sentinels dropped) -> (group, score float32, true), sorted by (group, score, true)."""
+        codes = codes[(codes >> 33) < n_groups]
         key = ((codes >> 1) & 0xFFFFFFFF).astype(np.uint32)
         bits = np.where(key & np.uint32(0x80000000), key ^ np.uint32(0x80000000), ~key)
         score = bits.astype(np.uint32).view(np.float32)
         group, true = (codes >> 33).astype(np.int64), (codes & 1).astype(np.int64)
         order = np.lexsort((true, score, group))
-        return dict(group=group[order], score=score[order], true=true[order], hard_fn=counters[:C * O].reshape(C, O).copy(),
-                    has_gt=counters[C * O:C * O + C] > 0, has_pred=counters[C * O + C:] > 0, status=status)
+        return group[order], score[order], true[order]

@@ -1986,3 +1986,83 @@ def ap_reduce_counters(counters, n_classes: int, n_overlaps: int):
     out = torch.empty(n, dtype=torch.int64, device=counters.device)
     _lib.check(lib.sd3d_ap_reduce_counters(p, S, C, O, _ptr(out), _stream()), "ap_reduce_counters")
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# streamed 3D box AP / AR (csrc/boxeval.hip)
+# --------------------------------------------------------------------------------------------
+BOX_AP_STATUS = AP_STATUS + ((32, "a ground-truth instance has a non-finite coordinate (or a ground-truth box a bad corner)"),
+                             (64, "a predicted box has a negative or non-finite size or a non-finite centre"))
+BOX_AP_INSTANCE_COLS = 1000
+_WS_BOX_GT = _PerThread()     # gt_boxes: per-column integer partials of one scene
+_WS_BOX = _PerThread()        # box_ap_scene: best ground truth per prediction, first prediction per (ground truth, threshold)
+_WS_BOX_FIN = _PerThread()    # box_ap_finish: sort buffers
+
+
+def gt_boxes(points, gt_sem, gt_inst, class_lut, n_classes: int, status, id_map=None, num_stuff: int = 0):
+    """Ground-truth boxes of one scene (`sd3d_gt_boxes`): points fp32 [N, >= 3] with contiguous rows (any pitch), gt_sem / gt_inst
+    int64 [N] (any element stride) read by the id rule of `ap_scene` -> (corners fp32 [1000, 6] = min xyz, max xyz per instance
+    column, cls int32 [1000], -1 = no such instance).  `status` int64 [1] persists across calls.  Enqueues only."""
+    lib = _lib.load()
+    pp, ld = _rows(points, "points")
+    ps, ss = _labels1d(gt_sem, "gt_sem")
+    pi, si = _labels1d(gt_inst, "gt_inst")
+    N = gt_sem.numel()
+    if gt_inst.numel() != N or points.shape[0] != N or points.shape[1] < 3:
+        raise ValueError("gt_boxes: points [N, >= 3], gt_sem and gt_inst must have one entry per point")
+    dev = gt_sem.device
+    corners = torch.empty(BOX_AP_INSTANCE_COLS, 6, dtype=torch.float32, device=dev)
+    cls = torch.empty(BOX_AP_INSTANCE_COLS, dtype=torch.int32, device=dev)
+    ws = _WS_BOX_GT.get(lib.sd3d_gt_boxes_ws_bytes(), dev)
+    _lib.check(lib.sd3d_gt_boxes(pp if N else None, max(ld, 3), N, ps if N else None, ss, pi if N else None, si,
+                                 _ptr(id_map, torch.int64, "id_map"), id_map.numel() if id_map is not None else 0, int(num_stuff),
+                                 _ptr(class_lut, torch.int32, "class_lut"), class_lut.numel(), int(n_classes), _ptr(corners), _ptr(cls),
+                                 _accumulator(status, torch.int64, 1, "status"), ws.data_ptr(), ws.numel(), _stream()), "gt_boxes")
+    return corners, cls
+
+
+def box_ap_scene(boxes, labels, scores, gt_corners, gt_cls, n_classes: int, thresholds, store, slot_begin: int, slot_cap: int, npos,
+                 has_pred, status):
+    """One scene of the streamed box AP protocol (`sd3d_box_ap_scene`): boxes fp32 [n, 6] (centre, size), labels int64 [n] class
+    index, scores fp32 [n], gt_corners fp32 [G, 6], gt_cls int32 [G] (-1 = none), thresholds float64 [T] on the device.  One entry per
+    (threshold, prediction) into `store[slot_begin + o * n + r]` (those below `slot_begin + slot_cap`); npos / has_pred int64 [C] and
+    status int64 [1] persist across calls.  Enqueues only; scratch comes from a per-stream buffer."""
+    lib = _lib.load()
+    n, G = labels.numel(), gt_cls.numel()
+    if n > AP_MAX_PREDS:
+        raise ValueError(f"box_ap_scene: at most {AP_MAX_PREDS} predictions per scene, got {n}")
+    if G > BOX_AP_INSTANCE_COLS:
+        raise ValueError(f"box_ap_scene: at most {BOX_AP_INSTANCE_COLS} ground-truth boxes per scene, got {G}")
+    if tuple(boxes.shape) != (n, 6) or scores.numel() != n:
+        raise ValueError("box_ap_scene: boxes [n, 6], labels and scores must have one entry per prediction")
+    if tuple(gt_corners.shape) != (G, 6):
+        raise ValueError("box_ap_scene: gt_corners [G, 6] and gt_cls [G] must have one entry per ground truth")
+    C, T = int(n_classes), thresholds.numel()
+    nb = lib.sd3d_box_ap_scene_ws_bytes(n, G, T)
+    if nb == 0:
+        raise ValueError(f"box_ap_scene: unsupported size (n = {n}, G = {G}, T = {T})")
+    ws = _WS_BOX.get(nb, npos.device)
+    _lib.check(lib.sd3d_box_ap_scene(_ptr(boxes, torch.float32, "boxes") if n else None, n, _ptr(labels, torch.int64, "labels") if n else None,
+                                     _ptr(scores, torch.float32, "scores") if n else None,
+                                     _ptr(gt_corners, torch.float32, "gt_corners") if G else None, _ptr(gt_cls, torch.int32, "gt_cls") if G else None,
+                                     G, C, _ptr(thresholds, torch.float64, "thresholds"), T, _ptr(store, torch.int64, "store"), int(slot_begin),
+                                     int(slot_cap), _accumulator(npos, torch.int64, C, "npos"), _accumulator(has_pred, torch.int64, C, "has_pred"),
+                                     _accumulator(status, torch.int64, 1, "status"), ws.data_ptr(), ws.numel(), _stream()), "box_ap_scene")
+
+
+def box_ap_finish(codes, n_classes: int, n_overlaps: int, npos):
+    """AP [C * T] and AR [C * T] (float64, on the device) from the entry codes of all scenes (`sd3d_box_ap_finish`; `codes` int64 is
+    clobbered) and the ground-truth counts.  Enqueues only."""
+    lib = _lib.load()
+    C, T = int(n_classes), int(n_overlaps)
+    dev = npos.device
+    n = codes.numel()
+    ap = torch.empty(C * T, dtype=torch.float64, device=dev)
+    ar = torch.empty(C * T, dtype=torch.float64, device=dev)
+    nb = lib.sd3d_box_ap_finish_ws_bytes(n)
+    if nb == 0:
+        raise ValueError(f"box_ap_finish: unsupported size (n_slots = {n})")
+    ws = _WS_BOX_FIN.get(nb, dev)
+    _lib.check(lib.sd3d_box_ap_finish(_ptr(codes, torch.int64, "codes") if n else None, n, C, T, _accumulator(npos, torch.int64, C, "npos"),
+                                      _ptr(ap), _ptr(ar), ws.data_ptr(), ws.numel(), _stream()), "box_ap_finish")
+    return ap, ar
