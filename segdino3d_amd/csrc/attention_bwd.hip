@@ -13,6 +13,8 @@
 //   attn_bwd_kv_kernel: one workgroup per (32-key tile, head); waves split the query tiles; the operand roles are swapped
 //                       so that S and dP come out with lane = key; dV^T += dO^T P and dK^T += Q^T dS.
 // Partial sums of the waves are added through LDS in a fixed order: bit-reproducible, no atomics.
+// Heads of D = 32 W channels (W = 1 or 2): a 64-channel head contracts S and dP over two 32-channel blocks and keeps two 32-channel
+// accumulator tiles per gradient; its kernels (attn_bwd_*_wide_kernel) run at most four waves per workgroup, so a wave may hold 512 registers.
 #include "common.h"
 #include "../../include/segdino3d_hip.h"
 #include <math.h>
@@ -240,15 +242,243 @@ __global__ __launch_bounds__(512) void attn_bwd_kv_kernel(const AttnBwdParams p)
     }
 }
 
+// ---- 64-channel heads (W = 2 blocks of 32 channels).  The 32-channel kernels above are kept as they were written so that they stay
+// the code they were; these differ from them only where a width appears.
+template <int NSRC>
+__global__ __launch_bounds__(256) void attn_bwd_q_wide_kernel(const AttnBwdParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];      // [nw][NSRC][64 ch][32 q]
+    constexpr int W = 2, D = 32 * W;
+    const int nw = blockDim.x >> 6;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int i = lane & 31, h = lane >> 5;
+    const int head = blockIdx.y;
+    const int q0 = blockIdx.x * 32;
+    const int qi = min(q0 + i, p.Lq - 1);
+    const int hc = head * D + h * 16;                            // channel block w of the head starts at hc + 32 w
+
+    float qreg[NSRC][16 * W], doreg[16 * W];
+#pragma unroll
+    for (int s = 0; s < NSRC; ++s) {
+        const float* src = p.q[s] + (int64_t)qi * p.ldq[s] + hc;
+#pragma unroll
+        for (int e = 0; e < 16 * W; ++e) qreg[s][e] = src[(e >> 4) * 32 + (e & 15)] * p.scale;
+    }
+    float dsum = 0.f;
+    {
+        const float* dsrc = p.d_o + (int64_t)qi * p.ld_do + hc;
+        const float* osrc = p.o + (int64_t)qi * p.ldo + hc;
+#pragma unroll
+        for (int e = 0; e < 16 * W; ++e) {
+            const int c = (e >> 4) * 32 + (e & 15);
+            doreg[e] = dsrc[c]; dsum += dsrc[c] * osrc[c];
+        }
+    }
+    dsum += __shfl_xor(dsum, 32);
+    if (wave == 0 && h == 0 && q0 + i < p.Lq) p.dsum[(int64_t)head * p.Lq + q0 + i] = dsum;
+    const float lse = p.lse[(int64_t)head * p.Lq + qi] * ABW_LOG2E;
+
+    f32x16 dQ[NSRC][W];
+#pragma unroll
+    for (int s = 0; s < NSRC; ++s)
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dQ[s][w][r] = 0.f;
+
+    const int ntiles = (p.Lk + 31) >> 5;
+    for (int t = wave; t < ntiles; t += nw) {
+        const int kt0 = t * 32;
+        const int kr = min(kt0 + i, p.Lk - 1);
+        f32x16 S, dP;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
+#pragma unroll
+        for (int s = 0; s < NSRC; ++s) {
+            const float* src = p.k[s] + (int64_t)kr * p.ldk[s] + hc;
+#pragma unroll
+            for (int e = 0; e < 16 * W; ++e) S = __builtin_amdgcn_mfma_f32_32x32x2f32(src[(e >> 4) * 32 + (e & 15)], qreg[s][e], S, 0, 0, 0);
+        }
+        {
+            const float* src = p.v + (int64_t)kr * p.ldv + hc;
+#pragma unroll
+            for (int e = 0; e < 16 * W; ++e) dP = __builtin_amdgcn_mfma_f32_32x32x2f32(src[(e >> 4) * 32 + (e & 15)], doreg[e], dP, 0, 0, 0);
+        }
+        const uint32_t word = p.bits ? p.bits[(int64_t)qi * p.nwords + t] : 0u;
+        float ds[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int kb = tile_row(r, h);
+            const bool blocked = ((word >> kb) & 1u) || (kt0 + kb >= p.Lk);
+            const float pr = blocked ? 0.f : prob_of(S[r], lse);
+            ds[r] = pr * (dP[r] - dsum);
+        }
+        // dQ^T[c][query] += sum_key K[key][c] dS[query][key];  A = K^T (row = channel i), B = dS^T
+#pragma unroll
+        for (int s = 0; s < NSRC; ++s) {
+            const float* kcol = p.k[s] + head * D + i;
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = min(kt0 + tile_row(r, h), p.Lk - 1);
+                    dQ[s][w] = __builtin_amdgcn_mfma_f32_32x32x2f32(kcol[(int64_t)key * p.ldk[s] + 32 * w], ds[r], dQ[s][w], 0, 0, 0);
+                }
+        }
+    }
+    constexpr int TILE = 1024 * W;                               // floats of one [32 W ch][32 q] accumulator
+    float* mine = smem + wave * NSRC * TILE;
+#pragma unroll
+    for (int s = 0; s < NSRC; ++s)
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mine[s * TILE + (32 * w + tile_row(r, h)) * 32 + i] = dQ[s][w][r];
+    __syncthreads();
+    for (int e = threadIdx.x; e < NSRC * TILE; e += blockDim.x) {
+        const int s = e >> (9 + W), qq = (e >> (4 + W)) & 31, c = e & (D - 1);          // consecutive threads -> consecutive channels
+        float a = 0.f;
+        for (int w = 0; w < nw; ++w) a += smem[w * NSRC * TILE + s * TILE + c * 32 + qq];
+        if (q0 + qq < p.Lq) p.dq[s][(int64_t)(q0 + qq) * p.ld_dq[s] + head * D + c] = a * p.scale;
+    }
+}
+
+template <int NSRC>
+__global__ __launch_bounds__(256) void attn_bwd_kv_wide_kernel(const AttnBwdParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];      // [nw][NSRC + 1][64 ch][32 keys]
+    constexpr int W = 2, D = 32 * W;
+    const int nw = blockDim.x >> 6;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int j = lane & 31, h = lane >> 5;
+    const int head = blockIdx.y;
+    const int k0 = blockIdx.x * 32;
+    const int ktile = blockIdx.x;
+    const int kj = min(k0 + j, p.Lk - 1);
+    const bool key_ok = k0 + j < p.Lk;
+    const int hc = head * D + h * 16;
+
+    float kreg[NSRC][16 * W], vreg[16 * W];
+#pragma unroll
+    for (int s = 0; s < NSRC; ++s) {
+        const float* src = p.k[s] + (int64_t)kj * p.ldk[s] + hc;
+#pragma unroll
+        for (int e = 0; e < 16 * W; ++e) kreg[s][e] = src[(e >> 4) * 32 + (e & 15)];
+    }
+    {
+        const float* src = p.v + (int64_t)kj * p.ldv + hc;
+#pragma unroll
+        for (int e = 0; e < 16 * W; ++e) vreg[e] = src[(e >> 4) * 32 + (e & 15)];
+    }
+    f32x16 dK[NSRC][W], dV[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            dV[w][r] = 0.f;
+#pragma unroll
+            for (int s = 0; s < NSRC; ++s) dK[s][w][r] = 0.f;
+        }
+
+    const int ntiles = (p.Lq + 31) >> 5;
+    for (int t = wave; t < ntiles; t += nw) {
+        const int qt0 = t * 32;
+        const int qr = min(qt0 + j, p.Lq - 1);          // A-operand row = query
+        f32x16 S, dP;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
+#pragma unroll
+        for (int s = 0; s < NSRC; ++s) {
+            const float* src = p.q[s] + (int64_t)qr * p.ldq[s] + hc;
+#pragma unroll
+            for (int e = 0; e < 16 * W; ++e)
+                S = __builtin_amdgcn_mfma_f32_32x32x2f32(src[(e >> 4) * 32 + (e & 15)] * p.scale, kreg[s][e], S, 0, 0, 0);
+        }
+        {
+            const float* src = p.d_o + (int64_t)qr * p.ld_do + hc;
+#pragma unroll
+            for (int e = 0; e < 16 * W; ++e) dP = __builtin_amdgcn_mfma_f32_32x32x2f32(src[(e >> 4) * 32 + (e & 15)], vreg[e], dP, 0, 0, 0);
+        }
+        // S[r], dP[r]: (query = qt0 + tile_row(r, h), key = k0 + j).  The per-query values (mask word, lse, D) are loaded once per
+        // tile by the lane whose index is the query's row in the tile and handed round with readlane - not 48 loads per lane and tile
+        const uint32_t my_word = p.bits ? p.bits[(int64_t)qr * p.nwords + ktile] : 0u;
+        const float my_lse = p.lse[(int64_t)head * p.Lq + qr] * ABW_LOG2E, my_dsum = p.dsum[(int64_t)head * p.Lq + qr];
+        float pr[16], ds[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row0 = tile_row(r, 0), row1 = tile_row(r, 1);             // compile-time lane numbers
+            const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)my_word, row0), w1 = (uint32_t)__builtin_amdgcn_readlane((int)my_word, row1);
+            const float l0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_lse), row0));
+            const float l1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_lse), row1));
+            const float d0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_dsum), row0));
+            const float d1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_dsum), row1));
+            const uint32_t word = h ? w1 : w0;
+            const float lse = h ? l1 : l0, dsum = h ? d1 : d0;
+            const int qq = qt0 + (h ? row1 : row0);
+            const bool blocked = !key_ok || qq >= p.Lq || ((word >> j) & 1u);
+            pr[r] = blocked ? 0.f : prob_of(S[r], lse);
+            ds[r] = pr[r] * (dP[r] - dsum);
+        }
+        // dV^T[dv][key] += sum_q dO[q][dv] P[q][key];  A = dO^T (row = dv = j), B = P
+        {
+            const float* dcol = p.d_o + head * D + j;
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int qc = min(qt0 + tile_row(r, h), p.Lq - 1);
+                    dV[w] = __builtin_amdgcn_mfma_f32_32x32x2f32(dcol[(int64_t)qc * p.ld_do + 32 * w], pr[r], dV[w], 0, 0, 0);
+                }
+        }
+        // dK^T[c][key] += sum_q (scale Q[q][c]) dS[q][key]
+#pragma unroll
+        for (int s = 0; s < NSRC; ++s) {
+            const float* qcol = p.q[s] + head * D + j;
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int qc = min(qt0 + tile_row(r, h), p.Lq - 1);
+                    dK[s][w] = __builtin_amdgcn_mfma_f32_32x32x2f32(qcol[(int64_t)qc * p.ldq[s] + 32 * w] * p.scale, ds[r], dK[s][w], 0, 0, 0);
+                }
+        }
+    }
+    constexpr int NA = NSRC + 1;
+    constexpr int TILE = 1024 * W;                               // floats of one [32 W ch][32 keys] accumulator
+    float* mine = smem + wave * NA * TILE;
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = 32 * w + tile_row(r, h);
+#pragma unroll
+            for (int s = 0; s < NSRC; ++s) mine[s * TILE + row * 32 + j] = dK[s][w][r];
+            mine[NSRC * TILE + row * 32 + j] = dV[w][r];
+        }
+    __syncthreads();
+    for (int e = threadIdx.x; e < NA * TILE; e += blockDim.x) {
+        const int s = e >> (9 + W), kk = (e >> (4 + W)) & 31, c = e & (D - 1);
+        float a = 0.f;
+        for (int w = 0; w < nw; ++w) a += smem[w * NA * TILE + s * TILE + c * 32 + kk];
+        if (k0 + kk < p.Lk) {
+            if (s < NSRC) p.dk[s][(int64_t)(k0 + kk) * p.ld_dk[s] + head * D + c] = a;
+            else p.dv[(int64_t)(k0 + kk) * p.ld_dv + head * D + c] = a;
+        }
+    }
+}
+
 #define ST ((hipStream_t)stream)
 extern "C" {
 
 size_t sd3d_attention_backward_ws_bytes(int Lq, int H) { return align_up((size_t)Lq * H * sizeof(float), 256); }
+// D = dO . O is one float per (head, query) whatever the head width
+size_t sd3d_attention_heads_backward_ws_bytes(int Lq, int H, int head_dim) {
+    return head_dim == 32 || head_dim == 64 ? sd3d_attention_backward_ws_bytes(Lq, H) : 0;
+}
 
-int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+static int attention_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
                             const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale, const float* out, int ldo,
                             const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0, float* dq1, int ld_dq1, float* dk0,
-                            int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes, void* stream) {
+                            int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes, void* stream, int W) {
+    if (W != 1 && W != 2) return sd3d_set_error(SD3D_ERR_ARG, "attention_backward: heads must be 32 or 64 channels wide");
     if ((q1 == nullptr) != (k1 == nullptr) || (q1 && (!dq1 || !dk1))) return sd3d_set_error(SD3D_ERR_ARG, "attention_backward: second source incomplete");
     if (Lq <= 0 || Lk <= 0 || !lse || !out || !d_out) return sd3d_set_error(SD3D_ERR_ARG, "attention_backward: missing forward state");
     if (ws_bytes < sd3d_attention_backward_ws_bytes(Lq, H)) return sd3d_set_error(SD3D_ERR_WS, "attention_backward: workspace too small");
@@ -264,7 +494,8 @@ int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1
     // training shapes (2441 queries x 3000 keys) 752 workgroups x 4 waves at two per SIMD ran two rounds of 19 query tiles each,
     // 611 us; 8 waves x 4 per SIMD: 396 us (4 waves at the same budget: 439).  The q kernel keeps 4 waves and its 256-register
     // budget (302 us; 324 / 362 with the kv kernel's settings).
-    const int nwq = kt >= 8 ? 4 : (kt >= 2 ? 2 : 1), nwk = qt >= 32 ? 8 : (qt >= 8 ? 4 : (qt >= 2 ? 2 : 1));
+    // 64-channel heads: at most four waves in the kv kernel too (its 512-register budget: 64 key + 32 value registers and six accumulator tiles)
+    const int nwq = kt >= 8 ? 4 : (kt >= 2 ? 2 : 1), nwk = qt >= 32 && W == 1 ? 8 : (qt >= 8 ? 4 : (qt >= 2 ? 2 : 1));
     const dim3 gq((unsigned)qt, (unsigned)H), gk((unsigned)kt, (unsigned)H);
     static std::atomic<bool> attr_set[64];                    // per device: a function attribute belongs to the current device
     int dev = 0;
@@ -272,7 +503,20 @@ int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1
     if (!attr_set[dev].load(std::memory_order_relaxed)) {
         (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 2 * 4096);
         (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 3 * 4096);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_kv_wide_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 3 * 8192);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_q_wide_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 8192);
         attr_set[dev].store(true, std::memory_order_relaxed);
+    }
+    if (W == 2) {                                             // LDS: nw waves x accumulators x 8 KiB; q<2> is the 64 KiB default exactly, kv<2> 96 KiB
+        if (nsrc == 1) {
+            attn_bwd_q_wide_kernel<1><<<gq, 64 * nwq, (size_t)nwq * 1 * 8192, ST>>>(p);
+            attn_bwd_kv_wide_kernel<1><<<gk, 64 * nwk, (size_t)nwk * 2 * 8192, ST>>>(p);
+        } else {
+            attn_bwd_q_wide_kernel<2><<<gq, 64 * nwq, (size_t)nwq * 2 * 8192, ST>>>(p);
+            attn_bwd_kv_wide_kernel<2><<<gk, 64 * nwk, (size_t)nwk * 3 * 8192, ST>>>(p);
+        }
+        SD3D_CHECK_LAUNCH();
+        return SD3D_OK;
     }
     if (nsrc == 1) {
         attn_bwd_q_kernel<1><<<gq, 64 * nwq, (size_t)nwq * 1 * 4096, ST>>>(p);
@@ -283,6 +527,23 @@ int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1
     }
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+
+int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                            const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale, const float* out, int ldo,
+                            const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0, float* dq1, int ld_dq1, float* dk0,
+                            int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes, void* stream) {
+    return attention_backward(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, lse, d_out, ld_do, dq0, ld_dq0,
+                              dq1, ld_dq1, dk0, ld_dk0, dk1, ld_dk1, dv, ld_dv, ws, ws_bytes, stream, 1);
+}
+int sd3d_attention_heads_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                                  const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
+                                  const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0, float* dq1,
+                                  int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    if (head_dim != 32 && head_dim != 64) return sd3d_set_error(SD3D_ERR_ARG, "attention_heads_backward: heads must be 32 or 64 channels wide");
+    return attention_backward(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, lse, d_out, ld_do, dq0, ld_dq0,
+                              dq1, ld_dq1, dk0, ld_dk0, dk1, ld_dk1, dv, ld_dv, ws, ws_bytes, stream, head_dim / 32);
 }
 
 }  // extern "C"

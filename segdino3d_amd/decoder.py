@@ -292,7 +292,7 @@ class _BatchF(_EvalF):
         return ops.linear_layernorm(x, w, b, ln_w, ln_b, res=res, max_rows=x.shape[0])
 
     def attention(self, q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, keys="s"):
-        a = torch.empty(q.shape[0], num_heads * 32, dtype=torch.float32, device=q.device)
+        a = torch.empty(q.shape[0], v.shape[1], dtype=torch.float32, device=q.device)        # num_heads x head width (32 or 64)
         at = lambda t, r: None if t is None else t[r]  # noqa: E731
         ops.attention_batch([(q[qr], k[kr], v[kr], at(mask_bits, b), at(q2, qr), at(k2, kr), a[qr])
                              for b, (qr, kr) in enumerate(zip(self._slices["q"], self._slices[keys]))], num_heads, scale)
@@ -373,8 +373,8 @@ class ScanNetQueryDecoder(DerivedWeights):
             unsupported.append("num_instance_queries > 0 (the reference's own forward cannot run it behind Baseline3D)")
         if num_semantic_queries != 0 and add_positional_embedding:
             unsupported.append("learned queries with add_positional_embedding (the reference has no positions for them, :631-640)")
-        if d_model != num_heads * 32:
-            unsupported.append("attention heads must be 32 channels wide (d_model == 32 * num_heads)")
+        if d_model not in (32 * num_heads, 64 * num_heads):
+            unsupported.append("attention heads must be 32 or 64 channels wide (d_model == 32 * num_heads or 64 * num_heads)")
         if add_dinox_query_ca and not add_dinox_query_ca_mask:
             unsupported.append("add_dinox_query_ca requires add_dinox_query_ca_mask")
         if box_modulate_ca:

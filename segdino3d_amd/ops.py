@@ -1074,8 +1074,29 @@ def fourier_pe(xyz, rng, gauss_b, d_pos, row_scene=None):
     return out
 
 
+HEAD_WIDTHS = (32, 64)                                          # channels per attention head the kernels are built for
+
+
+def head_width(q, v, num_heads, name):
+    """Channels per head of an attention over `num_heads` heads (q and v hold the heads side by side): 32 or 64, else ValueError."""
+    D = q.shape[1] // max(int(num_heads), 1)
+    if D not in HEAD_WIDTHS or q.shape[1] != num_heads * D or v.shape[1] != num_heads * D:
+        raise ValueError(f"{name}: head slices must be 32 or 64 channels wide (got {q.shape[1]} / {v.shape[1]} channels for {num_heads} heads)")
+    return D
+
+
+def attention_launch_config(Lq, Lk, num_heads, head_dim=32):
+    """(waves per workgroup, key split) the attention launcher chooses for this shape with its full split workspace."""
+    import ctypes as C
+    lib = _lib.load()
+    nw, ks = C.c_int(0), C.c_int(0)
+    _lib.check(lib.sd3d_attention_heads_config(Lq, Lk, num_heads, head_dim, lib.sd3d_attention_heads_ws_bytes(Lq, num_heads, head_dim),
+                                               C.byref(nw), C.byref(ks)), "attention_launch_config")
+    return nw.value, ks.value
+
+
 def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, out=None):
-    """q/k [L, H*32] (+ optional second source concatenated per head), v [Lk, H*32] -> [Lq, H*32] (`out`: rows to write into)."""
+    """q/k [L, H*D] (+ optional second source concatenated per head), v [Lk, H*D] -> [Lq, H*D] (`out`: rows to write into); D = 32 or 64."""
     lib = _lib.load()
     pq, ldq = _rows(q, "q")
     pk, ldk = _rows(k, "k")
@@ -1085,14 +1106,19 @@ def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, out=N
         pq2, ldq2 = _rows(q2, "q2")
         pk2, ldk2 = _rows(k2, "k2")
     Lq, Lk = q.shape[0], k.shape[0]
-    if q.shape[1] != num_heads * 32 or v.shape[1] != num_heads * 32:
-        raise ValueError("attention: head slices must be 32 channels wide")
+    D = head_width(q, v, num_heads, "attention")
     if mask_bits is not None and tuple(mask_bits.shape) != (Lq, (Lk + 31) // 32):
         raise ValueError(f"attention: mask bits shape {tuple(mask_bits.shape)} != ({Lq}, {(Lk + 31) // 32})")
     if out is None:
-        out = torch.empty(Lq, num_heads * 32, dtype=torch.float32, device=q.device)
-    elif tuple(out.shape) != (Lq, num_heads * 32) or not out.is_contiguous() or out.dtype != torch.float32:
-        raise ValueError("attention: `out` must be a contiguous fp32 [Lq, H * 32] tensor")
+        out = torch.empty(Lq, num_heads * D, dtype=torch.float32, device=q.device)
+    elif tuple(out.shape) != (Lq, num_heads * D) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("attention: `out` must be a contiguous fp32 [Lq, H * D] tensor")
+    if D != 32:
+        ws = _WS6.get(lib.sd3d_attention_heads_ws_bytes(Lq, num_heads, D), q.device)
+        _lib.check(lib.sd3d_attention_heads(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, _ptr(mask_bits, torch.int32, "mask_bits"),
+                                            Lq, Lk, num_heads, D, float(scale), _ptr(out), out.shape[1], None, 1 if bf16_decoder_active() else 0,
+                                            ws.data_ptr(), ws.numel(), _stream()), "attention")
+        return out
     ws = _WS6.get(lib.sd3d_attention_ws_bytes(Lq, num_heads), q.device)
     fn = lib.sd3d_attention_bf16 if bf16_decoder_active() else lib.sd3d_attention
     _lib.check(fn(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, _ptr(mask_bits, torch.int32, "mask_bits"),
@@ -1108,10 +1134,12 @@ assert _ATTN_JOB_DT.itemsize == 88
 
 def _attn_job_table(jobs, num_heads, name, strided_out):
     """Validates the jobs of `attention_batch` / `attention_parts` (`name`: the caller, for the messages) and fills their sd3d_attn_job
-    table -> (table, bytes of split workspace).  strided_out: `out` may be a view with strided rows; otherwise it must be contiguous."""
+    table -> (table, bytes of split workspace, head width).  strided_out: `out` may be a view with strided rows; otherwise it must be
+    contiguous.  All jobs share one head width (32 or 64 channels)."""
     lib = _lib.load()
     tab = np.zeros(len(jobs), dtype=_ATTN_JOB_DT)
     nb = 0
+    width = None
     for i, (q, k, v, bits, q2, k2, out) in enumerate(jobs):
         pq, ldq = _rows(q, "q")
         pk, ldk = _rows(k, "k")
@@ -1121,29 +1149,35 @@ def _attn_job_table(jobs, num_heads, name, strided_out):
             pq2, ldq2 = _rows(q2, "q2")
             pk2, ldk2 = _rows(k2, "k2")
         Lq, Lk = q.shape[0], k.shape[0]
-        if q.shape[1] != num_heads * 32 or v.shape[1] != num_heads * 32:
-            raise ValueError(f"{name}: head slices must be 32 channels wide")
+        D = head_width(q, v, num_heads, name)
+        if width not in (None, D):
+            raise ValueError(f"{name}: all jobs must have the same head width")
+        width = D
         if bits is not None and tuple(bits.shape) != (Lq, (Lk + 31) // 32):
             raise ValueError(f"{name}: mask bits shape mismatch")
         if strided_out:
             po, ldo = _rows(out, "out")
-            if out.shape[0] != Lq or out.shape[1] != num_heads * 32:
-                raise ValueError(f"{name}: `out` must be fp32 [Lq, H * 32] rows")
+            if out.shape[0] != Lq or out.shape[1] != num_heads * D:
+                raise ValueError(f"{name}: `out` must be fp32 [Lq, H * D] rows")
         else:
-            if tuple(out.shape) != (Lq, num_heads * 32) or not out.is_contiguous() or out.dtype != torch.float32:
-                raise ValueError(f"{name}: `out` must be a contiguous fp32 [Lq, H * 32] tensor")
+            if tuple(out.shape) != (Lq, num_heads * D) or not out.is_contiguous() or out.dtype != torch.float32:
+                raise ValueError(f"{name}: `out` must be a contiguous fp32 [Lq, H * D] tensor")
             po, ldo = out.data_ptr(), out.stride(0)
         tab[i] = (pq, pq2, pk, pk2, pv, 0 if bits is None else _ptr(bits, torch.int32, "mask_bits"), po, ldq, ldq2, ldk, ldk2, ldv, ldo, Lq, Lk)
-        nb += lib.sd3d_attention_ws_bytes(Lq, num_heads)
-    return tab, nb
+        nb += lib.sd3d_attention_ws_bytes(Lq, num_heads) if D == 32 else lib.sd3d_attention_heads_ws_bytes(Lq, num_heads, D)
+    return tab, nb, width
 
 
 def attention_batch(jobs, num_heads, scale):
     """jobs: list of (q, k, v, mask_bits | None, q2 | None, k2 | None, out) - the same attention for several scenes in ONE launch
     (sd3d_attention_batch): per scene the rows are the bits of `attention` on that scene alone."""
     lib = _lib.load()
-    tab, nb = _attn_job_table(jobs, num_heads, "attention_batch", strided_out=False)
+    tab, nb, D = _attn_job_table(jobs, num_heads, "attention_batch", strided_out=False)
     ws = _WS6.get(nb, jobs[0][0].device)
+    if D != 32:
+        _lib.check(lib.sd3d_attention_heads_batch(len(jobs), tab.ctypes.data, num_heads, D, float(scale), 1 if bf16_decoder_active() else 0,
+                                                  ws.data_ptr(), ws.numel(), _stream()), "attention_batch")
+        return
     _lib.check(lib.sd3d_attention_batch(len(jobs), tab.ctypes.data, num_heads, float(scale), 1 if bf16_decoder_active() else 0,
                                         ws.data_ptr(), ws.numel(), _stream()), "attention_batch")
 
@@ -1155,7 +1189,9 @@ def attention_parts(jobs, num_heads, scale):
     import ctypes as C
     lib = _lib.load()
     n = len(jobs)
-    tab, nb = _attn_job_table(jobs, num_heads, "attention_parts", strided_out=True)
+    tab, nb, D = _attn_job_table(jobs, num_heads, "attention_parts", strided_out=True)
+    if D != 32:
+        raise ValueError("attention_parts: head slices must be 32 channels wide (the row-chain decoder is built for 32-channel heads)")
     ws = _WS6.get(nb, jobs[0][0].device)                 # consumed by the next launch on this stream, before the next attention refills it
     ks = (C.c_int32 * n)()
     off = (C.c_int64 * n)()

@@ -296,15 +296,23 @@ class _Attention(torch.autograd.Function):
         if q2 is not None:
             pq2, ldq2 = ops._rows(q2.detach(), "q2"); pk2, ldk2 = ops._rows(k2.detach(), "k2")
         Lq, Lk = q.shape[0], k.shape[0]
-        out = torch.empty(Lq, num_heads * 32, dtype=torch.float32, device=q.device)
+        D = ops.head_width(q, v, num_heads, "attention")
+        out = torch.empty(Lq, num_heads * D, dtype=torch.float32, device=q.device)
         lse = torch.empty(num_heads, Lq, dtype=torch.float32, device=q.device)
-        ws = _WS_ATT.get(lib.sd3d_attention_ws_bytes(Lq, num_heads), q.device)
-        fn = lib.sd3d_attention_lse_bf16 if ops.bf16_decoder_active() else lib.sd3d_attention_lse
-        _lib.check(fn(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, ops._ptr(mask_bits, torch.int32, "mask_bits"),
-                      Lq, Lk, num_heads, float(scale), out.data_ptr(), out.shape[1], lse.data_ptr(), ws.data_ptr(),
-                      ws.numel(), ops._stream()), "attention_lse")
+        bits = ops._ptr(mask_bits, torch.int32, "mask_bits")
+        if D != 32:
+            ws = _WS_ATT.get(lib.sd3d_attention_heads_ws_bytes(Lq, num_heads, D), q.device)
+            _lib.check(lib.sd3d_attention_heads(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, bits, Lq, Lk, num_heads, D, float(scale),
+                                                out.data_ptr(), out.shape[1], lse.data_ptr(), 1 if ops.bf16_decoder_active() else 0,
+                                                ws.data_ptr(), ws.numel(), ops._stream()), "attention_lse")
+        else:
+            ws = _WS_ATT.get(lib.sd3d_attention_ws_bytes(Lq, num_heads), q.device)
+            fn = lib.sd3d_attention_lse_bf16 if ops.bf16_decoder_active() else lib.sd3d_attention_lse
+            _lib.check(fn(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, bits,
+                          Lq, Lk, num_heads, float(scale), out.data_ptr(), out.shape[1], lse.data_ptr(), ws.data_ptr(),
+                          ws.numel(), ops._stream()), "attention_lse")
         ctx.save_for_backward(q, k, v, q2, k2, mask_bits, out, lse)
-        ctx.H, ctx.scale = num_heads, float(scale)
+        ctx.H, ctx.D, ctx.scale = num_heads, D, float(scale)
         return out
 
     @staticmethod
@@ -314,15 +322,23 @@ class _Attention(torch.autograd.Function):
         d_out = d_out.contiguous()
         Lq, Lk, H = q.shape[0], k.shape[0], ctx.H
         dev = q.device
-        new = lambda n: torch.empty(n, H * 32, dtype=torch.float32, device=dev)
+        D = ctx.D
+        new = lambda n: torch.empty(n, H * D, dtype=torch.float32, device=dev)
         dq, dk, dv = new(Lq), new(Lk), new(Lk)
         dq2, dk2 = (new(Lq), new(Lk)) if q2 is not None else (None, None)
         pq, ldq = ops._rows(q.detach(), "q"); pk, ldk = ops._rows(k.detach(), "k"); pv, ldv = ops._rows(v.detach(), "v")
         pq2, ldq2, pk2, ldk2 = None, 0, None, 0
         if q2 is not None:
             pq2, ldq2 = ops._rows(q2.detach(), "q2"); pk2, ldk2 = ops._rows(k2.detach(), "k2")
+        W = H * D
+        if D != 32:
+            ws = _WS_ATT2.get(lib.sd3d_attention_heads_backward_ws_bytes(Lq, H, D), dev)
+            _lib.check(lib.sd3d_attention_heads_backward(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, ops._ptr(bits, torch.int32, "mask_bits"), Lq,
+                                                         Lk, H, D, ctx.scale, out.data_ptr(), W, lse.data_ptr(), d_out.data_ptr(), W, dq.data_ptr(), W,
+                                                         ops._ptr(dq2), W, dk.data_ptr(), W, ops._ptr(dk2), W, dv.data_ptr(), W, ws.data_ptr(),
+                                                         ws.numel(), ops._stream()), "attention_backward")
+            return dq, dk, dv, None, None, None, dq2, dk2
         ws = _WS_ATT2.get(lib.sd3d_attention_backward_ws_bytes(Lq, H), dev)
-        W = H * 32
         _lib.check(lib.sd3d_attention_backward(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, ops._ptr(bits, torch.int32, "mask_bits"), Lq, Lk, H,
                                                ctx.scale, out.data_ptr(), W, lse.data_ptr(), d_out.data_ptr(), W, dq.data_ptr(), W,
                                                ops._ptr(dq2), W, dk.data_ptr(), W, ops._ptr(dk2), W, dv.data_ptr(), W, ws.data_ptr(), ws.numel(),
