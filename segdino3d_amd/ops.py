@@ -101,6 +101,39 @@ def _rows(t: torch.Tensor, name="tensor"):
     return t.data_ptr(), t.stride(0)
 
 
+def _want_shape(t, shapes, name):
+    """ValueError unless t's shape is one of `shapes` (a -1 entry takes any extent >= 1): the kernels index by these shapes unchecked."""
+    got = tuple(t.shape)
+    for want in shapes:
+        if len(got) == len(want) and all(g == w or (w == -1 and g >= 1) for g, w in zip(got, want)):
+            return
+    raise ValueError(f"{name}: expected shape {' or '.join(str(list(w)).replace('-1', 'n_scenes') for w in shapes)}, got {list(got)}")
+
+
+def _want_ranges(rng, row_scene, n, name):
+    """rng [6] for one scene's rows; [n_scenes, 6] and row_scene [n] for the rows of several."""
+    if row_scene is None:
+        _want_shape(rng, [(6,)], f"{name}: rng (one scene)")
+    else:
+        _want_shape(rng, [(-1, 6)], f"{name}: rng (with row_scene)")
+        _want_shape(row_scene, [(n,)], f"{name}: row_scene")
+
+
+def _want_box_shapes(ref_points, d_center, size_prev, d_size, rng, row_scene=None):
+    """The shapes `box_refine` indexes by -> Q."""
+    Q = ref_points.shape[0]
+    _want_shape(ref_points, [(Q, 3)], "box_refine: ref_points")
+    _want_shape(d_center, [(Q, 3)], "box_refine: d_center")
+    if d_size is not None:
+        _want_shape(d_size, [(Q, 3)], "box_refine: d_size")
+        if size_prev is None:
+            raise ValueError("box_refine: d_size given without size_prev")
+    if size_prev is not None:
+        _want_shape(size_prev, [(3,), (Q, 3)], "box_refine: size_prev")
+    _want_ranges(rng, row_scene, Q, "box_refine")
+    return Q
+
+
 class HostRead:
     """Small device -> host read: asynchronous copy into pinned memory + an event the caller waits on through
     `wait_event` (which hands the issue baton of the pipelined runner to another scene's thread meanwhile)."""
@@ -1036,9 +1069,15 @@ def linear_layernorm(x, weight, bias, ln_weight, ln_bias, res=None, act=None, ep
 def sine_pe(xyz, rng, dim_t, axis, mod_num=None, mod_den=None, row_scene=None):
     """xyz [n,3]; rng [6] = (lo, hi); dim_t [d] fp32, axis [d] int8 -> [n, d].  row_scene int32 [n]: rows of several scenes,
     rng is then [n_scenes, 6] and row r uses rng[row_scene[r]] (sd3d_sine_pe_rows)."""
+    n, d = xyz.shape[0], dim_t.numel()
+    _want_ranges(rng, row_scene, n, "sine_pe")
+    if mod_num is not None:
+        if mod_den is None:
+            raise ValueError("sine_pe: mod_num given without mod_den")
+        _want_shape(mod_num, [(n, 3)], "sine_pe: mod_num")
+        _want_shape(mod_den, [(3,), (n, 3)], "sine_pe: mod_den")
     lib = _lib.load()
     px, ldx = _rows(xyz, "xyz")
-    n, d = xyz.shape[0], dim_t.numel()
     out = torch.empty(n, d, dtype=torch.float32, device=xyz.device)
     pn, ldn, pd, ldd = None, 0, None, 0
     if mod_num is not None:
@@ -1059,10 +1098,11 @@ def sine_pe(xyz, rng, dim_t, axis, mod_num=None, mod_den=None, row_scene=None):
 
 def fourier_pe(xyz, rng, gauss_b, d_pos, row_scene=None):
     """xyz [n,3]; rng [6] = (lo, hi); gauss_b [3, >= d_pos / 2] fp32 -> [n, d_pos] = [sin | cos] (utils.py:107-142)."""
+    n = xyz.shape[0]
+    _want_ranges(rng, row_scene, n, "fourier_pe")
     lib = _lib.load()
     px, ldx = _rows(xyz, "xyz")
     pb, ldb = _rows(gauss_b, "gauss_b")
-    n = xyz.shape[0]
     if gauss_b.shape[0] != 3 or gauss_b.shape[1] < d_pos // 2:
         raise ValueError("fourier_pe: gauss_b must be [3, >= d_pos / 2]")
     out = torch.empty(n, d_pos, dtype=torch.float32, device=xyz.device)
@@ -1277,9 +1317,10 @@ def dinox_mask_bits(blocked, near):
 
 
 def box_refine(ref_points, d_center, size_prev, d_size, rng, normalize, row_scene=None):
-    """row_scene int32 [Q]: rows of several scenes, rng [n_scenes, 6] (sd3d_box_refine_rows)."""
+    """ref_points, d_center, d_size [Q, 3]; size_prev [3] (one row for all queries) or [Q, 3]; rng [6].
+    row_scene int32 [Q]: rows of several scenes, rng [n_scenes, 6] (sd3d_box_refine_rows)."""
+    Q = _want_box_shapes(ref_points, d_center, size_prev, d_size, rng, row_scene)
     lib = _lib.load()
-    Q = ref_points.shape[0]
     dev = ref_points.device
     center = torch.empty(Q, 3, dtype=torch.float32, device=dev)
     size = size_metric = None

@@ -278,7 +278,13 @@ class _SinePEModulated(torch.autograd.Function):
 
 
 def sine_pe_modulated(xyz, rng, dim_t, axis, mod_num, mod_den):
-    """`ops.sine_pe` with box modulation, differentiable w.r.t. `mod_num` ([n, 3])."""
+    """`ops.sine_pe` with box modulation, differentiable w.r.t. `mod_num` ([n, 3]); `mod_den` [3] or [n, 3], rng [6]."""
+    n = xyz.shape[0]
+    if mod_num is None or mod_den is None:
+        raise ValueError("sine_pe_modulated: needs mod_num and mod_den")
+    ops._want_ranges(rng, None, n, "sine_pe_modulated")
+    ops._want_shape(mod_num, [(n, 3)], "sine_pe_modulated: mod_num")
+    ops._want_shape(mod_den, [(3,), (n, 3)], "sine_pe_modulated: mod_den")
     return _SinePEModulated.apply(xyz, rng, dim_t, axis, mod_num, mod_den)
 
 
@@ -430,4 +436,6 @@ class _BoxRefine(torch.autograd.Function):
 
 
 def box_refine(ref_points, d_center, size_prev, d_size, rng, normalize):
+    """Differentiable `ops.box_refine` of one scene's rows (shapes as there; refused before anything is launched)."""
+    ops._want_box_shapes(ref_points, d_center, size_prev, d_size, rng)
     return _BoxRefine.apply(ref_points, d_center, size_prev, d_size, rng, normalize)

@@ -46,3 +46,40 @@ def pairs_from_nbr(nbr: torch.Tensor):
         o = np.nonzero(t[k] >= 0)[0]
         out.append((t[k][o].astype(np.int64), o.astype(np.int64)))
     return out
+
+
+# ---- direct kernel tests: output buffers with sentinels, inputs with poisoned padding (tests/test_gpu_loss_kernels.py,
+# tests/test_gpu_decoder_kernels.py) --------------------------------------------------------------------------------------------------
+SENT = 64
+FILL = {torch.float32: -777.25, torch.int32: -77777, torch.uint8: 0xA5}
+
+
+def _dev():
+    return torch.device("cuda:0")
+
+
+class Out:
+    """n elements for the kernel plus SENT sentinel elements behind them."""
+
+    def __init__(self, n, dtype=torch.float32):
+        self.n, self.fill = int(n), FILL[dtype]
+        self.buf = torch.full((self.n + SENT,), self.fill, dtype=dtype, device=_dev())
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr()
+
+    def get(self, *shape):
+        assert bool((self.buf[self.n:] == self.fill).all()), "sentinels behind the output were overwritten"
+        return self.buf[:self.n].reshape(*shape).cpu()
+
+    def untouched(self):
+        return bool((self.buf == self.fill).all())
+
+
+def wide(t, pad, poison=float("nan")):
+    """[R, W] CPU tensor -> ([R, W + pad] device tensor whose extra columns hold `poison`, leading dimension)."""
+    t = t.contiguous()
+    full = torch.full((t.shape[0], t.shape[1] + pad), poison, dtype=t.dtype)
+    full[:, :t.shape[1]] = t
+    return full.to(_dev()), t.shape[1] + pad

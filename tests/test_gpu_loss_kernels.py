@@ -17,12 +17,11 @@ import torch
 
 from oracle import loss_ref
 from tests import loss_kernel_cases as K
+from tests.helpers import Out, wide
 from tests.loss_kernel_cases import check_float
 
 pytestmark = pytest.mark.gpu
 
-SENT = 64
-FILL = {torch.float32: -777.25, torch.int32: -77777, torch.uint8: 0xA5}
 F64, F32 = torch.float64, torch.float32
 
 
@@ -42,33 +41,6 @@ def _lib():
 def _stream():
     from segdino3d_amd import ops
     return ops._stream()
-
-
-class Out:
-    """n elements for the kernel plus SENT sentinel elements behind them."""
-
-    def __init__(self, n, dtype=torch.float32):
-        self.n, self.fill = int(n), FILL[dtype]
-        self.buf = torch.full((self.n + SENT,), self.fill, dtype=dtype, device=_dev())
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr()
-
-    def get(self, *shape):
-        assert bool((self.buf[self.n:] == self.fill).all()), "sentinels behind the output were overwritten"
-        return self.buf[:self.n].reshape(*shape).cpu()
-
-    def untouched(self):
-        return bool((self.buf == self.fill).all())
-
-
-def wide(t, pad, poison=float("nan")):
-    """[R, W] CPU tensor -> ([R, W + pad] device tensor whose extra columns hold `poison`, leading dimension)."""
-    t = t.contiguous()
-    full = torch.full((t.shape[0], t.shape[1] + pad), poison, dtype=t.dtype)
-    full[:, :t.shape[1]] = t
-    return full.to(_dev()), t.shape[1] + pad
 
 
 def up(t):
