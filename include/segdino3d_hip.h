@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 10
+#define SD3D_ABI_VERSION 11
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -449,54 +449,43 @@ int sd3d_box_refine_rows(const float* ref_points, const float* d_center, const f
                          const float* d_size, const float* ranges, const int32_t* row_scene, int normalize, int64_t Q, float* center,
                          float* size, float* size_metric, void* stream);
 /* Fused multi-head attention (replaces bmm + masked_fill + softmax + bmm of attention.py:361-385 and
- * nn.MultiheadAttention's SDPA at decoder :79).  Heads are 32-channel slices here (64-channel heads: the sd3d_attention_heads* entry
- * points below); nsrc = 2 concatenates
- * [q0|q1] . [k0|k1] per head (decoder :681-687).  mask_bits [Lq, ceil(Lk/32)]: bit = 1 -> blocked.
- * ws / ws_bytes: optional scratch (sd3d_attention_ws_bytes) that lets few-query launches split the keys over several
- * workgroups and merge the softmax states in a second pass; NULL = single pass. */
-size_t sd3d_attention_ws_bytes(int Lq, int H);
-int sd3d_attention(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1,
-                   int ldk1, const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale,
-                   float* out, int ldo, void* ws, size_t ws_bytes, void* stream);
-/* Same contract with Q, K, P and V rounded to bf16 for the two contractions (v_mfma_f32_32x32x16_bf16, fp32 accumulate;
- * scores, mask, softmax in fp32): the attention of the "bf16 decoder", BASELINE config #3. */
-int sd3d_attention_bf16(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1,
-                        int ldk1, const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale,
-                        float* out, int ldo, void* ws, size_t ws_bytes, void* stream);
-/* n <= SD3D_MAX_BATCH independent attentions of the same kind (heads, scale, one or two sources, fp32 / bf16 contractions) in ONE launch:
- * the decoder of a batched evaluation forward runs the scenes' cross- / self- / 2D-query attentions this way.  blockIdx.x runs over
- * the query tiles of all scenes; each scene keeps the waves per workgroup and the key split its own launch would have, so its rows are
- * the bits of sd3d_attention on that scene alone (scenes whose workgroup shapes differ are launched one by one inside the call).
- * ws: split workspace, scene i's sd3d_attention_ws_bytes(Lq_i, H) bytes back to back. */
+ * nn.MultiheadAttention's SDPA at decoder :79).  q / k / v / out hold H heads of head_dim channels side by side; head_dim is 32 or 64
+ * (one kernel body, the width a template parameter), any other width returns SD3D_ERR_ARG before anything is launched.  nsrc = 2
+ * (q1 / k1 given) concatenates [q0|q1] . [k0|k1] per head (decoder :681-687): the score contraction runs over head_dim channels per
+ * source.  mask_bits [Lq, ceil(Lk/32)]: bit = 1 -> blocked.
+ * lse: optional [H, Lq] log-sum-exp of the masked, scaled score rows (natural units; the backward pass needs it), NULL = not wanted.
+ * bf16 != 0: Q, K, P and V rounded to bf16 for the two contractions (v_mfma_f32_32x32x16_bf16, fp32 accumulate; scores, mask, softmax
+ * in fp32): the attention of the "bf16 decoder", BASELINE config #3.
+ * ws / ws_bytes: optional scratch (sd3d_attention_ws_bytes; 0 for an unsupported width) that lets few-query launches split the keys
+ * over several workgroups and merge the softmax states in a second pass; NULL = single pass.  One partial softmax state per (32-query
+ * tile, head, key split) is m[32], l[32], O[head_dim dv][32 q] in the log2 domain = 64 + 32 * head_dim floats, laid out
+ * [ceil(Lq/32)][H][ksplit] with ksplit <= 8.  The launcher splits the keys only as far as the workspace it was given holds (ksplit = 1
+ * without one) and never writes behind it.
+ * sd3d_attention_config: the waves per workgroup and the key split the launcher chooses for one attention given ws_bytes of split
+ * workspace (host-only, launches nothing). */
+size_t sd3d_attention_ws_bytes(int Lq, int H, int head_dim);
+int sd3d_attention(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                   const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
+                   float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, void* stream);
+int sd3d_attention_config(int Lq, int Lk, int H, int head_dim, size_t ws_bytes, int* waves_out, int* ksplit_out);
+/* n <= SD3D_MAX_BATCH independent attentions of the same kind (heads, width, scale, one or two sources, fp32 / bf16 contractions) in ONE
+ * launch: the decoder of a batched evaluation forward runs the scenes' cross- / self- / 2D-query attentions this way.  blockIdx.x runs
+ * over the query tiles of all scenes; each scene keeps the waves per workgroup and the key split its own launch would have, so its rows
+ * are the bits of sd3d_attention on that scene alone (scenes whose workgroup shapes differ are launched one by one inside the call).
+ * ws: split workspace, scene i's sd3d_attention_ws_bytes(Lq_i, H, head_dim) bytes back to back. */
 typedef struct sd3d_attn_job {
     const float *q0, *q1, *k0, *k1, *v;      /* q1 / k1 NULL for one source (all jobs alike) */
     const uint32_t* mask_bits;               /* [Lq, ceil(Lk / 32)] or NULL */
     float* out;
     int32_t ldq0, ldq1, ldk0, ldk1, ldv, ldo, Lq, Lk;
 } sd3d_attn_job;
-int sd3d_attention_batch(int n, const sd3d_attn_job* jobs, int H, float scale, int bf16, void* ws, size_t ws_bytes, void* stream);
-/* The same launch WITHOUT the pass that combines the key splits (its consumer does: sd3d_row_chain MERGE): on return scene i's rows
- * are final in its `out` where ksplit_out_host[i] == 1, and otherwise wait as partial softmax states [ceil(Lq/32)][H][ksplit][64 + 1024]
- * (m[32], l[32], O[32 dv][32 q], log2 domain) at ws + part_off_out_host[i] floats. */
+int sd3d_attention_batch(int n, const sd3d_attn_job* jobs, int H, int head_dim, float scale, int bf16, void* ws, size_t ws_bytes,
+                         void* stream);
+/* The same launch for 32-channel heads WITHOUT the pass that combines the key splits (its consumer does: sd3d_row_chain MERGE, built for
+ * that width): on return scene i's rows are final in its `out` where ksplit_out_host[i] == 1, and otherwise wait as partial softmax
+ * states [ceil(Lq/32)][H][ksplit][64 + 1024] (m[32], l[32], O[32 dv][32 q], log2 domain) at ws + part_off_out_host[i] floats. */
 int sd3d_attention_batch_parts(int n, const sd3d_attn_job* jobs, int H, float scale, int bf16, void* ws, size_t ws_bytes,
                                int32_t* ksplit_out_host, int64_t* part_off_out_host, void* stream);
-/* Attention with the head width as an argument: head_dim = 32 (the launches of the entry points above, bit for bit) or 64; any other
- * width returns SD3D_ERR_ARG before anything is launched.  q / k / v / out hold H heads of head_dim channels side by side; the score
- * contraction runs over head_dim channels per source.  lse: optional [H, Lq] log-sum-exp of the masked, scaled score rows (natural units;
- * sd3d_attention_lse), NULL = not wanted.  bf16 != 0: the contractions of sd3d_attention_bf16.
- * Split workspace (sd3d_attention_heads_ws_bytes; optional as above): one partial softmax state per (32-query tile, head, key split) is
- * m[32], l[32], O[head_dim dv][32 q] in the log2 domain = 64 + 32 * head_dim floats, laid out [ceil(Lq/32)][H][ksplit] with ksplit <= 8.
- * The launcher splits the keys only as far as the workspace it was given holds (ksplit = 1 without one) and never writes behind it.
- * sd3d_attention_heads_batch: sd3d_attention_batch at that width, scene i's sd3d_attention_heads_ws_bytes(Lq_i, H, head_dim) bytes back
- * to back in ws.  sd3d_attention_heads_config: the waves per workgroup and the key split the launcher chooses for one attention given
- * ws_bytes of split workspace (host-only, launches nothing). */
-size_t sd3d_attention_heads_ws_bytes(int Lq, int H, int head_dim);
-int sd3d_attention_heads(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
-                         const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
-                         float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, void* stream);
-int sd3d_attention_heads_batch(int n, const sd3d_attn_job* jobs, int H, int head_dim, float scale, int bf16, void* ws, size_t ws_bytes,
-                               void* stream);
-int sd3d_attention_heads_config(int Lq, int Lk, int H, int head_dim, size_t ws_bytes, int* waves_out, int* ksplit_out);
 /* _forward_head mask part (:567-572): bits = sigmoid(logits) < thr, dead rows reset to open. */
 int sd3d_mask_bits(const float* logits, int ld, int64_t Q, int S, float thr, uint32_t* bits, int nwords, void* stream);
 /* (dist < thr) of torch.cdist(p=1) (:721) as bits near[M, ceil(S/32)]. */
@@ -798,30 +787,17 @@ int sd3d_box_refine_backward(const float* d_center, const float* d_size_out, con
 int sd3d_sine_pe_mod_backward(const float* d_out, int ld_do, const float* xyz, int ld_xyz, int64_t n, const float* range, const float* dim_t,
                               const int8_t* axis, int d_pos, const float* mod_den, int ld_den, float* d_num, void* stream);
 
-/* Attention for training: sd3d_attention that also returns lse [H, Lq] = log sum exp of every masked,
- * scaled score row, and the backward pass (gradients of attention.py:361-385 / nn.MultiheadAttention, decoder :79):
- * given out, lse and d_out -> dq0 (dq1), dk0 (dk1), dv with the shapes / strides of their forward tensors.  Exact fp32
- * MFMA, P recomputed tile by tile, fixed summation order.  ws: sd3d_attention_backward_ws_bytes(Lq, H). */
-int sd3d_attention_lse(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1,
-                       int ldk1, const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale,
-                       float* out, int ldo, float* lse, void* ws, size_t ws_bytes, void* stream);
-/* bf16 forward (section "bf16 decoder") that keeps lse: mixed-precision training runs this forward and the fp32 backward below. */
-int sd3d_attention_lse_bf16(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1,
-                            int ldk1, const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale,
-                            float* out, int ldo, float* lse, void* ws, size_t ws_bytes, void* stream);
-size_t sd3d_attention_backward_ws_bytes(int Lq, int H);
+/* Attention for training: sd3d_attention with lse [H, Lq] = log sum exp of every masked, scaled score row kept
+ * (fp32 or, for mixed-precision training, the bf16 forward), and the backward pass (gradients of attention.py:361-385 /
+ * nn.MultiheadAttention, decoder :79): given out, lse and d_out -> dq0 (dq1), dk0 (dk1), dv with the shapes / strides of their forward
+ * tensors.  Exact fp32 MFMA, P recomputed tile by tile, fixed summation order.  head_dim: 32 or 64, else SD3D_ERR_ARG before anything is
+ * launched.  ws: sd3d_attention_backward_ws_bytes (one float per head and query, D = dO . O; 0 for an unsupported width). */
+size_t sd3d_attention_backward_ws_bytes(int Lq, int H, int head_dim);
 int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
-                            const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, float scale, const float* out, int ldo,
-                            const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0, float* dq1, int ld_dq1, float* dk0,
-                            int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes, void* stream);
-/* The backward pass with the head width as an argument (32 or 64 channels, else SD3D_ERR_ARG before anything is launched): gradients of
- * sd3d_attention_heads given its out and lse.  ws: sd3d_attention_heads_backward_ws_bytes (one float per head and query, D = dO . O). */
-size_t sd3d_attention_heads_backward_ws_bytes(int Lq, int H, int head_dim);
-int sd3d_attention_heads_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
-                                  const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
-                                  const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0,
-                                  float* dq1, int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws,
-                                  size_t ws_bytes, void* stream);
+                            const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
+                            const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0,
+                            float* dq1, int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws,
+                            size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Parameter update of a training iteration (csrc/optim.hip; segdino3d_amd/optim.py builds the tables): gradient-norm clipping, the AdamW

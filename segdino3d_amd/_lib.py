@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 
@@ -79,12 +79,8 @@ SIGNATURES = {
     "sd3d_sine_pe_rows": (_i, [_p, _i, _l, _p, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p]),
     "sd3d_fourier_pe_rows": (_i, [_p, _i, _l, _p, _p, _p, _i, _i, _p, _i, _p]),
     "sd3d_box_refine_rows": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _l, _p, _p, _p, _p]),
-    "sd3d_attention_batch": (_i, [_i, _p, _i, _f, _i, _p, _z, _p]),
     "sd3d_mask_bits_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _p]),
     "sd3d_dinox_mask_bits_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "sd3d_attention_ws_bytes": (_z, [_i, _i]),
-    "sd3d_attention": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _f, _p, _i, _p, _z, _p]),
-    "sd3d_attention_bf16": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _f, _p, _i, _p, _z, _p]),
     "sd3d_mask_bits": (_i, [_p, _i, _l, _i, _f, _p, _i, _p]),
     "sd3d_near_bits": (_i, [_p, _l, _p, _l, _f, _p, _i, _p]),
     "sd3d_dinox_mask_bits": (_i, [_p, _p, _i, _l, _l, _p, _i, _p]),
@@ -102,10 +98,10 @@ SIGNATURES = {
     "sd3d_nms_decay": (_i, [_p, _i, _p, _p, _i, _i, _f, _p, _p, _p, _p]),
     "sd3d_row_chain": (_i, [_p, _p]),
     "sd3d_row_chain_program_bytes": (_z, []),
-    "sd3d_attention_heads_ws_bytes": (_z, [_i, _i, _i]),
-    "sd3d_attention_heads": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _i, _p, _z, _p]),
-    "sd3d_attention_heads_batch": (_i, [_i, _p, _i, _i, _f, _i, _p, _z, _p]),
-    "sd3d_attention_heads_config": (_i, [_i, _i, _i, _i, _z, _p, _p]),
+    "sd3d_attention_ws_bytes": (_z, [_i, _i, _i]),
+    "sd3d_attention": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _i, _p, _z, _p]),
+    "sd3d_attention_batch": (_i, [_i, _p, _i, _i, _f, _i, _p, _z, _p]),
+    "sd3d_attention_config": (_i, [_i, _i, _i, _i, _z, _p, _p]),
     "sd3d_attention_batch_parts": (_i, [_i, _p, _i, _f, _i, _p, _z, _p, _p, _p]),
     "sd3d_pack_mask_rows": (_i, [_p, _l, _p, _i, _p, _l, _p]),
     "sd3d_unpack_bits_host": (_i, [_p, _l, _l, _l, _p]),
@@ -150,14 +146,9 @@ SIGNATURES = {
     "sd3d_layernorm_backward_ws_bytes": (_z, [_l, _i]),
     "sd3d_layernorm_backward": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _f, _l, _i, _i, _p, _i, _p, _p, _p, _z, _p]),
     "sd3d_sine_pe_mod_backward": (_i, [_p, _i, _p, _i, _l, _p, _p, _p, _i, _p, _i, _p, _p]),
-    "sd3d_attention_lse": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _f, _p, _i, _p, _p, _z, _p]),
-    "sd3d_attention_lse_bf16": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _f, _p, _i, _p, _p, _z, _p]),
-    "sd3d_attention_backward_ws_bytes": (_z, [_i, _i]),
-    "sd3d_attention_backward": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _f, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i,
-                                     _p, _i, _p, _z, _p]),
-    "sd3d_attention_heads_backward_ws_bytes": (_z, [_i, _i, _i]),
-    "sd3d_attention_heads_backward": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i,
-                                           _p, _i, _p, _i, _p, _z, _p]),
+    "sd3d_attention_backward_ws_bytes": (_z, [_i, _i, _i]),
+    "sd3d_attention_backward": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i,
+                                     _p, _i, _p, _i, _p, _z, _p]),
     "sd3d_semantic_loss_ws_bytes": (_z, [_i]),
     "sd3d_semantic_loss": (_i, [_p, _i, _i, _i, _i, _p, _i, _f, _p, _i, _p, _p, _z, _p]),
     "sd3d_mt_ws_bytes": (_z, [_i, _l]),

@@ -1130,8 +1130,8 @@ def attention_launch_config(Lq, Lk, num_heads, head_dim=32):
     import ctypes as C
     lib = _lib.load()
     nw, ks = C.c_int(0), C.c_int(0)
-    _lib.check(lib.sd3d_attention_heads_config(Lq, Lk, num_heads, head_dim, lib.sd3d_attention_heads_ws_bytes(Lq, num_heads, head_dim),
-                                               C.byref(nw), C.byref(ks)), "attention_launch_config")
+    _lib.check(lib.sd3d_attention_config(Lq, Lk, num_heads, head_dim, lib.sd3d_attention_ws_bytes(Lq, num_heads, head_dim),
+                                         C.byref(nw), C.byref(ks)), "attention_launch_config")
     return nw.value, ks.value
 
 
@@ -1153,16 +1153,10 @@ def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, out=N
         out = torch.empty(Lq, num_heads * D, dtype=torch.float32, device=q.device)
     elif tuple(out.shape) != (Lq, num_heads * D) or not out.is_contiguous() or out.dtype != torch.float32:
         raise ValueError("attention: `out` must be a contiguous fp32 [Lq, H * D] tensor")
-    if D != 32:
-        ws = _WS6.get(lib.sd3d_attention_heads_ws_bytes(Lq, num_heads, D), q.device)
-        _lib.check(lib.sd3d_attention_heads(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, _ptr(mask_bits, torch.int32, "mask_bits"),
-                                            Lq, Lk, num_heads, D, float(scale), _ptr(out), out.shape[1], None, 1 if bf16_decoder_active() else 0,
-                                            ws.data_ptr(), ws.numel(), _stream()), "attention")
-        return out
-    ws = _WS6.get(lib.sd3d_attention_ws_bytes(Lq, num_heads), q.device)
-    fn = lib.sd3d_attention_bf16 if bf16_decoder_active() else lib.sd3d_attention
-    _lib.check(fn(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, _ptr(mask_bits, torch.int32, "mask_bits"),
-                  Lq, Lk, num_heads, float(scale), _ptr(out), out.shape[1], ws.data_ptr(), ws.numel(), _stream()), "attention")
+    ws = _WS6.get(lib.sd3d_attention_ws_bytes(Lq, num_heads, D), q.device)
+    _lib.check(lib.sd3d_attention(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, _ptr(mask_bits, torch.int32, "mask_bits"),
+                                  Lq, Lk, num_heads, D, float(scale), _ptr(out), out.shape[1], None, 1 if bf16_decoder_active() else 0,
+                                  ws.data_ptr(), ws.numel(), _stream()), "attention")
     return out
 
 
@@ -1204,7 +1198,7 @@ def _attn_job_table(jobs, num_heads, name, strided_out):
                 raise ValueError(f"{name}: `out` must be a contiguous fp32 [Lq, H * D] tensor")
             po, ldo = out.data_ptr(), out.stride(0)
         tab[i] = (pq, pq2, pk, pk2, pv, 0 if bits is None else _ptr(bits, torch.int32, "mask_bits"), po, ldq, ldq2, ldk, ldk2, ldv, ldo, Lq, Lk)
-        nb += lib.sd3d_attention_ws_bytes(Lq, num_heads) if D == 32 else lib.sd3d_attention_heads_ws_bytes(Lq, num_heads, D)
+        nb += lib.sd3d_attention_ws_bytes(Lq, num_heads, D)
     return tab, nb, width
 
 
@@ -1214,11 +1208,7 @@ def attention_batch(jobs, num_heads, scale):
     lib = _lib.load()
     tab, nb, D = _attn_job_table(jobs, num_heads, "attention_batch", strided_out=False)
     ws = _WS6.get(nb, jobs[0][0].device)
-    if D != 32:
-        _lib.check(lib.sd3d_attention_heads_batch(len(jobs), tab.ctypes.data, num_heads, D, float(scale), 1 if bf16_decoder_active() else 0,
-                                                  ws.data_ptr(), ws.numel(), _stream()), "attention_batch")
-        return
-    _lib.check(lib.sd3d_attention_batch(len(jobs), tab.ctypes.data, num_heads, float(scale), 1 if bf16_decoder_active() else 0,
+    _lib.check(lib.sd3d_attention_batch(len(jobs), tab.ctypes.data, num_heads, D, float(scale), 1 if bf16_decoder_active() else 0,
                                         ws.data_ptr(), ws.numel(), _stream()), "attention_batch")
 
 

@@ -306,17 +306,10 @@ class _Attention(torch.autograd.Function):
         out = torch.empty(Lq, num_heads * D, dtype=torch.float32, device=q.device)
         lse = torch.empty(num_heads, Lq, dtype=torch.float32, device=q.device)
         bits = ops._ptr(mask_bits, torch.int32, "mask_bits")
-        if D != 32:
-            ws = _WS_ATT.get(lib.sd3d_attention_heads_ws_bytes(Lq, num_heads, D), q.device)
-            _lib.check(lib.sd3d_attention_heads(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, bits, Lq, Lk, num_heads, D, float(scale),
-                                                out.data_ptr(), out.shape[1], lse.data_ptr(), 1 if ops.bf16_decoder_active() else 0,
-                                                ws.data_ptr(), ws.numel(), ops._stream()), "attention_lse")
-        else:
-            ws = _WS_ATT.get(lib.sd3d_attention_ws_bytes(Lq, num_heads), q.device)
-            fn = lib.sd3d_attention_lse_bf16 if ops.bf16_decoder_active() else lib.sd3d_attention_lse
-            _lib.check(fn(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, bits,
-                          Lq, Lk, num_heads, float(scale), out.data_ptr(), out.shape[1], lse.data_ptr(), ws.data_ptr(),
-                          ws.numel(), ops._stream()), "attention_lse")
+        ws = _WS_ATT.get(lib.sd3d_attention_ws_bytes(Lq, num_heads, D), q.device)
+        _lib.check(lib.sd3d_attention(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, bits, Lq, Lk, num_heads, D, float(scale),
+                                      out.data_ptr(), out.shape[1], lse.data_ptr(), 1 if ops.bf16_decoder_active() else 0,
+                                      ws.data_ptr(), ws.numel(), ops._stream()), "attention_lse")
         ctx.save_for_backward(q, k, v, q2, k2, mask_bits, out, lse)
         ctx.H, ctx.D, ctx.scale = num_heads, D, float(scale)
         return out
@@ -337,16 +330,9 @@ class _Attention(torch.autograd.Function):
         if q2 is not None:
             pq2, ldq2 = ops._rows(q2.detach(), "q2"); pk2, ldk2 = ops._rows(k2.detach(), "k2")
         W = H * D
-        if D != 32:
-            ws = _WS_ATT2.get(lib.sd3d_attention_heads_backward_ws_bytes(Lq, H, D), dev)
-            _lib.check(lib.sd3d_attention_heads_backward(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, ops._ptr(bits, torch.int32, "mask_bits"), Lq,
-                                                         Lk, H, D, ctx.scale, out.data_ptr(), W, lse.data_ptr(), d_out.data_ptr(), W, dq.data_ptr(), W,
-                                                         ops._ptr(dq2), W, dk.data_ptr(), W, ops._ptr(dk2), W, dv.data_ptr(), W, ws.data_ptr(),
-                                                         ws.numel(), ops._stream()), "attention_backward")
-            return dq, dk, dv, None, None, None, dq2, dk2
-        ws = _WS_ATT2.get(lib.sd3d_attention_backward_ws_bytes(Lq, H), dev)
+        ws = _WS_ATT2.get(lib.sd3d_attention_backward_ws_bytes(Lq, H, D), dev)
         _lib.check(lib.sd3d_attention_backward(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, ops._ptr(bits, torch.int32, "mask_bits"), Lq, Lk, H,
-                                               ctx.scale, out.data_ptr(), W, lse.data_ptr(), d_out.data_ptr(), W, dq.data_ptr(), W,
+                                               D, ctx.scale, out.data_ptr(), W, lse.data_ptr(), d_out.data_ptr(), W, dq.data_ptr(), W,
                                                ops._ptr(dq2), W, dk.data_ptr(), W, ops._ptr(dk2), W, dv.data_ptr(), W, ws.data_ptr(), ws.numel(),
                                                ops._stream()), "attention_backward")
         return dq, dk, dv, None, None, None, dq2, dk2

@@ -65,22 +65,22 @@ def test_float64_attention_equals_the_oracle_attention_core():
 
 
 def test_c_entry_points_refuse_other_widths_and_report_the_split():
-    """Host-side contract of the width-carrying entry points (no launch): 16 / 128 channels -> SD3D_ERR_ARG and a zero workspace size;
+    """Host-side contract of the attention entry points (no launch): 16 / 128 channels -> SD3D_ERR_ARG and a zero workspace size;
     the partial-state layout (64 + 32 * head_dim floats, at most 8 splits) in the workspace size; the launcher's choice at the
     key-split shape of the GPU tests."""
     import ctypes as C
     from segdino3d_amd import _lib, ops
     lib = _lib.load()
     for bad in (16, 128, 0, 48):
-        assert lib.sd3d_attention_heads_ws_bytes(40, 2, bad) == 0 and lib.sd3d_attention_heads_backward_ws_bytes(40, 2, bad) == 0
-        assert lib.sd3d_attention_heads(None, 0, None, 0, None, 0, None, 0, None, 0, None, 8, 8, 2, bad, 1.0, None, 0, None, 0, None, 0, None) != 0
+        assert lib.sd3d_attention_ws_bytes(40, 2, bad) == 0 and lib.sd3d_attention_backward_ws_bytes(40, 2, bad) == 0
+        assert lib.sd3d_attention(None, 0, None, 0, None, 0, None, 0, None, 0, None, 8, 8, 2, bad, 1.0, None, 0, None, 0, None, 0, None) != 0
         assert b"32 or 64" in lib.sd3d_last_error()
-        assert lib.sd3d_attention_heads_batch(1, None, 2, bad, 1.0, 0, None, 0, None) != 0
-        assert lib.sd3d_attention_heads_backward(*([None, 0] * 5 + [None, 8, 8, 2, bad, 1.0, None, 0, None, None, 0] + [None, 0] * 5 + [None, 0, None])) != 0
+        assert lib.sd3d_attention_batch(1, None, 2, bad, 1.0, 0, None, 0, None) != 0
+        assert lib.sd3d_attention_backward(*([None, 0] * 5 + [None, 8, 8, 2, bad, 1.0, None, 0, None, None, 0] + [None, 0] * 5 + [None, 0, None])) != 0
         nw, ks = C.c_int(), C.c_int()
-        assert lib.sd3d_attention_heads_config(40, 1030, 2, bad, 1 << 20, C.byref(nw), C.byref(ks)) != 0
-    assert lib.sd3d_attention_heads_ws_bytes(40, 2, 64) == 2 * 2 * 8 * (64 + 2048) * 4
-    assert lib.sd3d_attention_heads_ws_bytes(40, 2, 32) == lib.sd3d_attention_ws_bytes(40, 2) == 2 * 2 * 8 * (64 + 1024) * 4
+        assert lib.sd3d_attention_config(40, 1030, 2, bad, 1 << 20, C.byref(nw), C.byref(ks)) != 0
+    assert lib.sd3d_attention_ws_bytes(40, 2, 64) == 2 * 2 * 8 * (64 + 2048) * 4
+    assert lib.sd3d_attention_ws_bytes(40, 2, 32) == 2 * 2 * 8 * (64 + 1024) * 4
     assert ops.attention_launch_config(40, 1030, 2, 64) == (4, 4)
     assert ops.attention_launch_config(200, 3000, 8, 32) == (4, 8) and ops.attention_launch_config(3000, 3000, 8, 32) == (8, 1)
     assert ops.attention_launch_config(3000, 3000, 4, 64) == (4, 1)

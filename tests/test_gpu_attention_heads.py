@@ -1,8 +1,9 @@
-"""Attention with 64-channel heads (csrc/dense.hip attention_wide_*, csrc/attention_bwd.hip attn_bwd_*_wide_kernel) against float64
-masked softmax attention (tests/attention_heads_case.py, pinned to the oracle in test_decoder_heads.py): forward fp32 / bf16, one and
-two score sources, bit-packed masks, key split and merge, the batched launch, the backward pass, and the 32-channel kernels against
-outputs recorded before the width became a parameter.  Bounds are those of test_gpu_train_dec.py / test_gpu_bf16_decoder.py for
-32-channel heads (relative to the output scale; the contraction only doubles)."""
+"""Attention with 64-channel heads (the W = 2 instantiations of csrc/dense.hip attention_body and of csrc/attention_bwd.hip
+attn_bwd_q_kernel / attn_bwd_kv_kernel) against float64 masked softmax attention (tests/attention_heads_case.py, pinned to the oracle in
+test_decoder_heads.py): forward fp32 / bf16, one and two score sources, bit-packed masks, key split and merge, the batched launch, the
+backward pass; and the kernels of both widths against device outputs recorded before the width became a template parameter of one body
+per pass.  Bounds are those of test_gpu_train_dec.py / test_gpu_bf16_decoder.py for 32-channel heads (relative to the output scale; the
+contraction only doubles)."""
 import functools
 import os
 
@@ -209,6 +210,22 @@ def test_narrow_heads_are_bitwise_unchanged(Lq, Lk, H, nsrc, bf16):
     recorded = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention32.npz"))[G.name(Lq, Lk, nsrc, bf16)]
     got = G.run(Lq, Lk, H, nsrc, bf16).numpy()
     assert got.shape == recorded.shape and np.array_equal(got.view(np.uint32), recorded.view(np.uint32))
+
+
+def test_attention_bits_are_unchanged():
+    """Forward with 64-channel heads (fp32, bf16) and the fp32 backward at both widths against what the same calls gave on the commit
+    before the two widths shared one kernel body per pass (tests/golden/attention_bits.npz, written there on the device by
+    tests/golden/make_golden_attention_bits.py; the two largest gradients are pinned by their SHA-256)."""
+    import sys
+    dev()
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_golden_attention_bits as G
+    recorded = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention_bits.npz"))
+    got = G.outputs()
+    assert sorted(got) == sorted(recorded.files)
+    for name, a in got.items():
+        want = recorded[name]
+        assert a.shape == want.shape and a.dtype == want.dtype and np.array_equal(a.view(np.uint32), want.view(np.uint32)), name
 
 
 def test_unsupported_widths_are_refused():

@@ -35,7 +35,7 @@ def parse(text):
 
 
 def pretty(mangled):
-    """_Z16attention_kernelILi2ELb0EEv10AttnParams -> attention_kernel<2, fp32>"""
+    """_Z16attention_kernelILi1ELi2ELb0EEv10AttnParams -> attention_kernel<1, 2, fp32> (<W, NSRC, dtype>; the backward kernels <W, NSRC>)"""
     m = re.match(r"_Z\d+([a-z_0-9]+?)(?:I((?:L[ib]\d+E)+)E)?v?\d", mangled)
     if not m:
         return mangled
