@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 11
+#define SD3D_ABI_VERSION 12
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -468,6 +468,19 @@ int sd3d_attention(const float* q0, int ldq0, const float* q1, int ldq1, const f
                    const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
                    float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, void* stream);
 int sd3d_attention_config(int Lq, int Lk, int H, int head_dim, size_t ws_bytes, int* waves_out, int* ksplit_out);
+/* sd3d_attention with dropout of rate p on the softmax probabilities, inside the kernel (nn.MultiheadAttention(dropout=p) in training,
+ * attention.py:383): out = (c K o softmax(S)) V with c = 1 / (1 - p); lse, the key split and its workspace are those of sd3d_attention.
+ * The keep mask K is a pure function of (key, call, head, q, k) (csrc/attention_dropout.h): Philox4x32-10 keyed by the two words at
+ * `key` (device memory) with the counter (k >> 2, q, head, call); element (head, q, k) takes output word k & 3 and is kept iff that
+ * word >= floor(p 2^32).  `call` tells the attentions of one step apart.  Neither the launch shape nor the head width enters, so
+ * sd3d_attention_dropout_backward regenerates the mask the forward drew and sd3d_attention_dropout_keep writes it out
+ * (keep[H, Lq, Lk] bytes, 1 = kept).  p == 0 runs sd3d_attention itself; p outside [0, 1), a NULL key or an unsupported head width
+ * returns SD3D_ERR_ARG before anything is launched. */
+int sd3d_attention_dropout(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                           const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
+                           float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, const uint32_t* key, int call, float p,
+                           void* stream);
+int sd3d_attention_dropout_keep(const uint32_t* key, int call, int H, int Lq, int Lk, float p, uint8_t* keep, void* stream);
 /* n <= SD3D_MAX_BATCH independent attentions of the same kind (heads, width, scale, one or two sources, fp32 / bf16 contractions) in ONE
  * launch: the decoder of a batched evaluation forward runs the scenes' cross- / self- / 2D-query attentions this way.  blockIdx.x runs
  * over the query tiles of all scenes; each scene keeps the waves per workgroup and the key split its own launch would have, so its rows
@@ -798,6 +811,13 @@ int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1
                             const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0,
                             float* dq1, int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws,
                             size_t ws_bytes, void* stream);
+/* The backward pass of sd3d_attention_dropout (same key, call and p; out and lse as that call left them): dV = (c K o P)^T dO,
+ * dP = c K o (dO V^T), dS = P o (dP - D) with D = dO . O as without dropout.  p == 0 is sd3d_attention_backward. */
+int sd3d_attention_dropout_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1,
+                                    int ldk1, const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim,
+                                    float scale, const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0,
+                                    int ld_dq0, float* dq1, int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv,
+                                    int ld_dv, void* ws, size_t ws_bytes, const uint32_t* key, int call, float p, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Parameter update of a training iteration (csrc/optim.hip; segdino3d_amd/optim.py builds the tables): gradient-norm clipping, the AdamW

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _lib = None
 
@@ -100,6 +100,8 @@ SIGNATURES = {
     "sd3d_row_chain_program_bytes": (_z, []),
     "sd3d_attention_ws_bytes": (_z, [_i, _i, _i]),
     "sd3d_attention": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _i, _p, _z, _p]),
+    "sd3d_attention_dropout": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _i, _p, _z, _p, _i, _f, _p]),
+    "sd3d_attention_dropout_keep": (_i, [_p, _i, _i, _i, _i, _f, _p, _p]),
     "sd3d_attention_batch": (_i, [_i, _p, _i, _i, _f, _i, _p, _z, _p]),
     "sd3d_attention_config": (_i, [_i, _i, _i, _i, _z, _p, _p]),
     "sd3d_attention_batch_parts": (_i, [_i, _p, _i, _f, _i, _p, _z, _p, _p, _p]),
@@ -149,6 +151,8 @@ SIGNATURES = {
     "sd3d_attention_backward_ws_bytes": (_z, [_i, _i, _i]),
     "sd3d_attention_backward": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i,
                                      _p, _i, _p, _i, _p, _z, _p]),
+    "sd3d_attention_dropout_backward": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i,
+                                     _p, _i, _p, _i, _p, _z, _p, _i, _f, _p]),
     "sd3d_semantic_loss_ws_bytes": (_z, [_i]),
     "sd3d_semantic_loss": (_i, [_p, _i, _i, _i, _i, _p, _i, _f, _p, _i, _p, _p, _z, _p]),
     "sd3d_mt_ws_bytes": (_z, [_i, _l]),

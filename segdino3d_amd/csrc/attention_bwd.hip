@@ -15,7 +15,12 @@
 // Partial sums of the waves are added through LDS in a fixed order: bit-reproducible, no atomics.
 // Heads of D = 32 W channels (W = 1 or 2): a 64-channel head contracts S and dP over two 32-channel blocks and keeps two 32-channel
 // accumulator tiles per gradient; its kernels run at most four waves per workgroup, so a wave may hold 512 registers.
+//
+// DROP (dropout on the probabilities, attention_dropout.h): with the keep mask K, c = 1 / (1 - p) and O = (c K o P) V
+//     dV = (c K o P)^T dO        dP = c K o (dO V^T)        dS = P o (dP - D),   D[q] = sum_k P c K (dO . v_k) = dO[q] . O[q]
+// so D is the same row statistic of the same saved out and lse, and the kernels only regenerate K from (key, call, head, q, k).
 #include "common.h"
+#include "attention_dropout.h"
 #include "../../include/segdino3d_hip.h"
 #include <math.h>
 #include <stdlib.h>
@@ -35,6 +40,7 @@ struct AttnBwdParams {
     float* dv; int ld_dv;
     int Lq, Lk, H;
     float scale;
+    AttnDrop drop;                            // read by the DROP instantiations only
 };
 
 __device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
@@ -47,7 +53,7 @@ __device__ __forceinline__ float prob_of(float s, float lse_log2) { return __bui
 // instruction streams of such a kernel (profiles/attention_heads.md).
 #define ATTN_BLK(w) (W == 1 ? 0 : (w))
 
-template <int W, int NSRC>
+template <int W, int NSRC, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const AttnBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];      // [nw][NSRC][32 W ch][32 q]
     constexpr int D = 32 * W;
@@ -79,6 +85,8 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const AttnBwdParams p) 
     dsum += __shfl_xor(dsum, 32);
     if (wave == 0 && h == 0 && q0 + i < p.Lq) p.dsum[(int64_t)head * p.Lq + q0 + i] = dsum;
     const float lse = p.lse[(int64_t)head * p.Lq + qi] * ABW_LOG2E;
+    uint32_t dkey0 = 0u, dkey1 = 0u;
+    if (DROP) { dkey0 = p.drop.key[0]; dkey1 = p.drop.key[1]; }
 
     f32x16 dQ[NSRC][W];
 #pragma unroll
@@ -108,6 +116,14 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const AttnBwdParams p) 
         }
         const uint32_t word = p.bits ? p.bits[(int64_t)qi * p.nwords + t] : 0u;
         float ds[16];
+        if (DROP) {                                     // register 4 g + c belongs to key kt0 + 8 g + 4 h + c, as in the forward kernel
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t keep = attn_keep4(dkey0, dkey1, p.drop.call, head, q0 + i, (kt0 >> 2) + 2 * g + h, p.drop.thr);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) dP[4 * g + c] = ((keep >> c) & 1u) ? dP[4 * g + c] * p.drop.c : 0.f;
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int kb = tile_row(r, h);
@@ -146,7 +162,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const AttnBwdParams p) 
 }
 
 // W = 1: up to eight waves per workgroup on a 128-register budget; W = 2: at most four, so a wave may hold 512 registers
-template <int W, int NSRC>
+template <int W, int NSRC, bool DROP>
 __global__ __launch_bounds__(W == 1 ? 512 : 256) void attn_bwd_kv_kernel(const AttnBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];      // [nw][NSRC + 1][32 W ch][32 keys]
     constexpr int D = 32 * W;
@@ -172,6 +188,8 @@ __global__ __launch_bounds__(W == 1 ? 512 : 256) void attn_bwd_kv_kernel(const A
 #pragma unroll
         for (int e = 0; e < 16 * W; ++e) vreg[e] = src[(e >> 4) * 32 + (e & 15)];
     }
+    uint32_t dkey0 = 0u, dkey1 = 0u;
+    if (DROP) { dkey0 = p.drop.key[0]; dkey1 = p.drop.key[1]; }
     f32x16 dK[NSRC][W], dV[W];
 #pragma unroll
     for (int w = 0; w < W; ++w)
@@ -205,6 +223,23 @@ __global__ __launch_bounds__(W == 1 ? 512 : 256) void attn_bwd_kv_kernel(const A
         // tile by the lane whose index is the query's row in the tile and handed round with readlane - not 48 loads per lane and tile
         const uint32_t my_word = p.bits ? p.bits[(int64_t)qr * p.nwords + ktile] : 0u;
         const float my_lse = p.lse[(int64_t)head * p.Lq + qr] * ABW_LOG2E, my_dsum = p.dsum[(int64_t)head * p.Lq + qr];
+        // DROP: the lane is a key and its 16 registers are queries; the four lanes of a quad share k >> 2, so quad lane a makes the four
+        // calls of queries qt0 + a + 8 g + 4 h (registers a + 4 g), packs their 16 keep bits into one word and the quad trades the words
+        // (16 calls per lane, each for one bit of its four words, cost 6 - 28 % more per backward: profiles/EXPERIMENTS.md)
+        uint32_t kbits[4] = {0u, 0u, 0u, 0u};
+        if (DROP) {
+            uint32_t mine_bits = 0u;
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                mine_bits |= attn_keep4(dkey0, dkey1, p.drop.call, head, qt0 + (j & 3) + 8 * g + 4 * h, (k0 + j) >> 2, p.drop.thr) << (4 * g);
+            // bit 4 g + c of quad lane a's word: (query register a + 4 g, key 4 kblk + c); quad_perm broadcasts of lanes 0 .. 3
+            kbits[0] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine_bits, 0x00, 0xF, 0xF, false);
+            kbits[1] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine_bits, 0x55, 0xF, 0xF, false);
+            kbits[2] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine_bits, 0xAA, 0xF, 0xF, false);
+            kbits[3] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine_bits, 0xFF, 0xF, 0xF, false);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) kbits[a] >>= (j & 3);
+        }
         float pr[16], ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -219,7 +254,13 @@ __global__ __launch_bounds__(W == 1 ? 512 : 256) void attn_bwd_kv_kernel(const A
             const int qq = qt0 + (h ? row1 : row0);
             const bool blocked = !key_ok || qq >= p.Lq || ((word >> j) & 1u);
             pr[r] = blocked ? 0.f : prob_of(S[r], lse);
-            ds[r] = pr[r] * (dP[r] - dsum);
+            if (DROP) {                                 // pr[r] becomes c K o P, what dV contracts
+                const bool keep = (kbits[r & 3] >> (4 * (r >> 2))) & 1u;
+                ds[r] = pr[r] * ((keep ? dP[r] * p.drop.c : 0.f) - dsum);
+                pr[r] = keep ? pr[r] * p.drop.c : 0.f;
+            } else {
+                ds[r] = pr[r] * (dP[r] - dsum);
+            }
         }
         // dV^T[dv][key] += sum_q dO[q][dv] P[q][key];  A = dO^T (row = dv = j), B = P
         {
@@ -277,11 +318,11 @@ size_t sd3d_attention_backward_ws_bytes(int Lq, int H, int head_dim) {
     return head_dim == 32 || head_dim == 64 ? align_up((size_t)Lq * H * sizeof(float), 256) : 0;
 }
 
-int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+static int attention_backward_impl(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
                             const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
                             const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0, float* dq1,
                             int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes,
-                            void* stream) {
+                            void* stream, const AttnDrop* drop) {
     if (head_dim != 32 && head_dim != 64) return sd3d_set_error(SD3D_ERR_ARG, "attention_backward: heads must be 32 or 64 channels wide");
     const int W = head_dim / 32;
     if ((q1 == nullptr) != (k1 == nullptr) || (q1 && (!dq1 || !dk1))) return sd3d_set_error(SD3D_ERR_ARG, "attention_backward: second source incomplete");
@@ -293,6 +334,7 @@ int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1
     p.lse = lse; p.dsum = (float*)ws;
     p.dq[0] = dq0; p.ld_dq[0] = ld_dq0; p.dq[1] = dq1; p.ld_dq[1] = ld_dq1; p.dk[0] = dk0; p.ld_dk[0] = ld_dk0; p.dk[1] = dk1; p.ld_dk[1] = ld_dk1;
     p.dv = dv; p.ld_dv = ld_dv; p.Lq = Lq; p.Lk = Lk; p.H = H; p.scale = scale;
+    p.drop = drop ? *drop : AttnDrop{nullptr, 0u, 0u, 1.f};
     const int nsrc = q1 ? 2 : 1;
     const int kt = (Lk + 31) / 32, qt = (Lq + 31) / 32;
     // kv kernel: 8 waves per workgroup when there are >= 32 query tiles and a 128-register budget (launch bounds 512): at the
@@ -302,25 +344,52 @@ int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1
     // 64-channel heads: at most four waves in the kv kernel too (its 512-register budget: 64 key + 32 value registers and six accumulator tiles)
     const int nwq = kt >= 8 ? 4 : (kt >= 2 ? 2 : 1), nwk = qt >= 32 && W == 1 ? 8 : (qt >= 8 ? 4 : (qt >= 2 ? 2 : 1));
     const dim3 gq((unsigned)qt, (unsigned)H), gk((unsigned)kt, (unsigned)H);
-    // the instantiations by [W - 1][nsrc - 1]
-    static void (*const q_kernels[2][2])(const AttnBwdParams) = {{attn_bwd_q_kernel<1, 1>, attn_bwd_q_kernel<1, 2>}, {attn_bwd_q_kernel<2, 1>, attn_bwd_q_kernel<2, 2>}};
-    static void (*const kv_kernels[2][2])(const AttnBwdParams) = {{attn_bwd_kv_kernel<1, 1>, attn_bwd_kv_kernel<1, 2>}, {attn_bwd_kv_kernel<2, 1>, attn_bwd_kv_kernel<2, 2>}};
+    // the instantiations by [dropout][W - 1][nsrc - 1]
+#define ABW_TABLE(K) {{{K<1, 1, false>, K<1, 2, false>}, {K<2, 1, false>, K<2, 2, false>}}, {{K<1, 1, true>, K<1, 2, true>}, {K<2, 1, true>, K<2, 2, true>}}}
+    static void (*const q_kernels[2][2][2])(const AttnBwdParams) = ABW_TABLE(attn_bwd_q_kernel);
+    static void (*const kv_kernels[2][2][2])(const AttnBwdParams) = ABW_TABLE(attn_bwd_kv_kernel);
+#undef ABW_TABLE
     static std::atomic<bool> attr_set[64];                    // per device: a function attribute belongs to the current device
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return sd3d_set_error(SD3D_ERR_LAUNCH, "attention_backward: no device");
     if (!attr_set[dev].load(std::memory_order_relaxed)) {     // the launches that reach or pass the 64 KiB default of dynamic LDS
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 2 * 4096);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 3 * 4096);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 3 * 8192);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_q_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 8192);
+        for (int d = 0; d < 2; ++d) {
+            (void)hipFuncSetAttribute((const void*)kv_kernels[d][0][0], hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 2 * 4096);
+            (void)hipFuncSetAttribute((const void*)kv_kernels[d][0][1], hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 3 * 4096);
+            (void)hipFuncSetAttribute((const void*)kv_kernels[d][1][1], hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 3 * 8192);
+            (void)hipFuncSetAttribute((const void*)q_kernels[d][1][1], hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 8192);
+        }
         attr_set[dev].store(true, std::memory_order_relaxed);
     }
     // LDS: nw waves x accumulators (nsrc in the q kernel, nsrc + 1 in the kv kernel) x 4 W KiB
     const size_t tile = (size_t)W * 4096;
-    hipLaunchKernelGGL(q_kernels[W - 1][nsrc - 1], gq, dim3(64 * nwq), (size_t)nwq * nsrc * tile, ST, p);
-    hipLaunchKernelGGL(kv_kernels[W - 1][nsrc - 1], gk, dim3(64 * nwk), (size_t)nwk * (nsrc + 1) * tile, ST, p);
+    const int dropping = drop ? 1 : 0;
+    hipLaunchKernelGGL(q_kernels[dropping][W - 1][nsrc - 1], gq, dim3(64 * nwq), (size_t)nwq * nsrc * tile, ST, p);
+    hipLaunchKernelGGL(kv_kernels[dropping][W - 1][nsrc - 1], gk, dim3(64 * nwk), (size_t)nwk * (nsrc + 1) * tile, ST, p);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
+}
+
+int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                            const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
+                            const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0, float* dq1,
+                            int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes,
+                            void* stream) {
+    return attention_backward_impl(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, head_dim, scale, out, ldo, lse, d_out, ld_do,
+                                   dq0, ld_dq0, dq1, ld_dq1, dk0, ld_dk0, dk1, ld_dk1, dv, ld_dv, ws, ws_bytes, stream, nullptr);
+}
+
+// backward of sd3d_attention_dropout with the same key, call and p: the kernels regenerate the keep mask.  p == 0 is sd3d_attention_backward.
+int sd3d_attention_dropout_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                                    const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
+                                    const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0,
+                                    float* dq1, int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws,
+                                    size_t ws_bytes, const uint32_t* key, int call, float p, void* stream) {
+    if (!(p >= 0.f && p < 1.f)) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout_backward: p must lie in [0, 1)");
+    if (!key) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout_backward: key missing");
+    const AttnDrop dr = {key, (uint32_t)call, attn_drop_threshold(p), 1.f / (1.f - p)};
+    return attention_backward_impl(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, head_dim, scale, out, ldo, lse, d_out, ld_do,
+                                   dq0, ld_dq0, dq1, ld_dq1, dk0, ld_dk0, dk1, ld_dk1, dv, ld_dv, ws, ws_bytes, stream, p == 0.f ? nullptr : &dr);
 }
 
 }  // extern "C"

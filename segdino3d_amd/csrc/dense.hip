@@ -8,6 +8,7 @@
 //   near_bits / dinox_mask_bits : boolean (mask . distance) product as AND/any over bit words (K19)
 //   box_refine       : iterative centre / size refinement (:735-759)
 #include "common.h"
+#include "attention_dropout.h"
 #include "../../include/segdino3d_hip.h"
 
 __device__ static inline float wsum(float v) {
@@ -370,8 +371,12 @@ typedef __bf16 abf16x8 __attribute__((ext_vector_type(8)));
 // template is instantiated, so the array is promoted to registers before the w loops unroll, as a single tile written without a
 // loop would be: the W = 1 kernels are then the instruction streams of a 32-channel-only body (profiles/attention_heads.md).
 #define ATTN_BLK(w) (W == 1 ? 0 : (w))
-template <int W, int NSRC, bool BF16>
-__device__ __forceinline__ void attention_body(const AttnParams& p, const int bx, float* smem) {
+// DROP: dropout on the probabilities (attention_dropout.h).  The keep mask multiplies the tile's probabilities AFTER they are summed into
+// l, so m, l, the partial states of a key split, the merge pass and lse are those of the attention without dropout (the reference
+// normalises before it drops, attention.py:381-383) and only the O^T contraction sees c K o P.  A lane is a query and holds four runs of
+// four consecutive keys of the tile: four Philox calls per lane and key tile.
+template <int W, int NSRC, bool BF16, bool DROP = false>
+__device__ __forceinline__ void attention_body(const AttnParams& p, const int bx, float* smem, const AttnDrop& dr = AttnDrop{}) {
     constexpr int D = 32 * W;                                   // channels per head: W blocks of 32
     constexpr int PART = 64 + 1024 * W;                         // floats of one partial softmax state
     if ((int)blockIdx.z >= p.ksplit) return;                   // (a batched launch: this scene splits its keys fewer ways than the widest)
@@ -409,6 +414,8 @@ __device__ __forceinline__ void attention_body(const AttnParams& p, const int bx
 #pragma unroll
         for (int r = 0; r < 16; ++r) O[ATTN_BLK(w)][r] = 0.f;
     float m = -INFINITY, l = 0.f;                       // running max (log2 units) and sum
+    uint32_t dkey0 = 0u, dkey1 = 0u;
+    if (DROP) { dkey0 = dr.key[0]; dkey1 = dr.key[1]; }
 
     const int ntiles = (p.Lk + 31) >> 5;
     const int tstep = nw * p.ksplit;
@@ -497,6 +504,14 @@ __device__ __forceinline__ void attention_body(const AttnParams& p, const int bx
             l = l * alpha + ls;
             m = mn;
         }
+        if (DROP) {                                     // pr[4 g + c] belongs to key kt0 + 8 g + 4 h + c: keys 4 kblk .. 4 kblk + 3
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t keep = attn_keep4(dkey0, dkey1, dr.call, head, q0 + i, (kt0 >> 2) + 2 * g + h, dr.thr);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) pr[4 * g + c] = ((keep >> c) & 1u) ? pr[4 * g + c] * dr.c : 0.f;
+            }
+        }
         if (__ballot(alpha != 1.f) != 0ull) {           // the running maxima settle after a few tiles: no rescale, no dependency on O
 #pragma unroll
             for (int w = 0; w < W; ++w)
@@ -570,6 +585,13 @@ template <int W, int NSRC, bool BF16>
 __global__ __launch_bounds__(W == 1 ? 512 : 256) void attention_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     attention_body<W, NSRC, BF16>(p, blockIdx.x, smem);
+}
+
+// the same workgroups with dropout on the probabilities (training, one scene per launch)
+template <int W, int NSRC, bool BF16>
+__global__ __launch_bounds__(W == 1 ? 512 : 256) void attention_dropout_kernel(const AttnParams p, const AttnDrop dr) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    attention_body<W, NSRC, BF16, true>(p, blockIdx.x, smem, dr);
 }
 
 // Several scenes' attentions in ONE launch (the decoder of a batched evaluation forward): blockIdx.x runs over the query tiles of all
@@ -673,9 +695,12 @@ static void attention_config(int Lq, int Lk, int H, int W, bool have_ws, size_t 
 #define ATTN_TABLE(K) {{{K<1, 1, false>, K<1, 1, true>}, {K<1, 2, false>, K<1, 2, true>}}, {{K<2, 1, false>, K<2, 1, true>}, {K<2, 2, false>, K<2, 2, true>}}}
 static void (*const attn_scene_kernels[2][2][2])(const AttnParams) = ATTN_TABLE(attention_kernel);
 static void (*const attn_batch_kernels[2][2][2])(const AttnBatch) = ATTN_TABLE(attention_batch_kernel);
+static void (*const attn_dropout_kernels[2][2][2])(const AttnParams, const AttnDrop) = ATTN_TABLE(attention_dropout_kernel);
 #undef ATTN_TABLE
 
-static int launch_attention(const AttnParams& p_in, int nsrc, int W, void* ws, size_t ws_bytes, hipStream_t st, bool merge = true) {
+// dr: dropout on the probabilities (same grid, waves and key split; the merge pass is the plain one), nullptr = none
+static int launch_attention(const AttnParams& p_in, int nsrc, int W, void* ws, size_t ws_bytes, hipStream_t st, bool merge = true,
+                            const AttnDrop* dr = nullptr) {
     AttnParams p = p_in;
     if (W != 1 && W != 2) return sd3d_set_error(SD3D_ERR_ARG, "attention: heads must be 32 or 64 channels wide");
     if (nsrc != 1 && nsrc != 2) return sd3d_set_error(SD3D_ERR_ARG, "attention: nsrc must be 1 or 2");
@@ -688,7 +713,8 @@ static int launch_attention(const AttnParams& p_in, int nsrc, int W, void* ws, s
     p.part = (float*)ws;
     const dim3 grid((unsigned)cdiv(p.Lq, 32), (unsigned)p.H, (unsigned)ks), block(64 * nw);
     const size_t sm = (size_t)nw * attention_part_floats(W) * sizeof(float);
-    hipLaunchKernelGGL(attn_scene_kernels[W - 1][nsrc - 1][p.bf16 ? 1 : 0], grid, block, sm, st, p);
+    if (dr) hipLaunchKernelGGL(attn_dropout_kernels[W - 1][nsrc - 1][p.bf16 ? 1 : 0], grid, block, sm, st, p, *dr);
+    else hipLaunchKernelGGL(attn_scene_kernels[W - 1][nsrc - 1][p.bf16 ? 1 : 0], grid, block, sm, st, p);
     if (ks > 1 && merge)
         hipLaunchKernelGGL(W == 1 ? attention_merge_kernel<1> : attention_merge_kernel<2>, dim3((unsigned)cdiv(p.Lq, 32), (unsigned)p.H), dim3(256), 0, st, p);
     SD3D_CHECK_LAUNCH();
@@ -773,6 +799,45 @@ extern "C" int sd3d_attention(const float* q0, int ldq0, const float* q1, int ld
     if ((q1 == nullptr) != (k1 == nullptr)) return sd3d_set_error(SD3D_ERR_ARG, "attention: q1 and k1 must be given together");
     const AttnParams p = attn_params(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, bf16, lse);
     return launch_attention(p, q1 ? 2 : 1, W, ws, ws_bytes, (hipStream_t)stream);
+}
+
+
+// sd3d_attention with dropout of rate p on the probabilities (training).  p == 0 is sd3d_attention itself.
+extern "C" int sd3d_attention_dropout(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+                                      const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
+                                      float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, const uint32_t* key, int call,
+                                      float p, void* stream) {
+    if (!(p >= 0.f && p < 1.f)) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout: p must lie in [0, 1)");
+    if (!key) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout: key missing");
+    if (p == 0.f)
+        return sd3d_attention(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, head_dim, scale, out, ldo, lse, bf16, ws, ws_bytes, stream);
+    const int W = attention_width(head_dim);
+    if (!W) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout: heads must be 32 or 64 channels wide");
+    if ((q1 == nullptr) != (k1 == nullptr)) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout: q1 and k1 must be given together");
+    const AttnParams ap = attn_params(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, bf16, lse);
+    const AttnDrop dr = {key, (uint32_t)call, attn_drop_threshold(p), 1.f / (1.f - p)};
+    return launch_attention(ap, q1 ? 2 : 1, W, ws, ws_bytes, (hipStream_t)stream, true, &dr);
+}
+
+// the keep mask alone, keep[H, Lq, Lk] bytes (1 = kept): one thread per (head, query, four consecutive keys)
+__global__ __launch_bounds__(256) void attention_dropout_keep_kernel(const AttnDrop dr, int H, int Lq, int Lk, uint8_t* __restrict__ keep) {
+    const int nblk = (Lk + 3) >> 2;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)H * Lq * nblk) return;
+    const int kblk = (int)(e % nblk), q = (int)((e / nblk) % Lq), head = (int)(e / ((int64_t)nblk * Lq));
+    const uint32_t bits = attn_keep4(dr.key[0], dr.key[1], dr.call, head, q, kblk, dr.thr);
+    uint8_t* dst = keep + ((int64_t)head * Lq + q) * Lk;
+    for (int c = 0; c < 4; ++c)
+        if (4 * kblk + c < Lk) dst[4 * kblk + c] = (uint8_t)((bits >> c) & 1u);
+}
+extern "C" int sd3d_attention_dropout_keep(const uint32_t* key, int call, int H, int Lq, int Lk, float p, uint8_t* keep, void* stream) {
+    if (!(p >= 0.f && p < 1.f)) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout_keep: p must lie in [0, 1)");
+    if (!key || !keep || H <= 0 || Lq <= 0 || Lk <= 0) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout_keep: key, output and positive sizes needed");
+    const AttnDrop dr = {key, (uint32_t)call, attn_drop_threshold(p), 1.f / (1.f - p)};
+    const int64_t n = (int64_t)H * Lq * ((Lk + 3) / 4);
+    hipLaunchKernelGGL(attention_dropout_keep_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, dr, H, Lq, Lk, keep);
+    SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
 }
 
 static int attention_batch_impl(int n, const sd3d_attn_job* jobs, int H, int W, float scale, int bf16, void* ws, size_t ws_bytes, void* stream,

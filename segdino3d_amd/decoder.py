@@ -237,8 +237,16 @@ class _TrainF(_EvalF):
     def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, keys=None):
         from . import train_dec
         p = getattr(_F_TLS, "p", 0.0)
-        if p > 0.0:                                             # nn.MultiheadAttention(dropout=p): dropout on the probabilities
-            return train_dec.attention_dropout(q, k, v, num_heads, scale, mask_bits=mask_bits, q2=q2, k2=k2, p=p)
+        if p > 0.0:
+            # nn.MultiheadAttention(dropout=p): dropout on the probabilities, inside the fused kernels.  The key is the running
+            # forward's (drawn once by ScanNetQueryDecoder.forward), `call` numbers its attentions across the scenes of a batch.
+            # SD3D_ATTN_DROPOUT=explicit: the same mask on explicitly formed probabilities, as a cross-check
+            key, call = _F_TLS.key, _F_TLS.call
+            _F_TLS.call = call + 1
+            if os.environ.get("SD3D_ATTN_DROPOUT", "") == "explicit":
+                keep = ops.attention_dropout_keep(key, call, num_heads, q.shape[0], k.shape[0], p)
+                return train_dec.attention_dropout(q, k, v, num_heads, scale, mask_bits=mask_bits, q2=q2, k2=k2, p=p, keep=keep)
+            return train_dec.attention(q, k, v, num_heads, scale, mask_bits=mask_bits, q2=q2, k2=k2, dropout_p=p, key=key, call=call)
         return train_dec.attention(q, k, v, num_heads, scale, mask_bits=mask_bits, q2=q2, k2=k2)
 
     @staticmethod
@@ -407,7 +415,7 @@ class ScanNetQueryDecoder(DerivedWeights):
             self.out_score = nn.Sequential(nn.Linear(d_model, d_model), nn.ReLU(), nn.Linear(d_model, 1))
         self.pos_type = pos_type
         # nn.Dropout is the identity in evaluation; training with p > 0 (no shipped config) drops between the autograd nodes with
-        # torch's generator and forms the attention probabilities explicitly (train_dec.attention_dropout)
+        # torch's generator and on the attention probabilities inside the fused kernels (train_dec.attention, dropout_p)
         self.dropout = float(dropout)
         # "fp32" (default, BASELINE config #2) or "bf16" (config #3: projections and both attention contractions on the bf16
         # MFMA with fp32 accumulation; LayerNorm, softmax, positional encodings, mask logits and thresholds stay fp32).  Not a
@@ -1051,14 +1059,21 @@ class ScanNetQueryDecoder(DerivedWeights):
     def forward(self, x, sp_pos=None, sp_pos_wo_elastic=None, queries=None, queries_pos=None, dinox_queries=None,
                 dinox_query_pos=None, scene_range=None):
         prev, prev_p = getattr(_F_TLS, "f", _EvalF), getattr(_F_TLS, "p", 0.0)
+        prev_key, prev_call = getattr(_F_TLS, "key", None), getattr(_F_TLS, "call", 0)
         # train mode drops under no_grad too (nn.Dropout looks at .training only): the autograd nodes run fine without a graph
         _F_TLS.f = _TrainF if (self.training and (torch.is_grad_enabled() or self.dropout > 0.0)) else _EvalF
         _F_TLS.p = self.dropout if _F_TLS.f is _TrainF else 0.0
+        if _F_TLS.p > 0.0:
+            # the key of this forward's attention dropout: two words from torch's device generator (torch.manual_seed governs them, no
+            # host read-back, the same draw under no_grad); the attentions of the forward count `call` up from 0
+            _F_TLS.key = torch.randint(-2 ** 31, 2 ** 31, (2,), dtype=torch.int32, device=x[0].device)
+            _F_TLS.call = 0
         try:
             with ops.bf16_decoder_scope(self.compute_dtype == "bf16"):      # training: bf16 forward and backward products of the projections
                 return self._forward(x, sp_pos, sp_pos_wo_elastic, queries, queries_pos, dinox_queries, dinox_query_pos, scene_range)
         finally:
             _F_TLS.f, _F_TLS.p = prev, prev_p
+            _F_TLS.key, _F_TLS.call = prev_key, prev_call
 
     def _forward(self, x, sp_pos, sp_pos_wo_elastic, queries, queries_pos, dinox_queries, dinox_query_pos, scene_range):
         n = len(x)

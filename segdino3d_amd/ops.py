@@ -1202,6 +1202,19 @@ def _attn_job_table(jobs, num_heads, name, strided_out):
     return tab, nb, width
 
 
+def attention_dropout_keep(key, call, H, Lq, Lk, p):
+    """The keep mask of attention dropout (csrc/attention_dropout.h) as bool [H, Lq, Lk]: what `train_dec.attention(..., dropout_p=p,
+    key=key, call=call)` keeps inside its kernels.  key: two int32 words on the device."""
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"attention_dropout_keep: p must lie in [0, 1), got {p}")
+    _want_shape(key, [(2,)], "attention_dropout_keep: key")
+    lib = _lib.load()
+    keep = torch.empty(int(H), int(Lq), int(Lk), dtype=torch.uint8, device=key.device)
+    _lib.check(lib.sd3d_attention_dropout_keep(_ptr(key, torch.int32, "key"), int(call), int(H), int(Lq), int(Lk), float(p), keep.data_ptr(),
+                                               _stream()), "attention_dropout_keep")
+    return keep.bool()
+
+
 def attention_batch(jobs, num_heads, scale):
     """jobs: list of (q, k, v, mask_bits | None, q2 | None, k2 | None, out) - the same attention for several scenes in ONE launch
     (sd3d_attention_batch): per scene the rows are the bits of `attention` on that scene alone."""

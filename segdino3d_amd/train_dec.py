@@ -338,9 +338,67 @@ class _Attention(torch.autograd.Function):
         return dq, dk, dv, None, None, None, dq2, dk2
 
 
-def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None):
-    """Differentiable `ops.attention` (fp32): gradients for q, k, v and the optional second source q2 / k2."""
-    return _Attention.apply(q, k, v, num_heads, scale, mask_bits, q2, k2)
+def _attn_sources(q, k, v, q2, k2):
+    """(q, ldq, q2, ldq2, k, ldk, k2, ldk2, v, ldv): the leading arguments of the sd3d_attention* family"""
+    pq, ldq = ops._rows(q.detach(), "q"); pk, ldk = ops._rows(k.detach(), "k"); pv, ldv = ops._rows(v.detach(), "v")
+    pq2, ldq2, pk2, ldk2 = None, 0, None, 0
+    if q2 is not None:
+        pq2, ldq2 = ops._rows(q2.detach(), "q2"); pk2, ldk2 = ops._rows(k2.detach(), "k2")
+    return pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv
+
+
+class _AttentionDropout(torch.autograd.Function):
+    """`_Attention` with dropout of rate p on the probabilities inside the kernels: the forward keeps what `_Attention` keeps (out, lse)
+    plus the key and the call number, and the backward kernels regenerate the keep mask from them."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, num_heads, scale, mask_bits, q2, k2, p, key, call):
+        lib = _lib.load()
+        Lq, Lk = q.shape[0], k.shape[0]
+        D = ops.head_width(q, v, num_heads, "attention")
+        out = torch.empty(Lq, num_heads * D, dtype=torch.float32, device=q.device)
+        lse = torch.empty(num_heads, Lq, dtype=torch.float32, device=q.device)
+        ws = _WS_ATT.get(lib.sd3d_attention_ws_bytes(Lq, num_heads, D), q.device)
+        _lib.check(lib.sd3d_attention_dropout(*_attn_sources(q, k, v, q2, k2), ops._ptr(mask_bits, torch.int32, "mask_bits"), Lq, Lk, num_heads, D,
+                                              float(scale), out.data_ptr(), out.shape[1], lse.data_ptr(), 1 if ops.bf16_decoder_active() else 0,
+                                              ws.data_ptr(), ws.numel(), ops._ptr(key, torch.int32, "key"), call, p, ops._stream()),
+                   "attention_dropout")
+        ctx.save_for_backward(q, k, v, q2, k2, mask_bits, out, lse, key)
+        ctx.H, ctx.D, ctx.scale, ctx.p, ctx.call = num_heads, D, float(scale), p, call
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        lib = _lib.load()
+        q, k, v, q2, k2, bits, out, lse, key = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        Lq, Lk, H, D = q.shape[0], k.shape[0], ctx.H, ctx.D
+        W = H * D
+        new = lambda n: torch.empty(n, W, dtype=torch.float32, device=q.device)
+        dq, dk, dv = new(Lq), new(Lk), new(Lk)
+        dq2, dk2 = (new(Lq), new(Lk)) if q2 is not None else (None, None)
+        ws = _WS_ATT2.get(lib.sd3d_attention_backward_ws_bytes(Lq, H, D), q.device)
+        _lib.check(lib.sd3d_attention_dropout_backward(*_attn_sources(q, k, v, q2, k2), ops._ptr(bits, torch.int32, "mask_bits"), Lq, Lk, H, D, ctx.scale,
+                                                       out.data_ptr(), W, lse.data_ptr(), d_out.data_ptr(), W, dq.data_ptr(), W, ops._ptr(dq2), W,
+                                                       dk.data_ptr(), W, ops._ptr(dk2), W, dv.data_ptr(), W, ws.data_ptr(), ws.numel(),
+                                                       ops._ptr(key, torch.int32, "key"), ctx.call, ctx.p, ops._stream()), "attention_dropout_backward")
+        return dq, dk, dv, None, None, None, dq2, dk2, None, None, None
+
+
+def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, dropout_p=0.0, key=None, call=0):
+    """Differentiable `ops.attention` (fp32): gradients for q, k, v and the optional second source q2 / k2.
+    dropout_p > 0: dropout on the softmax probabilities inside the kernels (`nn.MultiheadAttention(dropout=p)` in training); the keep
+    mask is a function of (key, call, head, query, key index) alone - `key` two int32 words on the device, `call` the number of this
+    attention within the step - and `ops.attention_dropout_keep` returns it."""
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"attention: dropout_p must lie in [0, 1), got {dropout_p}")
+    if dropout_p == 0.0:
+        return _Attention.apply(q, k, v, num_heads, scale, mask_bits, q2, k2)
+    if key is None:
+        raise ValueError("attention: dropout_p > 0 needs a key (two int32 words on the device)")
+    ops._want_shape(key, [(2,)], "attention: key")
+    return _AttentionDropout.apply(q, k, v, num_heads, scale, mask_bits, q2, k2, dropout_p, key, int(call))
 
 
 class _SplitCols(torch.autograd.Function):
@@ -371,12 +429,13 @@ def split_cols(t, width):
     return list(_SplitCols.apply(t, width))
 
 
-def attention_dropout(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, p=0.0):
+def attention_dropout(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, p=0.0, keep=None):
     """Attention with dropout on the softmax probabilities - what `nn.MultiheadAttention(dropout=p)` does in training
-    (`instance_seg_3d_decoder.py:48-49, 128-129`).  The fused kernel has no random stream, so for p > 0 - no shipped config,
-    `configs/models/base_3d.py:30` is 0.0 - the probabilities are formed explicitly on the device ([H, Lq, Lk] fp32: 19 MB at
-    200 x 3000, 288 MB at 3000 x 3000) and torch's dropout and autograd carry the rest.  Same arguments as `attention`;
-    bit = 1 in mask_bits blocks a key."""
+    (`instance_seg_3d_decoder.py:48-49, 128-129`) - with the probabilities formed explicitly on the device ([H, Lq, Lk] fp32: 19 MB
+    at 200 x 3000, 288 MB at 3000 x 3000) and torch's autograd carrying the rest: the cross-check of `attention(..., dropout_p=p)`,
+    which drops inside the fused kernels.  Same arguments as `attention`; bit = 1 in mask_bits blocks a key.
+    keep (bool [H, Lq, Lk], `ops.attention_dropout_keep`): the elements to keep, scaled by 1 / (1 - p) - the fused path's twin on
+    the same bits; None: torch's dropout draws them."""
     Lq, Lk, H = q.shape[0], k.shape[0], num_heads
     heads = lambda t, L: t.reshape(L, H, -1).transpose(0, 1)  # noqa: E731   [H, L, width / H]
     s = heads(q, Lq) @ heads(k, Lk).transpose(1, 2)
@@ -387,7 +446,11 @@ def attention_dropout(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=Non
         cols = torch.arange(Lk, device=q.device)
         blocked = (mask_bits[:, cols >> 5] >> (cols & 31)) & 1             # [Lq, Lk]
         s = s.masked_fill(blocked.bool().unsqueeze(0), float("-inf"))
-    prob = torch.nn.functional.dropout(torch.softmax(s, dim=-1), p, training=True)
+    prob = torch.softmax(s, dim=-1)
+    if keep is None:
+        prob = torch.nn.functional.dropout(prob, p, training=True)
+    else:
+        prob = prob * (keep.to(prob.dtype) * (1.0 / (1.0 - p)))
     return (prob @ heads(v, Lk)).transpose(0, 1).reshape(Lq, -1)
 
 

@@ -35,12 +35,14 @@ def parse(text):
 
 
 def pretty(mangled):
-    """_Z16attention_kernelILi1ELi2ELb0EEv10AttnParams -> attention_kernel<1, 2, fp32> (<W, NSRC, dtype>; the backward kernels <W, NSRC>)"""
+    """_Z16attention_kernelILi1ELi2ELb0EEv10AttnParams -> attention_kernel<1, 2, fp32> (<W, NSRC, dtype>; the dropout forward has its own
+    kernel name; the backward kernels are <W, NSRC, DROP>: attn_bwd_q_kernel<1, 2, drop> regenerates the keep mask)"""
     m = re.match(r"_Z\d+([a-z_0-9]+?)(?:I((?:L[ib]\d+E)+)E)?v?\d", mangled)
     if not m:
         return mangled
     args = re.findall(r"L([ib])(\d)E", m.group(2) or "")
-    names = [("bf16" if v == "1" else "fp32") if t == "b" else v for t, v in args]
+    words = ("plain", "drop") if m.group(1).startswith("attn_bwd") else ("fp32", "bf16")
+    names = [words[int(v)] if t == "b" else v for t, v in args]
     return m.group(1) + (f"<{', '.join(names)}>" if names else "")
 
 
