@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 12
+#define SD3D_ABI_VERSION 13
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1083,6 +1083,38 @@ int sd3d_box_ap_scene(const float* boxes, int n, const int64_t* labels, const fl
 size_t sd3d_box_ap_finish_ws_bytes(int64_t n_slots);
 int sd3d_box_ap_finish(int64_t* codes, int64_t n_slots, int n_classes, int n_overlaps, const int64_t* npos, double* ap, double* ar,
                        void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Multi-view lifting of posed 2D feature maps onto scene points (csrc/lift2d.hip): the producer of `points_2dfeats`.  The reference
+ * has no counterpart (it loads a per-scene dump); tests/lift2d_ref.py restates the rule below in float64.  All three calls only
+ * enqueue work, use no atomics, and their results are pure functions of their inputs.
+ *
+ *   Inputs.  points float [N, ld] (world x, y, z first, ld >= 3); world_to_cam float [V, 12] = the rows of [R | t] of every view;
+ *     intrinsics float [V, 4] = fx, fy, cx, cy in pixels of the depth image, pixel centres at integer coordinates; depth [V, Hd, Wd],
+ *     uint16 times depth_scale (depth_u16 != 0) or float metres, 0 = invalid.
+ *   Visibility of point n in view v.  p_c = R p + t, z = p_c.z, require z > near.  u = fx x / z + cx, v = fy y / z + cy,
+ *     ui = floor(u + 0.5), vi likewise, require border <= ui < Wd - border and border <= vi < Hd - border.  d = depth[v, vi, ui],
+ *     require d > 0 and |d - z| <= tol_abs + tol_rel d.  Every comparison is made on floats before a value becomes an integer or an
+ *     address: NaN, infinite and huge coordinates fail one and the point is not visible.
+ *   sd3d_lift_visibility: bits uint32 [N, ceil(V / 32)], bit (v % 32) of word v / 32 of point n = visible (unused high bits 0), every
+ *     word written by one thread; count int32 [N] = the set bits of the point, added to `count` when add_count != 0.
+ *   sd3d_lift_accumulate: maps [V, Hf, Wf, C] channels-last, __half (maps_f16 != 0) or float, 16-byte aligned, C a multiple of 64 up
+ *     to 1024.  For every set bit of views [v0, v1) in ascending order: sample at xf = (u + 0.5) Wf / Wd - 0.5, yf likewise
+ *     (align_corners = False), bilinear with the tap indices clamped to the map, and sum[n, c] = fma(w11, t11, fma(w10, t10,
+ *     fma(w01, t01, fma(w00, t00, sum[n, c])))) in fp32.  sum float [N, C] is read and written by the one owner of point n, so any cut
+ *     of the views into calls and ranges that keeps them ascending gives the same bits.  `bits` need not come from
+ *     sd3d_lift_visibility: the tap coordinates are clamped as floats first, whatever the mask says.
+ *   sd3d_lift_finish: mean = sum / count, 0 where count == 0.  scale_index 0 starts, later ones add to acc float [N, C] (may be NULL
+ *     when n_scales == 1); the last one writes out [N, C] = (acc + mean) / n_scales as float or __half (out_f16 != 0).
+ * ------------------------------------------------------------------------------------------- */
+int sd3d_lift_visibility(const float* points, int64_t ld, int64_t N, const float* world_to_cam, const float* intrinsics, const void* depth,
+                         int depth_u16, float depth_scale, int V, int Hd, int Wd, float near, int border, float tol_abs, float tol_rel,
+                         uint32_t* bits, int32_t* count, int add_count, void* stream);
+int sd3d_lift_accumulate(const float* points, int64_t ld, int64_t N, const float* world_to_cam, const float* intrinsics, int V, int Hd,
+                         int Wd, const uint32_t* bits, const void* maps, int maps_f16, int Hf, int Wf, int C, int v0, int v1, float* sum,
+                         void* stream);
+int sd3d_lift_finish(const float* sum, const int32_t* count, int64_t N, int C, int scale_index, int n_scales, float* acc, void* out,
+                     int out_f16, void* stream);
 
 #ifdef __cplusplus
 }

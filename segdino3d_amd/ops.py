@@ -2146,3 +2146,117 @@ def box_ap_finish(codes, n_classes: int, n_overlaps: int, npos):
     _lib.check(lib.sd3d_box_ap_finish(_ptr(codes, torch.int64, "codes") if n else None, n, C, T, _accumulator(npos, torch.int64, C, "npos"),
                                       _ptr(ap), _ptr(ar), ws.data_ptr(), ws.numel(), _stream()), "box_ap_finish")
     return ap, ar
+
+
+# ---------------------------------------------------------------------------------------------- multi-view lifting (csrc/lift2d.hip)
+LIFT_MAX_CHANNELS = 1024
+
+
+def _lift_views(points, world_to_cam, intrinsics, name):
+    """The shapes the lifting kernels index by -> (points ptr, ld, N, V)."""
+    pp, ld = _rows(points, f"{name}: points")
+    N = points.shape[0]
+    if points.shape[1] < 3:
+        raise ValueError(f"{name}: points must be fp32 [N, >= 3]")
+    if world_to_cam.dim() != 3 or tuple(world_to_cam.shape[1:]) != (3, 4) or world_to_cam.shape[0] < 1:
+        raise ValueError(f"{name}: world_to_cam must be [V, 3, 4] with V >= 1, got {list(world_to_cam.shape)}")
+    V = world_to_cam.shape[0]
+    _want_shape(intrinsics, [(V, 4)], f"{name}: intrinsics")
+    return pp, max(ld, 3), N, V
+
+
+def lift_visibility(points, world_to_cam, intrinsics, depth, depth_scale=None, near=0.05, border=0, tol_abs=0.05, tol_rel=0.0, count=None):
+    """Depth-tested visibility of every point in every view (`sd3d_lift_visibility`): points fp32 [N, >= 3], world_to_cam fp32
+    [V, 3, 4], intrinsics fp32 [V, 4] (fx, fy, cx, cy), depth uint16 [V, Hd, Wd] with `depth_scale` or fp32 metres ->
+    (bits int32 [N, ceil(V / 32)], the words of the point-major mask, and count int32 [N]).  With `count` given the set bits are
+    added to it.  Enqueues only."""
+    lib = _lib.load()
+    pp, ld, N, V = _lift_views(points, world_to_cam, intrinsics, "lift_visibility")
+    if depth.dim() != 3 or depth.shape[0] != V or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise ValueError(f"lift_visibility: depth must be [V = {V}, Hd, Wd], got {list(depth.shape)}")
+    if depth.dtype == torch.uint16:
+        if depth_scale is None or not float(depth_scale) > 0.0:
+            raise ValueError("lift_visibility: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
+        u16, scale = 1, float(depth_scale)
+    elif depth.dtype == torch.float32:
+        if depth_scale is not None:
+            raise ValueError("lift_visibility: fp32 depth is in metres and takes no depth_scale")
+        u16, scale = 0, 1.0
+    else:
+        raise TypeError(f"lift_visibility: depth must be uint16 or fp32, got {depth.dtype}")
+    if int(border) != border or border < 0 or not near >= 0.0 or not tol_abs >= 0.0 or not tol_rel >= 0.0:
+        raise ValueError("lift_visibility: border must be an integer >= 0; near, tol_abs and tol_rel must be >= 0")
+    W = (V + 31) // 32
+    bits = torch.empty(N, W, dtype=torch.int32, device=points.device)
+    add = count is not None
+    if add:
+        _accumulator(count, torch.int32, N, "lift_visibility: count")
+    else:
+        count = torch.empty(N, dtype=torch.int32, device=points.device)
+    _lib.check(lib.sd3d_lift_visibility(pp if N else None, ld, N, _ptr(world_to_cam, torch.float32, "lift_visibility: world_to_cam"),
+                                        _ptr(intrinsics, torch.float32, "lift_visibility: intrinsics"), _ptr(depth, None, "lift_visibility: depth"),
+                                        u16, scale, V, depth.shape[1], depth.shape[2], float(near), int(border), float(tol_abs), float(tol_rel),
+                                        _ptr(bits) if N else None, _ptr(count) if N else None, int(add), _stream()), "lift_visibility")
+    return bits, count
+
+
+def lift_accumulate(points, world_to_cam, intrinsics, depth_hw, bits, maps, sum, v0: int = 0, v1: Optional[int] = None):
+    """Adds the bilinear samples of the visible views [v0, v1) to `sum` fp32 [N, C] in ascending view order
+    (`sd3d_lift_accumulate`): bits int32 [N, ceil(V / 32)] as `lift_visibility` returns them, maps fp16 or fp32 [V, Hf, Wf, C]
+    channels-last with C a multiple of 64 up to 1024, depth_hw = (Hd, Wd) of the depth images the intrinsics refer to.  Enqueues
+    only."""
+    lib = _lib.load()
+    pp, ld, N, V = _lift_views(points, world_to_cam, intrinsics, "lift_accumulate")
+    Hd, Wd = int(depth_hw[0]), int(depth_hw[1])
+    if maps.dim() != 4 or maps.shape[0] != V or maps.shape[1] < 1 or maps.shape[2] < 1:
+        raise ValueError(f"lift_accumulate: maps must be channels-last [V = {V}, Hf, Wf, C], got {list(maps.shape)}")
+    if maps.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"lift_accumulate: maps must be fp16 or fp32, got {maps.dtype}")
+    C = maps.shape[3]
+    if C < 64 or C > LIFT_MAX_CHANNELS or C % 64:
+        raise ValueError(f"lift_accumulate: C must be a multiple of 64 up to {LIFT_MAX_CHANNELS}, got {C}")
+    if N:
+        _want_shape(bits, [(N, (V + 31) // 32)], "lift_accumulate: bits")
+        _want_shape(sum, [(N, C)], "lift_accumulate: sum")
+    v1 = V if v1 is None else int(v1)
+    if not 0 <= v0 <= v1 <= V:
+        raise ValueError(f"lift_accumulate: need 0 <= v0 <= v1 <= V, got [{v0}, {v1}) of {V}")
+    _lib.check(lib.sd3d_lift_accumulate(pp if N else None, ld, N, _ptr(world_to_cam, torch.float32, "lift_accumulate: world_to_cam"),
+                                        _ptr(intrinsics, torch.float32, "lift_accumulate: intrinsics"), V, Hd, Wd,
+                                        _ptr(bits, torch.int32, "lift_accumulate: bits") if N else None, _ptr(maps, None, "lift_accumulate: maps"),
+                                        int(maps.dtype == torch.float16), maps.shape[1], maps.shape[2], C, int(v0), v1,
+                                        _ptr(sum, torch.float32, "lift_accumulate: sum") if N else None, _stream()), "lift_accumulate")
+
+
+def lift_finish(sum, count, scale_index: int = 0, n_scales: int = 1, acc=None, out=None, out_dtype=torch.float32):
+    """mean = sum / count (0 where count == 0) of one scale, added to `acc` fp32 [N, C] over the scales; the last scale returns
+    (acc + mean) / n_scales as fp32 or fp16 [N, C], earlier ones return None (`sd3d_lift_finish`).  Enqueues only."""
+    lib = _lib.load()
+    if not sum.is_cuda:
+        raise RuntimeError(f"lift_finish: sum: expected a tensor on the HIP device, got {sum.device} (no CPU fallback)")
+    if sum.dim() != 2:
+        raise ValueError("lift_finish: sum must be fp32 [N, C]")
+    N, C = sum.shape
+    if C < 64 or C > LIFT_MAX_CHANNELS or C % 64:
+        raise ValueError(f"lift_finish: C must be a multiple of 64 up to {LIFT_MAX_CHANNELS}, got {C}")
+    if not 0 <= scale_index < n_scales:
+        raise ValueError("lift_finish: need 0 <= scale_index < n_scales")
+    _want_shape(count, [(N,)], "lift_finish: count")
+    last = scale_index == n_scales - 1
+    if n_scales > 1:
+        if acc is None:
+            raise ValueError("lift_finish: several scales need the fp32 [N, C] accumulator `acc`")
+        _want_shape(acc, [(N, C)], "lift_finish: acc")
+    if last:
+        if out_dtype not in (torch.float32, torch.float16):
+            raise TypeError(f"lift_finish: out_dtype must be fp32 or fp16, got {out_dtype}")
+        if out is None:
+            out = torch.empty(N, C, dtype=out_dtype, device=sum.device)
+        else:
+            _want_shape(out, [(N, C)], "lift_finish: out")
+            out_dtype = out.dtype
+    _lib.check(lib.sd3d_lift_finish(_ptr(sum, torch.float32, "lift_finish: sum") if N else None, _ptr(count, torch.int32, "lift_finish: count") if N else None,
+                                    N, C, int(scale_index), int(n_scales), _ptr(acc, torch.float32, "lift_finish: acc") if N else None,
+                                    _ptr(out, out_dtype, "lift_finish: out") if last and N else None, int(last and out_dtype == torch.float16),
+                                    _stream()), "lift_finish")
+    return out if last else None
