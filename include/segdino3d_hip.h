@@ -470,7 +470,7 @@ int sd3d_attention(const float* q0, int ldq0, const float* q1, int ldq1, const f
 int sd3d_attention_config(int Lq, int Lk, int H, int head_dim, size_t ws_bytes, int* waves_out, int* ksplit_out);
 /* sd3d_attention with dropout of rate p on the softmax probabilities, inside the kernel (nn.MultiheadAttention(dropout=p) in training,
  * attention.py:383): out = (c K o softmax(S)) V with c = 1 / (1 - p); lse, the key split and its workspace are those of sd3d_attention.
- * The keep mask K is a pure function of (key, call, head, q, k) (csrc/attention_dropout.h): Philox4x32-10 keyed by the two words at
+ * The keep mask K is a pure function of (key, call, head, q, k) (csrc/attention.h): Philox4x32-10 keyed by the two words at
  * `key` (device memory) with the counter (k >> 2, q, head, call); element (head, q, k) takes output word k & 3 and is kept iff that
  * word >= floor(p 2^32).  `call` tells the attentions of one step apart.  Neither the launch shape nor the head width enters, so
  * sd3d_attention_dropout_backward regenerates the mask the forward drew and sd3d_attention_dropout_keep writes it out

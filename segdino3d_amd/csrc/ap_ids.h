@@ -33,8 +33,7 @@ __device__ static inline int ap_point_column(int64_t s, int64_t in, const int64_
 __device__ static inline void ap_raise(unsigned long long* status, int bits) {         // every lane of the wave must arrive
     const unsigned long long any = __ballot(bits != 0);
     if (!any) return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bits |= __shfl_xor(bits, d);
+    bits = wave_or(bits);
     if ((threadIdx.x & 63) == 0) atomicOr(status, (unsigned long long)bits);
 }
 

@@ -127,8 +127,7 @@ __global__ __launch_bounds__(64) void ap_rows_kernel(const int32_t* __restrict__
     const int r = blockIdx.x, lane = threadIdx.x;
     int v = 0;
     for (int c = lane; c < SD3D_AP_COLS; c += 64) v += counts[(size_t)r * SD3D_AP_COLS + c];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    v = wave_sum(v);
     int bad = 0;
     if (lane == 0) {
         const int64_t lab = labels[r];

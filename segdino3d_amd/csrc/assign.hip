@@ -31,13 +31,11 @@
 // two agree.
 #include "common.h"
 #include "../../include/segdino3d_hip.h"
-#include <atomic>
 #include <math.h>
 
 #define HM_THREADS 512
 #define HM_WAVES (HM_THREADS / 64)
 #define HM_LDS_MAX_M 4096            // columns whose solver state fits LDS (37 B per column at n = m: 148 KB)
-#define HM_MAX_DEVICES 64
 #define HM_TILE 32
 
 struct HmProblem {
@@ -197,8 +195,6 @@ __global__ __launch_bounds__(HM_THREADS) void hm_solve_kernel(const HmBatch b) {
 }
 
 // ------------------------------------------------------------------ C ABI
-static std::atomic<bool> g_hm_attr[HM_MAX_DEVICES];            // the LDS limit of hm_solve_kernel<true> is raised on this device
-
 static inline size_t hm_problem_ws(int Q, int G) {
     if (Q <= 0 || G <= 0) return 0;
     const int n = Q < G ? Q : G, m = Q < G ? G : Q;
@@ -225,14 +221,9 @@ extern "C" int sd3d_hungarian_match_batch(int n, const float* const* cost, const
         if (Q[i] > 0 && G[i] > 0 && (!cost[i] || !match[i])) return sd3d_set_error(SD3D_ERR_ARG, "hungarian_match: null cost / match matrix");
     }
     if (!ws || ws_bytes < sd3d_hungarian_match_ws_bytes(n, Q, G)) return sd3d_set_error(SD3D_ERR_WS, "hungarian_match: workspace too small");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= HM_MAX_DEVICES) return sd3d_set_error(SD3D_ERR_LAUNCH, "hungarian_match: no device");
+    static Sd3dLdsRaised raised;
     const size_t lds_max = hm_state_bytes(HM_LDS_MAX_M, HM_LDS_MAX_M);
-    if (!g_hm_attr[dev].load(std::memory_order_relaxed)) {     // (a function attribute is per device; setting it twice is harmless)
-        if (hipFuncSetAttribute((const void*)hm_solve_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess)
-            return sd3d_set_error(SD3D_ERR_LAUNCH, "hungarian_match: cannot raise the LDS limit");
-        g_hm_attr[dev].store(true, std::memory_order_relaxed);
-    }
+    if (int rc = sd3d_raise_lds_limit(raised, {{(const void*)hm_solve_kernel<true>, (int)lds_max}})) return rc;
     int32_t* status_ws = (int32_t*)ws;
     char* w = (char*)ws + align_up((size_t)n * sizeof(int32_t), 256);
     if (hipMemsetAsync(status_ws, 0, (size_t)n * sizeof(int32_t), st) != hipSuccess) return sd3d_set_error(SD3D_ERR_LAUNCH, "hungarian_match: memset failed");

@@ -1,13 +1,24 @@
+// What the fused attention's forward (attention.hip) and backward (attention_bwd.hip) share: the constants of their common
+// register layout and softmax, and the keep mask of attention dropout.
+#pragma once
+#include <stdint.h>
+
+// Softmax in the log2 domain: a probability is one v_exp_f32 of (score - max or lse) * log2(e).  (The row chain's attention op
+// pre-scales its queries by the same constant.)
+#define SD3D_LOG2E 1.4426950408889634f
+// Index of 32-channel block w in a register array with one entry per block (W blocks per head).  With one block it is the constant 0
+// already when the template is instantiated, so the array is promoted to registers before the w loops unroll, as a single tile written
+// without a loop would be: the W = 1 kernels are then the instruction streams of a 32-channel-only body (profiles/attention_heads.md).
+#define ATTN_BLK(w) (W == 1 ? 0 : (w))
+
 // Keep mask of attention dropout (nn.MultiheadAttention(dropout=p): dropout on the softmax probabilities, attention.py:383):
-// ONE definition for the fused forward (dense.hip), the two backward kernels (attention_bwd.hip) and the mask kernel.
+// ONE definition for the fused forward, the two backward kernels and the mask kernel.
 //
 // Element (head, q, k) of attention number `call` is a pure function of (key, call, head, q, k): Philox4x32-10 (the counter-based
 // generator of Random123, torch and rocRAND) with the two key words read from device memory and the counter (k >> 2, q, head, call);
 // the element takes output word k & 3 and is KEPT iff that word >= thr, thr = floor(p 2^32).  Nothing about the asking kernel enters -
 // waves per workgroup, key split, tile order and head width cannot change a bit, and the backward regenerates what the forward drew.
 // Four consecutive keys share one call; in the forward and the q kernel a lane holds four such runs per key tile.
-#pragma once
-#include <stdint.h>
 
 struct AttnDrop {
     const uint32_t* key;                      // two words (device memory)

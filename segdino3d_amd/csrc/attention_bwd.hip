@@ -16,15 +16,14 @@
 // Heads of D = 32 W channels (W = 1 or 2): a 64-channel head contracts S and dP over two 32-channel blocks and keeps two 32-channel
 // accumulator tiles per gradient; its kernels run at most four waves per workgroup, so a wave may hold 512 registers.
 //
-// DROP (dropout on the probabilities, attention_dropout.h): with the keep mask K, c = 1 / (1 - p) and O = (c K o P) V
+// DROP (dropout on the probabilities, attention.h): with the keep mask K, c = 1 / (1 - p) and O = (c K o P) V
 //     dV = (c K o P)^T dO        dP = c K o (dO V^T)        dS = P o (dP - D),   D[q] = sum_k P c K (dO . v_k) = dO[q] . O[q]
 // so D is the same row statistic of the same saved out and lse, and the kernels only regenerate K from (key, call, head, q, k).
 #include "common.h"
-#include "attention_dropout.h"
+#include "attention.h"
 #include "../../include/segdino3d_hip.h"
 #include <math.h>
 #include <stdlib.h>
-#include <atomic>
 
 struct AttnBwdParams {
     const float* q[2]; int ldq[2];
@@ -43,15 +42,9 @@ struct AttnBwdParams {
     AttnDrop drop;                            // read by the DROP instantiations only
 };
 
-__device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 // P = exp(S - lse) as v_exp_f32 of (S - lse) * log2(e): one fused multiply-add and the hardware exponential instead of the library
 // expf's range handling (the forward kernel forms its probabilities the same way)
-#define ABW_LOG2E 1.4426950408889634f
-__device__ __forceinline__ float prob_of(float s, float lse_log2) { return __builtin_amdgcn_exp2f(__builtin_fmaf(s, ABW_LOG2E, -lse_log2)); }
-// Index of 32-channel block w in a register array that a 32-channel-only kernel would hold as one tile (dV): the constant 0 at W = 1
-// already when the template is instantiated, so the tile is promoted to registers before the w loops unroll and the W = 1 kernels are the
-// instruction streams of such a kernel (profiles/attention_heads.md).
-#define ATTN_BLK(w) (W == 1 ? 0 : (w))
+__device__ __forceinline__ float prob_of(float s, float lse_log2) { return __builtin_amdgcn_exp2f(__builtin_fmaf(s, SD3D_LOG2E, -lse_log2)); }
 
 template <int W, int NSRC, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const AttnBwdParams p) {
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const AttnBwdParams p) 
     }
     dsum += __shfl_xor(dsum, 32);
     if (wave == 0 && h == 0 && q0 + i < p.Lq) p.dsum[(int64_t)head * p.Lq + q0 + i] = dsum;
-    const float lse = p.lse[(int64_t)head * p.Lq + qi] * ABW_LOG2E;
+    const float lse = p.lse[(int64_t)head * p.Lq + qi] * SD3D_LOG2E;
     uint32_t dkey0 = 0u, dkey1 = 0u;
     if (DROP) { dkey0 = p.drop.key[0]; dkey1 = p.drop.key[1]; }
 
@@ -126,7 +119,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const AttnBwdParams p) 
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kb = tile_row(r, h);
+            const int kb = mfma32_row(r, h);
             const bool blocked = ((word >> kb) & 1u) || (kt0 + kb >= p.Lk);
             const float pr = blocked ? 0.f : prob_of(S[r], lse);
             ds[r] = pr * (dP[r] - dsum);
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const AttnBwdParams p) 
             for (int w = 0; w < W; ++w)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = min(kt0 + tile_row(r, h), p.Lk - 1);
+                    const int key = min(kt0 + mfma32_row(r, h), p.Lk - 1);
                     dQ[s][w] = __builtin_amdgcn_mfma_f32_32x32x2f32(kcol[(int64_t)key * p.ldk[s] + 32 * w], ds[r], dQ[s][w], 0, 0, 0);
                 }
         }
@@ -151,7 +144,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const AttnBwdParams p) 
 #pragma unroll
         for (int w = 0; w < W; ++w)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) mine[s * TILE + (32 * w + tile_row(r, h)) * 32 + i] = dQ[s][w][r];
+            for (int r = 0; r < 16; ++r) mine[s * TILE + (32 * w + mfma32_row(r, h)) * 32 + i] = dQ[s][w][r];
     __syncthreads();
     for (int e = threadIdx.x; e < NSRC * TILE; e += blockDim.x) {
         const int s = e >> (9 + W), qq = (e >> (4 + W)) & 31, c = e & (D - 1);          // consecutive threads -> consecutive channels
@@ -219,10 +212,10 @@ __global__ __launch_bounds__(W == 1 ? 512 : 256) void attn_bwd_kv_kernel(const A
 #pragma unroll
             for (int e = 0; e < 16 * W; ++e) dP = __builtin_amdgcn_mfma_f32_32x32x2f32(src[(e >> 4) * 32 + (e & 15)], vreg[e], dP, 0, 0, 0);
         }
-        // S[r], dP[r]: (query = qt0 + tile_row(r, h), key = k0 + j).  The per-query values (mask word, lse, D) are loaded once per
+        // S[r], dP[r]: (query = qt0 + mfma32_row(r, h), key = k0 + j).  The per-query values (mask word, lse, D) are loaded once per
         // tile by the lane whose index is the query's row in the tile and handed round with readlane - not 48 loads per lane and tile
         const uint32_t my_word = p.bits ? p.bits[(int64_t)qr * p.nwords + ktile] : 0u;
-        const float my_lse = p.lse[(int64_t)head * p.Lq + qr] * ABW_LOG2E, my_dsum = p.dsum[(int64_t)head * p.Lq + qr];
+        const float my_lse = p.lse[(int64_t)head * p.Lq + qr] * SD3D_LOG2E, my_dsum = p.dsum[(int64_t)head * p.Lq + qr];
         // DROP: the lane is a key and its 16 registers are queries; the four lanes of a quad share k >> 2, so quad lane a makes the four
         // calls of queries qt0 + a + 8 g + 4 h (registers a + 4 g), packs their 16 keep bits into one word and the quad trades the words
         // (16 calls per lane, each for one bit of its four words, cost 6 - 28 % more per backward: profiles/EXPERIMENTS.md)
@@ -243,7 +236,7 @@ __global__ __launch_bounds__(W == 1 ? 512 : 256) void attn_bwd_kv_kernel(const A
         float pr[16], ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row0 = tile_row(r, 0), row1 = tile_row(r, 1);             // compile-time lane numbers
+            const int row0 = mfma32_row(r, 0), row1 = mfma32_row(r, 1);             // compile-time lane numbers
             const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)my_word, row0), w1 = (uint32_t)__builtin_amdgcn_readlane((int)my_word, row1);
             const float l0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_lse), row0));
             const float l1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_lse), row1));
@@ -269,7 +262,7 @@ __global__ __launch_bounds__(W == 1 ? 512 : 256) void attn_bwd_kv_kernel(const A
             for (int w = 0; w < W; ++w)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int qc = min(qt0 + tile_row(r, h), p.Lq - 1);
+                    const int qc = min(qt0 + mfma32_row(r, h), p.Lq - 1);
                     dV[ATTN_BLK(w)] = __builtin_amdgcn_mfma_f32_32x32x2f32(dcol[(int64_t)qc * p.ld_do + 32 * w], pr[r], dV[ATTN_BLK(w)], 0, 0, 0);
                 }
         }
@@ -281,7 +274,7 @@ __global__ __launch_bounds__(W == 1 ? 512 : 256) void attn_bwd_kv_kernel(const A
             for (int w = 0; w < W; ++w)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int qc = min(qt0 + tile_row(r, h), p.Lq - 1);
+                    const int qc = min(qt0 + mfma32_row(r, h), p.Lq - 1);
                     dK[s][w] = __builtin_amdgcn_mfma_f32_32x32x2f32(qcol[(int64_t)qc * p.ldq[s] + 32 * w] * p.scale, ds[r], dK[s][w], 0, 0, 0);
                 }
         }
@@ -293,7 +286,7 @@ __global__ __launch_bounds__(W == 1 ? 512 : 256) void attn_bwd_kv_kernel(const A
     for (int w = 0; w < W; ++w)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = 32 * w + tile_row(r, h);
+            const int row = 32 * w + mfma32_row(r, h);
 #pragma unroll
             for (int s = 0; s < NSRC; ++s) mine[s * TILE + row * 32 + j] = dK[s][w][r];
             mine[NSRC * TILE + row * 32 + j] = dV[ATTN_BLK(w)][r];
@@ -349,18 +342,13 @@ static int attention_backward_impl(const float* q0, int ldq0, const float* q1, i
     static void (*const q_kernels[2][2][2])(const AttnBwdParams) = ABW_TABLE(attn_bwd_q_kernel);
     static void (*const kv_kernels[2][2][2])(const AttnBwdParams) = ABW_TABLE(attn_bwd_kv_kernel);
 #undef ABW_TABLE
-    static std::atomic<bool> attr_set[64];                    // per device: a function attribute belongs to the current device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return sd3d_set_error(SD3D_ERR_LAUNCH, "attention_backward: no device");
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {     // the launches that reach or pass the 64 KiB default of dynamic LDS
-        for (int d = 0; d < 2; ++d) {
-            (void)hipFuncSetAttribute((const void*)kv_kernels[d][0][0], hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 2 * 4096);
-            (void)hipFuncSetAttribute((const void*)kv_kernels[d][0][1], hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 3 * 4096);
-            (void)hipFuncSetAttribute((const void*)kv_kernels[d][1][1], hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 3 * 8192);
-            (void)hipFuncSetAttribute((const void*)q_kernels[d][1][1], hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 8192);
-        }
-        attr_set[dev].store(true, std::memory_order_relaxed);
-    }
+    static Sd3dLdsRaised raised;                              // the launches that reach or pass the 64 KiB default of dynamic LDS
+    static const Sd3dLdsKernel big[8] = {
+        {(const void*)kv_kernels[0][0][0], 8 * 2 * 4096}, {(const void*)kv_kernels[0][0][1], 8 * 3 * 4096},
+        {(const void*)kv_kernels[0][1][1], 4 * 3 * 8192}, {(const void*)q_kernels[0][1][1], 4 * 2 * 8192},
+        {(const void*)kv_kernels[1][0][0], 8 * 2 * 4096}, {(const void*)kv_kernels[1][0][1], 8 * 3 * 4096},
+        {(const void*)kv_kernels[1][1][1], 4 * 3 * 8192}, {(const void*)q_kernels[1][1][1], 4 * 2 * 8192}};
+    if (int rc = sd3d_raise_lds_limit(raised, big, 8)) return rc;
     // LDS: nw waves x accumulators (nsrc in the q kernel, nsrc + 1 in the kv kernel) x 4 W KiB
     const size_t tile = (size_t)W * 4096;
     const int dropping = drop ? 1 : 0;

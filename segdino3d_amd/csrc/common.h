@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <initializer_list>
+#include "wave.h"
 
 #define SD3D_OK 0
 #define SD3D_ERR_ARG -1
@@ -66,6 +69,44 @@ __device__ static inline uint32_t hash_u64(uint64_t k) {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+// The accumulator of a 32x32 MFMA: register r of lane (j = lane & 31, h = lane >> 5) is element (row, col = j) of the tile with
+// row = (r&3) + 8*(r>>2) + 4*h - four consecutive rows per group of four registers, the two half-waves interleaved in fours.
+__host__ __device__ __forceinline__ int mfma32_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// The fused activation of every epilogue; the codes are ops.ACT: 0 none, 1 relu, 2 gelu(erf), 3 sigmoid.
+__device__ __forceinline__ float sd3d_act(float y, int act) {
+    if (act == 1) y = fmaxf(y, 0.f);
+    else if (act == 2) y = 0.5f * y * (1.f + erff(y * 0.70710678118654752440f));
+    else if (act == 3) y = 1.f / (1.f + expf(-y));
+    return y;
+}
+
+// ------------------------------------------------------------------ per-device state
+// A function attribute belongs to the CURRENT device, and one process may drive several through the C ABI: what is set once
+// is set once per device.  Per-device tables have SD3D_MAX_DEVICES entries, indexed by sd3d_device().
+#define SD3D_MAX_DEVICES 64
+static inline int sd3d_device() {                          // the current device's index, or -1
+    int dev = 0;
+    return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < SD3D_MAX_DEVICES ? dev : -1;
+}
+// Raises hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, or of a group of kernels that launch together, once per device.
+// `done` is one static object per kernel or group.  Callers may race: the flags are relaxed atomics and setting the attribute
+// twice is harmless.  `dev` is the caller's sd3d_device() where it has one already (< 0: asked here).
+struct Sd3dLdsRaised { std::atomic<bool> on[SD3D_MAX_DEVICES]; };
+struct Sd3dLdsKernel { const void* fn; int bytes; };
+static inline int sd3d_raise_lds_limit(Sd3dLdsRaised& done, const Sd3dLdsKernel* kernels, int n, int dev = -1) {
+    if (dev < 0) dev = sd3d_device();
+    if (dev < 0 || dev >= SD3D_MAX_DEVICES) return sd3d_set_error(SD3D_ERR_LAUNCH, "raise_lds_limit: no device");
+    if (done.on[dev].load(std::memory_order_relaxed)) return SD3D_OK;
+    for (int i = 0; i < n; ++i)
+        if (hipFuncSetAttribute(kernels[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, kernels[i].bytes) != hipSuccess)
+            return sd3d_set_error(SD3D_ERR_LAUNCH, "raise_lds_limit: the runtime refused a kernel's dynamic LDS size");
+    done.on[dev].store(true, std::memory_order_relaxed);
+    return SD3D_OK;
+}
+static inline int sd3d_raise_lds_limit(Sd3dLdsRaised& done, std::initializer_list<Sd3dLdsKernel> kernels, int dev = -1) {
+    return sd3d_raise_lds_limit(done, kernels.begin(), (int)kernels.size(), dev);
+}
 
 // ------------------------------------------------------------------ internal launchers called across translation units
 // Declared here once, with names; the defining file includes this header too, so a call and its definition cannot drift apart.

@@ -48,13 +48,6 @@ struct SlabParams {
     int ncols;                                // columns of this launch (16 * waves)
 };
 
-__device__ __forceinline__ float slab_act(float t, int act) {
-    if (act == 1) return fmaxf(t, 0.f);
-    if (act == 2) return 0.5f * t * (1.f + erff(t * 0.70710678118654752440f));
-    if (act == 3) return 1.f / (1.f + expf(-t));
-    return t;
-}
-
 // CK = channels per step, NCH = Cin / CK, NCB = waves = 16-column blocks of this workgroup
 template <int CK, int NCH, int NCB, bool WPF>
 __device__ __forceinline__ void slab_conv_body(const SlabParams& p, float* smem) {
@@ -118,7 +111,7 @@ __device__ __forceinline__ void slab_conv_body(const SlabParams& p, float* smem)
             const int kk = k0 + lane;
             const int c = kk < KR ? cnt[kk] : 0;
             const int nu = (c + 31) >> 5;
-            int inc = nu;
+            int inc = nu;                                         // (the loop stays written out: through wave_scan_incl the compiler schedules this kernel differently)
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
                 const int t = __shfl_up(inc, d);
@@ -331,7 +324,7 @@ __device__ __forceinline__ void slab_conv_body(const SlabParams& p, float* smem)
             const int col = col0 + q + j;
             float t = a[j] * (p.scale ? p.scale[col] : 1.f) + (p.shift ? p.shift[col] : 0.f);
             if (p.res) t += p.res[(row0 + r) * p.ld_res + col];
-            y[j] = slab_act(t, p.act);
+            y[j] = sd3d_act(t, p.act);
         }
         *(f32x4_t*)(p.out + (row0 + r) * p.ld_out + col0 + q) = f32x4_t{y[0], y[1], y[2], y[3]};
     }
@@ -416,7 +409,7 @@ __device__ __forceinline__ void slab_direct_body(const SlabParams& p, float* sme
             const int kk = k0 + lane;
             const int c = kk < KR ? cnt[kk] : 0;
             const int nu = (c + 31) >> 5;
-            int inc = nu;
+            int inc = nu;                                         // (the loop stays written out: through wave_scan_incl the compiler schedules this kernel differently)
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
                 const int t = __shfl_up(inc, d);
@@ -573,7 +566,7 @@ __device__ __forceinline__ void slab_direct_body(const SlabParams& p, float* sme
             const int col = p.col0 + q + j;
             float t = a[j] * (p.scale ? p.scale[col] : 1.f) + (p.shift ? p.shift[col] : 0.f);
             if (p.res) t += p.res[(row0 + r) * p.ld_res + col];
-            y[j] = slab_act(t, p.act);
+            y[j] = sd3d_act(t, p.act);
         }
         *(f32x4_t*)(p.out + (row0 + r) * p.ld_out + p.col0 + q) = f32x4_t{y[0], y[1], y[2], y[3]};
     }
@@ -615,7 +608,7 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const SlabReduceParams
     for (int j = 0; j < 4; ++j) {
         float t = a[j] * (p.scale ? p.scale[q + j] : 1.f) + (p.shift ? p.shift[q + j] : 0.f);
         if (p.res) t += p.res[r * p.ld_res + q + j];
-        y[j] = slab_act(t, p.act);
+        y[j] = sd3d_act(t, p.act);
     }
     *(f32x4_t*)(p.out + r * p.ld_out + q) = f32x4_t{y[0], y[1], y[2], y[3]};
 }
@@ -785,17 +778,15 @@ extern "C" int sd3d_slab_conv(const float* in0, int ld0, int C0, const float* in
     const dim3 grid((unsigned)slabs, (unsigned)pl.ksplit), block(64 * pl.ncb);
 #define SLAB_CASE(CK, NCH, NCB)                                                                                          \
     if (pl.ck == CK && pl.nch == NCH && pl.ncb == NCB) {                                                                 \
-        static bool attr = false;                                                                                        \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)slab_conv_kernel_##CK##_##NCH##_##NCB,                       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }   \
+        static Sd3dLdsRaised raised;                                                                                     \
+        if (int rc = sd3d_raise_lds_limit(raised, {{(const void*)slab_conv_kernel_##CK##_##NCH##_##NCB, 160 * 1024}})) return rc; \
         p.col0 = 0;                                                                                                      \
         hipLaunchKernelGGL(slab_conv_kernel_##CK##_##NCH##_##NCB, dim3(grid.x, grid.y, pl.ncg), block, pl.lds, st, p);   \
     } else
 #define SLABD_CASE(CK, NCH, NW)                                                                                          \
     if (direct && pl.ck == CK && pl.nch == NCH && pl.ncb == NW) {                                                        \
-        static bool attr = false;                                                                                        \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)slab_direct_kernel_##CK##_##NCH##_##NW,                      \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }   \
+        static Sd3dLdsRaised raised;                                                                                     \
+        if (int rc = sd3d_raise_lds_limit(raised, {{(const void*)slab_direct_kernel_##CK##_##NCH##_##NW, 160 * 1024}})) return rc; \
         for (int cg = 0; cg < pl.ncg; ++cg) {                                                                            \
             p.col0 = cg * p.ncols;                                                                                       \
             hipLaunchKernelGGL(slab_direct_kernel_##CK##_##NCH##_##NW, grid, block, pl.lds, st, p);                      \

@@ -151,18 +151,11 @@ __device__ __forceinline__ void gather_gemm_body(const GGParams& p, const int64_
     for (int t = 0; t < NT; ++t) {
         const int n = ncol0 + t * 32 + j;
         if (n >= p.Cout) continue;
-        const float sc = p.scale ? p.scale[n] : 1.f;
-        const float sh = p.shift ? p.shift[n] : 0.f;
+        const float sc = gg_scale(p, n), sh = gg_shift(p, n);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t rr = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (rr >= p.M) continue;
-            float y = acc[t][r] * sc + sh;
-            if (p.res) y += p.res[rr * p.ld_res + n];
-            if (p.act == 1) y = fmaxf(y, 0.f);
-            else if (p.act == 2) y = 0.5f * y * (1.f + erff(y * 0.70710678118654752440f));
-            else if (p.act == 3) y = 1.f / (1.f + expf(-y));
-            p.out[rr * p.ld_out + n] = y;
+            const int64_t rr = row0 + mfma32_row(r, h);
+            if (rr < p.M) gg_finish(p, acc[t][r], rr, n, sc, sh);
         }
     }
 }
@@ -325,7 +318,7 @@ __device__ __forceinline__ void gather_gemm_lds_body(const GGParams& p, const in
             if (n >= p.Cout) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t rr = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t rr = row0 + mfma32_row(r, h);
                 if (rr < p.M) wsz[rr * p.Cout + n] = acc[t][r];
             }
         }
@@ -335,18 +328,11 @@ __device__ __forceinline__ void gather_gemm_lds_body(const GGParams& p, const in
     for (int t = 0; t < NT; ++t) {
         const int n = ncol0 + t * 32 + j;
         if (n >= p.Cout) continue;
-        const float sc = p.scale ? p.scale[n] : 1.f;
-        const float sh = p.shift ? p.shift[n] : 0.f;
+        const float sc = gg_scale(p, n), sh = gg_shift(p, n);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t rr = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (rr >= p.M) continue;
-            float y = acc[t][r] * sc + sh;
-            if (p.res) y += p.res[rr * p.ld_res + n];
-            if (p.act == 1) y = fmaxf(y, 0.f);
-            else if (p.act == 2) y = 0.5f * y * (1.f + erff(y * 0.70710678118654752440f));
-            else if (p.act == 3) y = 1.f / (1.f + expf(-y));
-            p.out[rr * p.ld_out + n] = y;
+            const int64_t rr = row0 + mfma32_row(r, h);
+            if (rr < p.M) gg_finish(p, acc[t][r], rr, n, sc, sh);
         }
     }
 }
@@ -377,12 +363,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const GGParams p) 
     const int n = (int)(e - rr * p.Cout);
     float a = 0.f;
     for (int z = 0; z < p.ksplit; ++z) a += p.ws[(int64_t)z * p.M * p.Cout + e];
-    float y = a * (p.scale ? p.scale[n] : 1.f) + (p.shift ? p.shift[n] : 0.f);
-    if (p.res) y += p.res[rr * p.ld_res + n];
-    if (p.act == 1) y = fmaxf(y, 0.f);
-    else if (p.act == 2) y = 0.5f * y * (1.f + erff(y * 0.70710678118654752440f));
-    else if (p.act == 3) y = 1.f / (1.f + expf(-y));
-    p.out[rr * p.ld_out + n] = y;
+    gg_finish(p, a, rr, n);
 }
 
 // (The pair-compacted variants of this output-stationary kernel - LDS accumulators fed with ds_add_f32, single-pass,

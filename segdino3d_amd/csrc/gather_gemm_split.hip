@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void gather_gemm_split_kernel(const GGParams p
             if (n >= p.Cout) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t rr = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t rr = row0 + mfma32_row(r, h);
                 if (rr < p.M) wsz[rr * p.Cout + n] = acc[t][r];
             }
         }
@@ -199,31 +199,23 @@ __global__ __launch_bounds__(256) void gather_gemm_split_kernel(const GGParams p
     for (int t = 0; t < NT; ++t) {
         const int n = ncol0 + t * 32 + j;
         if (n >= p.Cout) continue;
-        const float sc = p.scale ? p.scale[n] : 1.f;
-        const float sh = p.shift ? p.shift[n] : 0.f;
+        const float sc = gg_scale(p, n), sh = gg_shift(p, n);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t rr = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (rr >= p.M) continue;
-            float y = acc[t][r] * sc + sh;
-            if (p.res) y += p.res[rr * p.ld_res + n];
-            if (p.act == 1) y = fmaxf(y, 0.f);
-            else if (p.act == 2) y = 0.5f * y * (1.f + erff(y * 0.70710678118654752440f));
-            else if (p.act == 3) y = 1.f / (1.f + expf(-y));
-            p.out[rr * p.ld_out + n] = y;
+            const int64_t rr = row0 + mfma32_row(r, h);
+            if (rr < p.M) gg_finish(p, acc[t][r], rr, n, sc, sh);
         }
     }
 }
 
 template <int NT, int NS>
-static void launch_one(const GGParams& p, const __bf16* w, dim3 grid, hipStream_t st) {
+static int launch_one(const GGParams& p, const __bf16* w, dim3 grid, hipStream_t st) {
     const size_t sm = (size_t)2 * NS * NT * 32 * SB_LD * sizeof(__bf16);
-    static bool attr_set = false;
-    if (!attr_set && sm > 65536) {
-        (void)hipFuncSetAttribute((const void*)gather_gemm_split_kernel<NT, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        attr_set = true;
-    }
+    static Sd3dLdsRaised raised;
+    if (sm > 65536)
+        if (int rc = sd3d_raise_lds_limit(raised, {{(const void*)gather_gemm_split_kernel<NT, NS>, (int)sm}})) return rc;
     hipLaunchKernelGGL((gather_gemm_split_kernel<NT, NS>), grid, dim3(256), sm, st, p, w);
+    return SD3D_OK;
 }
 
 // terms: 1 (plain bf16), 3 (bf16x3) or 6 (bf16x6).  wsplit: [1, 2 or 3][K][Cout][Cin] bf16.
@@ -256,28 +248,12 @@ static int launch_gather_gemm_split(const GGParams& p_in, int nt, int terms, con
     }
     const dim3 grid((unsigned)cdiv(tiles, 4), (unsigned)p.col_groups, (unsigned)p.ksplit);
     const __bf16* w = (const __bf16*)wsplit;
-    if (terms == 1) {
-        switch (nt) {
-            case 1: launch_one<1, 1>(p, w, grid, st); break;
-            case 2: launch_one<2, 1>(p, w, grid, st); break;
-            case 3: launch_one<3, 1>(p, w, grid, st); break;
-            default: launch_one<4, 1>(p, w, grid, st); break;
-        }
-    } else if (terms == 3) {
-        switch (nt) {
-            case 1: launch_one<1, 2>(p, w, grid, st); break;
-            case 2: launch_one<2, 2>(p, w, grid, st); break;
-            case 3: launch_one<3, 2>(p, w, grid, st); break;
-            default: launch_one<4, 2>(p, w, grid, st); break;
-        }
-    } else {
-        switch (nt) {
-            case 1: launch_one<1, 3>(p, w, grid, st); break;
-            case 2: launch_one<2, 3>(p, w, grid, st); break;
-            case 3: launch_one<3, 3>(p, w, grid, st); break;
-            default: launch_one<4, 3>(p, w, grid, st); break;
-        }
-    }
+    // by [bf16 terms per weight: 1, 2 or 3][nt - 1]
+    static int (*const launchers[3][4])(const GGParams&, const __bf16*, dim3, hipStream_t) = {
+        {launch_one<1, 1>, launch_one<2, 1>, launch_one<3, 1>, launch_one<4, 1>},
+        {launch_one<1, 2>, launch_one<2, 2>, launch_one<3, 2>, launch_one<4, 2>},
+        {launch_one<1, 3>, launch_one<2, 3>, launch_one<3, 3>, launch_one<4, 3>}};
+    if (int rc = launchers[terms == 1 ? 0 : (terms == 3 ? 1 : 2)][nt - 1](p, w, grid, st)) return rc;
     if (p.ksplit > 1) launch_splitk_epilogue(p, st);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;

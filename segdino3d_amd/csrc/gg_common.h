@@ -35,6 +35,17 @@ static inline GGParams gg_params(const float* in0, int ld0, int C0, const float*
 int launch_gather_gemm(const GGParams& p_in, int nt, void* ws, size_t ws_bytes, hipStream_t st);
 void launch_splitk_epilogue(const GGParams& p, hipStream_t st);
 
+// The tail of every gather-GEMM epilogue: out[rr][n] = act(acc * scale[n] + shift[n] + res[rr][n]).
+// (sc, sh: column n's scale and shift, which a caller that finishes several rows of the column loads once)
+__device__ __forceinline__ float gg_scale(const GGParams& p, int n) { return p.scale ? p.scale[n] : 1.f; }
+__device__ __forceinline__ float gg_shift(const GGParams& p, int n) { return p.shift ? p.shift[n] : 0.f; }
+__device__ __forceinline__ void gg_finish(const GGParams& p, float acc, int64_t rr, int n, float sc, float sh) {
+    float y = acc * sc + sh;
+    if (p.res) y += p.res[rr * p.ld_res + n];
+    p.out[rr * p.ld_out + n] = sd3d_act(y, p.act);
+}
+__device__ __forceinline__ void gg_finish(const GGParams& p, float acc, int64_t rr, int n) { gg_finish(p, acc, rr, n, gg_scale(p, n), gg_shift(p, n)); }
+
 __device__ __forceinline__ int next_active(uint64_t m0, uint64_t m1, int after) {
     // smallest set bit index > after in the 128-bit mask (m1:m0), or -1
     int s = after + 1;

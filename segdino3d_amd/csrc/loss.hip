@@ -15,16 +15,6 @@
 #define LOSS_MAX_S 12288             // superpoints per scene the LDS staging holds (3 rows of floats = 144 KB)
 #define SPARSE_INF 1e8f              // loss_3d.py:326
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 // block-wide sum over 256 threads, same value returned to every thread; `red` holds >= 4 floats
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
@@ -395,8 +385,8 @@ int sd3d_match_costs(const float* cls, int ld_cls, int n_cls1, const float* mask
     CostParams p{cls, ld_cls, n_cls1, masks, ld_masks, Q, S, centers, sizes, labels, gt_bits, words, gt_count, G, gt_centers, ld_gc,
                  gt_sizes, ld_gs, query_masks, weights5[0], weights5[1], weights5[2], weights5[3], weights5[4], cost};
     const size_t lds = (size_t)2 * S * sizeof(float);
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)loss_cost_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * LOSS_MAX_S * 4); attr = true; }
+    static Sd3dLdsRaised raised;
+    if (int rc = sd3d_raise_lds_limit(raised, {{(const void*)loss_cost_kernel, 3 * LOSS_MAX_S * 4}})) return rc;
     loss_cost_kernel<<<Q, 256, lds, ST>>>(p);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
@@ -435,8 +425,8 @@ int sd3d_instance_loss(const float* cls, int ld_cls, int n_cls1, const float* ma
     p.row_n = (int32_t*)w; w += (size_t)Q * 4;
     p.rowsum = (float*)w;
     p.parts = parts8;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)loss_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * LOSS_MAX_S * 4); attr = true; }
+    static Sd3dLdsRaised raised;
+    if (int rc = sd3d_raise_lds_limit(raised, {{(const void*)loss_rows_kernel, 3 * LOSS_MAX_S * 4}})) return rc;
     loss_targets_kernel<<<1, 1024, 0, ST>>>(p);
     loss_rows_kernel<<<Q, 256, (size_t)3 * S * sizeof(float), ST>>>(p);
     loss_final_kernel<<<1, 1024, 0, ST>>>(p);

@@ -21,7 +21,6 @@
 #include "gg_common.h"
 #include "pair_conv.h"
 #include <stdlib.h>
-#include <atomic>
 #include <vector>
 
 static std::atomic<int> g_scenes_in_flight{1};
@@ -121,7 +120,7 @@ __device__ __forceinline__ float pg_affine(float x, const float* scale, const fl
     return __builtin_fmaf(x, scale ? scale[n] : 1.f, shift ? shift[n] : 0.f);
 }
 // (GELU / sigmoid never follow a sparse convolution in the shipped networks: kept out of line so that the 64 epilogue sites of a
-//  kernel do not each carry an inlined erff / expf)
+//  kernel do not each carry an inlined erff / expf; that is why this is not common.h's sd3d_act, whose expressions these are)
 __device__ __attribute__((noinline)) float pg_act_slow(float t, int act) {
     return act == 2 ? 0.5f * t * (1.f + erff(t * 0.70710678118654752440f)) : 1.f / (1.f + expf(-t));
 }
@@ -702,9 +701,8 @@ __global__ __launch_bounds__(256) void pair_reduce_rl_kernel(const PRLParams p) 
 }
 
 // ---- the shared tail's host side ------------------------------------------------------------------
-#define PG_MAX_DEVICES 64
-static std::atomic<unsigned long long*> g_pool_bases[PG_MAX_DEVICES];
-static std::atomic<unsigned long long> g_pool_tickets[PG_MAX_DEVICES];        // pooled launches handed out so far, per device
+static std::atomic<unsigned long long*> g_pool_bases[SD3D_MAX_DEVICES];
+static std::atomic<unsigned long long> g_pool_tickets[SD3D_MAX_DEVICES];        // pooled launches handed out so far, per device
 static std::atomic<int> g_pool_on{-1};                                         // -1: not decided yet (SD3D_PAIR_POOL, default 1)
 static bool pool_enabled() {
     int v = g_pool_on.load(std::memory_order_relaxed);
@@ -727,8 +725,8 @@ extern "C" int sd3d_set_pair_pool(int on) {
 // fell back to a static split of their pool: the results are unaffected, the event is reported here and through sd3d_last_error);
 // 0 is the healthy answer.  Synchronises the device.  < 0: error.
 extern "C" int sd3d_pair_pool_check(void) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PG_MAX_DEVICES) { sd3d_set_error(SD3D_ERR_LAUNCH, "pair_pool_check: no device"); return -1; }
+    const int dev = sd3d_device();
+    if (dev < 0) { sd3d_set_error(SD3D_ERR_LAUNCH, "pair_pool_check: no device"); return -1; }
     if (hipDeviceSynchronize() != hipSuccess) { sd3d_set_error(SD3D_ERR_LAUNCH, "pair_pool_check: device synchronisation failed"); return -1; }
     unsigned int zero = 0, bad = 0, seen = 0;
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_pool_bad), &zero, sizeof(zero)) != hipSuccess) { sd3d_set_error(SD3D_ERR_LAUNCH, "pair_pool_check: symbol write failed"); return -1; }
@@ -743,8 +741,8 @@ extern "C" int sd3d_pair_pool_check(void) {
 }
 // pooled launches so far on the current device (tests: did the pool really run?)
 extern "C" int sd3d_pair_pool_launches(int64_t* launches_out) {
-    int dev = 0;
-    if (!launches_out || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PG_MAX_DEVICES) return sd3d_set_error(SD3D_ERR_ARG, "pair_pool_launches: no device / no output");
+    const int dev = sd3d_device();
+    if (!launches_out || dev < 0) return sd3d_set_error(SD3D_ERR_ARG, "pair_pool_launches: no device / no output");
     *launches_out = (int64_t)g_pool_tickets[dev].load(std::memory_order_relaxed);
     return SD3D_OK;
 }
@@ -768,13 +766,16 @@ static const PGKernel k_ws[2][4] = {{pair_gemm_ws_kernel_1, pair_gemm_ws_kernel_
                                     {pair_gemm_ws_direct_kernel_1, pair_gemm_ws_direct_kernel_2, pair_gemm_ws_direct_kernel_3, pair_gemm_ws_direct_kernel_4}};
 static const PGKernel k_dense[4] = {pair_dense_kernel_1, pair_dense_kernel_2, pair_dense_kernel_3, pair_dense_kernel_4};
 
-static std::atomic<int> g_n_cu[PG_MAX_DEVICES];                                // CU count per device, 0: not asked yet
-static std::atomic<bool> g_ws_attr[PG_MAX_DEVICES];                            // the weight-stationary kernels' LDS limit is raised on this device
+static std::atomic<int> g_n_cu[SD3D_MAX_DEVICES];                                // CU count per device, 0: not asked yet
+static Sd3dLdsRaised g_ws_raised;                                              // the weight-stationary kernels' LDS limit, 80 KB (160 KB at nt = 4)
+#define WS_LDS(d, i) {(const void*)k_ws[d][i], (i == 3 ? 160 : 80) * 1024}
+static const Sd3dLdsKernel k_ws_lds[8] = {WS_LDS(0, 0), WS_LDS(0, 1), WS_LDS(0, 2), WS_LDS(0, 3), WS_LDS(1, 0), WS_LDS(1, 1), WS_LDS(1, 2), WS_LDS(1, 3)};
+#undef WS_LDS
 
 // the current device (the index of its per-device state) and its CU count; -1: no usable device
 static int pg_device(int* n_cu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PG_MAX_DEVICES) return -1;
+    const int dev = sd3d_device();
+    if (dev < 0) return -1;
     int n = g_n_cu[dev].load(std::memory_order_relaxed);
     if (!n) {
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return -1;
@@ -871,12 +872,7 @@ int launch_pair_conv(const float* in0, int ld0, int C0, const float* in1, int ld
     // (measured: level-3 256->256, 1808 tiles: 358 -> 347 us; level-4, 472 tiles: 104 -> 113 us - too few tiles for half the workgroups)
     const bool ws_two = !g.chained && !crowded && cgs == 2 && nt == 4 && Cout == 256 && g.n_tiles >= 1024 && w_lds_cg + WS_RANGE_TILES * PT * sizeof(int32_t) + 256 <= 160 * 1024;
     if (ws_one || ws_two) {
-        if (!g_ws_attr[dev].load(std::memory_order_relaxed)) {           // (a function attribute is per device; setting it twice is harmless)
-            for (int d = 0; d < 2; ++d)
-                for (int i = 0; i < 4; ++i)
-                    (void)hipFuncSetAttribute((const void*)k_ws[d][i], hipFuncAttributeMaxDynamicSharedMemorySize, (i == 3 ? 160 : 80) * 1024);
-            g_ws_attr[dev].store(true, std::memory_order_relaxed);
-        }
+        if (int rc = sd3d_raise_lds_limit(g_ws_raised, k_ws_lds, 8, dev)) return rc;
         // resident workgroups per CU: the pinned register budgets allow 4 / 3 / 3 / 2; LDS (160 KB) may allow fewer
         int per_cu = nt == 1 ? 4 : (nt == 3 ? 3 : 2);
         const size_t w_need = ws_two ? w_lds_cg : w_lds;

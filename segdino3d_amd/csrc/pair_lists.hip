@@ -7,7 +7,7 @@
 
 __device__ static inline int block_excl_scan_256p(int v, int* total, int* smem4) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
+    int inc = v;                                         // (the loop stays written out: through wave_scan_incl the compiler schedules this kernel differently)
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         int t = __shfl_up(inc, d);

@@ -151,7 +151,7 @@ __global__ __launch_bounds__(NW * 64) void pair_wgrad_kernel(const WGParams p) {
                 if (ci < p.Cin) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int row = co + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+                        const int row = co + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);   // = co + mfma32_row(r, lane >> 5); summed in that order the kernels compile differently
                         if (row < p.Cout) dst[(int64_t)row * p.Cin + ci] = acc[i][r];
                         acc[i][r] = 0.f;
                     }
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(LW_WAVES * 64) void linear_wgrad_small_kernel(const
             }
         }
     }
-    // D[row][col]: lane holds column (lane & 31), register r row 8 (r >> 2) + 4 (lane >> 5) + (r & 3).  Waves 8 .. 15 hand their block to
+    // D[row][col]: lane holds column (lane & 31), register r row mfma32_row(r, lane >> 5) = 8 (r >> 2) + 4 (lane >> 5) + (r & 3).  Waves 8 .. 15 hand their block to
     // waves 0 .. 7 (acc_w + acc_{w + 8}), then the eight sums are added in wave order: one fixed order whatever the timing.
     float (*red)[1024] = (float (*)[1024])smem;
     bs += __shfl_xor(bs, 32);
@@ -326,13 +326,13 @@ __global__ __launch_bounds__(LW_WAVES * 64) void linear_wgrad_small_kernel(const
     __syncthreads();                                            // the staging area becomes the reduction area
     if (wv >= LW_WAVES / 2) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) red[wv - LW_WAVES / 2][(8 * (r >> 2) + 4 * k + (r & 3)) * 32 + i] = acc[r];
+        for (int r = 0; r < 16; ++r) red[wv - LW_WAVES / 2][mfma32_row(r, k) * 32 + i] = acc[r];
     }
     __syncthreads();
     if (wv < LW_WAVES / 2) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float* slot = &red[wv][(8 * (r >> 2) + 4 * k + (r & 3)) * 32 + i];
+            float* slot = &red[wv][mfma32_row(r, k) * 32 + i];
             *slot = acc[r] + *slot;
         }
     }

@@ -5,17 +5,6 @@
 #include "common.h"
 #include "../../include/segdino3d_hip.h"
 
-__device__ static inline float wred_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ static inline float wred_max(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-    return v;
-}
-
 // scores[q*C + c] = softmax(cls[q, 0:C+1])[c], c < C   (:427)        one wave per query
 __global__ __launch_bounds__(256) void class_scores_kernel(const float* __restrict__ cls, int ld, int64_t Q, int C,
                                                            float* __restrict__ scores, float* __restrict__ rowmax) {
@@ -25,17 +14,17 @@ __global__ __launch_bounds__(256) void class_scores_kernel(const float* __restri
     const float* row = cls + q * ld;
     float mx = -INFINITY;
     for (int c = lane; c <= C; c += 64) mx = fmaxf(mx, row[c]);
-    mx = wred_max(mx);
+    mx = wave_max(mx);
     float s = 0.f;
     for (int c = lane; c <= C; c += 64) s += expf(row[c] - mx);
-    s = wred_sum(s);
+    s = wave_sum(s);
     float best = -INFINITY;
     for (int c = lane; c < C; c += 64) {
         const float pr = expf(row[c] - mx) / s;
         if (scores) scores[q * C + c] = pr;
         best = fmaxf(best, pr);
     }
-    best = wred_max(best);
+    best = wave_max(best);
     if (rowmax && lane == 0) rowmax[q] = best;
 }
 
@@ -57,8 +46,8 @@ __global__ __launch_bounds__(256) void mask_scores_kernel(const float* __restric
         const float x = row[s];
         if (x > 0.f) { num += 1.0f / (1.0f + expf(-x)); den += 1.f; }
     }
-    num = wred_sum(num);
-    den = wred_sum(den);
+    num = wave_sum(num);
+    den = wave_sum(den);
     if (lane == 0) {
         labels[r] = (int32_t)(f % (uint32_t)C);
         qidx[r] = q;
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(256) void gather_sigmoid_kernel(const float* __rest
         if (s < S) { y = 1.0f / (1.0f + expf(-row[s])); a += y; }
         sig[(int64_t)r * ld_out + s] = y;
     }
-    a = wred_sum(a);
+    a = wave_sum(a);
     if (lane == 0) area[r] = a;
 }
 
@@ -182,7 +171,7 @@ __global__ __launch_bounds__(256) void em_rowbits_kernel(const float* __restrict
     for (int rr = 0; rr < 32; ++rr) {
         const int r = g * 32 + rr;
         if (r >= n) break;
-        const float c = wred_sum(((w >> rr) & 1u) ? np : 0.f);
+        const float c = wave_sum(((w >> rr) & 1u) ? np : 0.f);
         if ((threadIdx.x & 63) == 0 && c > 0.f) atomicAdd(&count[r], (int)c);
     }
 }
@@ -572,10 +561,10 @@ __global__ __launch_bounds__(256) void instance_boxes_partial(const float* __res
         float l = lo[a], h = hi[a];
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) { l = fminf(l, __shfl_xor(l, d)); h = fmaxf(h, __shfl_xor(h, d)); }
-        const float s = wred_sum(su[a]);
+        const float s = wave_sum(su[a]);
         if (lane == 0) { sm[w][a] = l; sm[w][3 + a] = h; sm[w][6 + a] = s; }
     }
-    const float c = wred_sum(cnt);
+    const float c = wave_sum(cnt);
     if (lane == 0) sm[w][9] = c;
     __syncthreads();
     if (threadIdx.x < 10) {
@@ -743,7 +732,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_desc_kernel(const float* __re
             int c[4], sum = 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) { c[q] = hist[tid * 4 + q]; sum += c[q]; }
-            int inc = sum;
+            int inc = sum;                                          // (written out: through wave_scan_incl the compiler schedules this kernel differently)
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (tid >= d) inc += t; }
             int before = inc - sum;

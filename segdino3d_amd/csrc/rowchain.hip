@@ -16,7 +16,7 @@
 //   LN             dst = act(LayerNorm(src (+ res)) * g + b), wave w = row w, two-pass statistics
 //   PE             (box-modulated) sine positional encoding of the rows' reference points (utils.py:53-105)
 //   BOX            iterative box refinement (:735-759)
-//   MERGE          gathers the rows of the key-split superpoint cross-attention (dense.hip attention_body partial states)
+//   MERGE          gathers the rows of the key-split superpoint cross-attention (attention.hip attention_body partial states)
 //   BITS2D         blocked2d[q][m] = no superpoint both open for q and near 2D query m (:722-726), into LDS bit rows
 //   ATTN           multi-head attention of the 16 rows over <= a few thousand keys of their scene (K / V from global, L2-resident):
 //                  wave = (head, key half); S^T = K Q^T per 16-key tile puts a query in a lane column, online softmax in the
@@ -142,7 +142,7 @@ __device__ __forceinline__ void rc_linear(const RCOp& op, const RCCtx& cx) {
             const int r = 4 * kq + i;
             float y = acc[t][i] + bv[t];
             if (res) y += res[r * ldd + col];
-            y = rc_act(y, op.act);
+            y = sd3d_act(y, op.act);
             if (!(op.flag & SD3D_RC_F_NO_LDS_DST)) dst[r * ldd + col] = y;
             if (gout && r < cx.nrows) gout[(int64_t)(cx.row0 + r) * op.ld + col] = y;
         }
@@ -193,7 +193,7 @@ __device__ __forceinline__ void rc_attn(const RCOp& op, const RCCtx& cx, const R
         for (int g = 0; g < 2; ++g) {
             qf[g] = *(const f32x4*)(q + 16 * g);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) qf[g][e] *= op.f0 * RC_LOG2E;
+            for (int e = 0; e < 4; ++e) qf[g][e] *= op.f0 * SD3D_LOG2E;
         }
     }
     f32x4 O[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -410,8 +410,8 @@ extern "C" int sd3d_row_chain(const sd3d_rc_program* P, void* stream) {
     if (err) return sd3d_set_error(SD3D_ERR_ARG, err);
     const size_t sm = row_chain_lds_bytes(*P);
     if (sm > 160 * 1024) return sd3d_set_error(SD3D_ERR_ARG, "row_chain: more than 160 KB of LDS");
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)row_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+    static Sd3dLdsRaised raised;
+    if (int rc = sd3d_raise_lds_limit(raised, {{(const void*)row_chain_kernel, 160 * 1024}})) return rc;
     const int tiles = P->tile0[P->n_scenes];
     hipLaunchKernelGGL(row_chain_kernel, dim3((unsigned)tiles, (unsigned)P->n_programs), dim3(1024), sm, st, *P);
     SD3D_CHECK_LAUNCH();

@@ -98,7 +98,7 @@ __device__ __forceinline__ void rcn_linear(const RCOp& op, const RCCtx& cx) {
             for (int p = 1; p < kp; ++p) y += cx.scratch[(p * 4 + r) * CW + col];
             y += bv[m];
             if (res) y += res[r * ldd + col];
-            y = rc_act(y, op.act);
+            y = sd3d_act(y, op.act);
             if (!(op.flag & SD3D_RC_F_NO_LDS_DST)) dst[r * ldd + col] = y;
             if (gout && r < cx.nrows) gout[(int64_t)(cx.row0 + r) * op.ld + col] = y;
         }
@@ -125,7 +125,7 @@ __device__ __forceinline__ void rcn_attn(const RCOp& op, const RCCtx& cx, const 
         for (int c = 0; c < 8; ++c) {
             qf[c] = *(const f32x4*)(q + 4 * c);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) qf[c][e] *= op.f0 * RC_LOG2E;
+            for (int e = 0; e < 4; ++e) qf[c][e] *= op.f0 * SD3D_LOG2E;
         }
     }
     f32x4 O[8];
@@ -250,8 +250,8 @@ int launch_row_chain_narrow(const RCProgram* P, hipStream_t st) {
     if (err) return sd3d_set_error(SD3D_ERR_ARG, err);
     const size_t sm = ((size_t)P->n_slots * RC_SLOT + RCN_SCRATCH_FLOATS + (size_t)RC_R * (P->nw2_max + P->nw_max)) * sizeof(float);
     if (sm > 160 * 1024) return sd3d_set_error(SD3D_ERR_ARG, "row_chain: more than 160 KB of LDS");
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)row_chain_narrow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+    static Sd3dLdsRaised raised;
+    if (int rc = sd3d_raise_lds_limit(raised, {{(const void*)row_chain_narrow_kernel, 160 * 1024}})) return rc;
     const int tiles = P->tile0[P->n_scenes];
     hipLaunchKernelGGL(row_chain_narrow_kernel, dim3((unsigned)tiles, (unsigned)P->n_programs), dim3(RCN_THREADS), sm, st, *P);
     SD3D_CHECK_LAUNCH();

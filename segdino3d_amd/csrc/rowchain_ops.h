@@ -3,11 +3,11 @@
 // here is local to a row (or to a row and its scene's layer-invariant tables), so its arithmetic - and its bits - are the same in both.
 #pragma once
 #include "common.h"
+#include "attention.h"
 #include "../../include/segdino3d_hip.h"
 
 #define RC_LDW 260
 #define RC_SLOT (RC_R * RC_LDW)
-#define RC_LOG2E 1.4426950408889634f
 
 typedef sd3d_rc_op RCOp;
 typedef sd3d_rc_scene RCScene;
@@ -18,19 +18,6 @@ const char* rc_check(const RCProgram& P, int R);
 int launch_row_chain_narrow(const RCProgram* P, hipStream_t st);
 
 __device__ __forceinline__ int rc_ld(int width) { return width <= 256 ? RC_LDW : width + 4; }
-
-__device__ __forceinline__ float rc_wsum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ float rc_act(float y, int act) {
-    if (act == 1) return fmaxf(y, 0.f);
-    if (act == 2) return 0.5f * y * (1.f + erff(y * 0.70710678118654752440f));
-    if (act == 3) return 1.f / (1.f + expf(-y));
-    return y;
-}
 
 struct RCCtx {
     float* lds;            // slots
@@ -51,11 +38,11 @@ __device__ __forceinline__ void rc_layernorm(const RCOp& op, const RCCtx& cx) {
     const float* src = cx.lds + op.src0 * RC_SLOT + r * RC_LDW + 4 * lane;
     f32x4 v = *(const f32x4*)src;
     if (op.res != 0xFF) v += *(const f32x4*)(cx.lds + op.res * RC_SLOT + r * RC_LDW + 4 * lane);
-    const float mean = rc_wsum(v[0] + v[1] + v[2] + v[3]) / 256.0f;
+    const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) / 256.0f;
     float q = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; q += d * d; }
-    const float rstd = 1.0f / sqrtf(rc_wsum(q) / 256.0f + op.f0);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / 256.0f + op.f0);
     const f32x4 g = *(const f32x4*)((const float*)op.p0 + 4 * lane), b = *(const f32x4*)((const float*)op.p1 + 4 * lane);
     f32x4 y;
 #pragma unroll
@@ -155,7 +142,7 @@ __device__ __forceinline__ void rc_box(const RCOp& op, const RCCtx& cx, const RC
 
 // ------------------------------------------------------------------------------------------------ MERGE
 // rows of the superpoint cross-attention: either its finished output (key split 1) or the combination of its partial softmax
-// states (dense.hip attention_merge_body: the same expression, the same order over the splits)
+// states (attention.hip attention_merge_body: the same expression, the same order over the splits)
 __device__ __forceinline__ void rc_merge(const RCOp& op, const RCCtx& cx, const RCScene& sc) {
     float* dst = cx.lds + op.dst * RC_SLOT;
     const int H = 8;
@@ -183,7 +170,7 @@ __device__ __forceinline__ void rc_merge(const RCOp& op, const RCCtx& cx, const 
             const float* b = base + z * (64 + 1024);
             const float mz = b[qq];
             const float f = (mz == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mz - M);
-            L = __builtin_fmaf(b[32 + qq], f, L);                 // (explicit fused multiply-adds here and in dense.hip attention_merge_body:
+            L = __builtin_fmaf(b[32 + qq], f, L);                 // (explicit fused multiply-adds here and in attention.hip attention_merge_body:
             acc = __builtin_fmaf(b[64 + dv * 32 + qq], f, acc);   //  the two must agree bit for bit whatever the compiler would contract)
         }
         dst[r * RC_LDW + col] = acc / L;

@@ -58,8 +58,7 @@ __device__ static inline void se_wave_groups(K key, bool valid, K& pk, int& pc, 
 __device__ static inline void se_raise(unsigned long long* status, int bits) {
     const unsigned long long any = __ballot(bits != 0);
     if (!any) return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bits |= __shfl_xor(bits, d);
+    bits = wave_or(bits);
     if ((threadIdx.x & 63) == 0) atomicOr(status, (unsigned long long)bits);
 }
 
@@ -215,12 +214,7 @@ __global__ __launch_bounds__(256) void pq_rank_kernel(const uint32_t* __restrict
     int pc[SE_ID_WORDS / 256], s = 0;
 #pragma unroll
     for (int k = 0; k < SE_ID_WORDS / 256; ++k) { pc[k] = __popc(bits[w0 + k]); s += pc[k]; }
-    int inc = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(inc, d);
-        if (lane >= d) inc += v;
-    }
+    int inc = wave_scan_incl(s, lane);
     if (lane == 63) wave_sum[wv] = inc;
     __syncthreads();
     int run = inc - s, total = 0;

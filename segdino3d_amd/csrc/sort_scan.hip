@@ -19,7 +19,7 @@
 // ----------------------------------------------------------------------------------------------
 __device__ static inline int block_excl_scan_256(int v, int* total, int* smem4) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
+    int inc = v;                                         // (the loop stays written out: through wave_scan_incl the compiler schedules this kernel differently)
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         int t = __shfl_up(inc, d);
@@ -94,8 +94,7 @@ __global__ __launch_bounds__(256) void scan_apply_v2(const int* __restrict__ in,
     {
         int part = 0;
         for (int i = threadIdx.x; i < (int)blockIdx.x; i += 256) part += sums[i];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
+        part = wave_sum(part);
         if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = part;
         __syncthreads();
         if (threadIdx.x == 0) base_s = sm[0] + sm[1] + sm[2] + sm[3];
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(1024) void scan_small_kernel(const int* __restrict_
         int v[8], s = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) { v[i] = (base + i < n) ? in[base + i] : 0; s += v[i]; }
-        int inc = s;
+        int inc = s;                                         // (the loop stays written out: through wave_scan_incl the compiler schedules this kernel differently)
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const int t = __shfl_up(inc, d);

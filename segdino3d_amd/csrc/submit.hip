@@ -103,8 +103,7 @@ __device__ static inline int lt_length(int32_t v) {
 }
 
 __device__ static inline void lt_flush_status(int status, int32_t* info, int* red4) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) status |= __shfl_xor(status, d);
+    status = wave_or(status);
     if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = status;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -123,8 +122,7 @@ __global__ __launch_bounds__(LT_TILE) void lt_count_kernel(const int64_t* __rest
         const int32_t v = lt_value(values, i, lut, lut_len, ok, status);
         if (ok) len = lt_length(v);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) len += __shfl_xor(len, d);
+    len = wave_sum(len);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = len;
     lt_flush_status(status, info, sred);                                            // (has the barrier red[] needs)
     if (threadIdx.x == 0) tile_bytes[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
@@ -145,12 +143,7 @@ __global__ __launch_bounds__(LT_TILE) void lt_write_kernel(const int64_t* __rest
         if (ok) len = lt_length(v);
     }
     status = 0;                                                                     // the range bits were set by lt_count_kernel
-    int inc = len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
+    int inc = wave_scan_incl(len, lane);
     if (lane == 63) wsum[wv] = inc;
     __syncthreads();
     int at = inc - len;

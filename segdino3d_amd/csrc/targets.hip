@@ -186,12 +186,7 @@ __global__ __launch_bounds__(TG_RANK_THREADS) void tg_rank_kernel(const uint32_t
         const int w = t * per + k;
         if (w < words) s += __popc(bits[w]);
     }
-    int inc = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(inc, d);
-        if (lane >= d) inc += v;
-    }
+    int inc = wave_scan_incl(s, lane);
     if (lane == 63) wave_sum[wv] = inc;
     __syncthreads();
     int run = inc - s, total = 0;

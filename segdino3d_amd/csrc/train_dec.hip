@@ -6,12 +6,6 @@
 #include "../../include/segdino3d_hip.h"
 #include <math.h>
 
-__device__ __forceinline__ float wsum64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // g = dy * act'(.) with ref = the forward OUTPUT for relu / sigmoid and the PRE-activation for gelu; columns [C, C_pad)
 // of g are zeroed (the GEMMs that consume g want 32-column multiples)
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ dy, int ld_dy, const float* __restrict__ ref, int ld_ref, int act,
@@ -79,7 +73,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
             s += v[it][0] + v[it][1] + v[it][2] + v[it][3];
         }
     }
-    const float mean = wsum64(s) / (float)D;
+    const float mean = wave_sum(s) / (float)D;
     float q = 0.f;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
@@ -89,7 +83,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
             for (int e = 0; e < 4; ++e) { const float dlt = v[it][e] - mean; q += dlt * dlt; }
         }
     }
-    const float rstd = 1.0f / sqrtf(wsum64(q) / (float)D + eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
     float a = 0.f, b = 0.f;                                    // sum g w, sum g w xhat
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
@@ -103,7 +97,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
             }
         }
     }
-    a = wsum64(a) / (float)D; b = wsum64(b) / (float)D;
+    a = wave_sum(a) / (float)D; b = wave_sum(b) / (float)D;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const int c = (it * 64 + lane) * 4;
@@ -146,7 +140,7 @@ __global__ __launch_bounds__(256) void sine_pe_mod_bwd_kernel(const float* __res
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float t = wsum64(acc[a]);
+        const float t = wave_sum(acc[a]);
         if (lane == 0) d_num[r * 3 + a] = t / mod_den[(int64_t)r * ld_den + a];
     }
 }

@@ -17,21 +17,6 @@
 // scene statistics: stats[0:3]=min xyz, [3:6]=max xyz, [6:9]=sum xyz (fp32)
 // ---------------------------------------------------------------------------------------------
 #define STAT_BLOCKS 256
-__device__ static inline float wave_min(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
-    return v;
-}
-__device__ static inline float wave_max(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-    return v;
-}
-__device__ static inline float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void scene_stats_partial(const float* __restrict__ pts, int ld, int64_t n,
                                                            float* __restrict__ part /*[gridDim.x][9]*/) {
@@ -532,8 +517,7 @@ __global__ __launch_bounds__(256) void kernel_map_mirrored_kernel(const uint64_t
     }
     if (pair_count) {
         int c = found;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+        c = wave_sum(c);
         if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -770,8 +754,7 @@ __global__ __launch_bounds__(KH_THREADS) void kmap_hier_kernel(const KHParams P)
         if (bc) bc[(int64_t)(is_b ? tid - 64 : tid) * gridDim.x + blockIdx.x] = tot;
     }
     if (tid < 192) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
+        tot = wave_sum(tot);
         int32_t* pc = is_b ? P.pair_count_b : P.pair_count;
         if (lane == 0 && tot && pc) atomicAdd(&pc[(blockIdx.x * 2 + (tid >> 7)) & 63], tot);
     }

@@ -1,0 +1,37 @@
+// Reductions and scans over the 64 lanes of a wave (included from common.h).
+// Every reduction is the xor butterfly in the order 32, 16, .. 1, so each lane ends with the same value and a float sum
+// has one fixed association; kernels whose results are pinned bit for bit depend on that order.
+#pragma once
+#include <hip/hip_runtime.h>
+
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_or(T v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v |= __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
+    return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
+    return v;
+}
+// Inclusive prefix sum over the wave; `lane` is the caller's lane id (threadIdx.x & 63).
+__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(v, d);
+        if (lane >= d) v += t;
+    }
+    return v;
+}

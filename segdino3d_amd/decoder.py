@@ -819,7 +819,7 @@ class ScanNetQueryDecoder(DerivedWeights):
         """`_forward_ops` for B >= 1 scenes with every query-row-local stretch of a layer as ONE launch (rowchain.Program):
              A  positional query: anchor MLP -> box-modulated sine PE -> ref_point_head, the two cross-attention query projections
                 (+ the class head of the previous layer as a second program of the same launch)
-             -  masked cross-attention to the superpoints (dense.hip attention kernel, key-split pass only)
+             -  masked cross-attention to the superpoints (attention.hip kernel, key-split pass only)
              B  combine the key splits -> out-projection + residual + norm1 -> packed self-attention q / k / v projection
              C  self-attention over the scene's queries -> out-projection + norm2 -> 2D-query mask bits -> 2D cross-attention -> FFN
                 -> box MLPs + refinement -> head norm (+ semantic head on the last layer)

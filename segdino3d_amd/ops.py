@@ -1203,7 +1203,7 @@ def _attn_job_table(jobs, num_heads, name, strided_out):
 
 
 def attention_dropout_keep(key, call, H, Lq, Lk, p):
-    """The keep mask of attention dropout (csrc/attention_dropout.h) as bool [H, Lq, Lk]: what `train_dec.attention(..., dropout_p=p,
+    """The keep mask of attention dropout (csrc/attention.h) as bool [H, Lq, Lk]: what `train_dec.attention(..., dropout_p=p,
     key=key, call=call)` keeps inside its kernels.  key: two int32 words on the device."""
     if not 0.0 <= float(p) < 1.0:
         raise ValueError(f"attention_dropout_keep: p must lie in [0, 1), got {p}")

@@ -1,4 +1,4 @@
-"""The keep mask of attention dropout restated in numpy (csrc/attention_dropout.h is the definition the kernels share), and the
+"""The keep mask of attention dropout restated in numpy (csrc/attention.h is the definition the kernels share), and the
 float64 reference of attention with that mask applied to the probabilities.
 
 Element (head, q, k) of attention number `call`: Philox4x32-10 keyed by two uint32 words with the counter (k >> 2, q, head, call);

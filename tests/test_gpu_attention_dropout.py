@@ -1,4 +1,4 @@
-"""Attention dropout inside the fused kernels (csrc/attention_dropout.h; the DROP instantiations of csrc/dense.hip attention_body and of
+"""Attention dropout inside the fused kernels (csrc/attention.h; the DROP instantiations of csrc/attention.hip attention_body and of
 csrc/attention_bwd.hip attn_bwd_q_kernel / attn_bwd_kv_kernel) on the device: the mask kernel against the numpy restatement bit for
 bit, forward (fp32, bf16) and gradients against float64 attention with that mask on its probabilities, independence of the key split,
 rate 0, determinism, fully dropped rows, peak memory, and the decoder against its explicit-probability cross-check on the same bits.

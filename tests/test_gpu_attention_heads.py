@@ -1,4 +1,4 @@
-"""Attention with 64-channel heads (the W = 2 instantiations of csrc/dense.hip attention_body and of csrc/attention_bwd.hip
+"""Attention with 64-channel heads (the W = 2 instantiations of csrc/attention.hip attention_body and of csrc/attention_bwd.hip
 attn_bwd_q_kernel / attn_bwd_kv_kernel) against float64 masked softmax attention (tests/attention_heads_case.py, pinned to the oracle in
 test_decoder_heads.py): forward fp32 / bf16, one and two score sources, bit-packed masks, key split and merge, the batched launch, the
 backward pass; and the kernels of both widths against device outputs recorded before the width became a template parameter of one body

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Resource table of every attention kernel instantiation (csrc/dense.hip, csrc/attention_bwd.hip) as markdown: registers, LDS,
+"""Resource table of every attention kernel instantiation (csrc/attention.hip, csrc/attention_bwd.hip) as markdown: registers, LDS,
 occupancy and scratch as the compiler reports them (`-Rpass-analysis=kernel-resource-usage`; device code only, needs no GPU).
 
     python tools/attention_resources.py            # compiles the two files for gfx950 into a temporary directory"""
@@ -50,7 +50,7 @@ def main():
     texts = [open(p).read() for p in sys.argv[1:]]
     if not texts:
         with tempfile.TemporaryDirectory() as tmp:
-            texts = [remarks(s, tmp) for s in ("dense.hip", "attention_bwd.hip")]
+            texts = [remarks(s, tmp) for s in ("attention.hip", "attention_bwd.hip")]
     print("| kernel | VGPR | AGPR | scratch B/lane | VGPR spill | waves/SIMD | static LDS B |")
     print("|---|---|---|---|---|---|---|")
     for text in texts:
