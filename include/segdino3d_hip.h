@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 13
+#define SD3D_ABI_VERSION 14
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -66,19 +66,14 @@ int sd3d_scan_exclusive_i32(const int32_t* in, int32_t* out, int64_t n, int32_t*
                             void* stream);
 /* order-preserving key builders */
 int sd3d_keys_from_f32(const float* x, int64_t n, int descending, uint64_t* keys, void* stream);
-int sd3d_keys_from_i64(const int64_t* x, int64_t n, uint64_t* keys, void* stream);
-/* The same, and *flag |= flag_value when an id does not fit `bits` bits (a radix sort over fewer key bits is then not a full sort). */
-int sd3d_keys_from_i64_checked(const int64_t* x, int64_t n, uint64_t* keys, int bits, int32_t* flag, int flag_value, void* stream);
-/* ... and *max_out = max(*max_out, largest id, clamped to INT32_MAX) - the caller zeroes it; bits = 64: no width check.  An id that is negative or
- * larger than INT32_MAX - 1 ORs 8 into *flag whatever `bits` is (ids are row numbers: int32).  The superpoint count of a
- * scene (largest id + 1; `minkunet.py:631-639` scatter_mean sizes its output the same way) is known without waiting for the sort of the ids. */
-int sd3d_keys_from_i64_checked_max(const int64_t* x, int64_t n, uint64_t* keys, int bits, int32_t* flag, int flag_value, int32_t* max_out,
-                                   void* stream);
-
-/* keys[i] = x[i] + add (sd3d_keys_from_i64_offset: the scene's bits of a batch-wide key) with the check and the maximum of
- * sd3d_keys_from_i64_checked_max taken on x[i]. */
-int sd3d_keys_from_i64_offset_checked_max(const int64_t* x, int64_t n, int64_t add, uint64_t* keys, int bits, int32_t* flag, int flag_value,
-                                          int32_t* max_out, void* stream);
+/* keys[i] = x[i] + add (add: the scene's bits of a batch-wide key - superpoint ids of scene b become (b << 32) | id before the batch-wide
+ * sort; 0 for one scene).  The checks and the maximum are taken on x[i], not on the key: *flag |= flag_value when an id does not fit `bits`
+ * bits (a radix sort over fewer key bits is then not a full sort; bits = 1..64, 64: no width check), *max_out = max(*max_out, largest id,
+ * clamped to INT32_MAX) - the caller zeroes it - and an id that is negative or larger than INT32_MAX - 1 ORs 8 into *flag whatever `bits` is
+ * (ids are row numbers: int32).  flag and max_out are required.  The superpoint count of a scene (largest id + 1; `minkunet.py:631-639`
+ * scatter_mean sizes its output the same way) is known without waiting for the sort of the ids. */
+int sd3d_keys_from_i64(const int64_t* x, int64_t n, int64_t add, uint64_t* keys, int bits, int32_t* flag, int flag_value, int32_t* max_out,
+                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Voxelisation and coordinate maps.
@@ -162,20 +157,16 @@ int sd3d_kernel_map(const uint64_t* out_keys, int64_t n_out, const uint64_t* tab
  * [(n_levels + 1) x 64], zeroed - 64 partial rulebook counters per table (levels 0 .. n_levels - 1, then the 5^3 table).  The tables
  * are those of sd3d_kernel_map, entry for entry (MinkowskiEngine kernel map generation: minkunet.py:146-162).
  * perm8 + nbr_down[l] [8, n_{l+1}] / nbr_up[l] [8, n_l] for l < n_levels - 1 (all optional: NULL): the stride-2 maps of every level pair
- * (the tables of sd3d_stride_maps) from the same launches, every entry written by the thread that owns it (no pre-fill). */
+ * (the tables of sd3d_stride_maps) from the same launches, every entry written by the thread that owns it (no pre-fill).
+ * blk_cnt3 / blk_cnt5 (optional): while a workgroup holds the 256 rows of a block, the entry counts per (offset, 256-row block) of the tables
+ * it writes: blk_cnt3[l] (l < n_levels - 1; the array or any entry may be NULL) device int32 [27, ceil(n_l / 256)], blk_cnt5 (NULL or)
+ * [125, ceil(n_0 / 256)], count of offset k in rows [256 b, 256 b + 256) at [k * nblk + b] - what sd3d_pair_lists_desc takes as blk_counts
+ * in place of its own count pass.  (The coarsest level's map is searched directly and brings no counts.) */
 size_t sd3d_kernel_maps_hier_ws_bytes(int n_levels, const int64_t* n);
 int sd3d_kernel_maps_hier(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n,
                           int32_t* const* nbr3, int32_t* nbr5, const int8_t* offsets3, const int8_t* offsets5, const int8_t* inv27,
-                          int32_t* pair_counts, const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up, void* ws,
-                          size_t ws_bytes, void* stream);
-/* ... and, while a workgroup holds the 256 rows of a block, the entry counts per (offset, 256-row block) of the tables it writes:
- * blk_cnt3[l] (l < n_levels - 1; the array or any entry may be NULL) device int32 [27, ceil(n_l / 256)], blk_cnt5 (NULL or)
- * [125, ceil(n_0 / 256)], count of offset k in rows [256 b, 256 b + 256) at [k * nblk + b] - what sd3d_pair_lists_desc_counts takes in
- * place of its own count pass.  (The coarsest level's map is searched directly and brings no counts.) */
-int sd3d_kernel_maps_hier_counts(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n,
-                                 int32_t* const* nbr3, int32_t* nbr5, const int8_t* offsets3, const int8_t* offsets5, const int8_t* inv27,
-                                 int32_t* pair_counts, const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up,
-                                 int32_t* const* blk_cnt3, int32_t* blk_cnt5, void* ws, size_t ws_bytes, void* stream);
+                          int32_t* pair_counts, const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up,
+                          int32_t* const* blk_cnt3, int32_t* blk_cnt5, void* ws, size_t ws_bytes, void* stream);
 /* 2x2x2 stride-2 maps from the parent array: nbr_down [8, n_coarse], nbr_up [8, n_fine]; perm8[8]
  * maps the child's Z-order position (x | y<<1 | z<<2) to the weight index. */
 int sd3d_stride_maps(const uint64_t* fine_keys, const int32_t* parent, int64_t n_fine, int64_t n_coarse,
@@ -205,8 +196,6 @@ typedef struct sd3d_scene_src {
  * batch-global point numbers.  `scenes` is a HOST array (copied into the launch). */
 int sd3d_voxel_mean_batch(const sd3d_scene_src* scenes, int n_scenes, int F, int mode, const uint64_t* ukeys,
                           const uint32_t* sorted_idx, const int32_t* seg_start, int64_t n_vox, float* out, int ld_out, void* stream);
-/* keys[i] = x[i] + add: superpoint ids of scene b become (b << 32) | id before the batch-wide sort. */
-int sd3d_keys_from_i64_offset(const int64_t* x, int64_t n, int64_t add, uint64_t* keys, void* stream);
 /* sd3d_segment_starts for sorted (scene << 32 | id) keys: dense id = id_off[scene] + id, S = number of dense ids of the batch.
  * `id_off` is a HOST array of n_scenes entries. */
 int sd3d_segment_starts_batch(const uint64_t* sorted_ids, int64_t n, int64_t S, const int32_t* id_off, int n_scenes, int32_t* start,
@@ -313,13 +302,11 @@ typedef struct sd3d_pair_table_desc {
     int64_t M, p_cap;
     int32_t K, center, rl_stride, meta;
 } sd3d_pair_table_desc;
-int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* tables, void* ws, size_t ws_bytes, void* stream);
-/* The same, with the count pass of some tables already done: blk_counts (NULL or) [n] pointers, each NULL or device int32
- * [K, ceil(M / 256)] as sd3d_kernel_maps_hier_counts leaves them.  Only a table built in the row-block form (pos == NULL, K <= 128, not
- * chained) may bring counts; it has no workgroups in the count launch, its counts are scanned in place (consumed), and its lists are
- * those of sd3d_pair_lists_desc bit for bit. */
-int sd3d_pair_lists_desc_counts(int n, const sd3d_pair_table_desc* tables, int32_t* const* blk_counts, void* ws, size_t ws_bytes,
-                                void* stream);
+/* blk_counts: the count pass of some tables already done - (NULL or) [n] pointers, each NULL or device int32 [K, ceil(M / 256)] as
+ * sd3d_kernel_maps_hier leaves them in blk_cnt3 / blk_cnt5.  Only a table built in the row-block form (pos == NULL, K <= 128, not chained) may
+ * bring counts; it has no workgroups in the count launch, its counts are scanned in place (consumed), and its lists are those of a call
+ * without counts bit for bit. */
+int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* tables, int32_t* const* blk_counts, void* ws, size_t ws_bytes, void* stream);
 int sd3d_pair_conv_ex(const float* in0, int ld0, int C0, const float* in1, int ld1, const int32_t* in_idx,
                       const int32_t* tile_k, int64_t p_cap, const int32_t* pos, const int32_t* rlist, int rl_stride, int center,
                       const int32_t* out_idx, const float* wt, int K, int Cin, int Cout, int64_t M, const float* scale,
@@ -429,25 +416,18 @@ int sd3d_layernorm(const float* x, int ld_x, const float* res, int ld_res, const
 int sd3d_linear_layernorm(const float* x, int ld_x, int64_t M, int Cin, const float* wt, int Cout, const float* bias, const float* res, int ld_res,
                           const float* ln_w, const float* ln_b, float eps, int act, float* out, int ld_out, void* stream);
 /* PositionEmbeddingCoordsSine.get_sine_embeddings (utils.py:53-105) incl. shift_scale_points
- * (pc_util.py:48-76).  range = (lo[3], hi[3]); dim_t / axis: per output channel (host tables);
- * optional box modulation out *= mod_num / mod_den (decoder :660-663; ld_den may be 0 = broadcast). */
-int sd3d_sine_pe(const float* xyz, int ld_xyz, int64_t n, const float* range, const float* dim_t, const int8_t* axis,
-                 int d_pos, const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out, int ld_out,
-                 void* stream);
+ * (pc_util.py:48-76).  A range is (lo[3], hi[3]); dim_t / axis: per output channel (host tables);
+ * optional box modulation out *= mod_num / mod_den (decoder :660-663; ld_den may be 0 = broadcast; mod_num without mod_den is refused).
+ * ranges / row_scene, here and in sd3d_fourier_pe and sd3d_box_refine: row_scene NULL = ranges is ONE [6] range for every row; otherwise the
+ * rows of SEVERAL scenes at once (the decoder of a batched evaluation forward): ranges [n_scenes, 6], row_scene [n] = scene of every row, row r
+ * uses ranges[row_scene[r]].  Per row the arithmetic is the same either way. */
+int sd3d_sine_pe(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* dim_t,
+                 const int8_t* axis, int d_pos, const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out,
+                 int ld_out, void* stream);
 /* PositionEmbeddingCoordsSine.get_fourier_embeddings (utils.py:107-142; decoder `pos_type="fourier"`): out[:, :d/2] = sin(p),
- * out[:, d/2:] = cos(p), p = (2 pi * shift_scale(xyz)) @ gauss_b[:, :d/2]; gauss_b [3, >= d/2] is the module's buffer. */
-int sd3d_fourier_pe(const float* xyz, int ld_xyz, int64_t n, const float* range, const float* gauss_b, int ld_b, int d_pos,
-                    float* out, int ld_out, void* stream);
-/* The same two encodings and sd3d_box_refine over the rows of SEVERAL scenes at once (the decoder of a batched evaluation forward):
- * ranges [n_scenes, 6], row_scene [n] = scene of every row; row r uses ranges[row_scene[r]].  Per row the arithmetic is unchanged. */
-int sd3d_sine_pe_rows(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* dim_t,
-                      const int8_t* axis, int d_pos, const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out,
-                      int ld_out, void* stream);
-int sd3d_fourier_pe_rows(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* gauss_b,
-                         int ld_b, int d_pos, float* out, int ld_out, void* stream);
-int sd3d_box_refine_rows(const float* ref_points, const float* d_center, const float* size_prev, int ld_size_prev,
-                         const float* d_size, const float* ranges, const int32_t* row_scene, int normalize, int64_t Q, float* center,
-                         float* size, float* size_metric, void* stream);
+ * out[:, d/2:] = cos(p), p = (2 pi * shift_scale(xyz)) @ gauss_b[:, :d/2]; gauss_b [3, >= d/2] is the module's buffer.  An odd d_pos is refused. */
+int sd3d_fourier_pe(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* gauss_b,
+                    int ld_b, int d_pos, float* out, int ld_out, void* stream);
 /* Fused multi-head attention (replaces bmm + masked_fill + softmax + bmm of attention.py:361-385 and
  * nn.MultiheadAttention's SDPA at decoder :79).  q / k / v / out hold H heads of head_dim channels side by side; head_dim is 32 or 64
  * (one kernel body, the width a template parameter), any other width returns SD3D_ERR_ARG before anything is launched.  nsrc = 2
@@ -461,25 +441,22 @@ int sd3d_box_refine_rows(const float* ref_points, const float* d_center, const f
  * tile, head, key split) is m[32], l[32], O[head_dim dv][32 q] in the log2 domain = 64 + 32 * head_dim floats, laid out
  * [ceil(Lq/32)][H][ksplit] with ksplit <= 8.  The launcher splits the keys only as far as the workspace it was given holds (ksplit = 1
  * without one) and never writes behind it.
+ * key, call, p: dropout of rate p on the softmax probabilities, inside the kernel (nn.MultiheadAttention(dropout=p) in training,
+ * attention.py:383): out = (c K o softmax(S)) V with c = 1 / (1 - p); lse, the key split and its workspace are unchanged.
+ * The keep mask K is a pure function of (key, call, head, q, k) (csrc/attention.h): Philox4x32-10 keyed by the two words at
+ * `key` (device memory) with the counter (k >> 2, q, head, call); element (head, q, k) takes output word k & 3 and is kept iff that
+ * word >= floor(p 2^32).  `call` tells the attentions of one step apart.  Neither the launch shape nor the head width enters, so
+ * sd3d_attention_backward regenerates the mask the forward drew and sd3d_attention_dropout_keep writes it out
+ * (keep[H, Lq, Lk] bytes, 1 = kept).  p == 0 (evaluation; key NULL, call 0) launches the kernels without dropout and ignores key; p outside
+ * [0, 1) (NaN included), p > 0 with a NULL key or an unsupported head width returns SD3D_ERR_ARG before anything is launched.
  * sd3d_attention_config: the waves per workgroup and the key split the launcher chooses for one attention given ws_bytes of split
  * workspace (host-only, launches nothing). */
 size_t sd3d_attention_ws_bytes(int Lq, int H, int head_dim);
 int sd3d_attention(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
                    const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
-                   float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, void* stream);
+                   float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, const uint32_t* key, int call, float p,
+                   void* stream);
 int sd3d_attention_config(int Lq, int Lk, int H, int head_dim, size_t ws_bytes, int* waves_out, int* ksplit_out);
-/* sd3d_attention with dropout of rate p on the softmax probabilities, inside the kernel (nn.MultiheadAttention(dropout=p) in training,
- * attention.py:383): out = (c K o softmax(S)) V with c = 1 / (1 - p); lse, the key split and its workspace are those of sd3d_attention.
- * The keep mask K is a pure function of (key, call, head, q, k) (csrc/attention.h): Philox4x32-10 keyed by the two words at
- * `key` (device memory) with the counter (k >> 2, q, head, call); element (head, q, k) takes output word k & 3 and is kept iff that
- * word >= floor(p 2^32).  `call` tells the attentions of one step apart.  Neither the launch shape nor the head width enters, so
- * sd3d_attention_dropout_backward regenerates the mask the forward drew and sd3d_attention_dropout_keep writes it out
- * (keep[H, Lq, Lk] bytes, 1 = kept).  p == 0 runs sd3d_attention itself; p outside [0, 1), a NULL key or an unsupported head width
- * returns SD3D_ERR_ARG before anything is launched. */
-int sd3d_attention_dropout(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
-                           const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
-                           float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, const uint32_t* key, int call, float p,
-                           void* stream);
 int sd3d_attention_dropout_keep(const uint32_t* key, int call, int H, int Lq, int Lk, float p, uint8_t* keep, void* stream);
 /* n <= SD3D_MAX_BATCH independent attentions of the same kind (heads, width, scale, one or two sources, fp32 / bf16 contractions) in ONE
  * launch: the decoder of a batched evaluation forward runs the scenes' cross- / self- / 2D-query attentions this way.  blockIdx.x runs
@@ -512,10 +489,10 @@ int sd3d_mask_bits_batch(int n, const float* const* logits, const int* ld, const
                          const int* nwords, float thr, void* stream);
 int sd3d_dinox_mask_bits_batch(int n, const uint32_t* const* blocked, const uint32_t* const* near, const int* nwords, const int64_t* Q,
                                const int64_t* Mq, uint32_t* const* out, const int* nwords_out, void* stream);
-/* centre / size refinement (:735-759, :768-772). d_size may be NULL (no size head). */
+/* centre / size refinement (:735-759, :768-772). d_size may be NULL (no size head).  ranges / row_scene: as in sd3d_sine_pe. */
 int sd3d_box_refine(const float* ref_points, const float* d_center, const float* size_prev, int ld_size_prev,
-                    const float* d_size, const float* range, int normalize, int64_t Q, float* center, float* size,
-                    float* size_metric, void* stream);
+                    const float* d_size, const float* ranges, const int32_t* row_scene, int normalize, int64_t Q, float* center,
+                    float* size, float* size_metric, void* stream);
 /* out = act(x * scale + shift) + add, x = [x0 (C0 channels) | x1] (x1 may be NULL).  add NULL: the pre-activation
  * BatchNorm1d + ReLU of the spconv residual blocks (spconvunet.py:48-51, 154-156, 184-187, 227-229); with add: the tail of a
  * normalize_before=False residual block - conv -> BatchNorm1d -> ReLU, then the identity branch summed in AFTER the
@@ -804,20 +781,16 @@ int sd3d_sine_pe_mod_backward(const float* d_out, int ld_do, const float* xyz, i
  * (fp32 or, for mixed-precision training, the bf16 forward), and the backward pass (gradients of attention.py:361-385 /
  * nn.MultiheadAttention, decoder :79): given out, lse and d_out -> dq0 (dq1), dk0 (dk1), dv with the shapes / strides of their forward
  * tensors.  Exact fp32 MFMA, P recomputed tile by tile, fixed summation order.  head_dim: 32 or 64, else SD3D_ERR_ARG before anything is
- * launched.  ws: sd3d_attention_backward_ws_bytes (one float per head and query, D = dO . O; 0 for an unsupported width). */
+ * launched.  ws: sd3d_attention_backward_ws_bytes (one float per head and query, D = dO . O; 0 for an unsupported width).
+ * key, call, p: those of the forward call (out and lse as that call left them).  With p > 0: dV = (c K o P)^T dO, dP = c K o (dO V^T),
+ * dS = P o (dP - D) with D = dO . O as without dropout; the kernels regenerate the keep mask K.  p == 0 launches the kernels without
+ * dropout and ignores key; p outside [0, 1) or p > 0 with a NULL key returns SD3D_ERR_ARG before anything is launched. */
 size_t sd3d_attention_backward_ws_bytes(int Lq, int H, int head_dim);
 int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
                             const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
                             const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0,
                             float* dq1, int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws,
-                            size_t ws_bytes, void* stream);
-/* The backward pass of sd3d_attention_dropout (same key, call and p; out and lse as that call left them): dV = (c K o P)^T dO,
- * dP = c K o (dO V^T), dS = P o (dP - D) with D = dO . O as without dropout.  p == 0 is sd3d_attention_backward. */
-int sd3d_attention_dropout_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1,
-                                    int ldk1, const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim,
-                                    float scale, const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0,
-                                    int ld_dq0, float* dq1, int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv,
-                                    int ld_dv, void* ws, size_t ws_bytes, const uint32_t* key, int call, float p, void* stream);
+                            size_t ws_bytes, const uint32_t* key, int call, float p, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Parameter update of a training iteration (csrc/optim.hip; segdino3d_amd/optim.py builds the tables): gradient-norm clipping, the AdamW

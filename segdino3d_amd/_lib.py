@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _lib = None
 
@@ -37,10 +37,7 @@ SIGNATURES = {
     "sd3d_scan_ws_bytes": (_z, [_l]),
     "sd3d_scan_exclusive_i32": (_i, [_p, _p, _l, _p, _p, _z, _p]),
     "sd3d_keys_from_f32": (_i, [_p, _l, _i, _p, _p]),
-    "sd3d_keys_from_i64": (_i, [_p, _l, _p, _p]),
-    "sd3d_keys_from_i64_checked": (_i, [_p, _l, _p, _i, _p, _i, _p]),
-    "sd3d_keys_from_i64_checked_max": (_i, [_p, _l, _p, _i, _p, _i, _p, _p]),
-    "sd3d_keys_from_i64_offset_checked_max": (_i, [_p, _l, _l, _p, _i, _p, _i, _p, _p]),
+    "sd3d_keys_from_i64": (_i, [_p, _l, _l, _p, _i, _p, _i, _p, _p]),
     "sd3d_voxel_levels_all": (_i, [_p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
     "sd3d_voxelise_scene_ws_bytes": (_z, [_l, _i]),
     "sd3d_voxelise_scene": (_i, [_p, _p, _p]),
@@ -54,13 +51,11 @@ SIGNATURES = {
     "sd3d_hash_build": (_i, [_p, _l, _p, _p, _l, _p]),
     "sd3d_kernel_map": (_i, [_p, _l, _p, _p, _l, _p, _i, _i, _p, _p, _p]),
     "sd3d_kernel_maps_hier_ws_bytes": (_z, [_i, _p]),
-    "sd3d_kernel_maps_hier": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "sd3d_kernel_maps_hier_counts": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "sd3d_kernel_maps_hier": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "sd3d_stride_maps": (_i, [_p, _p, _l, _l, _p, _p, _p, _p]),
     "sd3d_voxel_mean": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _p, _l, _p, _i, _p]),
     "sd3d_segment_starts": (_i, [_p, _l, _l, _p, _p]),
     "sd3d_voxel_mean_batch": (_i, [_p, _i, _i, _i, _p, _p, _p, _l, _p, _i, _p]),
-    "sd3d_keys_from_i64_offset": (_i, [_p, _l, _l, _p, _p]),
     "sd3d_segment_starts_batch": (_i, [_p, _l, _l, _p, _i, _p, _p]),
     "sd3d_pool_superpoints": (_i, [_p, _i, _i, _p, _p, _f, _p, _p, _l, _p, _p, _p]),
     "sd3d_gather_gemm": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _l, _p, _p, _p, _i, _p, _i, _i, _i, _p, _z, _p]),
@@ -68,23 +63,19 @@ SIGNATURES = {
     "sd3d_linear_group": (_i, [_i, _p, _p]),
     "sd3d_gather_gemm_split": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _l, _p, _p, _p, _i, _p, _i, _i, _i, _p, _z, _p]),
     "sd3d_pair_lists_ws_bytes": (_z, [_i, _l]),
-    "sd3d_pair_lists_desc": (_i, [_i, _p, _p, _z, _p]),
-    "sd3d_pair_lists_desc_counts": (_i, [_i, _p, _p, _p, _z, _p]),
+    "sd3d_pair_lists_desc": (_i, [_i, _p, _p, _p, _z, _p]),
     "sd3d_pair_conv_ex": (_i, [_p, _i, _i, _p, _i, _p, _p, _l, _p, _p, _i, _i, _p, _p, _i, _i, _i, _l, _p, _p, _p, _i, _p, _i, _i, _p, _z, _p]),
     "sd3d_run_layers": (_i, [_p, _i, _p, _i, _p, _i, _p, _z, _p, _z, _p]),
     "sd3d_layernorm": (_i, [_p, _i, _p, _i, _p, _p, _f, _l, _i, _p, _i, _i, _p]),
     "sd3d_linear_layernorm": (_i, [_p, _i, _l, _i, _p, _i, _p, _p, _i, _p, _p, _f, _i, _p, _i, _p]),
-    "sd3d_sine_pe": (_i, [_p, _i, _l, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p]),
-    "sd3d_fourier_pe": (_i, [_p, _i, _l, _p, _p, _i, _i, _p, _i, _p]),
-    "sd3d_sine_pe_rows": (_i, [_p, _i, _l, _p, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p]),
-    "sd3d_fourier_pe_rows": (_i, [_p, _i, _l, _p, _p, _p, _i, _i, _p, _i, _p]),
-    "sd3d_box_refine_rows": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _l, _p, _p, _p, _p]),
+    "sd3d_sine_pe": (_i, [_p, _i, _l, _p, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p]),
+    "sd3d_fourier_pe": (_i, [_p, _i, _l, _p, _p, _p, _i, _i, _p, _i, _p]),
+    "sd3d_box_refine": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _l, _p, _p, _p, _p]),
     "sd3d_mask_bits_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _p]),
     "sd3d_dinox_mask_bits_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "sd3d_mask_bits": (_i, [_p, _i, _l, _i, _f, _p, _i, _p]),
     "sd3d_near_bits": (_i, [_p, _l, _p, _l, _f, _p, _i, _p]),
     "sd3d_dinox_mask_bits": (_i, [_p, _p, _i, _l, _l, _p, _i, _p]),
-    "sd3d_box_refine": (_i, [_p, _p, _p, _i, _p, _p, _i, _l, _p, _p, _p, _p]),
     "sd3d_scale_shift_act_add": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _l, _i, _p, _i, _p, _i, _p]),
     "sd3d_class_scores": (_i, [_p, _i, _l, _i, _p, _p, _p]),
     "sd3d_mask_scores": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
@@ -99,8 +90,7 @@ SIGNATURES = {
     "sd3d_row_chain": (_i, [_p, _p]),
     "sd3d_row_chain_program_bytes": (_z, []),
     "sd3d_attention_ws_bytes": (_z, [_i, _i, _i]),
-    "sd3d_attention": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _i, _p, _z, _p]),
-    "sd3d_attention_dropout": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _i, _p, _z, _p, _i, _f, _p]),
+    "sd3d_attention": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _i, _p, _z, _p, _i, _f, _p]),
     "sd3d_attention_dropout_keep": (_i, [_p, _i, _i, _i, _i, _f, _p, _p]),
     "sd3d_attention_batch": (_i, [_i, _p, _i, _i, _f, _i, _p, _z, _p]),
     "sd3d_attention_config": (_i, [_i, _i, _i, _i, _z, _p, _p]),
@@ -150,8 +140,6 @@ SIGNATURES = {
     "sd3d_sine_pe_mod_backward": (_i, [_p, _i, _p, _i, _l, _p, _p, _p, _i, _p, _i, _p, _p]),
     "sd3d_attention_backward_ws_bytes": (_z, [_i, _i, _i]),
     "sd3d_attention_backward": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i,
-                                     _p, _i, _p, _i, _p, _z, _p]),
-    "sd3d_attention_dropout_backward": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i,
                                      _p, _i, _p, _i, _p, _z, _p, _i, _f, _p]),
     "sd3d_semantic_loss_ws_bytes": (_z, [_i]),
     "sd3d_semantic_loss": (_i, [_p, _i, _i, _i, _i, _p, _i, _f, _p, _i, _p, _p, _z, _p]),

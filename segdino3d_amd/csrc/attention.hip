@@ -464,33 +464,20 @@ static AttnParams attn_params(const float* q0, int ldq0, const float* q1, int ld
     p.Lq = Lq; p.Lk = Lk; p.H = H; p.scale = scale; p.ksplit = 1; p.part = nullptr; p.bf16 = bf16 ? 1 : 0; p.lse = lse;
     return p;
 }
-// Heads of 32 or 64 channels; any other width -> SD3D_ERR_ARG before anything is launched.
+// Heads of 32 or 64 channels, dropout rate p in [0, 1) on the probabilities (p > 0: training, needs the key; p == 0: the kernels without
+// dropout, key ignored); anything else -> SD3D_ERR_ARG before anything is launched.
 extern "C" int sd3d_attention(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
                               const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
-                              float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, void* stream) {
+                              float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, const uint32_t* key, int call, float p,
+                              void* stream) {
+    if (!(p >= 0.f && p < 1.f)) return sd3d_set_error(SD3D_ERR_ARG, "attention: p must lie in [0, 1)");
+    if (p > 0.f && !key) return sd3d_set_error(SD3D_ERR_ARG, "attention: dropout needs a key");
     const int W = attention_width(head_dim);
     if (!W) return sd3d_set_error(SD3D_ERR_ARG, "attention: heads must be 32 or 64 channels wide");
     if ((q1 == nullptr) != (k1 == nullptr)) return sd3d_set_error(SD3D_ERR_ARG, "attention: q1 and k1 must be given together");
-    const AttnParams p = attn_params(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, bf16, lse);
-    return launch_attention(p, q1 ? 2 : 1, W, ws, ws_bytes, (hipStream_t)stream);
-}
-
-
-// sd3d_attention with dropout of rate p on the probabilities (training).  p == 0 is sd3d_attention itself.
-extern "C" int sd3d_attention_dropout(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
-                                      const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
-                                      float* out, int ldo, float* lse, int bf16, void* ws, size_t ws_bytes, const uint32_t* key, int call,
-                                      float p, void* stream) {
-    if (!(p >= 0.f && p < 1.f)) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout: p must lie in [0, 1)");
-    if (!key) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout: key missing");
-    if (p == 0.f)
-        return sd3d_attention(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, head_dim, scale, out, ldo, lse, bf16, ws, ws_bytes, stream);
-    const int W = attention_width(head_dim);
-    if (!W) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout: heads must be 32 or 64 channels wide");
-    if ((q1 == nullptr) != (k1 == nullptr)) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout: q1 and k1 must be given together");
     const AttnParams ap = attn_params(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, scale, out, ldo, bf16, lse);
     const AttnDrop dr = {key, (uint32_t)call, attn_drop_threshold(p), 1.f / (1.f - p)};
-    return launch_attention(ap, q1 ? 2 : 1, W, ws, ws_bytes, (hipStream_t)stream, true, &dr);
+    return launch_attention(ap, q1 ? 2 : 1, W, ws, ws_bytes, (hipStream_t)stream, true, p > 0.f ? &dr : nullptr);
 }
 
 // the keep mask alone, keep[H, Lq, Lk] bytes (1 = kept): one thread per (head, query, four consecutive keys)

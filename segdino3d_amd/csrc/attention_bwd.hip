@@ -311,11 +311,15 @@ size_t sd3d_attention_backward_ws_bytes(int Lq, int H, int head_dim) {
     return head_dim == 32 || head_dim == 64 ? align_up((size_t)Lq * H * sizeof(float), 256) : 0;
 }
 
-static int attention_backward_impl(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
+// backward of sd3d_attention with the same key, call and p: for p > 0 the kernels regenerate the keep mask
+int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
                             const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
                             const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0, float* dq1,
                             int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes,
-                            void* stream, const AttnDrop* drop) {
+                            const uint32_t* key, int call, float drop_p, void* stream) {
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return sd3d_set_error(SD3D_ERR_ARG, "attention_backward: p must lie in [0, 1)");
+    const int dropping = drop_p > 0.f ? 1 : 0;
+    if (dropping && !key) return sd3d_set_error(SD3D_ERR_ARG, "attention_backward: dropout needs a key");
     if (head_dim != 32 && head_dim != 64) return sd3d_set_error(SD3D_ERR_ARG, "attention_backward: heads must be 32 or 64 channels wide");
     const int W = head_dim / 32;
     if ((q1 == nullptr) != (k1 == nullptr) || (q1 && (!dq1 || !dk1))) return sd3d_set_error(SD3D_ERR_ARG, "attention_backward: second source incomplete");
@@ -327,7 +331,7 @@ static int attention_backward_impl(const float* q0, int ldq0, const float* q1, i
     p.lse = lse; p.dsum = (float*)ws;
     p.dq[0] = dq0; p.ld_dq[0] = ld_dq0; p.dq[1] = dq1; p.ld_dq[1] = ld_dq1; p.dk[0] = dk0; p.ld_dk[0] = ld_dk0; p.dk[1] = dk1; p.ld_dk[1] = ld_dk1;
     p.dv = dv; p.ld_dv = ld_dv; p.Lq = Lq; p.Lk = Lk; p.H = H; p.scale = scale;
-    p.drop = drop ? *drop : AttnDrop{nullptr, 0u, 0u, 1.f};
+    p.drop = dropping ? AttnDrop{key, (uint32_t)call, attn_drop_threshold(drop_p), 1.f / (1.f - drop_p)} : AttnDrop{nullptr, 0u, 0u, 1.f};
     const int nsrc = q1 ? 2 : 1;
     const int kt = (Lk + 31) / 32, qt = (Lq + 31) / 32;
     // kv kernel: 8 waves per workgroup when there are >= 32 query tiles and a 128-register budget (launch bounds 512): at the
@@ -351,33 +355,10 @@ static int attention_backward_impl(const float* q0, int ldq0, const float* q1, i
     if (int rc = sd3d_raise_lds_limit(raised, big, 8)) return rc;
     // LDS: nw waves x accumulators (nsrc in the q kernel, nsrc + 1 in the kv kernel) x 4 W KiB
     const size_t tile = (size_t)W * 4096;
-    const int dropping = drop ? 1 : 0;
     hipLaunchKernelGGL(q_kernels[dropping][W - 1][nsrc - 1], gq, dim3(64 * nwq), (size_t)nwq * nsrc * tile, ST, p);
     hipLaunchKernelGGL(kv_kernels[dropping][W - 1][nsrc - 1], gk, dim3(64 * nwk), (size_t)nwk * (nsrc + 1) * tile, ST, p);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
-}
-
-int sd3d_attention_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
-                            const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
-                            const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0, float* dq1,
-                            int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws, size_t ws_bytes,
-                            void* stream) {
-    return attention_backward_impl(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, head_dim, scale, out, ldo, lse, d_out, ld_do,
-                                   dq0, ld_dq0, dq1, ld_dq1, dk0, ld_dk0, dk1, ld_dk1, dv, ld_dv, ws, ws_bytes, stream, nullptr);
-}
-
-// backward of sd3d_attention_dropout with the same key, call and p: the kernels regenerate the keep mask.  p == 0 is sd3d_attention_backward.
-int sd3d_attention_dropout_backward(const float* q0, int ldq0, const float* q1, int ldq1, const float* k0, int ldk0, const float* k1, int ldk1,
-                                    const float* v, int ldv, const uint32_t* mask_bits, int Lq, int Lk, int H, int head_dim, float scale,
-                                    const float* out, int ldo, const float* lse, const float* d_out, int ld_do, float* dq0, int ld_dq0,
-                                    float* dq1, int ld_dq1, float* dk0, int ld_dk0, float* dk1, int ld_dk1, float* dv, int ld_dv, void* ws,
-                                    size_t ws_bytes, const uint32_t* key, int call, float p, void* stream) {
-    if (!(p >= 0.f && p < 1.f)) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout_backward: p must lie in [0, 1)");
-    if (!key) return sd3d_set_error(SD3D_ERR_ARG, "attention_dropout_backward: key missing");
-    const AttnDrop dr = {key, (uint32_t)call, attn_drop_threshold(p), 1.f / (1.f - p)};
-    return attention_backward_impl(q0, ldq0, q1, ldq1, k0, ldk0, k1, ldk1, v, ldv, mask_bits, Lq, Lk, H, head_dim, scale, out, ldo, lse, d_out, ld_do,
-                                   dq0, ld_dq0, dq1, ld_dq1, dk0, ld_dk0, dk1, ld_dk1, dv, ld_dv, ws, ws_bytes, stream, p == 0.f ? nullptr : &dr);
 }
 
 }  // extern "C"

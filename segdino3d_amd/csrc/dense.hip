@@ -263,15 +263,11 @@ static int launch_sine_pe(const float* xyz, int ld_xyz, int64_t n, const float* 
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-extern "C" int sd3d_sine_pe(const float* xyz, int ld_xyz, int64_t n, const float* range, const float* dim_t, const int8_t* axis, int d_pos,
-                            const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out, int ld_out, void* stream) {
+// ranges / row_scene (here and in sd3d_fourier_pe / sd3d_box_refine): row r takes ranges[row_scene[r]]; row_scene NULL = one [6] range for all rows
+extern "C" int sd3d_sine_pe(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* dim_t,
+                            const int8_t* axis, int d_pos, const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out,
+                            int ld_out, void* stream) {
     if (mod_num && !mod_den) return sd3d_set_error(SD3D_ERR_ARG, "sine_pe: mod_den missing");
-    return launch_sine_pe(xyz, ld_xyz, n, range, dim_t, axis, d_pos, mod_num, ld_num, mod_den, ld_den, out, ld_out, nullptr, (hipStream_t)stream);
-}
-extern "C" int sd3d_sine_pe_rows(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* dim_t,
-                                 const int8_t* axis, int d_pos, const float* mod_num, int ld_num, const float* mod_den, int ld_den, float* out,
-                                 int ld_out, void* stream) {
-    if (mod_num && !mod_den) return sd3d_set_error(SD3D_ERR_ARG, "sine_pe_rows: mod_den missing");
     return launch_sine_pe(xyz, ld_xyz, n, ranges, dim_t, axis, d_pos, mod_num, ld_num, mod_den, ld_den, out, ld_out, row_scene, (hipStream_t)stream);
 }
 
@@ -308,12 +304,8 @@ static int launch_fourier_pe(const float* xyz, int ld_xyz, int64_t n, const floa
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-extern "C" int sd3d_fourier_pe(const float* xyz, int ld_xyz, int64_t n, const float* range, const float* gauss_b, int ld_b, int d_pos, float* out,
-                               int ld_out, void* stream) {
-    return launch_fourier_pe(xyz, ld_xyz, n, range, gauss_b, ld_b, d_pos, out, ld_out, nullptr, (hipStream_t)stream);
-}
-extern "C" int sd3d_fourier_pe_rows(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* gauss_b,
-                                    int ld_b, int d_pos, float* out, int ld_out, void* stream) {
+extern "C" int sd3d_fourier_pe(const float* xyz, int ld_xyz, int64_t n, const float* ranges, const int32_t* row_scene, const float* gauss_b,
+                               int ld_b, int d_pos, float* out, int ld_out, void* stream) {
     return launch_fourier_pe(xyz, ld_xyz, n, ranges, gauss_b, ld_b, d_pos, out, ld_out, row_scene, (hipStream_t)stream);
 }
 
@@ -625,13 +617,8 @@ static int launch_box_refine(const float* ref, const float* dc, const float* spr
     return SD3D_OK;
 }
 extern "C" int sd3d_box_refine(const float* ref_points, const float* d_center, const float* size_prev, int ld_size_prev, const float* d_size,
-                               const float* range, int normalize, int64_t Q, float* center, float* size, float* size_metric, void* stream) {
-    return launch_box_refine(ref_points, d_center, size_prev, ld_size_prev, d_size, range, normalize, Q, center, size, size_metric, nullptr,
-                             (hipStream_t)stream);
-}
-extern "C" int sd3d_box_refine_rows(const float* ref_points, const float* d_center, const float* size_prev, int ld_size_prev, const float* d_size,
-                                    const float* ranges, const int32_t* row_scene, int normalize, int64_t Q, float* center, float* size,
-                                    float* size_metric, void* stream) {
+                               const float* ranges, const int32_t* row_scene, int normalize, int64_t Q, float* center, float* size,
+                               float* size_metric, void* stream) {
     return launch_box_refine(ref_points, d_center, size_prev, ld_size_prev, d_size, ranges, normalize, Q, center, size, size_metric, row_scene,
                              (hipStream_t)stream);
 }

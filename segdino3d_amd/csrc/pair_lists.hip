@@ -541,11 +541,10 @@ extern "C" size_t sd3d_pair_lists_ws_bytes(int K, int64_t M) {
 // rounded up to 256).  p_cap: capacity of in_idx in pairs (multiple of 128, >= pairs + K * 127); tile_k has p_cap / 128 + 1 entries
 // (the last one receives the number of real tiles).  rlist / out_idx / the two centre slots of tile_k are optional products (see sd3d_pair_table_desc).
 // blk_counts: NULL, or per table NULL or device int32 [K, cdiv(M, 256)]: the entry counts per (offset, 256-row block) that the count
-// pass of the row-block form would produce (sd3d_kernel_maps_hier_counts leaves them while it writes the table).  Such a table has no
+// pass of the row-block form would produce (sd3d_kernel_maps_hier leaves them while it writes the table).  Such a table has no
 // workgroups in the count launch; scan and fill run as ever, the scan in place over the given counts (they are consumed).  Only a
 // table that takes the row-block form (no pos, K <= 128, not chained) may bring counts.
-extern "C" int sd3d_pair_lists_desc_counts(int n, const sd3d_pair_table_desc* d, int32_t* const* blk_counts, void* ws, size_t ws_bytes,
-                                           void* stream) {
+extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, int32_t* const* blk_counts, void* ws, size_t ws_bytes, void* stream) {
     if (n > 0 && !d) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_desc: tables is NULL");
     hipStream_t st = (hipStream_t)stream;
     if (n <= 0) return SD3D_OK;
@@ -565,7 +564,7 @@ extern "C" int sd3d_pair_lists_desc_counts(int n, const sd3d_pair_table_desc* d,
         const int64_t M = d[i].M, p_cap = d[i].p_cap;
         int32_t* const given = blk_counts ? blk_counts[i] : nullptr;
         if (given && (d[i].center == SD3D_PAIR_CHAINED || d[i].pos || K > PR_MAX_K))
-            return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_desc_counts: only a row-block table (no pos, K <= 128, not chained) takes block counts");
+            return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_desc: only a row-block table (no pos, K <= 128, not chained) takes block counts");
         if (d[i].center == SD3D_PAIR_CHAINED && K > 0 && M > 0) {
             // chained lists (mirror groups + centre share a partial product): their own builder
             if (!(K & 1) || K < 3) return sd3d_set_error(SD3D_ERR_ARG, "pair_lists_batch: chained lists need an odd kernel (symmetric offsets)");
@@ -648,7 +647,4 @@ extern "C" int sd3d_pair_lists_desc_counts(int n, const sd3d_pair_table_desc* d,
     if (rb > 0) hipLaunchKernelGGL(pair_rowlist_batch_kernel, dim3(rb), dim3(RL_ROWS), 0, st, b);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
-}
-extern "C" int sd3d_pair_lists_desc(int n, const sd3d_pair_table_desc* d, void* ws, size_t ws_bytes, void* stream) {
-    return sd3d_pair_lists_desc_counts(n, d, nullptr, ws, ws_bytes, stream);
 }

@@ -399,10 +399,6 @@ __global__ void f32_to_sortkey(const float* __restrict__ x, int64_t n, int desc,
     if (desc) u = ~u;
     keys[i] = (uint64_t)u;
 }
-__global__ void i64_to_sortkey(const int64_t* __restrict__ x, int64_t n, uint64_t* __restrict__ keys) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) keys[i] = (uint64_t)x[i];
-}
 
 extern "C" int sd3d_keys_from_f32(const float* x, int64_t n, int descending, uint64_t* keys, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -411,35 +407,8 @@ extern "C" int sd3d_keys_from_f32(const float* x, int64_t n, int descending, uin
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-__global__ void i64_to_sortkey_add(const int64_t* __restrict__ x, int64_t n, uint64_t add, uint64_t* __restrict__ keys) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) keys[i] = (uint64_t)x[i] + add;
-}
-extern "C" int sd3d_keys_from_i64_offset(const int64_t* x, int64_t n, int64_t add, uint64_t* keys, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (n <= 0) return SD3D_OK;
-    hipLaunchKernelGGL(i64_to_sortkey_add, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, (uint64_t)add, keys);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
-}
-__global__ void i64_to_sortkey_checked(const int64_t* __restrict__ x, int64_t n, uint64_t* __restrict__ keys, int bits, int32_t* __restrict__ flag, int value) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const uint64_t k = (uint64_t)x[i];
-        keys[i] = k;
-        if (k >> bits) atomicOr(flag, value);
-    }
-}
-extern "C" int sd3d_keys_from_i64_checked(const int64_t* x, int64_t n, uint64_t* keys, int bits, int32_t* flag, int flag_value, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (n <= 0) return SD3D_OK;
-    if (!flag || bits < 1 || bits > 63) return sd3d_set_error(SD3D_ERR_ARG, "keys_from_i64_checked: flag pointer and 1..63 bits");
-    hipLaunchKernelGGL(i64_to_sortkey_checked, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, keys, bits, flag, flag_value);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
-}
-// ... and *max_out = max(*max_out, largest id) (one atomic per wave): the number of superpoints of a scene rides in the scene's
-// read-back without waiting for the sort of the ids
+// int64 ids -> u64 keys with the width check, and *max_out = max(*max_out, largest id): the number of superpoints of a scene rides in the
+// scene's read-back without waiting for the sort of the ids
 __global__ void i64_to_sortkey_checked_max(const int64_t* __restrict__ x, int64_t n, uint64_t* __restrict__ keys, int bits, int32_t* __restrict__ flag,
                                            int value, int32_t* __restrict__ max_out, uint64_t add) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -470,23 +439,12 @@ __global__ void i64_to_sortkey_checked_max(const int64_t* __restrict__ x, int64_
 int launch_i64_to_sortkey_checked_max(const int64_t* x, int64_t n, uint64_t* keys, int bits, int32_t* flag, int value, int32_t* max_out, hipStream_t st,
                                       uint64_t add) {
     if (n <= 0) return SD3D_OK;
-    if (!flag || !max_out || bits < 1 || bits > 64) return sd3d_set_error(SD3D_ERR_ARG, "keys_from_i64_checked_max: flag / max pointers and 1..64 bits");
+    if (!flag || !max_out || bits < 1 || bits > 64) return sd3d_set_error(SD3D_ERR_ARG, "keys_from_i64: flag / max pointers and 1..64 bits");
     hipLaunchKernelGGL(i64_to_sortkey_checked_max, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, keys, bits, flag, value, max_out, add);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
-extern "C" int sd3d_keys_from_i64_checked_max(const int64_t* x, int64_t n, uint64_t* keys, int bits, int32_t* flag, int flag_value, int32_t* max_out,
-                                              void* stream) {
-    return launch_i64_to_sortkey_checked_max(x, n, keys, bits, flag, flag_value, max_out, (hipStream_t)stream, 0);
-}
-extern "C" int sd3d_keys_from_i64_offset_checked_max(const int64_t* x, int64_t n, int64_t add, uint64_t* keys, int bits, int32_t* flag, int flag_value,
-                                                     int32_t* max_out, void* stream) {
+extern "C" int sd3d_keys_from_i64(const int64_t* x, int64_t n, int64_t add, uint64_t* keys, int bits, int32_t* flag, int flag_value, int32_t* max_out,
+                                  void* stream) {
     return launch_i64_to_sortkey_checked_max(x, n, keys, bits, flag, flag_value, max_out, (hipStream_t)stream, (uint64_t)add);
-}
-extern "C" int sd3d_keys_from_i64(const int64_t* x, int64_t n, uint64_t* keys, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (n <= 0) return SD3D_OK;
-    hipLaunchKernelGGL(i64_to_sortkey, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, n, keys);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
 }

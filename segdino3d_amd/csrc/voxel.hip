@@ -770,12 +770,12 @@ extern "C" size_t sd3d_kernel_maps_hier_ws_bytes(int n_levels, const int64_t* n)
 // [(n_levels + 1) * 64], zeroed: 64 partial counters per table (levels 0 .. n_levels - 1, then the 5^3 table).
 // nbr_down[l] [8, n_{l+1}] / nbr_up[l] [8, n_l] (l < n_levels - 1): optional stride-2 maps of the level pair (NULL arrays or entries: not built).
 // blk_cnt3[l] (l < n_levels - 1) / blk_cnt5: NULL or device int32 [27, cdiv(n_l, 256)] / [125, cdiv(n_0, 256)]: the entry counts per (offset,
-// 256-row block) of that table, the form sd3d_pair_lists_desc_counts takes in place of its own count pass.  (The coarsest level's map is
+// 256-row block) of that table, the form sd3d_pair_lists_desc takes in place of its own count pass.  (The coarsest level's map is
 // searched, not derived: it brings none.)
-extern "C" int sd3d_kernel_maps_hier_counts(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n,
-                                            int32_t* const* nbr3, int32_t* nbr5, const int8_t* offs3, const int8_t* offs5, const int8_t* inv27,
-                                            int32_t* pair_counts, const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up,
-                                            int32_t* const* blk_cnt3, int32_t* blk_cnt5, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int sd3d_kernel_maps_hier(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n,
+                                     int32_t* const* nbr3, int32_t* nbr5, const int8_t* offs3, const int8_t* offs5, const int8_t* inv27,
+                                     int32_t* pair_counts, const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up,
+                                     int32_t* const* blk_cnt3, int32_t* blk_cnt5, void* ws, size_t ws_bytes, void* stream) {
     if (!keys || !parent || !n || !nbr3 || !offs3 || !inv27 || (nbr5 && !offs5)) return sd3d_set_error(SD3D_ERR_ARG, "kernel_maps_hier: null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (n_levels < 1 || n_levels > 8) return sd3d_set_error(SD3D_ERR_ARG, "kernel_maps_hier: 1..8 levels");
@@ -818,14 +818,6 @@ extern "C" int sd3d_kernel_maps_hier_counts(int n_levels, const uint64_t* const*
     }
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
-}
-
-extern "C" int sd3d_kernel_maps_hier(int n_levels, const uint64_t* const* keys, const int32_t* const* parent, const int64_t* n, int32_t* const* nbr3,
-                                     int32_t* nbr5, const int8_t* offs3, const int8_t* offs5, const int8_t* inv27, int32_t* pair_counts,
-                                     const int32_t* perm8, int32_t* const* nbr_down, int32_t* const* nbr_up, void* ws, size_t ws_bytes,
-                                     void* stream) {
-    return sd3d_kernel_maps_hier_counts(n_levels, keys, parent, n, nbr3, nbr5, offs3, offs5, inv27, pair_counts, perm8, nbr_down, nbr_up, nullptr,
-                                        nullptr, ws, ws_bytes, stream);
 }
 
 // Stride-2, kernel-2 maps from the parent array.  The child's position inside its parent is the low

@@ -303,23 +303,20 @@ def keys_from_f32(x: torch.Tensor, descending=False):
     return keys
 
 
-def keys_from_i64(x: torch.Tensor, check=None, max_out=None):
-    """check = (bits, flag int32 [1], value): flag |= value when an id needs more than `bits` bits.  max_out int32 [1] (zeroed by the
-    caller; needs `check`, bits = 64 for none): receives the largest id."""
+def keys_from_i64(x: torch.Tensor, check, max_out, add: int = 0, out=None):
+    """keys[i] = x[i] + add (add: the scene's bits of a batch-wide key).  check = (bits, flag int32 [1], value): flag |= value when an id
+    needs more than `bits` bits (bits = 64 for no width check).  max_out int32 [1] (zeroed by the caller): receives the largest id.  Check
+    and maximum are taken on x[i].  out: the caller's contiguous int64 slice of a batch-wide key buffer (default: a new tensor)."""
     lib = _lib.load()
-    keys = torch.empty(x.numel(), dtype=torch.int64, device=x.device)
-    if max_out is not None:
-        bits, flag, value = check
-        _lib.check(lib.sd3d_keys_from_i64_checked_max(_ptr(x, torch.int64, "x"), x.numel(), _ptr(keys), int(bits), _ptr(flag, torch.int32, "flag"),
-                                                      int(value), _ptr(max_out, torch.int32, "max_out"), _stream()), "keys_from_i64_checked_max")
-        return keys
-    if check is not None:
-        bits, flag, value = check
-        _lib.check(lib.sd3d_keys_from_i64_checked(_ptr(x, torch.int64, "x"), x.numel(), _ptr(keys), int(bits), _ptr(flag, torch.int32, "flag"),
-                                                  int(value), _stream()), "keys_from_i64_checked")
-        return keys
-    _lib.check(lib.sd3d_keys_from_i64(_ptr(x, torch.int64, "x"), x.numel(), _ptr(keys), _stream()), "keys_from_i64")
-    return keys
+    if out is None:
+        out = torch.empty(x.numel(), dtype=torch.int64, device=x.device)
+    elif out.numel() != x.numel():
+        raise ValueError("keys_from_i64: output slice has another length")
+    bits, flag, value = check
+    _lib.check(lib.sd3d_keys_from_i64(_ptr(x, torch.int64, "x"), x.numel(), int(add), _ptr(out, torch.int64, "out"), int(bits),
+                                      _ptr(flag, torch.int32, "flag"), int(value), _ptr(max_out, torch.int32, "max_out"), _stream()),
+               "keys_from_i64")
+    return out
 
 
 # --------------------------------------------------------------------------------------------
@@ -509,14 +506,14 @@ def kernel_maps_hier(keys, parents, n_vox, offs3, offs5, inv27, pair_counts=None
         if nbr5 is not None and L > 1:
             block_counts[(0, 5)] = c5 = torch.empty(125, (int(n_vox[0]) + 255) // 256, dtype=torch.int32, device=dev)
     ws = _WS.get(lib.sd3d_kernel_maps_hier_ws_bytes(L, ctypes.addressof(n)), dev)
-    _lib.check(lib.sd3d_kernel_maps_hier_counts(L, ctypes.addressof(kp), ctypes.addressof(pp), ctypes.addressof(n), ctypes.addressof(np_),
-                                                _ptr(nbr5), _ptr(offs3, torch.int8, "offs3"), _ptr(offs5, torch.int8, "offs5"),
-                                                ctypes.addressof(inv), _ptr(pair_counts, torch.int32, "pair_counts"),
-                                                _ptr(perm8, torch.int32, "perm8") if strides is not None else None,
-                                                ctypes.addressof(dp) if strides is not None else None,
-                                                ctypes.addressof(up) if strides is not None else None,
-                                                ctypes.addressof(c3) if c3 is not None else None, _ptr(c5),
-                                                ws.data_ptr(), ws.numel(), _stream()), "kernel_maps_hier")
+    _lib.check(lib.sd3d_kernel_maps_hier(L, ctypes.addressof(kp), ctypes.addressof(pp), ctypes.addressof(n), ctypes.addressof(np_),
+                                         _ptr(nbr5), _ptr(offs3, torch.int8, "offs3"), _ptr(offs5, torch.int8, "offs5"),
+                                         ctypes.addressof(inv), _ptr(pair_counts, torch.int32, "pair_counts"),
+                                         _ptr(perm8, torch.int32, "perm8") if strides is not None else None,
+                                         ctypes.addressof(dp) if strides is not None else None,
+                                         ctypes.addressof(up) if strides is not None else None,
+                                         ctypes.addressof(c3) if c3 is not None else None, _ptr(c5),
+                                         ws.data_ptr(), ws.numel(), _stream()), "kernel_maps_hier")
     return nbr3, nbr5, strides
 
 
@@ -567,23 +564,6 @@ def voxel_mean_batch(scenes, mode, ukeys, sorted_idx, seg_start, n_vox, ld_out):
     _lib.check(lib.sd3d_voxel_mean_batch(tab.ctypes.data, len(scenes), F, mode, _ptr(ukeys, torch.int64, "ukeys"),
                                          _ptr(sorted_idx, torch.int32, "sorted_idx"), _ptr(seg_start, torch.int32, "seg_start"),
                                          n_vox, _ptr(out), ld_out, _stream()), "voxel_mean_batch")
-    return out
-
-
-def keys_from_i64_offset(x: torch.Tensor, add: int, out: torch.Tensor, check=None, max_out=None):
-    """out[i] = x[i] + add (out: a contiguous int64 slice of the batch-wide key buffer).  check = (bits, flag, value) + max_out: as
-    `keys_from_i64`, taken on x[i]."""
-    lib = _lib.load()
-    if out.numel() != x.numel():
-        raise ValueError("keys_from_i64_offset: output slice has another length")
-    if max_out is not None:
-        bits, flag, value = check
-        _lib.check(lib.sd3d_keys_from_i64_offset_checked_max(_ptr(x, torch.int64, "x"), x.numel(), int(add), _ptr(out, torch.int64, "out"), int(bits),
-                                                             _ptr(flag, torch.int32, "flag"), int(value), _ptr(max_out, torch.int32, "max_out"),
-                                                             _stream()), "keys_from_i64_offset_checked_max")
-        return out
-    _lib.check(lib.sd3d_keys_from_i64_offset(_ptr(x, torch.int64, "x"), x.numel(), int(add), _ptr(out, torch.int64, "out"), _stream()),
-               "keys_from_i64_offset")
     return out
 
 
@@ -801,8 +781,8 @@ def pair_lists_batch(tables):
             res.append(PairLists(pos, in_idx, tile_k, p_cap, K, M, rlist=rlist, rl_stride=rl_stride, center=center, out_idx=out_idx,
                                  direct=direct))
         ws = _WS4.get(nb, dev)
-        _lib.check(lib.sd3d_pair_lists_desc_counts(len(chunk), desc.ctypes.data, ctypes.addressof(given) if any(given) else None,
-                                                   ws.data_ptr(), ws.numel(), _stream()), "pair_lists_desc")
+        _lib.check(lib.sd3d_pair_lists_desc(len(chunk), desc.ctypes.data, ctypes.addressof(given) if any(given) else None,
+                                            ws.data_ptr(), ws.numel(), _stream()), "pair_lists_desc")
         out += res
     return out
 
@@ -1068,7 +1048,7 @@ def linear_layernorm(x, weight, bias, ln_weight, ln_bias, res=None, act=None, ep
 
 def sine_pe(xyz, rng, dim_t, axis, mod_num=None, mod_den=None, row_scene=None):
     """xyz [n,3]; rng [6] = (lo, hi); dim_t [d] fp32, axis [d] int8 -> [n, d].  row_scene int32 [n]: rows of several scenes,
-    rng is then [n_scenes, 6] and row r uses rng[row_scene[r]] (sd3d_sine_pe_rows)."""
+    rng is then [n_scenes, 6] and row r uses rng[row_scene[r]]."""
     n, d = xyz.shape[0], dim_t.numel()
     _want_ranges(rng, row_scene, n, "sine_pe")
     if mod_num is not None:
@@ -1086,13 +1066,9 @@ def sine_pe(xyz, rng, dim_t, axis, mod_num=None, mod_den=None, row_scene=None):
             pd, ldd = _ptr(mod_den, torch.float32, "mod_den"), 0
         else:
             pd, ldd = _rows(mod_den, "mod_den")
-    if row_scene is not None:
-        _lib.check(lib.sd3d_sine_pe_rows(px, ldx, n, _ptr(rng, torch.float32, "rng"), _ptr(row_scene, torch.int32, "row_scene"),
-                                         _ptr(dim_t, torch.float32, "dim_t"), _ptr(axis, torch.int8, "axis"), d, pn, ldn, pd, ldd,
-                                         _ptr(out), d, _stream()), "sine_pe_rows")
-        return out
-    _lib.check(lib.sd3d_sine_pe(px, ldx, n, _ptr(rng, torch.float32, "rng"), _ptr(dim_t, torch.float32, "dim_t"),
-                                _ptr(axis, torch.int8, "axis"), d, pn, ldn, pd, ldd, _ptr(out), d, _stream()), "sine_pe")
+    _lib.check(lib.sd3d_sine_pe(px, ldx, n, _ptr(rng, torch.float32, "rng"), _ptr(row_scene, torch.int32, "row_scene"),
+                                _ptr(dim_t, torch.float32, "dim_t"), _ptr(axis, torch.int8, "axis"), d, pn, ldn, pd, ldd,
+                                _ptr(out), d, _stream()), "sine_pe")
     return out
 
 
@@ -1106,11 +1082,8 @@ def fourier_pe(xyz, rng, gauss_b, d_pos, row_scene=None):
     if gauss_b.shape[0] != 3 or gauss_b.shape[1] < d_pos // 2:
         raise ValueError("fourier_pe: gauss_b must be [3, >= d_pos / 2]")
     out = torch.empty(n, d_pos, dtype=torch.float32, device=xyz.device)
-    if row_scene is not None:
-        _lib.check(lib.sd3d_fourier_pe_rows(px, ldx, n, _ptr(rng, torch.float32, "rng"), _ptr(row_scene, torch.int32, "row_scene"), pb, ldb,
-                                            d_pos, _ptr(out), d_pos, _stream()), "fourier_pe_rows")
-        return out
-    _lib.check(lib.sd3d_fourier_pe(px, ldx, n, _ptr(rng, torch.float32, "rng"), pb, ldb, d_pos, _ptr(out), d_pos, _stream()), "fourier_pe")
+    _lib.check(lib.sd3d_fourier_pe(px, ldx, n, _ptr(rng, torch.float32, "rng"), _ptr(row_scene, torch.int32, "row_scene"), pb, ldb,
+                                   d_pos, _ptr(out), d_pos, _stream()), "fourier_pe")
     return out
 
 
@@ -1156,7 +1129,7 @@ def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, out=N
     ws = _WS6.get(lib.sd3d_attention_ws_bytes(Lq, num_heads, D), q.device)
     _lib.check(lib.sd3d_attention(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, _ptr(mask_bits, torch.int32, "mask_bits"),
                                   Lq, Lk, num_heads, D, float(scale), _ptr(out), out.shape[1], None, 1 if bf16_decoder_active() else 0,
-                                  ws.data_ptr(), ws.numel(), _stream()), "attention")
+                                  ws.data_ptr(), ws.numel(), None, 0, 0.0, _stream()), "attention")
     return out
 
 
@@ -1321,7 +1294,7 @@ def dinox_mask_bits(blocked, near):
 
 def box_refine(ref_points, d_center, size_prev, d_size, rng, normalize, row_scene=None):
     """ref_points, d_center, d_size [Q, 3]; size_prev [3] (one row for all queries) or [Q, 3]; rng [6].
-    row_scene int32 [Q]: rows of several scenes, rng [n_scenes, 6] (sd3d_box_refine_rows)."""
+    row_scene int32 [Q]: rows of several scenes, rng [n_scenes, 6]."""
     Q = _want_box_shapes(ref_points, d_center, size_prev, d_size, rng, row_scene)
     lib = _lib.load()
     dev = ref_points.device
@@ -1333,15 +1306,10 @@ def box_refine(ref_points, d_center, size_prev, d_size, rng, normalize, row_scen
         size_metric = torch.empty(Q, 3, dtype=torch.float32, device=dev)
         ps = _ptr(size_prev, torch.float32, "size_prev")
         lds = 0 if size_prev.dim() == 1 else 3
-    if row_scene is not None:
-        _lib.check(lib.sd3d_box_refine_rows(_ptr(ref_points, torch.float32, "ref_points"), _ptr(d_center, torch.float32, "d_center"),
-                                            ps, lds, _ptr(d_size, torch.float32, "d_size"), _ptr(rng, torch.float32, "rng"),
-                                            _ptr(row_scene, torch.int32, "row_scene"), int(normalize), Q, _ptr(center), _ptr(size),
-                                            _ptr(size_metric), _stream()), "box_refine_rows")
-        return center, size, size_metric
     _lib.check(lib.sd3d_box_refine(_ptr(ref_points, torch.float32, "ref_points"), _ptr(d_center, torch.float32, "d_center"),
                                    ps, lds, _ptr(d_size, torch.float32, "d_size"), _ptr(rng, torch.float32, "rng"),
-                                   int(normalize), Q, _ptr(center), _ptr(size), _ptr(size_metric), _stream()), "box_refine")
+                                   _ptr(row_scene, torch.int32, "row_scene"), int(normalize), Q, _ptr(center), _ptr(size),
+                                   _ptr(size_metric), _stream()), "box_refine")
     return center, size, size_metric
 
 

@@ -454,8 +454,8 @@ class BatchSceneMaps(SceneMaps):
         if superpoints is not None:                        # (every scene's largest id - its superpoint count - does not wait for the sort)
             sp_keys = torch.empty(N, dtype=torch.int64, device=dev)
             for i, sp in enumerate(superpoints):
-                ops.keys_from_i64_offset(sp.contiguous(), i << 32, sp_keys[self.point_off[i]:self.point_off[i + 1]],
-                                         check=(16 if optimistic else 64, err, 4), max_out=rb[n_levels + 1 + i:n_levels + 2 + i])
+                ops.keys_from_i64(sp.contiguous(), (16 if optimistic else 64, err, 4), rb[n_levels + 1 + i:n_levels + 2 + i], add=i << 32,
+                                  out=sp_keys[self.point_off[i]:self.point_off[i + 1]])
         return rb, keys_l, parents, sp_keys
 
     def _sort_superpoints(self, sp_keys, optimistic):

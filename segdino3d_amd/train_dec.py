@@ -292,52 +292,6 @@ _WS_ATT = ops._PerThread()
 _WS_ATT2 = ops._PerThread()
 
 
-class _Attention(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, num_heads, scale, mask_bits, q2, k2):
-        lib = _lib.load()
-        qd, kd, vd = q.detach(), k.detach(), v.detach()
-        pq, ldq = ops._rows(qd, "q"); pk, ldk = ops._rows(kd, "k"); pv, ldv = ops._rows(vd, "v")
-        pq2, ldq2, pk2, ldk2 = None, 0, None, 0
-        if q2 is not None:
-            pq2, ldq2 = ops._rows(q2.detach(), "q2"); pk2, ldk2 = ops._rows(k2.detach(), "k2")
-        Lq, Lk = q.shape[0], k.shape[0]
-        D = ops.head_width(q, v, num_heads, "attention")
-        out = torch.empty(Lq, num_heads * D, dtype=torch.float32, device=q.device)
-        lse = torch.empty(num_heads, Lq, dtype=torch.float32, device=q.device)
-        bits = ops._ptr(mask_bits, torch.int32, "mask_bits")
-        ws = _WS_ATT.get(lib.sd3d_attention_ws_bytes(Lq, num_heads, D), q.device)
-        _lib.check(lib.sd3d_attention(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, bits, Lq, Lk, num_heads, D, float(scale),
-                                      out.data_ptr(), out.shape[1], lse.data_ptr(), 1 if ops.bf16_decoder_active() else 0,
-                                      ws.data_ptr(), ws.numel(), ops._stream()), "attention_lse")
-        ctx.save_for_backward(q, k, v, q2, k2, mask_bits, out, lse)
-        ctx.H, ctx.D, ctx.scale = num_heads, D, float(scale)
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        lib = _lib.load()
-        q, k, v, q2, k2, bits, out, lse = ctx.saved_tensors
-        d_out = d_out.contiguous()
-        Lq, Lk, H = q.shape[0], k.shape[0], ctx.H
-        dev = q.device
-        D = ctx.D
-        new = lambda n: torch.empty(n, H * D, dtype=torch.float32, device=dev)
-        dq, dk, dv = new(Lq), new(Lk), new(Lk)
-        dq2, dk2 = (new(Lq), new(Lk)) if q2 is not None else (None, None)
-        pq, ldq = ops._rows(q.detach(), "q"); pk, ldk = ops._rows(k.detach(), "k"); pv, ldv = ops._rows(v.detach(), "v")
-        pq2, ldq2, pk2, ldk2 = None, 0, None, 0
-        if q2 is not None:
-            pq2, ldq2 = ops._rows(q2.detach(), "q2"); pk2, ldk2 = ops._rows(k2.detach(), "k2")
-        W = H * D
-        ws = _WS_ATT2.get(lib.sd3d_attention_backward_ws_bytes(Lq, H, D), dev)
-        _lib.check(lib.sd3d_attention_backward(pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv, ops._ptr(bits, torch.int32, "mask_bits"), Lq, Lk, H,
-                                               D, ctx.scale, out.data_ptr(), W, lse.data_ptr(), d_out.data_ptr(), W, dq.data_ptr(), W,
-                                               ops._ptr(dq2), W, dk.data_ptr(), W, ops._ptr(dk2), W, dv.data_ptr(), W, ws.data_ptr(), ws.numel(),
-                                               ops._stream()), "attention_backward")
-        return dq, dk, dv, None, None, None, dq2, dk2
-
-
 def _attn_sources(q, k, v, q2, k2):
     """(q, ldq, q2, ldq2, k, ldk, k2, ldk2, v, ldv): the leading arguments of the sd3d_attention* family"""
     pq, ldq = ops._rows(q.detach(), "q"); pk, ldk = ops._rows(k.detach(), "k"); pv, ldv = ops._rows(v.detach(), "v")
@@ -347,9 +301,9 @@ def _attn_sources(q, k, v, q2, k2):
     return pq, ldq, pq2, ldq2, pk, ldk, pk2, ldk2, pv, ldv
 
 
-class _AttentionDropout(torch.autograd.Function):
-    """`_Attention` with dropout of rate p on the probabilities inside the kernels: the forward keeps what `_Attention` keeps (out, lse)
-    plus the key and the call number, and the backward kernels regenerate the keep mask from them."""
+class _Attention(torch.autograd.Function):
+    """The forward keeps out and lse, and for dropout of rate p > 0 on the probabilities (inside the kernels) the key and the call number:
+    the backward kernels regenerate the keep mask from them.  p == 0: key None, call 0."""
 
     @staticmethod
     def forward(ctx, q, k, v, num_heads, scale, mask_bits, q2, k2, p, key, call):
@@ -359,10 +313,9 @@ class _AttentionDropout(torch.autograd.Function):
         out = torch.empty(Lq, num_heads * D, dtype=torch.float32, device=q.device)
         lse = torch.empty(num_heads, Lq, dtype=torch.float32, device=q.device)
         ws = _WS_ATT.get(lib.sd3d_attention_ws_bytes(Lq, num_heads, D), q.device)
-        _lib.check(lib.sd3d_attention_dropout(*_attn_sources(q, k, v, q2, k2), ops._ptr(mask_bits, torch.int32, "mask_bits"), Lq, Lk, num_heads, D,
-                                              float(scale), out.data_ptr(), out.shape[1], lse.data_ptr(), 1 if ops.bf16_decoder_active() else 0,
-                                              ws.data_ptr(), ws.numel(), ops._ptr(key, torch.int32, "key"), call, p, ops._stream()),
-                   "attention_dropout")
+        _lib.check(lib.sd3d_attention(*_attn_sources(q, k, v, q2, k2), ops._ptr(mask_bits, torch.int32, "mask_bits"), Lq, Lk, num_heads, D,
+                                      float(scale), out.data_ptr(), out.shape[1], lse.data_ptr(), 1 if ops.bf16_decoder_active() else 0,
+                                      ws.data_ptr(), ws.numel(), ops._ptr(key, torch.int32, "key"), call, p, ops._stream()), "attention_lse")
         ctx.save_for_backward(q, k, v, q2, k2, mask_bits, out, lse, key)
         ctx.H, ctx.D, ctx.scale, ctx.p, ctx.call = num_heads, D, float(scale), p, call
         return out
@@ -378,10 +331,10 @@ class _AttentionDropout(torch.autograd.Function):
         dq, dk, dv = new(Lq), new(Lk), new(Lk)
         dq2, dk2 = (new(Lq), new(Lk)) if q2 is not None else (None, None)
         ws = _WS_ATT2.get(lib.sd3d_attention_backward_ws_bytes(Lq, H, D), q.device)
-        _lib.check(lib.sd3d_attention_dropout_backward(*_attn_sources(q, k, v, q2, k2), ops._ptr(bits, torch.int32, "mask_bits"), Lq, Lk, H, D, ctx.scale,
-                                                       out.data_ptr(), W, lse.data_ptr(), d_out.data_ptr(), W, dq.data_ptr(), W, ops._ptr(dq2), W,
-                                                       dk.data_ptr(), W, ops._ptr(dk2), W, dv.data_ptr(), W, ws.data_ptr(), ws.numel(),
-                                                       ops._ptr(key, torch.int32, "key"), ctx.call, ctx.p, ops._stream()), "attention_dropout_backward")
+        _lib.check(lib.sd3d_attention_backward(*_attn_sources(q, k, v, q2, k2), ops._ptr(bits, torch.int32, "mask_bits"), Lq, Lk, H, D, ctx.scale,
+                                               out.data_ptr(), W, lse.data_ptr(), d_out.data_ptr(), W, dq.data_ptr(), W, ops._ptr(dq2), W,
+                                               dk.data_ptr(), W, ops._ptr(dk2), W, dv.data_ptr(), W, ws.data_ptr(), ws.numel(),
+                                               ops._ptr(key, torch.int32, "key"), ctx.call, ctx.p, ops._stream()), "attention_backward")
         return dq, dk, dv, None, None, None, dq2, dk2, None, None, None
 
 
@@ -394,11 +347,12 @@ def attention(q, k, v, num_heads, scale, mask_bits=None, q2=None, k2=None, dropo
     if not 0.0 <= dropout_p < 1.0:
         raise ValueError(f"attention: dropout_p must lie in [0, 1), got {dropout_p}")
     if dropout_p == 0.0:
-        return _Attention.apply(q, k, v, num_heads, scale, mask_bits, q2, k2)
-    if key is None:
+        key, call = None, 0
+    elif key is None:
         raise ValueError("attention: dropout_p > 0 needs a key (two int32 words on the device)")
-    ops._want_shape(key, [(2,)], "attention: key")
-    return _AttentionDropout.apply(q, k, v, num_heads, scale, mask_bits, q2, k2, dropout_p, key, int(call))
+    else:
+        ops._want_shape(key, [(2,)], "attention: key")
+    return _Attention.apply(q, k, v, num_heads, scale, mask_bits, q2, k2, dropout_p, key, int(call))
 
 
 class _SplitCols(torch.autograd.Function):

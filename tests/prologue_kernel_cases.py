@@ -1,6 +1,7 @@
 """Inputs for the direct tests of the prologue kernels in `segdino3d_amd/csrc/voxel.hip` (tests/test_gpu_prologue_kernels.py) and the
 reference of every one of them: scene statistics, voxel keys, the run-length unique per level (with and without spconv's output-extent
-clip), the stride-2 maps, per-voxel feature means, segment starts and superpoint pooling.
+clip), the stride-2 maps, per-voxel feature means, segment starts and superpoint pooling - and of the superpoint ids' key builder
+`sd3d_keys_from_i64` in `csrc/sort_scan.hip`.
 
 Inputs are seeded CPU arrays.  Integer work (quantised coordinates, keys, unique, parents, segment starts, neighbour tables, error
 flags) is numpy and is compared exactly; `voxel_keys_ref` performs the kernel's fp32 operations in the same order in numpy float32.
@@ -158,6 +159,47 @@ def flag_case(rel, axis):
     p = np.zeros((2, 6), np.float32)
     p[1, axis] = float(rel - 32) + 0.5
     return torch.from_numpy(p)
+
+
+# ---- keys_from_i64 -----------------------------------------------------------------------------------------------------------------------
+KEYS64_N = [0, 1, 63, 64, 65, 255, 256, 257, 1025]             # around a wave, a 256-thread workgroup (one atomic each for the maximum), five of them
+KEYS64_ADD = [0, 5 << 32]
+KEYS64_BITS = [16, 64]
+KEYS64_FLAG_PRESET, KEYS64_FLAG_VALUE = 16, 4                  # the flag word is OR-ed into: an overwrite loses the 16
+KEYS64_MAX_PRESETS = [0, 7]                                    # the maximum only grows
+KEYS64_IDS = {"zeros": 0, "fits16": 65535, "over16": 65536, "below_limit": 0x7FFFFFFE, "limit": 0x7FFFFFFF, "negative": -1}
+INT32_MAX = 0x7FFFFFFF
+
+
+def keys64_positions(n):
+    """First, one interior and last position of n ids (fewer when they coincide)."""
+    return sorted({0, n // 2, n - 1}) if n > 0 else []
+
+
+def keys64_case(n, name, pos):
+    """int64 [n]: small random ids (below 100) with KEYS64_IDS[name] at position `pos`; `zeros`: every id 0."""
+    x = np.random.default_rng(7000 + n).integers(0, 100, n).astype(np.int64)
+    if name == "zeros":
+        x[:] = 0
+    elif n:
+        x[pos] = KEYS64_IDS[name]
+    return x
+
+
+def keys_from_i64_ref(x, add, bits, flag_value, flag, max_out):
+    """The contract of `sd3d_keys_from_i64` in include/segdino3d_hip.h: keys[i] = x[i] + add (mod 2^64); on the ids x[i], read as
+    unsigned: flag |= flag_value when one does not fit `bits` bits (bits = 64: no check), flag |= 8 when one is negative or above
+    INT32_MAX - 1, max_out = max(max_out, largest id clamped to INT32_MAX).  -> (keys uint64 [n], flag, max_out)"""
+    u = np.asarray(x, dtype=np.int64).view(np.uint64)
+    keys = u + np.uint64(add % (1 << 64))
+    if len(u):
+        top = int(u.max())
+        if bits < 64 and top >> bits:
+            flag |= flag_value
+        if top > INT32_MAX - 1:
+            flag |= 8
+        max_out = max(max_out, min(top, INT32_MAX))
+    return keys, flag, max_out
 
 
 # ---- run-length unique, levels -----------------------------------------------------------------------------------------------------------

@@ -105,15 +105,15 @@ def test_training_namespace_routes_dropout_to_the_fused_node(monkeypatch):
 
 
 def test_entry_points_refuse_bad_arguments_before_any_launch():
-    """p outside [0, 1), a NULL key or an unsupported head width: SD3D_ERR_ARG from the three C entry points, nothing launched (no GPU here)"""
+    """p outside [0, 1), p > 0 with a NULL key or an unsupported head width: SD3D_ERR_ARG from the three C entry points, nothing launched (no GPU here)"""
     import ctypes as C
     from segdino3d_amd import _lib
     lib = _lib.load()
     words = (C.c_uint32 * 2)(1, 2)
     key = C.addressof(words)
-    fwd = lambda D, k, p: lib.sd3d_attention_dropout(*([None, 0] * 5 + [None, 8, 8, 2, D, 1.0, None, 0, None, 0, None, 0, k, 0, p, None]))  # noqa: E731
-    bwd = lambda D, k, p: lib.sd3d_attention_dropout_backward(*([None, 0] * 5 + [None, 8, 8, 2, D, 1.0, None, 0, None, None, 0] + [None, 0] * 5  # noqa: E731
-                                                                + [None, 0, k, 0, p, None]))
+    fwd = lambda D, k, p: lib.sd3d_attention(*([None, 0] * 5 + [None, 8, 8, 2, D, 1.0, None, 0, None, 0, None, 0, k, 0, p, None]))  # noqa: E731
+    bwd = lambda D, k, p: lib.sd3d_attention_backward(*([None, 0] * 5 + [None, 8, 8, 2, D, 1.0, None, 0, None, None, 0] + [None, 0] * 5  # noqa: E731
+                                                        + [None, 0, k, 0, p, None]))
     for f in (fwd, bwd):
         for D, k, p in ((32, key, 1.0), (32, key, -0.5), (64, key, float("nan")), (32, None, 0.1), (48, key, 0.1), (128, key, 0.0)):
             assert f(D, k, p) != 0, (D, k, p)

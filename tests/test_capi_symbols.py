@@ -1,4 +1,4 @@
-"""The C-ABI library loads without a GPU, exports every symbol include/segdino3d_hip.h declares, and
+"""The C-ABI library loads without a GPU, exports the symbols include/segdino3d_hip.h declares and no other sd3d_ name, and
 the ctypes signature table of segdino3d_amd/_lib.py agrees with the header prototype by prototype."""
 import ctypes as C
 import os
@@ -38,10 +38,15 @@ def test_header_and_binding_agree():
 
 
 def test_library_loads_and_exports_every_symbol():
+    import subprocess
     from segdino3d_amd import _lib
     lib = _lib.load()
     for name in _prototypes():
         assert hasattr(lib, name), name
+    # ... and nothing else: an entry point whose prototype left the header must leave the library too (mangled C++ names begin with _Z)
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.split() and line.split()[-1].startswith("sd3d_")}
+    assert exported == set(_prototypes()), exported ^ set(_prototypes())
     assert lib.sd3d_abi_version() == _lib.ABI_VERSION
     assert lib.sd3d_selftest_host() == 0, lib.sd3d_last_error()
     assert lib.sd3d_sort_ws_bytes(150000) > 0 and lib.sd3d_unique_ws_bytes(1000) > 0

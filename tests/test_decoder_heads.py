@@ -73,10 +73,10 @@ def test_c_entry_points_refuse_other_widths_and_report_the_split():
     lib = _lib.load()
     for bad in (16, 128, 0, 48):
         assert lib.sd3d_attention_ws_bytes(40, 2, bad) == 0 and lib.sd3d_attention_backward_ws_bytes(40, 2, bad) == 0
-        assert lib.sd3d_attention(None, 0, None, 0, None, 0, None, 0, None, 0, None, 8, 8, 2, bad, 1.0, None, 0, None, 0, None, 0, None) != 0
+        assert lib.sd3d_attention(None, 0, None, 0, None, 0, None, 0, None, 0, None, 8, 8, 2, bad, 1.0, None, 0, None, 0, None, 0, None, 0, 0.0, None) != 0
         assert b"32 or 64" in lib.sd3d_last_error()
         assert lib.sd3d_attention_batch(1, None, 2, bad, 1.0, 0, None, 0, None) != 0
-        assert lib.sd3d_attention_backward(*([None, 0] * 5 + [None, 8, 8, 2, bad, 1.0, None, 0, None, None, 0] + [None, 0] * 5 + [None, 0, None])) != 0
+        assert lib.sd3d_attention_backward(*([None, 0] * 5 + [None, 8, 8, 2, bad, 1.0, None, 0, None, None, 0] + [None, 0] * 5 + [None, 0, None, 0, 0.0, None])) != 0
         nw, ks = C.c_int(), C.c_int()
         assert lib.sd3d_attention_config(40, 1030, 2, bad, 1 << 20, C.byref(nw), C.byref(ks)) != 0
     assert lib.sd3d_attention_ws_bytes(40, 2, 64) == 2 * 2 * 8 * (64 + 2048) * 4

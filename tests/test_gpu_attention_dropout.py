@@ -135,9 +135,9 @@ def test_key_split_does_not_change_the_mask(D):
         _lib.check(lib.sd3d_attention_config(Lq, Lk, H, D, nbytes, C.byref(nw), C.byref(ks)), "config")
         assert ks.value == want
         out = torch.full((Lq, H * D), float("nan"), device=d)
-        _lib.check(lib.sd3d_attention_dropout(q.data_ptr(), H * D, q2.data_ptr(), H * D, k.data_ptr(), H * D, k2.data_ptr(), H * D, v.data_ptr(), H * D,
-                                              bits.data_ptr(), Lq, Lk, H, D, c["scale"], out.data_ptr(), H * D, None, 0,
-                                              ws.data_ptr() if nbytes else None, nbytes, key.data_ptr(), CALL, p, ops._stream()), "attention_dropout")
+        _lib.check(lib.sd3d_attention(q.data_ptr(), H * D, q2.data_ptr(), H * D, k.data_ptr(), H * D, k2.data_ptr(), H * D, v.data_ptr(), H * D,
+                                      bits.data_ptr(), Lq, Lk, H, D, c["scale"], out.data_ptr(), H * D, None, 0,
+                                      ws.data_ptr() if nbytes else None, nbytes, key.data_ptr(), CALL, p, ops._stream()), "attention")
         close(out, reference(SPLIT, D, p), f"key split {want}, {D} channels", 2e-5)
         outs.append(out)
     assert not torch.equal(outs[0], outs[1])                                                   # two different summation orders did run

@@ -151,7 +151,7 @@ def test_batch_maps_equal_the_scenes_own_maps():
 
 
 def test_voxel_mean_and_pooling_of_the_batch_equal_the_single_scene_kernels():
-    """C-ABI entries sd3d_voxel_mean_batch / sd3d_segment_starts_batch / sd3d_keys_from_i64_offset against the single-scene
+    """C-ABI entries sd3d_voxel_mean_batch / sd3d_segment_starts_batch / sd3d_keys_from_i64 with a scene offset against the single-scene
     entries, including a scene whose superpoint ids have gaps (unused ids give zero rows, `torch_scatter` semantics)."""
     from segdino3d_amd.sparse import BatchSceneMaps, SceneMaps
     d = dev()

@@ -1,5 +1,5 @@
 """The decoder's small kernels in `segdino3d_amd/csrc/dense.hip` and `csrc/train_dec.hip` - sd3d_layernorm, sd3d_layernorm_backward,
-sd3d_act_backward, sd3d_col_sums, sd3d_sine_pe(_rows), sd3d_fourier_pe(_rows), sd3d_sine_pe_mod_backward, sd3d_box_refine(_rows),
+sd3d_act_backward, sd3d_col_sums, sd3d_sine_pe, sd3d_fourier_pe, sd3d_sine_pe_mod_backward, sd3d_box_refine (each with and without row_scene),
 sd3d_box_refine_backward, sd3d_transpose_batch, sd3d_linear_layernorm - called directly through ctypes (so that every leading dimension
 can differ from its width), each against the float64 reference of the same operation in tests/decoder_kernel_cases.py, at the sizes the
 launch geometry cares about: one wave per row and 4 x 64 lanes x float4 in LayerNorm, 256 threads over the elements of the elementwise
@@ -237,7 +237,7 @@ def test_col_sums(C):
     assert rc == ERR_WS and out.untouched() and ws.untouched()
 
 
-# ---- sd3d_sine_pe / sd3d_sine_pe_rows ---------------------------------------------------------------------------------------------------------
+# ---- sd3d_sine_pe (one range / row_scene) ---------------------------------------------------------------------------------------------------------
 def device_sine_pe(p, rows, dim_t, axis, rng, row_scene, mod):
     """Rows `rows` (bool mask) of case p; rng [6] with row_scene None, else [n_scenes, 6].  mod: None | 'den1' | 'den2'."""
     L, lib = _lib()
@@ -250,12 +250,9 @@ def device_sine_pe(p, rows, dim_t, axis, rng, row_scene, mod):
         num, ld_num = wide(p["mod_num"][rows], 2)
         den, ld_den = (up(p["den1"]), 0) if mod == "den1" else wide(p["den2"][rows], 1)
     dt, ax, rg = up(dim_t), up(axis), up(rng)
-    if row_scene is None:
-        rc = lib.sd3d_sine_pe(pts.data_ptr(), 6, n, rg.data_ptr(), dt.data_ptr(), ax.data_ptr(), d, ptr(num), ld_num, ptr(den), ld_den, out.ptr, ld_out, _stream())
-    else:
-        rs = up(row_scene[rows])
-        rc = lib.sd3d_sine_pe_rows(pts.data_ptr(), 6, n, rg.data_ptr(), rs.data_ptr(), dt.data_ptr(), ax.data_ptr(), d, ptr(num), ld_num, ptr(den), ld_den,
-                                   out.ptr, ld_out, _stream())
+    rs = None if row_scene is None else up(row_scene[rows])
+    rc = lib.sd3d_sine_pe(pts.data_ptr(), 6, n, rg.data_ptr(), ptr(rs), dt.data_ptr(), ax.data_ptr(), d, ptr(num), ld_num, ptr(den), ld_den, out.ptr, ld_out,
+                          _stream())
     torch.cuda.synchronize()
     L.check(rc, "sine_pe")
     return rows_of(out, n, ld_out, d)
@@ -273,7 +270,7 @@ def test_sine_pe(d_pos):
             r64 = K.sine_pe_ref(d64(p["xyz"]), d64(p["rng_rows"]), dim_t, axis, d64(num), d64(den))
             r32 = K.sine_pe_ref(p["xyz"], p["rng_rows"], dim_t, axis, num, den)
             check_float("sine_pe_rows", f"n{n} d{d_pos} mod={mod}", got, r64, r32, K.sine_pe_scale(p["xyz"], p["rng_rows"], dim_t, axis, num, den))
-            for s in (0, 2):                                    # the single-scene entry on that scene's rows: the same bits
+            for s in (0, 2):                                    # one range (no row_scene) on that scene's rows: the same bits
                 rows = p["row_scene"] == s
                 if bool(rows.any()):
                     one = device_sine_pe(p, rows, dim_t, axis, K.SCENE_RANGES[s], None, mod)
@@ -292,13 +289,13 @@ def test_sine_pe_refusals():
     dim_t, axis = K.pe_tables(6)
     pts, dt, ax, rg, num = up(p["pts"]), up(dim_t), up(axis), up(K.SCENE_RANGES), up(p["mod_num"])
     out = Out(17 * 6)
-    rc = lib.sd3d_sine_pe(pts.data_ptr(), 6, 17, rg.data_ptr(), dt.data_ptr(), ax.data_ptr(), 6, num.data_ptr(), 3, None, 0, out.ptr, 6, _stream())
+    rc = lib.sd3d_sine_pe(pts.data_ptr(), 6, 17, rg.data_ptr(), None, dt.data_ptr(), ax.data_ptr(), 6, num.data_ptr(), 3, None, 0, out.ptr, 6, _stream())
     assert rc == ERR_ARG and out.untouched()                   # numerator without denominator
-    rc = lib.sd3d_sine_pe(pts.data_ptr(), 6, 0, rg.data_ptr(), dt.data_ptr(), ax.data_ptr(), 6, None, 0, None, 0, out.ptr, 6, _stream())
+    rc = lib.sd3d_sine_pe(pts.data_ptr(), 6, 0, rg.data_ptr(), None, dt.data_ptr(), ax.data_ptr(), 6, None, 0, None, 0, out.ptr, 6, _stream())
     assert rc == 0 and out.untouched()                         # no rows
 
 
-# ---- sd3d_fourier_pe / sd3d_fourier_pe_rows -----------------------------------------------------------------------------------------------------
+# ---- sd3d_fourier_pe (one range / row_scene) -----------------------------------------------------------------------------------------------------
 def device_fourier_pe(p, rows, gb, d_pos, rng, row_scene):
     L, lib = _lib()
     pts = up(p["pts"][rows])
@@ -306,11 +303,8 @@ def device_fourier_pe(p, rows, gb, d_pos, rng, row_scene):
     ld_out = d_pos + 3
     out = Out(n * ld_out)
     b, rg = up(gb), up(rng)
-    if row_scene is None:
-        rc = lib.sd3d_fourier_pe(pts.data_ptr(), 6, n, rg.data_ptr(), b.data_ptr(), gb.shape[1], d_pos, out.ptr, ld_out, _stream())
-    else:
-        rs = up(row_scene[rows])
-        rc = lib.sd3d_fourier_pe_rows(pts.data_ptr(), 6, n, rg.data_ptr(), rs.data_ptr(), b.data_ptr(), gb.shape[1], d_pos, out.ptr, ld_out, _stream())
+    rs = None if row_scene is None else up(row_scene[rows])
+    rc = lib.sd3d_fourier_pe(pts.data_ptr(), 6, n, rg.data_ptr(), ptr(rs), b.data_ptr(), gb.shape[1], d_pos, out.ptr, ld_out, _stream())
     torch.cuda.synchronize()
     return rc, out, n, ld_out
 
@@ -341,7 +335,7 @@ def test_fourier_pe(d_pos):
         L.check(rc, "fourier_pe")
         check_float("fourier_pe", f"n{n} d{d_pos} one scene", rows_of(out, n, ld_out, d_pos), K.fourier_pe_ref(d64(q["xyz"]), d64(q["rng_rows"]), gb, d_pos),
                     K.fourier_pe_ref(q["xyz"], q["rng_rows"], gb, d_pos), K.fourier_pe_scale(q["xyz"], q["rng_rows"], gb, d_pos))
-    for odd in (d_pos + 1, 1):                                  # odd d_pos: refused, by both entries
+    for odd in (d_pos + 1, 1):                                  # odd d_pos: refused, with and without row_scene
         rc, out, _, _ = device_fourier_pe(p, torch.ones(n, dtype=torch.bool), K.gauss_b(d_pos + 2), odd, K.SCENE_RANGES, p["row_scene"])
         assert rc == ERR_ARG and out.untouched()
         rc, out, _, _ = device_fourier_pe(p, torch.ones(n, dtype=torch.bool), K.gauss_b(d_pos + 2), odd, K.SCENE_RANGES[0], None)
@@ -378,7 +372,7 @@ def test_sine_pe_mod_backward(d_pos):
     assert rc == ERR_ARG and d_num.untouched()                 # no denominator
 
 
-# ---- sd3d_box_refine / sd3d_box_refine_rows / sd3d_box_refine_backward ----------------------------------------------------------------------------
+# ---- sd3d_box_refine (one range / row_scene) / sd3d_box_refine_backward ----------------------------------------------------------------------------
 def device_box_refine(c, rows, sp, normalize, with_size, rng, row_scene):
     """sp: 'sp1' ([3], stride 0) or 'sp2' ([Q, 3], passed with leading dimension 5 and NaN behind every row)."""
     L, lib = _lib()
@@ -387,13 +381,9 @@ def device_box_refine(c, rows, sp, normalize, with_size, rng, row_scene):
     prev, ld_prev = (up(c["sp1"]), 0) if sp == "sp1" else wide(c["sp2"][rows], 2)
     center, size, metric = Out(Q * 3), Out(Q * 3), Out(Q * 3)
     rg = up(rng)
-    if row_scene is None:
-        rc = lib.sd3d_box_refine(ref.data_ptr(), dc.data_ptr(), prev.data_ptr(), ld_prev, ds.data_ptr() if with_size else None, rg.data_ptr(), normalize, Q,
-                                 center.ptr, size.ptr, metric.ptr, _stream())
-    else:
-        rs = up(row_scene[rows])
-        rc = lib.sd3d_box_refine_rows(ref.data_ptr(), dc.data_ptr(), prev.data_ptr(), ld_prev, ds.data_ptr() if with_size else None, rg.data_ptr(),
-                                      rs.data_ptr(), normalize, Q, center.ptr, size.ptr, metric.ptr, _stream())
+    rs = None if row_scene is None else up(row_scene[rows])
+    rc = lib.sd3d_box_refine(ref.data_ptr(), dc.data_ptr(), prev.data_ptr(), ld_prev, ds.data_ptr() if with_size else None, rg.data_ptr(), ptr(rs),
+                             normalize, Q, center.ptr, size.ptr, metric.ptr, _stream())
     torch.cuda.synchronize()
     L.check(rc, "box_refine")
     return center, size, metric
@@ -429,7 +419,7 @@ def test_box_refine(Q):
             name = f"Q{Q} normalize={normalize} size_prev={'[3]' if sp == 'sp1' else '[Q, 3]'}"
             outs = device_box_refine(c, every, sp, normalize, True, K.SCENE_RANGES, c["row_scene"])
             check_box_outputs(name + " rows", c, every, sp, normalize, outs)
-            for s in (0, 2):                                    # the single-scene entry on that scene's rows: the same bits
+            for s in (0, 2):                                    # one range (no row_scene) on that scene's rows: the same bits
                 rows = c["row_scene"] == s
                 if bool(rows.any()):
                     one = device_box_refine(c, rows, sp, normalize, True, K.SCENE_RANGES[s], None)

@@ -3,7 +3,8 @@ without spconv's output-extent clip), stride-2 maps, per-voxel feature means, se
 its `segdino3d_amd.ops` wrapper on inputs the test builds itself, against the references of tests/prologue_kernel_cases.py, at the sizes
 the launch geometry cares about: 256-thread workgroups and the grid-stride loop of the statistics, runs of equal keys across workgroup
 boundaries, voxels of 1 .. 700 points around the four-at-a-time loop of `voxel_mean_body` and both sides of its `ld_out > 320` branch,
-superpoints around the 64-point passes and 256-point chunks of `pool_superpoints_kernel`.
+superpoints around the 64-point passes and 256-point chunks of `pool_superpoints_kernel`.  The superpoint ids' key builder
+`sd3d_keys_from_i64` (`csrc/sort_scan.hip`) is called through ctypes, so that its refusals of NULL pointers can be seen.
 
 Integer outputs are compared exactly; means and sums against the derived bounds of the cases file (`check_bound`, which prints one
 `[prologue-kernel-error]` line per float case; profiles/prologue_kernels.md holds the table).  Padded columns and the rows of empty
@@ -473,7 +474,59 @@ def test_pool_superpoints(C, layout):
     assert torch.equal(of[one], c["feat"][c["inverse"][p].astype(np.int64)]), "a superpoint of one point is its voxel's row"
 
 
-# ---- 10. refusals ------------------------------------------------------------------------------------------------------------------------
+# ---- 10. keys_from_i64 -------------------------------------------------------------------------------------------------------------------
+KEY_FILL, ERR_ARG = -0x0123456789ABCDEF, -1
+
+
+def _keys64_lib():
+    from segdino3d_amd import _lib
+    return _lib.load(), torch.cuda.current_stream().cuda_stream
+
+
+@pytest.mark.parametrize("n", K.KEYS64_N[1:])
+def test_keys_from_i64(n):
+    """Every (id pattern, position, add, bits, preset of the maximum) at n ids: keys, flag word and maximum equal the numpy model written
+    from the header.  All cases of one n are launched on rows of shared buffers (sentinels behind every key row, the flag and maximum
+    words of the cases side by side) and read back once."""
+    lib, st = _keys64_lib()
+    P, V = K.KEYS64_FLAG_PRESET, K.KEYS64_FLAG_VALUE
+    cases = [(name, at, add, bits, preset) for name in K.KEYS64_IDS for at in (K.keys64_positions(n) if name != "zeros" else [0])
+             for add in K.KEYS64_ADD for bits in K.KEYS64_BITS for preset in K.KEYS64_MAX_PRESETS]
+    xs = np.stack([K.keys64_case(n, name, at) for name, at, *_ in cases])
+    x = up(xs)
+    ld = n + 64
+    keys = torch.full((len(cases), ld), KEY_FILL, dtype=torch.int64, device=_dev())
+    flag = torch.full((len(cases),), P, dtype=torch.int32, device=_dev())
+    mx = up(np.array([c[4] for c in cases], dtype=np.int32))
+    for i, (name, at, add, bits, preset) in enumerate(cases):
+        rc = lib.sd3d_keys_from_i64(x.data_ptr() + 8 * n * i, n, add, keys.data_ptr() + 8 * ld * i, bits, flag.data_ptr() + 4 * i, V,
+                                    mx.data_ptr() + 4 * i, st)
+        assert rc == 0, (cases[i], lib.sd3d_last_error())
+    torch.cuda.synchronize()
+    keys, flag, mx = host(keys), host(flag), host(mx)
+    assert (keys[:, n:] == KEY_FILL).all(), "sentinels behind the keys were overwritten"
+    for i, (name, at, add, bits, preset) in enumerate(cases):
+        rk, rf, rm = K.keys_from_i64_ref(xs[i], add, bits, V, P, preset)
+        assert np.array_equal(keys[i, :n].view(np.uint64), rk), cases[i]
+        assert (int(flag[i]), int(mx[i])) == (rf, rm), (cases[i], int(flag[i]), int(mx[i]), rf, rm)
+
+
+def test_keys_from_i64_no_ids_and_refusals():
+    lib, st = _keys64_lib()
+    x = up(K.keys64_case(257, "negative", 256))
+    keys = torch.full((257 + 64,), KEY_FILL, dtype=torch.int64, device=_dev())
+    words = torch.tensor([K.KEYS64_FLAG_PRESET, 7], dtype=torch.int32, device=_dev())
+    flag, mx = words.data_ptr(), words.data_ptr() + 4
+
+    def untouched():
+        torch.cuda.synchronize()
+        return bool((keys == KEY_FILL).all()) and words.tolist() == [K.KEYS64_FLAG_PRESET, 7]
+    assert lib.sd3d_keys_from_i64(x.data_ptr(), 0, 5 << 32, keys.data_ptr(), 16, flag, 4, mx, st) == 0 and untouched()      # no ids: nothing written
+    for f, m, bits in ((None, mx, 16), (flag, None, 16), (flag, mx, 0), (flag, mx, 65)):
+        assert lib.sd3d_keys_from_i64(x.data_ptr(), 257, 0, keys.data_ptr(), bits, f, 4, m, st) == ERR_ARG and untouched(), (f, m, bits)
+
+
+# ---- 11. refusals ------------------------------------------------------------------------------------------------------------------------
 def _valid_call_still_works():
     p = K.stats_case(257, 6)
     got = _ops().scene_stats(up(p)).cpu()

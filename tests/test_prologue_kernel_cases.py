@@ -59,6 +59,36 @@ def test_key_range_flags_of_the_reference():
     assert [flag(2047, 0), flag(2048, 0), flag(2047, 1), flag(2048, 1), flag(1023, 2), flag(1024, 2)] == [0, 2, 0, 2, 0, 2]
 
 
+def test_keys_from_i64_reference():
+    """The numpy model of `sd3d_keys_from_i64` on its planted ids: what each of them must and must not raise, hand-stated."""
+    P, V = K.KEYS64_FLAG_PRESET, K.KEYS64_FLAG_VALUE
+    assert V & P == 0 and 8 & (P | V) == 0 and K.KEYS64_N[0] == 0
+    assert {n % 64 for n in K.KEYS64_N} >= {0, 1, 63} and {n % 256 for n in K.KEYS64_N if n > 64} >= {0, 1, 255} and max(K.KEYS64_N) > 4 * 256
+    # id -> (flag bits beyond the preset at bits = 16, at bits = 64, the maximum it brings)
+    want = {"zeros": (0, 0, 0), "fits16": (0, 0, 65535), "over16": (V, 0, 65536), "below_limit": (V, 0, 0x7FFFFFFE), "limit": (V | 8, 8, 0x7FFFFFFF),
+            "negative": (V | 8, 8, 0x7FFFFFFF)}
+    assert set(want) == set(K.KEYS64_IDS)
+    for n in K.KEYS64_N[1:]:
+        pos = K.keys64_positions(n)
+        assert pos[0] == 0 and pos[-1] == n - 1 and (n < 3 or 0 < pos[1] < n - 1)
+        for name in K.KEYS64_IDS:
+            for at in pos:
+                x = K.keys64_case(n, name, at)
+                small = np.delete(x, at)
+                assert (small >= 0).all() and (small < 100).all() and (name == "zeros" or x[at] == K.KEYS64_IDS[name])
+                for add in K.KEYS64_ADD:
+                    for bi, bits in enumerate(K.KEYS64_BITS):
+                        for preset in K.KEYS64_MAX_PRESETS:
+                            keys, flag, mx = K.keys_from_i64_ref(x, add, bits, V, P, preset)
+                            assert keys.dtype == np.uint64 and keys.tolist() == [(int(v) + add) % (1 << 64) for v in x]
+                            assert flag == P | want[name][bi], (n, name, at, bits)
+                            top = want[name][2] if name == "zeros" or n == 1 else max(want[name][2], int(small.max()))
+                            assert mx == max(preset, top), (n, name, at, preset)
+    assert K.keys_from_i64_ref(np.zeros(0, np.int64), 5 << 32, 16, V, P, 7)[1:] == (P, 7)                # no ids: nothing changes
+    # the checks see the id, not the key: an offset above 16 bits raises nothing
+    assert K.keys_from_i64_ref(np.array([3], np.int64), 5 << 32, 16, V, P, 0)[1:] == (P, 3)
+
+
 # ---- levels ------------------------------------------------------------------------------------------------------------------------------
 def _scene_keys(pts, inv_voxel=50.0, shift=False):
     ref = K.voxel_keys_ref(pts[:, :3].numpy(), inv_voxel, K.stats_ref(pts[:, :3], F32).numpy(), shift, 0)

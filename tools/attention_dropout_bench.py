@@ -80,8 +80,8 @@ def main():
                                     return calls[ARMS[2]](q, k, v, q2, k2)
                             return calls[ARMS[2]](q, k, v, q2, k2)
                     rows.append(("forward", "bf16" if bf16 else "fp32",
-                                 {ARMS[0]: lambda a=head(bf16): _lib.check(lib.sd3d_attention(*a, ops._stream()), "attention"),
-                                  ARMS[1]: lambda a=head(bf16): _lib.check(lib.sd3d_attention_dropout(*a, key.data_ptr(), 1, P, ops._stream()), "attention_dropout"),
+                                 {ARMS[0]: lambda a=head(bf16): _lib.check(lib.sd3d_attention(*a, None, 0, 0.0, ops._stream()), "attention"),
+                                  ARMS[1]: lambda a=head(bf16): _lib.check(lib.sd3d_attention(*a, key.data_ptr(), 1, P, ops._stream()), "attention"),
                                   ARMS[2]: explicit}))
             if "backward" in args.passes:
                 bwd = {}
