@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 14
+#define SD3D_ABI_VERSION 15
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1088,6 +1088,53 @@ int sd3d_lift_accumulate(const float* points, int64_t ld, int64_t N, const float
                          void* stream);
 int sd3d_lift_finish(const float* sum, const int32_t* count, int64_t N, int C, int scale_index, int n_scales, float* acc, void* out,
                      int out_f16, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Lifting of a 2D detector's queries to 3D centres (csrc/lift_queries.hip): the producer of `query2d_feats` [M, C] and `query2d_pos`
+ * [M, 3].  The reference has no counterpart (it loads a per-scene dump, `scannet200.py:218-232`); tests/lift_queries_ref.py restates
+ * the rule below in float64.  The calls only enqueue work; their results are pure functions of their inputs, with the same bits under
+ * any schedule, cut of the views into calls, or stream: every decision is an integer one or a single rounded fp32 operation, and the
+ * centres are sums of int64 fixed-point numbers.
+ *
+ *   Inputs.  depth [V, Hd, Wd], uint16 times depth_scale (depth_u16 != 0) or float metres; intrinsics float [V, 4] = fx, fy, cx, cy in
+ *     pixels of the depth image, pixel centres at integer coordinates; cam_to_world float [V, 12] = the rows of [R | t]; masks uint8
+ *     [V, Q, Hm, Wm], non-zero = set (a bool tensor's bytes), at any resolution; Hd Wd <= 2^28 so that the sums cannot overflow.
+ *   1. Mask sample.  Depth pixel (vi, ui) reads mask pixel ym = ((2 vi + 1) Hm) / (2 Hd), xm = ((2 ui + 1) Wm) / (2 Wd), integer
+ *      divisions: the mask pixel nearest to the depth pixel's centre, exactly.
+ *   2. Depth key.  d = depth in fp32 metres (raw * depth_scale in fp32 for uint16); require d > 0; t = d * 1000 + 0.5 in fp32 (two
+ *      rounded operations); require t < 65536; k = (int)floor(t), millimetres; require 1 <= k <= far_mm.  Every comparison is made on
+ *      floats before anything becomes an integer: NaN, infinite, negative and huge depths are invalid.
+ *   3. Median.  Over the n valid masked pixels of (v, q), k_med = the key of rank (n - 1) / 2 in ascending order (the lower median),
+ *      exact.  n == 0 gives count = 0, centre = 0, median_mm = 0.
+ *   4. Gate.  Keep a pixel iff 1000 |k - k_med| <= 1000 gate_mm + gate_permille k_med (integers): it removes the background a mask
+ *      leaks onto at depth edges.
+ *   5. Back-projection.  p_c = ((ui - cx) d / fx, (vi - cy) d / fy, d) in fp32, w = R p_c + t, each component as ((r0 x + r1 y) + r2 z)
+ *      + t with every operation rounded on its own (no fused multiply-add: the kernel computes what a float32 evaluation of the
+ *      restatement computes); require every component finite and |w| < 2^SD3D_LIFTQ_WORLD_BITS, otherwise the pixel is dropped and not
+ *      counted.
+ *   6. Centre.  Each kept component becomes rint(w * 2^SD3D_LIFTQ_FIXED_BITS) as int64; the three sums are int64; count = the kept
+ *      pixels; centre = (float)((double)sum / (double)count / 2^SD3D_LIFTQ_FIXED_BITS), zero where count == 0.
+ *   7. Selection.  Row i = v * Q + q of the stores is valid iff score[i] >= score_thr (a NaN fails) and count[i] >= min_pixels.  With
+ *      max_queries < 0, or no more valid rows than max_queries, all valid rows are emitted in ascending order; otherwise the
+ *      max_queries best by score descending, ties to the lower row, again in ascending row order.  Equal floats are ties; the order
+ *      is the one of sd3d_keys_from_f32(descending), under which +0 sorts before -0.
+ *   8. Output.  out_feats float [M, C] = the selected rows of feats (__half -> float is exact), out_pos float [M, 3] = of centre.
+ *
+ *   sd3d_lift_query_centres: centre float [V Q, 3], count int32 [V Q], median_mm int32 [V Q]; one workgroup owns one (v, q).
+ *   sd3d_lift_query_select: scores float [n], count int32 [n] -> rows int32 [rows_cap >= min(max_queries, n)], the first *m_dev of
+ *     them written, m_dev int32 on the device.  ws: sd3d_lift_query_select_ws_bytes(n), 256-byte aligned.
+ *   sd3d_lift_query_gather: feats [n, C] __half (feats_f16 != 0) or float, 16-byte aligned, C a multiple of 8; rows int32 [M] < n.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_LIFTQ_FIXED_BITS 20         /* fixed-point fraction bits of the centre sums */
+#define SD3D_LIFTQ_WORLD_BITS 14         /* world coordinates at or beyond 2^14 m are dropped */
+int sd3d_lift_query_centres(const void* depth, int depth_u16, float depth_scale, const float* intrinsics, const float* cam_to_world,
+                            const void* masks, int V, int Q, int Hd, int Wd, int Hm, int Wm, int far_mm, int gate_mm, int gate_permille,
+                            float* centre, int32_t* count, int32_t* median_mm, void* stream);
+size_t sd3d_lift_query_select_ws_bytes(int64_t n);
+int sd3d_lift_query_select(const float* scores, const int32_t* count, int64_t n, float score_thr, int min_pixels, int64_t max_queries,
+                           int32_t* rows, int64_t rows_cap, int32_t* m_dev, void* ws, size_t ws_bytes, void* stream);
+int sd3d_lift_query_gather(const void* feats, int feats_f16, const float* centre, const int32_t* rows, int64_t n, int64_t M, int C,
+                           float* out_feats, float* out_pos, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,8 @@ order in fp32, `mean = sum / count` (zero where `count == 0`), and the output is
 Visibility is computed once per view and shared by the scales.  The result is a pure function of the inputs: it does not depend on
 `views_per_pass`, on how the views are split over `add` calls (as long as they arrive in the same order), or on the stream.
 
-Out of scope: the 2D network that makes the maps, reading image files, and the DINO-X query side (`query2d_feats` / `query2d_pos`)."""
+Out of scope: the 2D network that makes the maps and reading image files.  The DINO-X query side (`query2d_feats` / `query2d_pos`)
+is made by `lift_queries.py` from the same `Views`."""
 from __future__ import annotations
 
 from typing import Optional
@@ -54,7 +55,8 @@ class Views:
     """A batch of posed depth frames: `depth` [V, Hd, Wd] on the device, uint16 with `depth_scale` (ScanNet: 0.001) or fp32 metres
     (0 = invalid); `intrinsics` [V, 4] = (fx, fy, cx, cy) in pixels of the depth image, on the device or the host; `cam_to_world`
     [V, 4, 4] on the host.  Views with a non-finite pose are dropped here, before anything is launched: `kept` holds the indices of
-    the others (host int64), `n_given` the number handed in, and `depth` / `intrinsics` / `world_to_cam` have one row per kept view."""
+    the others (host int64), `n_given` the number handed in, and `depth` / `intrinsics` / `world_to_cam` / `cam_to_world` (both fp32
+    [K, 3, 4] on the device) have one row per kept view."""
 
     def __init__(self, depth, intrinsics, cam_to_world, depth_scale: Optional[float] = None):
         if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
@@ -92,6 +94,9 @@ class Views:
             self._kept_dev = None
         self.depth, self.intrinsics = depth.contiguous(), intrinsics.contiguous()
         self.world_to_cam = torch.from_numpy(w2c).to(dev)
+        # the poses themselves, rounded to fp32 [K, 3, 4]: what lift_queries back-projects with
+        c2w = _host_f64(cam_to_world, "poses")[kept][:, :3, :]
+        self.cam_to_world = torch.from_numpy(np.ascontiguousarray(c2w.astype(np.float32))).to(dev)
 
     def __len__(self) -> int:
         return len(self.kept)

@@ -2228,3 +2228,100 @@ def lift_finish(sum, count, scale_index: int = 0, n_scales: int = 1, acc=None, o
                                     _ptr(out, out_dtype, "lift_finish: out") if last and N else None, int(last and out_dtype == torch.float16),
                                     _stream()), "lift_finish")
     return out if last else None
+
+
+# --------------------------------------------------------------------------------------------
+# lifting of 2D detector queries to 3D centres (csrc/lift_queries.hip; the rule: include/segdino3d_hip.h, segdino3d_amd/lift_queries.py)
+# --------------------------------------------------------------------------------------------
+LIFTQ_MAX_PIXELS = 1 << 28
+
+
+def lift_query_centres(depth, depth_scale, intrinsics, cam_to_world, masks, far_mm, gate_mm, gate_permille, centre, count, median_mm):
+    """Robust 3D centre of every (view, query) (`sd3d_lift_query_centres`): depth uint16 [V, Hd, Wd] with `depth_scale` or fp32 metres,
+    intrinsics fp32 [V, 4], cam_to_world fp32 [V, 3, 4], masks bool or uint8 [V, Q, Hm, Wm] -> written into centre fp32 [V, Q, 3],
+    count int32 [V, Q] and median_mm int32 [V, Q] (contiguous, e.g. slices of a store).  Enqueues only."""
+    lib = _lib.load()
+    if depth.dim() != 3 or depth.shape[0] < 1:
+        raise ValueError(f"lift_query_centres: depth must be [V >= 1, Hd, Wd], got {list(depth.shape)}")
+    V, Hd, Wd = depth.shape
+    if Hd < 1 or Wd < 1 or Hd * Wd > LIFTQ_MAX_PIXELS:
+        raise ValueError(f"lift_query_centres: depth images must have 1 .. 2^28 pixels (the int64 sums cannot overflow then), got {Hd} x {Wd}")
+    if depth.dtype == torch.uint16:
+        if depth_scale is None or not float(depth_scale) > 0.0:
+            raise ValueError("lift_query_centres: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
+        u16, scale = 1, float(depth_scale)
+    elif depth.dtype == torch.float32:
+        if depth_scale is not None:
+            raise ValueError("lift_query_centres: fp32 depth is in metres and takes no depth_scale")
+        u16, scale = 0, 1.0
+    else:
+        raise TypeError(f"lift_query_centres: depth must be uint16 or fp32, got {depth.dtype}")
+    _want_shape(intrinsics, [(V, 4)], "lift_query_centres: intrinsics")
+    _want_shape(cam_to_world, [(V, 3, 4)], "lift_query_centres: cam_to_world")
+    if masks.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"lift_query_centres: masks must be bool or uint8, got {masks.dtype}")
+    if masks.dim() != 4 or masks.shape[0] != V or masks.shape[2] < 1 or masks.shape[3] < 1:
+        raise ValueError(f"lift_query_centres: masks must be [V = {V}, Q, Hm, Wm], got {list(masks.shape)}")
+    Q, Hm, Wm = masks.shape[1:]
+    _want_shape(centre, [(V, Q, 3)], "lift_query_centres: centre")
+    _want_shape(count, [(V, Q)], "lift_query_centres: count")
+    _want_shape(median_mm, [(V, Q)], "lift_query_centres: median_mm")
+    for name, x, lowest in (("far_mm", far_mm, 1), ("gate_mm", gate_mm, 0), ("gate_permille", gate_permille, 0)):
+        if int(x) != x or not lowest <= x <= 65535:
+            raise ValueError(f"lift_query_centres: {name} must be an integer in [{lowest}, 65535], got {x}")
+    if Q == 0:
+        return
+    _lib.check(lib.sd3d_lift_query_centres(_ptr(depth, None, "lift_query_centres: depth"), u16, scale,
+                                           _ptr(intrinsics, torch.float32, "lift_query_centres: intrinsics"),
+                                           _ptr(cam_to_world, torch.float32, "lift_query_centres: cam_to_world"),
+                                           _ptr(masks, None, "lift_query_centres: masks"), V, Q, Hd, Wd, Hm, Wm, int(far_mm), int(gate_mm),
+                                           int(gate_permille), _ptr(centre, torch.float32, "lift_query_centres: centre"),
+                                           _ptr(count, torch.int32, "lift_query_centres: count"),
+                                           _ptr(median_mm, torch.int32, "lift_query_centres: median_mm"), _stream()), "lift_query_centres")
+
+
+def lift_query_select(scores, count, score_thr, min_pixels, max_queries=None):
+    """The rows with score >= score_thr and count >= min_pixels, all of them or the `max_queries` best by score (ties to the lower row),
+    in ascending row order (`sd3d_lift_query_select`): scores fp32 [n], count int32 [n] -> (rows int32 [min(max_queries, n)], m int32
+    [1] = how many of them are written, on the device).  Enqueues only."""
+    lib = _lib.load()
+    if scores.dim() != 1:
+        raise ValueError(f"lift_query_select: scores must be fp32 [n], got {list(scores.shape)}")
+    n = scores.shape[0]
+    _want_shape(count, [(n,)], "lift_query_select: count")
+    if int(min_pixels) != min_pixels or min_pixels < 1:
+        raise ValueError(f"lift_query_select: min_pixels must be an integer >= 1, got {min_pixels}")
+    if max_queries is not None and (int(max_queries) != max_queries or max_queries < 0):
+        raise ValueError(f"lift_query_select: max_queries must be None or an integer >= 0, got {max_queries}")
+    sp, cp = _ptr(scores, torch.float32, "lift_query_select: scores"), _ptr(count, torch.int32, "lift_query_select: count")
+    cap = n if max_queries is None else min(int(max_queries), n)
+    rows = torch.empty(cap, dtype=torch.int32, device=scores.device)
+    m = torch.empty(1, dtype=torch.int32, device=scores.device)
+    ws = _WS.get(lib.sd3d_lift_query_select_ws_bytes(n), scores.device)
+    _lib.check(lib.sd3d_lift_query_select(sp if n else None, cp if n else None, n, float(score_thr), int(min_pixels),
+                                          -1 if max_queries is None else int(max_queries), _ptr(rows) if cap else None, cap, _ptr(m),
+                                          ws.data_ptr(), ws.numel(), _stream()), "lift_query_select")
+    return rows, m
+
+
+def lift_query_gather(feats, centre, rows, M: int):
+    """(fp32 [M, C], fp32 [M, 3]) = rows `rows[:M]` of feats fp16 or fp32 [n, C] (C a multiple of 8) and of centre fp32 [n, 3]
+    (`sd3d_lift_query_gather`).  Enqueues only."""
+    lib = _lib.load()
+    if feats.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"lift_query_gather: feats must be fp16 or fp32, got {feats.dtype}")
+    if feats.dim() != 2 or feats.shape[1] < 8 or feats.shape[1] % 8:
+        raise ValueError(f"lift_query_gather: feats must be [n, C] with C a multiple of 8, got {list(feats.shape)}")
+    n, C = feats.shape
+    _want_shape(centre, [(n, 3)], "lift_query_gather: centre")
+    M = int(M)
+    if not 0 <= M <= rows.numel() or M > n or rows.dim() != 1:
+        raise ValueError(f"lift_query_gather: need 0 <= M <= len(rows) and M <= n, got M = {M}, rows {list(rows.shape)}, n = {n}")
+    out_feats = torch.empty(M, C, dtype=torch.float32, device=feats.device)
+    out_pos = torch.empty(M, 3, dtype=torch.float32, device=feats.device)
+    fp, cp, rp = _ptr(feats, None, "lift_query_gather: feats"), _ptr(centre, torch.float32, "lift_query_gather: centre"), \
+        _ptr(rows, torch.int32, "lift_query_gather: rows")
+    if M:
+        _lib.check(lib.sd3d_lift_query_gather(fp, int(feats.dtype == torch.float16), cp, rp, n, M, C, _ptr(out_feats), _ptr(out_pos), _stream()),
+                   "lift_query_gather")
+    return out_feats, out_pos
