@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 15
+#define SD3D_ABI_VERSION 16
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1135,6 +1135,52 @@ int sd3d_lift_query_select(const float* scores, const int32_t* count, int64_t n,
                            int32_t* rows, int64_t rows_cap, int32_t* m_dev, void* ws, size_t ws_bytes, void* stream);
 int sd3d_lift_query_gather(const void* feats, int feats_f16, const float* centre, const int32_t* rows, int64_t n, int64_t M, int C,
                            float* out_feats, float* out_pos, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Merging of lifted 2D queries across views into one query per object (csrc/merge_queries.hip): the stage between the lifter's
+ * stores and the decoder's `query2d_feats` / `query2d_pos`.  The reference has no counterpart; tests/merge_queries_ref.py restates
+ * the rule below, and every decision of it is an integer one, so the kernels EQUAL the restatement (the feature mean apart, which is
+ * a fixed sequence of rounded fp32 operations).
+ *
+ *   Inputs.  feats [n, C] __half (feats_f16 != 0) or float, C <= 1024; centre float [n, 3]; scores float [n]; count int32 [n];
+ *     view of a row = row / queries_per_view.
+ *   1. Valid rows.  score >= score_thr (a NaN fails), count >= min_pixels, every centre component finite with
+ *      |c| < 2^SD3D_LIFTQ_WORLD_BITS.  If more than SD3D_MERGE_MAX_ROWS rows are valid the best by score enter, ties to the lower row
+ *      (the order of sd3d_lift_query_select).
+ *   2. Order.  Entering rows are ranked by score descending, ties to the lower row (sd3d_keys_from_f32(descending)).
+ *   3. Fixed-point centre.  p = rint(centre * 1024) per component as int32 (|p| <= 2^24).
+ *   4. Quantised feature.  s = max_j |f_j| in fp32; if s is not finite or s < 2^-100 the code is all zero; otherwise with
+ *      2^(e-1) <= s < 2^e, q_j = clamp(rint(f_j * 2^(7-e)), -127, 127) as int8; nrm = sum q_j^2 (int32).
+ *   5. Adjacency of ranks a < b.  r_q = radius_q = round(radius * 1024) in 1 .. 2^20: dx^2 + dy^2 + dz^2 <= r_q^2 (int64); and, if
+ *      sim_q = round(sim * 128) in 1 .. 128 is given (0 = distance only): d = sum q_a q_b > 0 and
+ *      (int64) d d 16384 >= (int64) sim_q sim_q nrm_a nrm_b.  A zero code (nrm = 0) is adjacent to nothing, with or without sim_q.
+ *   6. Leader clustering.  Walk the ranks upward: an unlabelled rank becomes a seed and labels every later unlabelled rank adjacent to
+ *      it (the greedy order of NMS; not a transitive closure).
+ *   7. Per cluster, members in ascending row order: w_i = min(count_i, 2^20); pos = (float)((double) sum w_i p_i / (double) sum w_i
+ *      / 1024) (int64 sums); views = the distinct row / queries_per_view; score = the seed's; feat = per channel in fp32
+ *      acc = acc + (float) w_i * f_i (two rounded operations per member) then acc / (float) sum w_i, or the seed's row (reduce_best).
+ *   8. Emit.  Clusters with views < min_views are dropped; if more than max_queries (< 0: no cap) remain, the best by seed score, ties
+ *      to the lower seed row; emitted in ascending seed row.  labels int32 [n] = the output index of each row's cluster, or -1.
+ *
+ *   The four calls share one workspace (sd3d_merge_queries_ws_bytes(n, C), 256-byte aligned) and run in this order on one stream:
+ *   sd3d_merge_queries_adjacency (steps 1-5: the bit matrix [M, ceil(M / 64)] in the workspace), sd3d_merge_queries_sweep (step 6),
+ *   sd3d_merge_queries_reduce (steps 7-8 but the features: *k_dev int32 = the number of emitted clusters, on the device),
+ *   sd3d_merge_queries_emit (K = the value read from k_dev: out_feats float [K, C], out_pos float [K, 3], out_scores float [K],
+ *   out_views int32 [K], labels int32 [n]).  sd3d_merge_queries_adjacency_read copies what the first call left: rank_row int32
+ *   [Mp] (the row of each rank, -1 beyond M; Mp = min(n, SD3D_MERGE_MAX_ROWS) rounded up to 64) and the bit matrix uint64
+ *   [Mp, Mp / 64] with zeros below the diagonal, for tests and tools.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_MERGE_MAX_ROWS 16384        /* rows that enter the clustering */
+size_t sd3d_merge_queries_ws_bytes(int64_t n, int C);
+int sd3d_merge_queries_adjacency(const void* feats, int feats_f16, const float* centre, const float* scores, const int32_t* count, int64_t n,
+                                 int C, float score_thr, int min_pixels, int radius_q, int sim_q, void* ws, size_t ws_bytes, void* stream);
+int sd3d_merge_queries_adjacency_read(int64_t n, int C, const void* ws, size_t ws_bytes, int32_t* rank_row, void* adj, void* stream);
+int sd3d_merge_queries_sweep(int64_t n, int C, void* ws, size_t ws_bytes, void* stream);
+int sd3d_merge_queries_reduce(const float* scores, const int32_t* count, int64_t n, int C, int queries_per_view, float score_thr,
+                              int min_views, int64_t max_queries, int32_t* k_dev, void* ws, size_t ws_bytes, void* stream);
+int sd3d_merge_queries_emit(const void* feats, int feats_f16, const float* scores, const int32_t* count, int64_t n, int C, int64_t K,
+                            int reduce_best, float* out_feats, float* out_pos, float* out_scores, int32_t* out_views, int32_t* labels,
+                            const void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _lib = None
 
@@ -178,6 +178,12 @@ SIGNATURES = {
     "sd3d_lift_query_select_ws_bytes": (_z, [_l]),
     "sd3d_lift_query_select": (_i, [_p, _p, _l, _f, _i, _l, _p, _l, _p, _p, _z, _p]),
     "sd3d_lift_query_gather": (_i, [_p, _i, _p, _p, _l, _l, _i, _p, _p, _p]),
+    "sd3d_merge_queries_ws_bytes": (_z, [_l, _i]),
+    "sd3d_merge_queries_adjacency": (_i, [_p, _i, _p, _p, _p, _l, _i, _f, _i, _i, _i, _p, _z, _p]),
+    "sd3d_merge_queries_adjacency_read": (_i, [_l, _i, _p, _z, _p, _p, _p]),
+    "sd3d_merge_queries_sweep": (_i, [_l, _i, _p, _z, _p]),
+    "sd3d_merge_queries_reduce": (_i, [_p, _p, _l, _i, _i, _f, _i, _l, _p, _p, _z, _p]),
+    "sd3d_merge_queries_emit": (_i, [_p, _i, _p, _p, _l, _i, _l, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
 }
 
 

@@ -30,9 +30,36 @@ Inputs per batch of frames: a `lift2d.Views` (depth, intrinsics, poses; views wi
   8. Output.  `query2d_feats` fp32 [M, C] = the selected rows of `feats` (fp16 to fp32 is exact), `query2d_pos` fp32 [M, 3]; both
      contiguous device tensors, ready for `extra_features`, `targets.drop_2d_queries` and `io_scene.pack_scene`.
 
-Out of scope: the 2D detector, reading image files, and merging the same object's queries across views - duplicates are kept; the
-dataset's `dropout_rate_2dfeats` and the decoder's distance mask are what the reference applies to them."""
+`result()` keeps duplicates: the object in front of the camera is in dozens of its rows.  `merged()` / `merge_queries` /
+`lift_queries(..., merge=dict(...))` group the rows that are the same object (csrc/merge_queries.hip) and emit one query per group.
+The rule is restated with exact integers in tests/merge_queries_ref.py; inputs are rows `feats [n, C]`, `centre [n, 3]`, `scores [n]`,
+`count [n]` with `view = row // queries_per_view`:
+
+  1. Valid rows.  `score >= score_thr` (a NaN fails), `count >= min_pixels`, every centre component finite with `|c| < 2^14`.  If
+     more than 16384 rows are valid the best by score enter, ties to the lower row.
+  2. Order.  Entering rows are ranked by score descending, ties to the lower row (the order of `sd3d_keys_from_f32`).
+  3. Fixed-point centre.  `p = rint(centre * 1024)` per component as int32.
+  4. Quantised feature.  `s = max_j |f_j|` in fp32; a row whose `s` is not finite or below `2^-100` has an all-zero code; otherwise,
+     with `2^(e-1) <= s < 2^e`, `q_j = clamp(rint(f_j * 2^(7-e)), -127, 127)` as int8 and `nrm = sum q_j^2`.
+  5. Adjacency of ranks `a < b`.  `r_q = round(radius * 1024)` in `1 .. 2^20`: `dx^2 + dy^2 + dz^2 <= r_q^2`; and, unless `sim` is
+     None, with `s7 = round(sim * 128)` in `1 .. 128` and `d = sum q_a q_b`: `d > 0` and `d d 16384 >= s7 s7 nrm_a nrm_b` in int64.  A
+     zero code is adjacent to nothing, with or without `sim`.
+  6. Leader clustering, the greedy order of NMS.  Walk the ranks upward; an unlabelled rank becomes a seed and labels every later
+     unlabelled rank adjacent to it.  Not a transitive closure: a chair next to a table does not chain into one cluster.
+  7. Per cluster, members in ascending row order: `w_i = min(count_i, 2^20)`, `pos = (float)((double) sum w_i p_i / (double) sum w_i /
+     1024)` with int64 sums, `views` = the distinct `row // queries_per_view`, `score` = the seed's, `feat` = per channel in fp32
+     `acc = acc + (float) w_i * f_i` (two rounded operations per member) then `acc / (float) sum w_i` (`reduce="mean"`), or the seed's
+     row (`reduce="best"`).
+  8. Emit.  Clusters with `views < min_views` are dropped; of the rest at most the `max_queries` best by seed score, ties to the lower
+     seed row; in ascending seed row.  `labels` int32 [n] = the output index of each input row's cluster, or -1.
+
+Two detections of one object in the same frame merge too, and count as one view.
+
+Out of scope: the 2D detector and reading image files; the dataset's `dropout_rate_2dfeats` and the decoder's distance mask are what
+the reference applies to the queries."""
 from __future__ import annotations
+
+from collections import namedtuple
 
 import torch
 
@@ -40,6 +67,56 @@ from . import ops
 from .lift2d import Views
 
 RULE_DEFAULTS = dict(far=20.0, gate_abs=0.10, gate_rel=0.05, min_pixels=16, score_thr=0.3, max_queries=None)
+MERGE_DEFAULTS = dict(radius=0.3, sim=0.75, min_views=1, max_queries=None, reduce="mean")
+
+Merged = namedtuple("Merged", "feats pos scores views labels")
+Merged.__doc__ = """One query per object: feats fp32 [K, C], pos fp32 [K, 3], scores fp32 [K] (the seed's), views int32 [K] (the distinct
+frames behind it), labels int32 [n] (the output index of each input row's cluster, or -1); contiguous device tensors."""
+
+
+def _merge_rule(rule: dict, score_thr, min_pixels) -> dict:
+    """MERGE_DEFAULTS plus the lifter's own `score_thr` and `min_pixels` -> the checked rule with its integer forms."""
+    known = set(MERGE_DEFAULTS) | {"score_thr", "min_pixels"}
+    bad = set(rule) - known
+    if bad:
+        raise TypeError(f"unknown query-merging parameter(s) {sorted(bad)}; known: {sorted(known)}")
+    r = {**MERGE_DEFAULTS, "score_thr": score_thr, "min_pixels": min_pixels, **rule}
+    r["radius_q"] = round(float(r["radius"]) * 1024)
+    if not 1 <= r["radius_q"] <= 1 << 20:
+        raise ValueError(f"radius must lie in [1/1024, 1024] m, got {r['radius']}")
+    if r["sim"] is None:
+        r["sim_q"] = 0
+    else:
+        r["sim_q"] = round(float(r["sim"]) * 128)
+        if not 0.0 <= float(r["sim"]) <= 1.0 or not 1 <= r["sim_q"] <= 128:
+            raise ValueError(f"sim must be None (distance only) or a cosine in [1/256, 1], got {r['sim']}")
+    if int(r["min_views"]) != r["min_views"] or r["min_views"] < 1:
+        raise ValueError(f"min_views must be an integer >= 1, got {r['min_views']}")
+    if int(r["min_pixels"]) != r["min_pixels"] or r["min_pixels"] < 1:
+        raise ValueError(f"min_pixels must be an integer >= 1, got {r['min_pixels']}")
+    if r["max_queries"] is not None and (int(r["max_queries"]) != r["max_queries"] or r["max_queries"] < 0):
+        raise ValueError(f"max_queries must be None or an integer >= 0, got {r['max_queries']}")
+    if r["reduce"] not in ("mean", "best"):
+        raise ValueError(f"reduce must be 'mean' or 'best', got {r['reduce']!r}")
+    return r
+
+
+def merge_queries(feats, centre, scores, count, queries_per_view: int, **rule) -> Merged:
+    """One query per object from rows `feats` fp16 or fp32 [n, C <= 1024], `centre` fp32 [n, 3], `scores` fp32 [n], `count` int32 [n]
+    (the pixels behind each centre), `view = row // queries_per_view`: the rule of the module docstring, steps 1 to 8.  `rule`:
+    MERGE_DEFAULTS, plus `score_thr` and `min_pixels` (the lifter's defaults).  Two detections of one object in the same frame merge
+    too, and count as one view.  One host read, of the cluster count."""
+    r = _merge_rule(rule, RULE_DEFAULTS["score_thr"], RULE_DEFAULTS["min_pixels"])
+    for t, name in ((feats, "feats"), (centre, "centre"), (scores, "scores"), (count, "count")):
+        _on_device(t, f"merge_queries: {name}")
+    if int(queries_per_view) != queries_per_view or queries_per_view < 1:
+        raise ValueError(f"merge_queries: queries_per_view must be an integer >= 1, got {queries_per_view}")
+    ws = ops.merge_queries_adjacency(feats, centre, scores, count, r["score_thr"], r["min_pixels"], r["radius_q"], r["sim_q"])
+    n, C = feats.shape
+    ops.merge_queries_sweep(n, C, ws)
+    k = ops.merge_queries_reduce(scores, count, C, queries_per_view, r["score_thr"], r["min_views"], r["max_queries"], ws)
+    K = int(k.item()) if n else 0                                                       # the one host read
+    return Merged(*ops.merge_queries_emit(feats, scores, count, K, r["reduce"] == "best", ws))
 
 
 def _rule(rule: dict) -> dict:
@@ -166,11 +243,33 @@ class QueryLifter:
         return ops.lift_query_gather(self._feats[:self.n_views].view(n, self.channels), self._centre[:self.n_views].view(n, 3), rows, M)
 
 
-def lift_queries(views: Views, masks, scores, feats, **rule):
+    def merged(self, **merge_rule) -> Merged:
+        """One query per object over the live stores (`merge_queries` with the lifter's `score_thr` and `min_pixels`; `merge_rule`:
+        MERGE_DEFAULTS).  One host read, of the cluster count.  May be called at any time; the lifter goes on, and `result()` is
+        what it was."""
+        r = self.rule
+        _merge_rule(merge_rule, r["score_thr"], r["min_pixels"])                        # refuse a bad rule before anything else
+        if self._centre is None or self.n_views == 0:
+            dev = self._centre.device if self._centre is not None else torch.device("cuda", torch.cuda.current_device())
+            return Merged(torch.empty(0, self.channels, device=dev), torch.empty(0, 3, device=dev), torch.empty(0, device=dev),
+                          torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev))
+        n = self.n_views * self.n_queries
+        rule = {"score_thr": r["score_thr"], "min_pixels": r["min_pixels"], **merge_rule}
+        return merge_queries(self._feats[:self.n_views].view(n, self.channels), self._centre[:self.n_views].view(n, 3),
+                             self._scores[:self.n_views].view(n), self._count[:self.n_views].view(n), self.n_queries, **rule)
+
+
+def lift_queries(views: Views, masks, scores, feats, merge=None, **rule):
     """The one-shot form: -> (query2d_feats fp32 [M, C], query2d_pos fp32 [M, 3]), ready for `extra_features["query2d_feats"]` /
-    `["query2d_pos"]` or `io_scene.pack_scene`."""
+    `["query2d_pos"]` or `io_scene.pack_scene`.  With `merge=dict(...)` (MERGE_DEFAULTS; `{}` takes them as they are) the rows of one
+    object are merged first and the pair is `Merged.feats`, `Merged.pos`: one query per object."""
     if not isinstance(feats, torch.Tensor) or feats.dim() != 3:
         raise ValueError(f"lift_queries: feats must be a tensor [V, Q, C], got {list(getattr(feats, 'shape', []))}")
+    if merge is not None and not isinstance(merge, dict):
+        raise TypeError(f"lift_queries: merge must be None or a dict of merging parameters, got {type(merge).__name__}")
     lifter = QueryLifter(feats.shape[2], **rule)
     lifter.add(views, masks, scores, feats)
-    return lifter.result()
+    if merge is None:
+        return lifter.result()
+    m = lifter.merged(**merge)
+    return m.feats, m.pos

@@ -2325,3 +2325,124 @@ def lift_query_gather(feats, centre, rows, M: int):
         _lib.check(lib.sd3d_lift_query_gather(fp, int(feats.dtype == torch.float16), cp, rp, n, M, C, _ptr(out_feats), _ptr(out_pos), _stream()),
                    "lift_query_gather")
     return out_feats, out_pos
+
+
+# --------------------------------------------------------------------------------------------
+# merging of lifted queries across views (csrc/merge_queries.hip; the rule: include/segdino3d_hip.h, segdino3d_amd/lift_queries.py)
+# --------------------------------------------------------------------------------------------
+MERGE_MAX_ROWS = 1 << 14
+MERGE_MAX_CHANNELS = 1024
+_WS_MERGE = _PerThread()  # merge_queries: codes, bit matrix, labels and cluster tables, alive from the adjacency call to the emit call
+
+
+def _merge_rows(feats, centre, scores, count, who):
+    """The checks the four calls share -> (n, C, pointers of feats, centre, scores, count)."""
+    if feats.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"{who}: feats must be fp16 or fp32, got {feats.dtype}")
+    if feats.dim() != 2 or not 1 <= feats.shape[1] <= MERGE_MAX_CHANNELS:
+        raise ValueError(f"{who}: feats must be [n, C] with 1 <= C <= {MERGE_MAX_CHANNELS} (the int64 cosine test is exact up to there), "
+                         f"got {list(feats.shape)}")
+    n, C = feats.shape
+    if centre is not None:
+        _want_shape(centre, [(n, 3)], f"{who}: centre")
+    _want_shape(scores, [(n,)], f"{who}: scores")
+    _want_shape(count, [(n,)], f"{who}: count")
+    return n, C, _ptr(feats, None, f"{who}: feats"), _ptr(centre, torch.float32, f"{who}: centre"), \
+        _ptr(scores, torch.float32, f"{who}: scores"), _ptr(count, torch.int32, f"{who}: count")
+
+
+def _merge_ws(lib, n, C, ws, who):
+    need = lib.sd3d_merge_queries_ws_bytes(n, C)
+    if not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.dtype != torch.uint8 or ws.numel() < need:
+        raise ValueError(f"{who}: ws must be the workspace merge_queries_adjacency returned for these rows ({need} bytes)")
+    return ws
+
+
+def merge_queries_adjacency(feats, centre, scores, count, score_thr, min_pixels, radius_q, sim_q):
+    """Steps 1 to 5 of the merging rule (`sd3d_merge_queries_adjacency`): the valid rows ranked by score, their int8 codes and
+    fixed-point centres, and the adjacency bit matrix of the ranks, all left in the workspace that is returned and that the sweep, the
+    reduction and the emit calls take.  feats fp16 or fp32 [n, C <= 1024], centre fp32 [n, 3], scores fp32 [n], count int32 [n];
+    radius_q = round(radius * 1024) in 1 .. 2^20, sim_q = round(sim * 128) in 1 .. 128 or 0 for distance only.  Enqueues only."""
+    lib = _lib.load()
+    who = "merge_queries_adjacency"
+    n, C, fp, cp, sp, np_ = _merge_rows(feats, centre, scores, count, who)
+    if int(min_pixels) != min_pixels or min_pixels < 1:
+        raise ValueError(f"{who}: min_pixels must be an integer >= 1, got {min_pixels}")
+    if int(radius_q) != radius_q or not 1 <= radius_q <= 1 << 20:
+        raise ValueError(f"{who}: radius_q must be an integer in [1, 2^20], got {radius_q}")
+    if int(sim_q) != sim_q or not 0 <= sim_q <= 128:
+        raise ValueError(f"{who}: sim_q must be an integer in [0, 128], got {sim_q}")
+    ws = _WS_MERGE.get(lib.sd3d_merge_queries_ws_bytes(n, C), feats.device)
+    if n:
+        _lib.check(lib.sd3d_merge_queries_adjacency(fp, int(feats.dtype == torch.float16), cp, sp, np_, n, C, float(score_thr), int(min_pixels),
+                                                    int(radius_q), int(sim_q), ws.data_ptr(), ws.numel(), _stream()), who)
+    return ws
+
+
+def merge_queries_adjacency_read(n: int, C: int, ws):
+    """What `merge_queries_adjacency` left in `ws` -> (rank_row int32 [Mp]: the row of each rank, -1 beyond the entering rows; adj int64
+    [Mp, Mp / 64]: bit b % 64 of word [a, b / 64] = ranks a < b are adjacent), Mp = min(n, 16384) rounded up to 64.  For tests and tools."""
+    lib = _lib.load()
+    n, C = int(n), int(C)
+    mp = (min(max(n, 1), MERGE_MAX_ROWS) + 63) // 64 * 64
+    rank_row = torch.full((mp,), -1, dtype=torch.int32, device=ws.device)
+    adj = torch.zeros(mp, mp // 64, dtype=torch.int64, device=ws.device)
+    if n:
+        ws = _merge_ws(lib, n, C, ws, "merge_queries_adjacency_read")
+        _lib.check(lib.sd3d_merge_queries_adjacency_read(n, C, ws.data_ptr(), ws.numel(), _ptr(rank_row), _ptr(adj), _stream()),
+                   "merge_queries_adjacency_read")
+    return rank_row, adj
+
+
+def merge_queries_sweep(n: int, C: int, ws):
+    """Step 6 (`sd3d_merge_queries_sweep`): the leader clustering over the bit matrix in `ws`.  Enqueues only."""
+    lib = _lib.load()
+    if int(n):
+        ws = _merge_ws(lib, int(n), int(C), ws, "merge_queries_sweep")
+        _lib.check(lib.sd3d_merge_queries_sweep(int(n), int(C), ws.data_ptr(), ws.numel(), _stream()), "merge_queries_sweep")
+
+
+def merge_queries_reduce(scores, count, C: int, queries_per_view: int, score_thr, min_views, max_queries, ws):
+    """Steps 7 and 8 but the features (`sd3d_merge_queries_reduce`) -> k int32 [1] on the device: the number of emitted clusters.
+    Enqueues only."""
+    lib = _lib.load()
+    who = "merge_queries_reduce"
+    if scores.dim() != 1:
+        raise ValueError(f"{who}: scores must be fp32 [n], got {list(scores.shape)}")
+    n = scores.shape[0]
+    _want_shape(count, [(n,)], f"{who}: count")
+    if int(queries_per_view) != queries_per_view or queries_per_view < 1:
+        raise ValueError(f"{who}: queries_per_view must be an integer >= 1, got {queries_per_view}")
+    if int(min_views) != min_views or min_views < 1:
+        raise ValueError(f"{who}: min_views must be an integer >= 1, got {min_views}")
+    if max_queries is not None and (int(max_queries) != max_queries or max_queries < 0):
+        raise ValueError(f"{who}: max_queries must be None or an integer >= 0, got {max_queries}")
+    sp, np_ = _ptr(scores, torch.float32, f"{who}: scores"), _ptr(count, torch.int32, f"{who}: count")
+    k = torch.zeros(1, dtype=torch.int32, device=scores.device)
+    if n:
+        ws = _merge_ws(lib, n, int(C), ws, who)
+        _lib.check(lib.sd3d_merge_queries_reduce(sp, np_, n, int(C), int(queries_per_view), float(score_thr), int(min_views),
+                                                 -1 if max_queries is None else int(max_queries), _ptr(k), ws.data_ptr(), ws.numel(), _stream()),
+                   who)
+    return k
+
+
+def merge_queries_emit(feats, scores, count, K: int, best: bool, ws):
+    """The emitted clusters (`sd3d_merge_queries_emit`), K = the value read from `merge_queries_reduce` -> (feats fp32 [K, C], pos fp32
+    [K, 3], scores fp32 [K], views int32 [K], labels int32 [n]).  Enqueues only."""
+    lib = _lib.load()
+    who = "merge_queries_emit"
+    n, C, fp, _, sp, np_ = _merge_rows(feats, None, scores, count, who)
+    K = int(K)
+    if not 0 <= K <= min(n, MERGE_MAX_ROWS):
+        raise ValueError(f"{who}: need 0 <= K <= min(n, {MERGE_MAX_ROWS}), got K = {K}, n = {n}")
+    dev = feats.device
+    out = (torch.empty(K, C, dtype=torch.float32, device=dev), torch.empty(K, 3, dtype=torch.float32, device=dev),
+           torch.empty(K, dtype=torch.float32, device=dev), torch.empty(K, dtype=torch.int32, device=dev),
+           torch.empty(n, dtype=torch.int32, device=dev))
+    if n:
+        ws = _merge_ws(lib, n, C, ws, who)
+        _lib.check(lib.sd3d_merge_queries_emit(fp, int(feats.dtype == torch.float16), sp, np_, n, C, K, int(bool(best)),
+                                               *(_ptr(t) if t.numel() else None for t in out[:4]), _ptr(out[4]), ws.data_ptr(), ws.numel(),
+                                               _stream()), who)
+    return out
