@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 16
+#define SD3D_ABI_VERSION 17
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1181,6 +1181,39 @@ int sd3d_merge_queries_reduce(const float* scores, const int32_t* count, int64_t
 int sd3d_merge_queries_emit(const void* feats, int feats_f16, const float* scores, const int32_t* count, int64_t n, int C, int64_t K,
                             int reduce_best, float* out_feats, float* out_pos, float* out_scores, int32_t* out_views, int32_t* labels,
                             const void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Superpoints from a triangle mesh (csrc/superpoints.hip): the graph segmentation ScanNet's segmentator applies to a scan, the input
+ * `super_points` of the model.  The reference loads it from a dump; tests/superpoints_ref.py restates the rule below and the kernels
+ * EQUAL the restatement label for label.  Every step is one correctly rounded fp32 operation (never contracted) or an exact integer one.
+ *
+ *   Inputs.  vertices float [N, 3]; faces int32 or int64 (faces_i64 != 0) [F, 3], indices local to the face's scene; 3 F < 2^31;
+ *     k_thresh finite >= 0; min_verts >= 1.  A batch is concatenated: vertex_offsets / face_offsets int64 [n_scenes + 1] on the device
+ *     ascend from 0 to N / F.  A face with an index outside its scene's [0, N_s) is ignored and counted in bad_faces; a face with a
+ *     repeated index is kept (its self-edges join nothing, its normal is zero).
+ *   1. Face normal.  a = p1 - p0, b = p2 - p0, n = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), every product and
+ *      difference rounded; l = sqrt((n.x n.x + n.y n.y) + n.z n.z); valid iff l is finite and > 0, then n /= l per component.
+ *   2. Vertex normal.  Each valid face adds rint(n 2^24) to its three vertices (int64 sums); m = (float)(double)sum, normalised as
+ *      above; a zero or invalid m is (0, 0, 0).
+ *   3. Edges.  Face f = (i, j, k) gives edges 3 f = (i, j), 3 f + 1 = (i, k), 3 f + 2 = (k, j).  For edge (a, b):
+ *      dot = (m_a.x m_b.x + m_a.y m_b.y) + m_a.z m_b.z; w = 1 - dot if that is > 0, else 0;
+ *      s = (m_b.x (p_b.x - p_a.x) + m_b.y (p_b.y - p_a.y)) + m_b.z (p_b.z - p_a.z); if s > 0 (a NaN is not) w = w w.
+ *   4. Order.  Ascending (bits of w as uint32, edge index).
+ *   5. Pass 1.  Every vertex is a component with size 1 and thr = k_thresh.  In order: components A != B of the ends join iff
+ *      w <= thr[A] and w <= thr[B]; then size = size_A + size_B and thr = w + k_thresh / (float)size (a divide, then an add).
+ *   6. Pass 2.  In the same order: A != B join iff size[A] < min_verts or size[B] < min_verts.
+ *   7. Output.  labels int64 [N], dense 0 .. S_s - 1 per scene, components numbered by their smallest vertex; info int32
+ *      [n_scenes, 2] = {S_s, bad_faces_s}.  A vertex in no face is a component of its own.
+ *
+ *   Optional outputs (NULL: not written), for tests and tools: normals_out float [N, 3] (step 2), weights_out uint32 [3 F] (the bits
+ *   of step 3, 0 for an ignored face), sweep_stats_out int64 [n_scenes, 2] = the edges of pass 1 / pass 2 whose ends lay in different
+ *   components (in pass 2: one of them below min_verts) when their batch began: those the sweep settles in LDS.  ws: sd3d_superpoints_ws_bytes, 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+size_t sd3d_superpoints_ws_bytes(int64_t n_vertices, int64_t n_faces, int n_scenes);
+int sd3d_mesh_superpoints(const float* vertices, const void* faces, int faces_i64, const int64_t* vertex_offsets,
+                          const int64_t* face_offsets, int64_t n_vertices, int64_t n_faces, int n_scenes, float k_thresh, int min_verts,
+                          int64_t* labels, int32_t* info, float* normals_out, void* weights_out, int64_t* sweep_stats_out, void* ws,
+                          size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

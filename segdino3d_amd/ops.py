@@ -2446,3 +2446,55 @@ def merge_queries_emit(feats, scores, count, K: int, best: bool, ws):
                                                *(_ptr(t) if t.numel() else None for t in out[:4]), _ptr(out[4]), ws.data_ptr(), ws.numel(),
                                                _stream()), who)
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# superpoints from a mesh (csrc/superpoints.hip; the rule: include/segdino3d_hip.h, segdino3d_amd/superpoints.py)
+# --------------------------------------------------------------------------------------------
+SUPERPOINTS_MAX_VERTICES = 1 << 24      # per scene
+_WS_SP = _PerThread()    # mesh_superpoints: normal sums, edge keys and sort buffers, the forest and the label tables
+
+
+def mesh_superpoints(vertices, faces, vertex_offsets, face_offsets, k_thresh: float, min_verts: int, debug: bool = False):
+    """Graph segmentation of a batch of concatenated meshes (`sd3d_mesh_superpoints`): vertices fp32 [N, 3], faces int32 or int64
+    [F, 3] with indices local to each scene, vertex_offsets / face_offsets int64 [n_scenes + 1] on the device -> (labels int64 [N],
+    info int32 [n_scenes, 2] = {superpoints, ignored faces} per scene, on the device), and with `debug` also (normals fp32 [N, 3],
+    weight bits int32 [3 F], sweep_stats int64 [n_scenes, 2]).  Enqueues only."""
+    lib = _lib.load()
+    who = "mesh_superpoints"
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"{who}: vertices must be fp32 [N, 3], got {list(vertices.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{who}: faces must be int32 or int64 [F, 3], got {list(faces.shape)}")
+    if vertices.dtype != torch.float32:
+        raise ValueError(f"{who}: vertices must be fp32, got {vertices.dtype}")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{who}: faces must be int32 or int64, got {faces.dtype}")
+    N, F = vertices.shape[0], faces.shape[0]
+    S = vertex_offsets.numel() - 1
+    if S < 1 or face_offsets.numel() != S + 1:
+        raise ValueError(f"{who}: vertex_offsets and face_offsets must both be int64 [n_scenes + 1] with n_scenes >= 1")
+    if 3 * F >= 1 << 31 or N >= 1 << 31:
+        raise ValueError(f"{who}: need N < 2^31 and 3 F < 2^31 over the batch, got N = {N}, F = {F}")
+    if not (np.isfinite(k_thresh) and k_thresh >= 0):
+        raise ValueError(f"{who}: k_thresh must be finite and >= 0, got {k_thresh}")
+    if int(min_verts) != min_verts or min_verts < 1:
+        raise ValueError(f"{who}: min_verts must be an integer >= 1, got {min_verts}")
+    vp, fp = _ptr(vertices, torch.float32, f"{who}: vertices"), _ptr(faces, None, f"{who}: faces")
+    vo, fo = _ptr(vertex_offsets, torch.int64, f"{who}: vertex_offsets"), _ptr(face_offsets, torch.int64, f"{who}: face_offsets")
+    dev = vertices.device
+    labels = torch.empty(N, dtype=torch.int64, device=dev)
+    info = torch.empty(S, 2, dtype=torch.int32, device=dev)
+    extra = ()
+    if debug:
+        extra = (torch.empty(N, 3, dtype=torch.float32, device=dev), torch.empty(3 * F, dtype=torch.int32, device=dev),
+                 torch.empty(S, 2, dtype=torch.int64, device=dev))
+    need = lib.sd3d_superpoints_ws_bytes(N, F, S)
+    if need == 0:
+        raise ValueError(f"{who}: sizes out of range (N = {N}, F = {F}, n_scenes = {S})")
+    ws = _WS_SP.get(need, dev)
+    _lib.check(lib.sd3d_mesh_superpoints(vp if N else None, fp if F else None, int(faces.dtype == torch.int64), vo, fo, N, F, S, float(k_thresh),
+                                         int(min_verts), _ptr(labels) if N else None, _ptr(info),
+                                         *((_ptr(t) if t.numel() else None for t in extra) if debug else (None, None, None)),
+                                         ws.data_ptr(), ws.numel(), _stream()), who)
+    return (labels, info) + tuple(extra)
