@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 17
+#define SD3D_ABI_VERSION 18
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1214,6 +1214,49 @@ int sd3d_mesh_superpoints(const float* vertices, const void* faces, int faces_i6
                           const int64_t* face_offsets, int64_t n_vertices, int64_t n_faces, int n_scenes, float k_thresh, int min_verts,
                           int64_t* labels, int32_t* info, float* normals_out, void* weights_out, int64_t* sweep_stats_out, void* ws,
                           size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Superpoints from a point cloud (csrc/superpoints.hip): the segmentator's second entry, segment_point(vertices, normals, edges),
+ * for scans without faces, with the two steps in front of it: an exact k-nearest-neighbour graph and normals from the neighbourhood.
+ * tests/point_superpoints_ref.py restates the three rules below and the kernels EQUAL it bit for bit.  A batch is concatenated;
+ * vertex_offsets / edge_offsets int64 [n_scenes + 1] on the device ascend from 0; indices (nbr, ea, eb) are local to their scene.
+ *
+ * sd3d_graph_superpoints.  points, normals float [N, 3]; ea, eb int32 [E]; E < 2^31.  An edge with an end outside its scene's [0, N_s)
+ *   is ignored, counted in info[s][1] (bad_edges) and never looked at.  Otherwise step 3 of the mesh rule on the given normals:
+ *   dot = (m_a.x m_b.x + m_a.y m_b.y) + m_a.z m_b.z; w = 1 - dot if that is > 0, else 0; s = (m_b.x (p_b.x - p_a.x) + m_b.y
+ *   (p_b.y - p_a.y)) + m_b.z (p_b.z - p_a.z); if s > 0, w = w w.  oriented == 0 (normals without a sign): dot = |dot| before the
+ *   subtraction and no squaring.  Steps 4 to 7 are the mesh's, the edge index being the position in the list: both copies of a mutual
+ *   edge are kept.  weights_out uint32 [E], sweep_stats_out int64 [n_scenes, 2]: optional, as for the mesh.
+ *
+ * sd3d_knn_graph.  1 <= k <= 64, 0 < radius <= 4, N k < 2^31.  A point is valid iff its coordinates are finite with |c| < 2^14.
+ *   r2 = (float)(radius radius).  For valid i != j of one scene: dx = p_j.x - p_i.x (dy, dz alike), d2 = (dx dx + dy dy) + dz dz, one
+ *   fp32 rounding per operation; j is a candidate iff d2 <= r2.  Row i of nbr int32 [N, k] holds the k smallest candidates by
+ *   (bits of d2 as uint32, j), ascending; missing slots hold -1; the row of an invalid point is all -1 and it is nobody's neighbour.
+ *   d2_out float [N, k] (optional): the distances, +inf in a missing slot.  A hashed uniform grid of fixed-point cells chooses the
+ *   pairs that are evaluated and cannot change the answer (the argument: csrc/superpoints.hip).
+ *
+ * sd3d_point_normals.  nbr int32 [N, k] (k <= 64).  A slot counts iff 0 <= j < N_s and d = p_j - p_i (fp32) has |d| <= 8 in every
+ *   component; c = the slots that count.  c < 3: the normal is (0, 0, 0).  Otherwise q = rint(d 2^20) as int64, n = c + 1 (the point
+ *   itself, q = 0), exact sums Sq [3] and Sqq [6], C = n Sqq - Sq Sq^T (exact), its six entries converted to fp64; cyclic Jacobi in
+ *   fp64, every operation one IEEE rounding: exactly 8 sweeps over (0,1), (0,2), (1,2); a rotation is skipped when a_pq == 0;
+ *   theta = (a_qq - a_pp) / (2 a_pq), t = 1 / (|theta| + sqrt(theta theta + 1)), negated when theta < 0, c = 1 / sqrt(t t + 1),
+ *   s = t c; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0, (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq), and the columns p, q of
+ *   V (from the identity) alike: (v_ip, v_iq) = (c v_ip - s v_iq, s v_ip + c v_iq); tests/point_superpoints_ref.py has them one
+ *   operation per line and is their definition.  The normal is the column of V at the smallest diagonal entry (ties: the lowest
+ *   index), cast to fp32 and normalised as a face normal is (a failure gives (0, 0, 0)).  viewpoint float [n_scenes, 3], or [N, 3]
+ *   with viewpoint_per_point != 0: the normal is negated iff (n.x (v.x - p.x) + n.y (v.y - p.y)) + n.z (v.z - p.z) < 0 in fp32;
+ *   viewpoint NULL: negated so that its first non-zero component is positive (segment such normals with oriented = 0).
+ * ------------------------------------------------------------------------------------------- */
+size_t sd3d_graph_superpoints_ws_bytes(int64_t n_points, int64_t n_edges, int n_scenes);
+int sd3d_graph_superpoints(const float* points, const float* normals, const int32_t* ea, const int32_t* eb,
+                           const int64_t* vertex_offsets, const int64_t* edge_offsets, int64_t n_points, int64_t n_edges, int n_scenes,
+                           int oriented, float k_thresh, int min_verts, int64_t* labels, int32_t* info, void* weights_out,
+                           int64_t* sweep_stats_out, void* ws, size_t ws_bytes, void* stream);
+size_t sd3d_knn_graph_ws_bytes(int64_t n_points, int n_scenes);
+int sd3d_knn_graph(const float* points, const int64_t* vertex_offsets, int64_t n_points, int n_scenes, int k, float radius, int32_t* nbr,
+                   float* d2_out, void* ws, size_t ws_bytes, void* stream);
+int sd3d_point_normals(const float* points, const int32_t* nbr, const int64_t* vertex_offsets, int64_t n_points, int n_scenes, int k,
+                       const float* viewpoint, int viewpoint_per_point, float* normals, void* stream);
 
 #ifdef __cplusplus
 }

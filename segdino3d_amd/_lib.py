@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _lib = None
 
@@ -186,6 +186,11 @@ SIGNATURES = {
     "sd3d_merge_queries_emit": (_i, [_p, _i, _p, _p, _l, _i, _l, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
     "sd3d_superpoints_ws_bytes": (_z, [_l, _l, _i]),
     "sd3d_mesh_superpoints": (_i, [_p, _p, _i, _p, _p, _l, _l, _i, _f, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "sd3d_graph_superpoints_ws_bytes": (_z, [_l, _l, _i]),
+    "sd3d_graph_superpoints": (_i, [_p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _f, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "sd3d_knn_graph_ws_bytes": (_z, [_l, _i]),
+    "sd3d_knn_graph": (_i, [_p, _p, _l, _i, _i, _f, _p, _p, _p, _z, _p]),
+    "sd3d_point_normals": (_i, [_p, _p, _p, _l, _i, _i, _p, _i, _p, _p]),
 }
 
 

@@ -25,6 +25,12 @@
 //                       keep them in order, and pass 2 sweeps that list alone.
 //   sp_min_kernel .. sp_info_kernel   the root of every vertex, the smallest vertex of every component (integer atomicMin), a flag at
 //                       that vertex, scan_exclusive_i32 over the flags = the component's number, labels int64 and {S, bad_faces} per scene.
+//
+// A point cloud (no faces) enters through sd3d_graph_superpoints: the sweep and the candidate kernel are templated on the edge SOURCE
+// (SpFaceSrc: edge 3 f + k of a face list, as above; SpListSrc: ea, eb int32 [E] with edge_offsets), sp_gedge_kernel computes the weights
+// from given normals (oriented or not) and sorts the ignored edges of a scene behind its live ones, where pass 1 stops.  In front of
+// it, further down in this file: sd3d_knn_graph (knn_*_kernel: an exact k-NN graph over a hashed grid of fixed-point cells, one wave
+// per point) and sd3d_point_normals (pn_normal_kernel: int64 moments, fp64 cyclic Jacobi, one thread per point).
 // All values are written with plain vector stores.
 #include "common.h"
 #include "../../include/segdino3d_hip.h"
@@ -50,14 +56,15 @@ struct SpWs {
     void *sort_ws, *scan_ws;
     size_t sort_bytes, scan_bytes, total_bytes;
 };
-static SpWs sp_ws(void* ws, int64_t N, int64_t F, int S) {
+// E = the number of edges (3 F for a mesh); `mesh`: with the normal sums and the vertex normals (a graph brings its normals)
+static SpWs sp_ws(void* ws, int64_t N, int64_t E, int S, bool mesh) {
     SpWs w;
     char* p = (char*)ws;
     size_t o = 0;
     auto take = [&](size_t bytes) { char* q = p + o; o += align_up(bytes, 256); return (void*)q; };
-    const size_t n = (size_t)(N > 0 ? N : 1), e = (size_t)(F > 0 ? 3 * F : 1), s = (size_t)(S > 0 ? S : 1);
-    w.sums = (long long*)take(n * 3 * 8);
-    w.vnorm = (float*)take(n * 3 * 4);
+    const size_t n = (size_t)(N > 0 ? N : 1), e = (size_t)(E > 0 ? E : 1), s = (size_t)(S > 0 ? S : 1);
+    w.sums = mesh ? (long long*)take(n * 3 * 8) : nullptr;
+    w.vnorm = mesh ? (float*)take(n * 3 * 4) : nullptr;
     w.parent = (int32_t*)take(n * 4); w.size = (int32_t*)take(n * 4); w.minv = (int32_t*)take(n * 4);
     w.root = (int32_t*)take(n * 4); w.flag = (int32_t*)take(n * 4); w.excl = (int32_t*)take(n * 4);
     w.thr = (float*)take(n * 4);
@@ -154,6 +161,63 @@ __device__ __forceinline__ void sp_ends(const int64_t v[3], int k, int64_t& a, i
     b = k == 1 ? v[2] : v[1];
 }
 
+// ---------------------------------------------------------------------------------------------- edge sources
+// Where the sweep and the candidate kernel get an edge's ends from.  A source has `edges()` (the batch's edge count), `range(s, e0, e1)`
+// (the scene's share of them), `scene_of(S, g)` and `ends(g, s, voff, N, a, b)` -> whether edge g is live, with its global ends.
+template <typename I>
+struct SpFaceSrc {                                      // edge 3 f + k of face f
+    const I* faces;
+    const int64_t* foff;
+    int64_t F;
+    __device__ __forceinline__ int64_t edges() const { return 3 * F; }
+    __device__ __forceinline__ void range(int s, int64_t& e0, int64_t& e1) const {
+        e0 = 3 * sp_clamp(foff[s], 0, F);
+        e1 = 3 * sp_clamp(foff[s + 1], e0 / 3, F);
+    }
+    __device__ __forceinline__ int scene_of(int S, int64_t g) const { return sp_scene_of(foff, S, g / 3); }
+    __device__ __forceinline__ bool ends(int64_t g, int s, const int64_t* __restrict__ voff, int64_t N, int64_t& a, int64_t& b) const {
+        const int64_t f = g / 3;
+        int64_t v[3];
+        if (!sp_face(faces, f, s, voff, N, v)) return false;
+        sp_ends(v, (int)(g - 3 * f), a, b);
+        return true;
+    }
+};
+struct SpListSrc {                                      // edge g = (ea[g], eb[g]), indices local to the scene
+    const int32_t *ea, *eb;
+    const int64_t* eoff;
+    int64_t E;
+    __device__ __forceinline__ int64_t edges() const { return E; }
+    __device__ __forceinline__ void range(int s, int64_t& e0, int64_t& e1) const {
+        e0 = sp_clamp(eoff[s], 0, E);
+        e1 = sp_clamp(eoff[s + 1], e0, E);
+    }
+    __device__ __forceinline__ int scene_of(int S, int64_t g) const { return sp_scene_of(eoff, S, g); }
+    __device__ __forceinline__ bool ends(int64_t g, int s, const int64_t* __restrict__ voff, int64_t N, int64_t& a, int64_t& b) const {
+        const int64_t v0 = sp_clamp(voff[s], 0, N), n_s = sp_clamp(voff[s + 1], v0, N) - v0;
+        const int64_t ia = (int64_t)ea[g], ib = (int64_t)eb[g];
+        a = v0 + ia;
+        b = v0 + ib;
+        return ia >= 0 && ia < n_s && ib >= 0 && ib < n_s;
+    }
+};
+
+// step 3 for the edge (a, b) with normals `nrm`: the bits of its weight.  `oriented` = 0: the normals carry no sign - |dot|, no convexity
+__device__ __forceinline__ uint32_t sp_weight_bits(const float* __restrict__ vert, const float* __restrict__ nrm, int64_t a, int64_t b, int oriented) {
+    const float max_ = nrm[a * 3], may = nrm[a * 3 + 1], maz = nrm[a * 3 + 2];
+    const float mbx = nrm[b * 3], mby = nrm[b * 3 + 1], mbz = nrm[b * 3 + 2];
+    float dot = (max_ * mbx + may * mby) + maz * mbz;
+    if (!oriented) dot = fabsf(dot);
+    const float t = 1.0f - dot;
+    float w = t > 0.0f ? t : 0.0f;
+    if (oriented) {
+        const float dx = vert[b * 3] - vert[a * 3], dy = vert[b * 3 + 1] - vert[a * 3 + 1], dz = vert[b * 3 + 2] - vert[a * 3 + 2];
+        const float sd = (mbx * dx + mby * dy) + mbz * dz;
+        if (sd > 0.0f) w = w * w;                                                     // a NaN is not > 0
+    }
+    return __float_as_uint(w);
+}
+
 template <typename I>
 __global__ __launch_bounds__(256) void sp_edge_kernel(const float* __restrict__ vert, const I* __restrict__ faces,
                                                       const int64_t* __restrict__ voff, const int64_t* __restrict__ foff, int S, int64_t N,
@@ -169,18 +233,34 @@ __global__ __launch_bounds__(256) void sp_edge_kernel(const float* __restrict__ 
     if (sp_face(faces, f, s, voff, N, v)) {
         int64_t a, b;
         sp_ends(v, k, a, b);
-        const float max_ = vnorm[a * 3], may = vnorm[a * 3 + 1], maz = vnorm[a * 3 + 2];
-        const float mbx = vnorm[b * 3], mby = vnorm[b * 3 + 1], mbz = vnorm[b * 3 + 2];
-        const float dot = (max_ * mbx + may * mby) + maz * mbz;
-        const float t = 1.0f - dot;
-        float w = t > 0.0f ? t : 0.0f;
-        const float dx = vert[b * 3] - vert[a * 3], dy = vert[b * 3 + 1] - vert[a * 3 + 1], dz = vert[b * 3 + 2] - vert[a * 3 + 2];
-        const float sd = (mbx * dx + mby * dy) + mbz * dz;
-        if (sd > 0.0f) w = w * w;                                                     // a NaN is not > 0
-        bits = __float_as_uint(w);
+        bits = sp_weight_bits(vert, vnorm, a, b, 1);
     }
     wbits[g] = bits;
     keys[g] = ((uint64_t)(uint32_t)s << 32) | bits;
+    if (weights_out) weights_out[g] = bits;
+}
+
+// one thread per edge of the list: an edge with an end outside its scene only counts in bad[scene] and is never looked at
+__global__ __launch_bounds__(256) void sp_gedge_kernel(const float* __restrict__ vert, const float* __restrict__ nrm, SpListSrc src,
+                                                       const int64_t* __restrict__ voff, int S, int64_t N, int oriented,
+                                                       uint32_t* __restrict__ wbits, uint64_t* __restrict__ keys, int32_t* __restrict__ bad,
+                                                       uint32_t* __restrict__ weights_out) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool in = g < src.E;
+    const int s = in ? src.scene_of(S, g) : -1;
+    int64_t a, b;
+    uint32_t bits = 0u;
+    const bool ignored = in && !src.ends(g, s, voff, N, a, b);
+    // A k-NN graph's missing slots are ignored edges by the hundred thousand: the wave's first lane adds the count of its own scene
+    // in one atomic, and only lanes of another scene (a wave across a scene boundary) add their own.
+    const int s_first = __shfl(s, 0);
+    const unsigned long long together = __ballot(ignored && s == s_first);
+    if ((threadIdx.x & 63) == 0 && together) atomicAdd(&bad[s_first], __popcll(together));
+    if (ignored && s != s_first) atomicAdd(&bad[s], 1);
+    if (!in) return;
+    if (!ignored) bits = sp_weight_bits(vert, nrm, a, b, oriented);
+    wbits[g] = bits;
+    keys[g] = ((uint64_t)(uint32_t)s << 32) | (ignored ? 0xFFFFFFFFu : bits);        // no weight is a NaN: an ignored edge sorts behind every live one of its scene
     if (weights_out) weights_out[g] = bits;
 }
 
@@ -226,13 +306,12 @@ __device__ __forceinline__ void sp_wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-template <typename I>
-__global__ __launch_bounds__(SP_BATCH) void sp_sweep_kernel(const I* __restrict__ faces, const int64_t* __restrict__ voff,
-                                                            const int64_t* __restrict__ foff, int64_t N, int64_t F,
+template <typename Src>
+__global__ __launch_bounds__(SP_BATCH) void sp_sweep_kernel(Src src, const int64_t* __restrict__ voff, int64_t N,
                                                             const uint32_t* __restrict__ order, const uint32_t* __restrict__ wbits,
                                                             float k_thresh, int min_verts, int pass, const int32_t* __restrict__ cand_excl,
                                                             const int32_t* __restrict__ cand_total, int32_t* parent, int32_t* size,
-                                                            float* thr, long long* __restrict__ stats) {
+                                                            float* thr, long long* __restrict__ stats, const int32_t* __restrict__ tail) {
     __shared__ int t_key[SP_TABLE];
     __shared__ int t_size[SP_TABLE];
     __shared__ float t_thr[SP_TABLE];
@@ -243,10 +322,15 @@ __global__ __launch_bounds__(SP_BATCH) void sp_sweep_kernel(const I* __restrict_
     __shared__ int s_cnt[SP_BATCH / 64];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int s = blockIdx.x;
-    int64_t e0 = 3 * sp_clamp(foff[s], 0, F), e1 = 3 * sp_clamp(foff[s + 1], e0 / 3, F);
+    const int64_t E = src.edges();
+    int64_t e0, e1;
+    src.range(s, e0, e1);
     if (pass == 1) {                                                                  // `order` holds the candidates only: the scene's share of them
-        e0 = e0 < 3 * F ? cand_excl[e0] : *cand_total;
-        e1 = e1 < 3 * F ? cand_excl[e1] : *cand_total;
+        e0 = e0 < E ? cand_excl[e0] : *cand_total;
+        e1 = e1 < E ? cand_excl[e1] : *cand_total;
+    } else if (tail) {                                                                // the scene's ignored edges were sorted behind its live ones
+        const int64_t live = e1 - (int64_t)tail[s];
+        e1 = live > e0 ? live : e0;
     }
     const int64_t v0 = sp_clamp(voff[s], 0, N), n_s = sp_clamp(voff[s + 1], v0, N) - v0;
     {
@@ -259,11 +343,9 @@ __global__ __launch_bounds__(SP_BATCH) void sp_sweep_kernel(const I* __restrict_
             bool surv = false;
             if (e < e1) {
                 const int64_t g = (int64_t)order[e];
-                if (g < 3 * F) {
-                    const int64_t f = g / 3;
-                    int64_t v[3], va, vb;
-                    if (sp_face(faces, f, s, voff, N, v)) {
-                        sp_ends(v, (int)(g - 3 * f), va, vb);
+                if (g < E) {
+                    int64_t va, vb;
+                    if (src.ends(g, s, voff, N, va, vb)) {
                         a = (int)va; b = (int)vb;
                         w = __uint_as_float(wbits[g]);
                         ra = sp_find(parent, a, n_s, ha);
@@ -346,20 +428,18 @@ __global__ __launch_bounds__(SP_BATCH) void sp_sweep_kernel(const I* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------- the candidates of pass 2
-template <typename I>
-__global__ __launch_bounds__(256) void sp_cand_kernel(const I* __restrict__ faces, const int64_t* __restrict__ voff,
-                                                      const int64_t* __restrict__ foff, int S, int64_t N, int64_t F,
+template <typename Src>
+__global__ __launch_bounds__(256) void sp_cand_kernel(Src src, const int64_t* __restrict__ voff, int S, int64_t N,
                                                       const uint32_t* __restrict__ order, const int32_t* __restrict__ parent,
                                                       const int32_t* __restrict__ size, int min_verts, int32_t* __restrict__ flag) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= 3 * F) return;
+    const int64_t E = src.edges();
+    if (e >= E) return;
     const int64_t g = (int64_t)order[e];
     int keep = 0;
-    if (g < 3 * F) {
-        const int64_t f = g / 3;
-        int64_t v[3], va, vb;
-        if (sp_face(faces, f, sp_scene_of(foff, S, f), voff, N, v)) {
-            sp_ends(v, (int)(g - 3 * f), va, vb);
+    if (g < E) {
+        int64_t va, vb;
+        if (src.ends(g, src.scene_of(S, g), voff, N, va, vb)) {
             int ra = (int)va, rb = (int)vb;
             for (int64_t h = 0; h < N; ++h) { const int p = parent[ra]; if (p == ra) break; ra = p; }
             for (int64_t h = 0; h < N; ++h) { const int p = parent[rb]; if (p == rb) break; rb = p; }
@@ -422,7 +502,49 @@ static bool sp_sizes_ok(int64_t N, int64_t F, int S) {
 
 extern "C" size_t sd3d_superpoints_ws_bytes(int64_t n_vertices, int64_t n_faces, int n_scenes) {
     if (!sp_sizes_ok(n_vertices, n_faces, n_scenes)) return 0;
-    return sp_ws(nullptr, n_vertices, n_faces, n_scenes).total_bytes;
+    return sp_ws(nullptr, n_vertices, 3 * n_faces, n_scenes, true).total_bytes;
+}
+
+// Steps 4 to 6 for the E > 0 edges of `src`, whose keys are in w.keys_a and whose weights are in w.wbits: the order, pass 1, the
+// candidates of pass 2, pass 2.  `tail` (or NULL): per scene, the number of ignored edges whose keys put them behind the scene's live
+// edges; pass 1 stops in front of them.
+template <typename Src>
+static int sp_segment(const Src& src, int64_t E, const int64_t* vertex_offsets, int64_t N, int S, float k_thresh, int min_verts,
+                      const SpWs& w, const int32_t* tail, hipStream_t st) {
+    const dim3 b256(256), ge((unsigned)cdiv(E, 256)), gs((unsigned)S), bs(SP_BATCH);
+    int scene_bits = 0;
+    while ((1 << scene_bits) < S) ++scene_bits;
+    int landed = 0;
+    if (int rc = sort_pairs_u64(w.keys_a, nullptr, w.keys_b, w.vals_b, E, 0, 32 + scene_bits, w.sort_ws, w.sort_bytes, st, w.vals_a, &landed))
+        return rc;
+    const uint32_t* order = landed ? w.vals_a : w.vals_b;
+    uint32_t* order2 = landed ? w.vals_b : w.vals_a;                                  // the candidates of pass 2
+    int32_t *cflag = (int32_t*)w.keys_a, *cexcl = (int32_t*)w.keys_b;                 // the sorted keys are done with
+    hipLaunchKernelGGL(sp_sweep_kernel<Src>, gs, bs, 0, st, src, vertex_offsets, N, order, w.wbits, k_thresh, min_verts, 0, cexcl, w.cand_total,
+                       w.parent, w.size, w.thr, w.stats, tail);
+    if (min_verts > 1) {                                                              // (no component is below one vertex)
+        hipLaunchKernelGGL(sp_cand_kernel<Src>, ge, b256, 0, st, src, vertex_offsets, S, N, order, w.parent, w.size, min_verts, cflag);
+        if (int rc = scan_exclusive_i32(cflag, cexcl, E, nullptr, w.cand_total, w.scan_ws, w.scan_bytes, st)) return rc;
+        hipLaunchKernelGGL(sp_compact_kernel, ge, b256, 0, st, order, cflag, cexcl, E, order2);
+        hipLaunchKernelGGL(sp_sweep_kernel<Src>, gs, bs, 0, st, src, vertex_offsets, N, order2, w.wbits, k_thresh, min_verts, 1, cexcl, w.cand_total,
+                           w.parent, w.size, w.thr, w.stats, tail);
+    }
+    return SD3D_OK;
+}
+// Step 7: labels and {count, bad} per scene.
+static int sp_finish(const int64_t* vertex_offsets, int64_t N, int S, int64_t* labels, int32_t* info, int64_t* sweep_stats_out, const SpWs& w,
+                     hipStream_t st) {
+    const dim3 b256(256), gv((unsigned)cdiv(N > 0 ? N : 1, 256));
+    if (N > 0) {
+        hipLaunchKernelGGL(sp_min_kernel, gv, b256, 0, st, w.parent, N, w.root, w.minv);
+        hipLaunchKernelGGL(sp_flag_kernel, gv, b256, 0, st, w.root, w.minv, N, w.flag);
+        if (int rc = scan_exclusive_i32(w.flag, w.excl, N, nullptr, w.total, w.scan_ws, w.scan_bytes, st)) return rc;
+        hipLaunchKernelGGL(sp_label_kernel, gv, b256, 0, st, w.root, w.minv, w.excl, vertex_offsets, S, N, labels);
+    }
+    hipLaunchKernelGGL(sp_info_kernel, dim3((unsigned)cdiv(S, 256)), b256, 0, st, w.excl, w.total, w.bad, vertex_offsets, S, N, w.stats, info,
+                       (long long*)sweep_stats_out);
+    SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
 }
 
 extern "C" int sd3d_mesh_superpoints(const float* vertices, const void* faces, int faces_i64, const int64_t* vertex_offsets,
@@ -439,7 +561,7 @@ extern "C" int sd3d_mesh_superpoints(const float* vertices, const void* faces, i
     if (!vertex_offsets || !face_offsets || !info || (N > 0 && (!vertices || !labels)) || (F > 0 && !faces))
         return sd3d_set_error(SD3D_ERR_ARG, "mesh_superpoints: NULL argument");
     if (!ws || ((uintptr_t)ws & 255) != 0) return sd3d_set_error(SD3D_ERR_ARG, "mesh_superpoints: ws must be given and 256-byte aligned");
-    const SpWs w = sp_ws(ws, N, F, S);
+    const SpWs w = sp_ws(ws, N, 3 * F, S, true);
     if (ws_bytes < w.total_bytes) return sd3d_set_error(SD3D_ERR_WS, "mesh_superpoints: workspace too small");
     const dim3 b256(256), gv((unsigned)cdiv(N > 0 ? N : 1, 256)), gf((unsigned)cdiv(F > 0 ? F : 1, 256)), ge((unsigned)cdiv(F > 0 ? 3 * F : 1, 256));
     if (hipMemsetAsync(w.bad, 0, (size_t)S * 4, st) != hipSuccess || hipMemsetAsync(w.stats, 0, (size_t)S * 16, st) != hipSuccess ||
@@ -461,42 +583,357 @@ extern "C" int sd3d_mesh_superpoints(const float* vertices, const void* faces, i
         else
             hipLaunchKernelGGL(sp_edge_kernel<int32_t>, ge, b256, 0, st, vertices, (const int32_t*)faces, vertex_offsets, face_offsets, S, N, F, w.vnorm,
                                w.wbits, w.keys_a, (uint32_t*)weights_out);
-        int scene_bits = 0;
-        while ((1 << scene_bits) < S) ++scene_bits;
-        int landed = 0;
-        if (int rc = sort_pairs_u64(w.keys_a, nullptr, w.keys_b, w.vals_b, E, 0, 32 + scene_bits, w.sort_ws, w.sort_bytes, st, w.vals_a, &landed))
-            return rc;
-        const uint32_t* order = landed ? w.vals_a : w.vals_b;
-        uint32_t* order2 = landed ? w.vals_b : w.vals_a;                              // the candidates of pass 2
-        int32_t *cflag = (int32_t*)w.keys_a, *cexcl = (int32_t*)w.keys_b;             // the sorted keys are done with
-        const dim3 gs((unsigned)S), bs(SP_BATCH);
-#define SP_SWEEP(T, pass, ord) \
-    hipLaunchKernelGGL(sp_sweep_kernel<T>, gs, bs, 0, st, (const T*)faces, vertex_offsets, face_offsets, N, F, ord, w.wbits, k_thresh, min_verts, \
-                       pass, cexcl, w.cand_total, w.parent, w.size, w.thr, w.stats)
-        if (faces_i64) SP_SWEEP(int64_t, 0, order); else SP_SWEEP(int32_t, 0, order);
-        if (min_verts > 1) {                                                          // (no component is below one vertex)
-            if (faces_i64)
-                hipLaunchKernelGGL(sp_cand_kernel<int64_t>, ge, b256, 0, st, (const int64_t*)faces, vertex_offsets, face_offsets, S, N, F, order,
-                                   w.parent, w.size, min_verts, cflag);
-            else
-                hipLaunchKernelGGL(sp_cand_kernel<int32_t>, ge, b256, 0, st, (const int32_t*)faces, vertex_offsets, face_offsets, S, N, F, order,
-                                   w.parent, w.size, min_verts, cflag);
-            if (int rc = scan_exclusive_i32(cflag, cexcl, E, nullptr, w.cand_total, w.scan_ws, w.scan_bytes, st)) return rc;
-            hipLaunchKernelGGL(sp_compact_kernel, ge, b256, 0, st, order, cflag, cexcl, E, order2);
-            if (faces_i64) SP_SWEEP(int64_t, 1, order2); else SP_SWEEP(int32_t, 1, order2);
-        }
-#undef SP_SWEEP
+        int rc;
+        if (faces_i64)
+            rc = sp_segment(SpFaceSrc<int64_t>{(const int64_t*)faces, face_offsets, F}, E, vertex_offsets, N, S, k_thresh, min_verts, w, nullptr, st);
+        else
+            rc = sp_segment(SpFaceSrc<int32_t>{(const int32_t*)faces, face_offsets, F}, E, vertex_offsets, N, S, k_thresh, min_verts, w, nullptr, st);
+        if (rc) return rc;
     } else if (F > 0 && weights_out) {
         if (hipMemsetAsync(weights_out, 0, (size_t)F * 12, st) != hipSuccess) return sd3d_set_error(SD3D_ERR_LAUNCH, "mesh_superpoints: memset");
     }
-    if (N > 0) {
-        hipLaunchKernelGGL(sp_min_kernel, gv, b256, 0, st, w.parent, N, w.root, w.minv);
-        hipLaunchKernelGGL(sp_flag_kernel, gv, b256, 0, st, w.root, w.minv, N, w.flag);
-        if (int rc = scan_exclusive_i32(w.flag, w.excl, N, nullptr, w.total, w.scan_ws, w.scan_bytes, st)) return rc;
-        hipLaunchKernelGGL(sp_label_kernel, gv, b256, 0, st, w.root, w.minv, w.excl, vertex_offsets, S, N, labels);
+    return sp_finish(vertex_offsets, N, S, labels, info, sweep_stats_out, w, st);
+}
+
+// ---------------------------------------------------------------------------------------------- a general edge list
+static bool sp_graph_sizes_ok(int64_t N, int64_t E, int S) {
+    return N >= 0 && N <= SP_MAX_VERTICES && E >= 0 && E <= 0x7FFFFFFFll && S >= 1 && S <= SP_MAX_SCENES;
+}
+extern "C" size_t sd3d_graph_superpoints_ws_bytes(int64_t n_points, int64_t n_edges, int n_scenes) {
+    if (!sp_graph_sizes_ok(n_points, n_edges, n_scenes)) return 0;
+    return sp_ws(nullptr, n_points, n_edges, n_scenes, false).total_bytes;
+}
+
+extern "C" int sd3d_graph_superpoints(const float* points, const float* normals, const int32_t* ea, const int32_t* eb,
+                                      const int64_t* vertex_offsets, const int64_t* edge_offsets, int64_t n_points, int64_t n_edges,
+                                      int n_scenes, int oriented, float k_thresh, int min_verts, int64_t* labels, int32_t* info,
+                                      void* weights_out, int64_t* sweep_stats_out, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = n_points, E = n_edges;
+    const int S = n_scenes;
+    if (!sp_graph_sizes_ok(N, E, S))
+        return sd3d_set_error(SD3D_ERR_ARG, "graph_superpoints: 0 <= n_points < 2^31, 0 <= n_edges < 2^31, 1 <= n_scenes <= 65536");
+    if (!(k_thresh >= 0.0f && k_thresh < __builtin_inff()) || min_verts < 1)
+        return sd3d_set_error(SD3D_ERR_ARG, "graph_superpoints: k_thresh must be finite and >= 0, min_verts >= 1");
+    if (!vertex_offsets || !edge_offsets || !info || (N > 0 && (!points || !normals || !labels)) || (E > 0 && (!ea || !eb)))
+        return sd3d_set_error(SD3D_ERR_ARG, "graph_superpoints: NULL argument");
+    if (!ws || ((uintptr_t)ws & 255) != 0) return sd3d_set_error(SD3D_ERR_ARG, "graph_superpoints: ws must be given and 256-byte aligned");
+    const SpWs w = sp_ws(ws, N, E, S, false);
+    if (ws_bytes < w.total_bytes) return sd3d_set_error(SD3D_ERR_WS, "graph_superpoints: workspace too small");
+    const dim3 b256(256), gv((unsigned)cdiv(N > 0 ? N : 1, 256)), ge((unsigned)cdiv(E > 0 ? E : 1, 256));
+    if (hipMemsetAsync(w.bad, 0, (size_t)S * 4, st) != hipSuccess || hipMemsetAsync(w.stats, 0, (size_t)S * 16, st) != hipSuccess ||
+        hipMemsetAsync(w.total, 0, 4, st) != hipSuccess)
+        return sd3d_set_error(SD3D_ERR_LAUNCH, "graph_superpoints: memset");
+    if (N > 0) hipLaunchKernelGGL(sp_init_kernel, gv, b256, 0, st, N, k_thresh, w.parent, w.size, w.thr, w.minv);
+    if (E > 0) {
+        const SpListSrc src{ea, eb, edge_offsets, E};
+        hipLaunchKernelGGL(sp_gedge_kernel, ge, b256, 0, st, points, normals, src, vertex_offsets, S, N, oriented != 0, w.wbits, w.keys_a, w.bad,
+                           (uint32_t*)weights_out);
+        if (N > 0)
+            if (int rc = sp_segment(src, E, vertex_offsets, N, S, k_thresh, min_verts, w, w.bad, st)) return rc;
     }
-    hipLaunchKernelGGL(sp_info_kernel, dim3((unsigned)cdiv(S, 256)), b256, 0, st, w.excl, w.total, w.bad, vertex_offsets, S, N, w.stats, info,
-                       (long long*)sweep_stats_out);
+    return sp_finish(vertex_offsets, N, S, labels, info, sweep_stats_out, w, st);
+}
+
+// ---------------------------------------------------------------------------------------------- k nearest neighbours
+// The exact k-NN graph of a batch of point clouds (the rule: include/segdino3d_hip.h).  A uniform grid only chooses WHICH pairs are
+// evaluated; whether j is a neighbour of i is decided by d2 <= r2 alone, and the row is the k smallest (bits of d2, j).
+//
+// The grid is conservative by construction.  A valid point has |c| < 2^14, so c 2^10 is exact in fp32 and below 2^24 in magnitude, and
+// q = rint(c 2^10) is an integer with |q - c 2^10| <= 1/2.  If d2 <= r2 then fl(dx dx) <= d2 <= r2 = fl(r r) (sums of non-negative
+// terms round monotonically), so |dx| <= r (1 + 2^-23), and the exact difference of the two coordinates is within a factor
+// 1 + 2^-24 of its rounding dx: |p_j.x - p_i.x| <= r (1 + 2^-22) < r + 2^-20 for r <= 4.  Hence |q_j - q_i| <= 2^10 r + 2^-10 + 1
+// < ceil(2^10 r) + 2 <= H, and with cells of H fixed-point units, cell = (q + 2^24) / H, two candidates never lie more than one cell
+// apart on any axis: the 27 cells around a point's own hold every candidate.
+//
+// Cells are hashed (with the scene) into B >= 2 N buckets, B a power of two.  A bucket may hold points of several cells and scenes;
+// they are evaluated like any other and refused by d2 or by their scene.  Two of the 27 cells may share a bucket: a repeated bucket
+// is dropped before the walk, and every point lies in exactly one bucket, so no candidate is visited twice.
+//
+//   knn_key_kernel      one thread per point: its bucket as the sort key; an invalid point gets the key B and sorts behind all others.
+//   knn_gather_kernel   sort_pairs_u64 with "value = original index", then per sorted position (x, y, z, index) side by side and the
+//                       first / one-past-last position of every bucket (zeroed before: an empty bucket is [0, 0)).
+//   knn_search_kernel   one wave per point, in bucket order, so that the waves of a workgroup read the same buckets.  Lanes 0 .. 26 look up
+//                       the 27 buckets; the wave walks their concatenated ranges 64 points at a time, one distance per lane; lane l
+//                       keeps entry l of the sorted list of the best keys (k <= 64 = the lanes of a wave: no LDS table), and a candidate
+//                       below the k-th key is inserted by one ballot and one shift.  Trip counts: ceil(T / 64) walks for the T points
+//                       of the searched buckets, at most 64 insertions per walk, 5 rounds per range lookup, 17 per scene lookup.
+#define KNN_BIAS (1 << 24)
+#define KNN_WAVES 4                                     // waves = points per workgroup
+
+struct KnnWs {
+    uint64_t *keys_a, *keys_b;                          // [N]
+    uint32_t *vals_a, *vals_b;                          // [N]
+    float4* sorted;                                     // [N]
+    int32_t *cell_lo, *cell_hi;                         // [B]
+    void* sort_ws;
+    size_t sort_bytes, total_bytes;
+};
+static int knn_bucket_bits(int64_t N) {
+    int bits = 10;
+    while (bits < 26 && (1ll << bits) < 2 * N) ++bits;
+    return bits;
+}
+static KnnWs knn_ws(void* ws, int64_t N) {
+    KnnWs w;
+    char* p = (char*)ws;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { char* q = p + o; o += align_up(bytes, 256); return (void*)q; };
+    const size_t n = (size_t)(N > 0 ? N : 1), b = (size_t)1 << knn_bucket_bits(N);
+    w.keys_a = (uint64_t*)take(n * 8); w.keys_b = (uint64_t*)take(n * 8);
+    w.vals_a = (uint32_t*)take(n * 4); w.vals_b = (uint32_t*)take(n * 4);
+    w.sorted = (float4*)take(n * 16);
+    w.cell_lo = (int32_t*)take(b * 4); w.cell_hi = (int32_t*)take(b * 4);
+    w.sort_bytes = sort_ws_bytes((int64_t)n); w.sort_ws = take(w.sort_bytes);
+    w.total_bytes = o;
+    return w;
+}
+
+__device__ __forceinline__ bool knn_valid(float x, float y, float z) {
+    return fabsf(x) < 16384.0f && fabsf(y) < 16384.0f && fabsf(z) < 16384.0f;         // a NaN or an infinity is not
+}
+__device__ __forceinline__ int knn_cell(float c, int H) { return ((int)rintf(c * 1024.0f) + KNN_BIAS) / H; }     // 0 <= q + 2^24 <= 2^25
+__device__ __forceinline__ uint32_t knn_bucket(int cx, int cy, int cz, int s, int bucket_bits) {
+    const uint32_t h = hash_u64(((uint64_t)(uint32_t)cx << 32) | (uint32_t)cy);
+    return hash_u64(((uint64_t)h << 32) ^ ((uint64_t)(uint32_t)s << 40) ^ (uint32_t)cz) & ((1u << bucket_bits) - 1u);
+}
+__device__ __forceinline__ uint64_t knn_shfl(uint64_t v, int src) {
+    return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src);
+}
+__device__ __forceinline__ uint64_t knn_shfl_up1(uint64_t v) {
+    return ((uint64_t)(uint32_t)__shfl_up((int)(v >> 32), 1) << 32) | (uint32_t)__shfl_up((int)(uint32_t)v, 1);
+}
+
+__global__ __launch_bounds__(256) void knn_key_kernel(const float* __restrict__ pts, const int64_t* __restrict__ voff, int S, int64_t N, int H,
+                                                      int bucket_bits, uint64_t* __restrict__ keys) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const float x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+    uint64_t key = 1ull << bucket_bits;
+    if (knn_valid(x, y, z)) key = knn_bucket(knn_cell(x, H), knn_cell(y, H), knn_cell(z, H), sp_scene_of(voff, S, i), bucket_bits);
+    keys[i] = key;
+}
+
+__global__ __launch_bounds__(256) void knn_gather_kernel(const float* __restrict__ pts, const uint64_t* __restrict__ keys,
+                                                         const uint32_t* __restrict__ idx, int64_t N, int bucket_bits,
+                                                         float4* __restrict__ sorted, int32_t* __restrict__ cell_lo, int32_t* __restrict__ cell_hi) {
+    const int64_t pos = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pos >= N) return;
+    const int64_t i = (int64_t)idx[pos];
+    sorted[pos] = make_float4(pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2], __uint_as_float((uint32_t)i));
+    const uint64_t key = keys[pos];
+    if (key >> bucket_bits) return;                                                   // an invalid point: in no bucket
+    if (pos == 0 || keys[pos - 1] != key) cell_lo[key] = (int32_t)pos;
+    if (pos == N - 1 || keys[pos + 1] != key) cell_hi[key] = (int32_t)(pos + 1);
+}
+
+__global__ __launch_bounds__(64 * KNN_WAVES) void knn_search_kernel(const float4* __restrict__ sorted, const uint64_t* __restrict__ keys,
+                                                                    const int32_t* __restrict__ cell_lo, const int32_t* __restrict__ cell_hi,
+                                                                    const int64_t* __restrict__ voff, int S, int64_t N, int H, int bucket_bits,
+                                                                    int k, float r2, int32_t* __restrict__ nbr, float* __restrict__ d2_out) {
+    __shared__ int s_end[KNN_WAVES][32], s_lo[KNN_WAVES][32];                         // per wave: the 27 ranges, concatenated
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t pos = (int64_t)blockIdx.x * KNN_WAVES + wv;
+    if (pos >= N) return;                                                             // the whole wave: no workgroup barrier below
+    const float4 me = sorted[pos];
+    const int64_t i = (int64_t)__float_as_uint(me.w);
+    const uint64_t no_key = ~0ull;
+    uint64_t best = no_key;                                                           // lane l: the l-th smallest key so far
+    if ((keys[pos] >> bucket_bits) == 0) {                                            // a valid point (wave-uniform)
+        const int s = sp_scene_of(voff, S, i);
+        const int64_t v0 = sp_clamp(voff[s], 0, N), v1 = sp_clamp(voff[s + 1], v0, N);
+        const int cx = knn_cell(me.x, H), cy = knn_cell(me.y, H), cz = knn_cell(me.z, H);
+        uint32_t b = 0xFFFFFFFFu;
+        if (lane < 27) b = knn_bucket(cx + lane % 3 - 1, cy + (lane / 3) % 3 - 1, cz + lane / 9 - 1, s, bucket_bits);
+        bool first = lane < 27;
+        for (int m = 0; m < 26; ++m) {                                                // a bucket a lower lane holds already is dropped
+            const uint32_t other = (uint32_t)__shfl((int)b, m);
+            if (m < lane && other == b) first = false;
+        }
+        int lo = 0, len = 0;
+        if (first) { lo = cell_lo[b]; len = cell_hi[b] - lo; }
+        if (len < 0) len = 0;
+        const int end = wave_scan_incl(len, lane);
+        if (lane < 32) { s_end[wv][lane] = end; s_lo[wv][lane] = lo - (end - len); }  // position = flat index + s_lo
+        sp_wave_sync();
+        const int total = __shfl(end, 63);
+        uint64_t kth = no_key;
+        for (int base = 0; base < total; base += 64) {
+            const int f = base + lane;
+            uint64_t key = no_key;
+            if (f < total) {
+                int r = 0;                                                            // the first range with end > f: 5 rounds over 32 entries
+#pragma unroll
+                for (int step = 16; step >= 1; step >>= 1)
+                    if (s_end[wv][r + step - 1] <= f) r += step;
+                const float4 c = sorted[f + s_lo[wv][r]];
+                const int64_t j = (int64_t)__float_as_uint(c.w);
+                const float dx = c.x - me.x, dy = c.y - me.y, dz = c.z - me.z;
+                const float d2 = (dx * dx + dy * dy) + dz * dz;
+                if (j >= v0 && j < v1 && j != i && d2 <= r2) key = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)(j - v0);
+            }
+            unsigned long long todo = __ballot(key < kth);
+            while (todo) {                                                            // at most 64 rounds
+                const int src = __ffsll((long long)todo) - 1;
+                todo &= todo - 1ull;
+                const uint64_t c = knn_shfl(key, src);
+                if (c < kth) {                                                        // wave-uniform; the k-th key only ever falls
+                    const int at = __popcll(__ballot(best < c));                      // the list ascends: lanes [0, at) hold smaller keys
+                    const uint64_t up = knn_shfl_up1(best);
+                    best = lane < at ? best : (lane == at ? c : up);
+                    kth = knn_shfl(best, k - 1);
+                }
+            }
+        }
+    }
+    if (lane < k) {
+        const bool none = best == no_key;
+        nbr[i * k + lane] = none ? -1 : (int32_t)(uint32_t)best;
+        if (d2_out) d2_out[i * k + lane] = none ? __builtin_inff() : __uint_as_float((uint32_t)(best >> 32));
+    }
+}
+
+static bool knn_sizes_ok(int64_t N, int S) { return N >= 0 && N <= SP_MAX_VERTICES && S >= 1 && S <= SP_MAX_SCENES; }
+
+extern "C" size_t sd3d_knn_graph_ws_bytes(int64_t n_points, int n_scenes) {
+    if (!knn_sizes_ok(n_points, n_scenes)) return 0;
+    return knn_ws(nullptr, n_points).total_bytes;
+}
+
+extern "C" int sd3d_knn_graph(const float* points, const int64_t* vertex_offsets, int64_t n_points, int n_scenes, int k, float radius,
+                              int32_t* nbr, float* d2_out, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = n_points;
+    const int S = n_scenes;
+    if (!knn_sizes_ok(N, S)) return sd3d_set_error(SD3D_ERR_ARG, "knn_graph: 0 <= n_points < 2^31, 1 <= n_scenes <= 65536");
+    if (k < 1 || k > 64 || !(radius > 0.0f && radius <= 4.0f)) return sd3d_set_error(SD3D_ERR_ARG, "knn_graph: 1 <= k <= 64, 0 < radius <= 4");
+    if (N * k > 0x7FFFFFFFll) return sd3d_set_error(SD3D_ERR_ARG, "knn_graph: n_points k must stay below 2^31");
+    if (!vertex_offsets || (N > 0 && (!points || !nbr))) return sd3d_set_error(SD3D_ERR_ARG, "knn_graph: NULL argument");
+    if (!ws || ((uintptr_t)ws & 255) != 0) return sd3d_set_error(SD3D_ERR_ARG, "knn_graph: ws must be given and 256-byte aligned");
+    const KnnWs w = knn_ws(ws, N);
+    if (ws_bytes < w.total_bytes) return sd3d_set_error(SD3D_ERR_WS, "knn_graph: workspace too small");
+    if (N == 0) return SD3D_OK;
+    const float r2 = radius * radius;
+    const int H = (int)ceilf(radius * 1024.0f) + 2;                                   // radius 2^10 is exact; 3 <= H <= 4098
+    const int bucket_bits = knn_bucket_bits(N);
+    const dim3 b256(256), gv((unsigned)cdiv(N, 256));
+    if (hipMemsetAsync(w.cell_lo, 0, (size_t)4 << bucket_bits, st) != hipSuccess || hipMemsetAsync(w.cell_hi, 0, (size_t)4 << bucket_bits, st) != hipSuccess)
+        return sd3d_set_error(SD3D_ERR_LAUNCH, "knn_graph: memset");
+    hipLaunchKernelGGL(knn_key_kernel, gv, b256, 0, st, points, vertex_offsets, S, N, H, bucket_bits, w.keys_a);
+    int landed = 0;
+    if (int rc = sort_pairs_u64(w.keys_a, nullptr, w.keys_b, w.vals_b, N, 0, bucket_bits + 1, w.sort_ws, w.sort_bytes, st, w.vals_a, &landed)) return rc;
+    const uint64_t* keys = landed ? w.keys_a : w.keys_b;
+    const uint32_t* idx = landed ? w.vals_a : w.vals_b;
+    hipLaunchKernelGGL(knn_gather_kernel, gv, b256, 0, st, points, keys, idx, N, bucket_bits, w.sorted, w.cell_lo, w.cell_hi);
+    hipLaunchKernelGGL(knn_search_kernel, dim3((unsigned)cdiv(N, KNN_WAVES)), dim3(64 * KNN_WAVES), 0, st, w.sorted, keys, w.cell_lo, w.cell_hi,
+                       vertex_offsets, S, N, H, bucket_bits, k, r2, nbr, d2_out);
+    SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- normals from the neighbourhood
+// One thread per point: exact int64 moments of its row's offsets, the covariance as six fp64 values, 8 sweeps of cyclic Jacobi in fp64,
+// the eigenvector of the smallest eigenvalue.  tests/point_superpoints_ref.py writes the same operations one per line; every fp64
+// operation here is one IEEE rounding (contraction is off; `/` and sqrt are correctly rounded).  All indices below are compile-time
+// constants once unrolled, so the two matrices live in registers.
+template <int P, int Q>
+__device__ __forceinline__ void pn_rotate(double (&a)[3][3], double (&v)[3][3]) {
+    constexpr int R = 3 - P - Q;
+    const double apq = a[P][Q];
+    if (apq == 0.0) return;
+    const double diff = a[Q][Q] - a[P][P];
+    const double two = 2.0 * apq;
+    const double theta = diff / two;
+    const double th2 = theta * theta;
+    const double rad = sqrt(th2 + 1.0);
+    const double den = fabs(theta) + rad;
+    double t = 1.0 / den;
+    if (theta < 0.0) t = -t;
+    const double t2 = t * t;
+    const double c = 1.0 / sqrt(t2 + 1.0);
+    const double s = t * c;
+    const double tap = t * apq;
+    a[P][P] = a[P][P] - tap;
+    a[Q][Q] = a[Q][Q] + tap;
+    a[P][Q] = 0.0; a[Q][P] = 0.0;
+    const double arp = a[R][P], arq = a[R][Q];
+    const double c_arp = c * arp, s_arq = s * arq, s_arp = s * arp, c_arq = c * arq;
+    a[R][P] = c_arp - s_arq; a[P][R] = a[R][P];
+    a[R][Q] = s_arp + c_arq; a[Q][R] = a[R][Q];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double vip = v[i][P], viq = v[i][Q];
+        const double c_vip = c * vip, s_viq = s * viq, s_vip = s * vip, c_viq = c * viq;
+        v[i][P] = c_vip - s_viq;
+        v[i][Q] = s_vip + c_viq;
+    }
+}
+
+__global__ __launch_bounds__(256) void pn_normal_kernel(const float* __restrict__ pts, const int32_t* __restrict__ nbr,
+                                                        const int64_t* __restrict__ voff, int S, int64_t N, int k,
+                                                        const float* __restrict__ view, int view_per_point, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int s = sp_scene_of(voff, S, i);
+    const int64_t v0 = sp_clamp(voff[s], 0, N), n_s = sp_clamp(voff[s + 1], v0, N) - v0;
+    const float px = pts[i * 3], py = pts[i * 3 + 1], pz = pts[i * 3 + 2];
+    long long sq[3] = {0, 0, 0}, sqq[6] = {0, 0, 0, 0, 0, 0};
+    int cnt = 0;
+    for (int e = 0; e < k; ++e) {
+        const int64_t j = (int64_t)nbr[i * k + e];
+        if (j < 0 || j >= n_s) continue;
+        const float dx = pts[(v0 + j) * 3] - px, dy = pts[(v0 + j) * 3 + 1] - py, dz = pts[(v0 + j) * 3 + 2] - pz;
+        if (!(fabsf(dx) <= 8.0f && fabsf(dy) <= 8.0f && fabsf(dz) <= 8.0f)) continue;          // beyond any radius, or not a number
+        const long long qx = (long long)rintf(dx * 1048576.0f), qy = (long long)rintf(dy * 1048576.0f), qz = (long long)rintf(dz * 1048576.0f);
+        sq[0] += qx; sq[1] += qy; sq[2] += qz;
+        sqq[0] += qx * qx; sqq[1] += qx * qy; sqq[2] += qx * qz; sqq[3] += qy * qy; sqq[4] += qy * qz; sqq[5] += qz * qz;
+        ++cnt;
+    }
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    if (cnt >= 3) {
+        const long long n = cnt + 1;                                                  // the point itself: q = 0
+        double a[3][3], v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+        a[0][0] = (double)(n * sqq[0] - sq[0] * sq[0]);
+        a[0][1] = a[1][0] = (double)(n * sqq[1] - sq[0] * sq[1]);
+        a[0][2] = a[2][0] = (double)(n * sqq[2] - sq[0] * sq[2]);
+        a[1][1] = (double)(n * sqq[3] - sq[1] * sq[1]);
+        a[1][2] = a[2][1] = (double)(n * sqq[4] - sq[1] * sq[2]);
+        a[2][2] = (double)(n * sqq[5] - sq[2] * sq[2]);
+        for (int sweep = 0; sweep < 8; ++sweep) {
+            pn_rotate<0, 1>(a, v);
+            pn_rotate<0, 2>(a, v);
+            pn_rotate<1, 2>(a, v);
+        }
+        const bool c1 = a[1][1] < a[0][0];                                            // the smallest diagonal entry, ties to the lowest index
+        const double d01 = c1 ? a[1][1] : a[0][0];
+        const bool c2 = a[2][2] < d01;
+        nx = (float)(c2 ? v[0][2] : (c1 ? v[0][1] : v[0][0]));
+        ny = (float)(c2 ? v[1][2] : (c1 ? v[1][1] : v[1][0]));
+        nz = (float)(c2 ? v[2][2] : (c1 ? v[2][1] : v[2][0]));
+        if (!sp_normalise(nx, ny, nz)) nx = ny = nz = 0.0f;
+        bool flip;
+        if (view) {
+            const float* vp = view + (view_per_point ? i * 3 : (int64_t)s * 3);
+            const float side = (nx * (vp[0] - px) + ny * (vp[1] - py)) + nz * (vp[2] - pz);
+            flip = side < 0.0f;
+        } else {
+            flip = nx < 0.0f || (nx == 0.0f && (ny < 0.0f || (ny == 0.0f && nz < 0.0f)));      // the first non-zero component is positive
+        }
+        if (flip) { nx = -nx; ny = -ny; nz = -nz; }
+    }
+    out[i * 3] = nx; out[i * 3 + 1] = ny; out[i * 3 + 2] = nz;
+}
+
+extern "C" int sd3d_point_normals(const float* points, const int32_t* nbr, const int64_t* vertex_offsets, int64_t n_points, int n_scenes, int k,
+                                  const float* viewpoint, int viewpoint_per_point, float* normals, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = n_points;
+    if (!knn_sizes_ok(N, n_scenes)) return sd3d_set_error(SD3D_ERR_ARG, "point_normals: 0 <= n_points < 2^31, 1 <= n_scenes <= 65536");
+    if (k < 1 || k > 64 || N * k > 0x7FFFFFFFll) return sd3d_set_error(SD3D_ERR_ARG, "point_normals: 1 <= k <= 64, n_points k < 2^31");
+    if (!vertex_offsets || (N > 0 && (!points || !nbr || !normals))) return sd3d_set_error(SD3D_ERR_ARG, "point_normals: NULL argument");
+    if (N == 0) return SD3D_OK;
+    hipLaunchKernelGGL(pn_normal_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, points, nbr, vertex_offsets, n_scenes, N, k, viewpoint,
+                       viewpoint_per_point != 0, normals);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }

@@ -2498,3 +2498,117 @@ def mesh_superpoints(vertices, faces, vertex_offsets, face_offsets, k_thresh: fl
                                          *((_ptr(t) if t.numel() else None for t in extra) if debug else (None, None, None)),
                                          ws.data_ptr(), ws.numel(), _stream()), who)
     return (labels, info) + tuple(extra)
+
+
+# --------------------------------------------------------------------------------------------
+# superpoints from a point cloud: k-NN graph, normals, segmentation of a general edge list (csrc/superpoints.hip)
+# --------------------------------------------------------------------------------------------
+KNN_MAX_K = 64
+KNN_MAX_RADIUS = 4.0
+_WS_KNN = _PerThread()   # knn_graph: bucket keys and sort buffers, the points in bucket order, the bucket ranges
+_WS_GSP = _PerThread()   # graph_superpoints: edge keys and sort buffers, the forest and the label tables
+
+
+def _scene_count(vertex_offsets, who):
+    S = vertex_offsets.numel() - 1
+    if S < 1:
+        raise ValueError(f"{who}: vertex_offsets must be int64 [n_scenes + 1] with n_scenes >= 1")
+    return S
+
+
+def knn_graph(points, vertex_offsets, k: int, radius: float, return_d2: bool = False):
+    """The exact k-NN graph of a batch of concatenated clouds (`sd3d_knn_graph`): points fp32 [N, 3], vertex_offsets int64
+    [n_scenes + 1] on the device -> nbr int32 [N, k] with indices local to each scene (-1: no neighbour), and with `return_d2` the
+    squared distances fp32 [N, k] (+inf: no neighbour).  Enqueues only."""
+    lib = _lib.load()
+    who = "knn_graph"
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError(f"{who}: points must be fp32 [N, 3], got {points.dtype} {list(points.shape)}")
+    if int(k) != k or k < 1 or k > KNN_MAX_K:
+        raise ValueError(f"{who}: k must be an integer in [1, {KNN_MAX_K}], got {k}")
+    if not (np.isfinite(radius) and 0 < radius <= KNN_MAX_RADIUS):
+        raise ValueError(f"{who}: radius must lie in (0, {KNN_MAX_RADIUS}], got {radius}")
+    N, S = points.shape[0], _scene_count(vertex_offsets, who)
+    if N * int(k) >= 1 << 31:
+        raise ValueError(f"{who}: need N k < 2^31, got N = {N}, k = {k}")
+    pp, vo = _ptr(points, torch.float32, f"{who}: points"), _ptr(vertex_offsets, torch.int64, f"{who}: vertex_offsets")
+    dev = points.device
+    nbr = torch.empty(N, int(k), dtype=torch.int32, device=dev)
+    d2 = torch.empty(N, int(k), dtype=torch.float32, device=dev) if return_d2 else None
+    need = lib.sd3d_knn_graph_ws_bytes(N, S)
+    if need == 0:
+        raise ValueError(f"{who}: sizes out of range (N = {N}, n_scenes = {S})")
+    ws = _WS_KNN.get(need, dev)
+    _lib.check(lib.sd3d_knn_graph(pp if N else None, vo, N, S, int(k), float(radius), _ptr(nbr) if N else None,
+                                  _ptr(d2) if return_d2 and N else None, ws.data_ptr(), ws.numel(), _stream()), who)
+    return (nbr, d2) if return_d2 else nbr
+
+
+def point_normals(points, nbr, vertex_offsets, viewpoint=None):
+    """Normals from each point's neighbourhood (`sd3d_point_normals`): points fp32 [N, 3], nbr int32 [N, k], viewpoint None (the
+    canonical sign), fp32 [n_scenes, 3] or fp32 [N, 3] -> normals fp32 [N, 3].  Enqueues only."""
+    lib = _lib.load()
+    who = "point_normals"
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError(f"{who}: points must be fp32 [N, 3], got {points.dtype} {list(points.shape)}")
+    N, S = points.shape[0], _scene_count(vertex_offsets, who)
+    if nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype != torch.int32 or not 1 <= nbr.shape[1] <= KNN_MAX_K:
+        raise ValueError(f"{who}: nbr must be int32 [N, k] with 1 <= k <= {KNN_MAX_K}, got {nbr.dtype} {list(nbr.shape)}")
+    k = nbr.shape[1]
+    per_point = 0
+    if viewpoint is not None:
+        if viewpoint.dtype != torch.float32 or tuple(viewpoint.shape) not in ((S, 3), (N, 3)):
+            raise ValueError(f"{who}: viewpoint must be fp32 [n_scenes, 3] or [N, 3], got {viewpoint.dtype} {list(viewpoint.shape)}")
+        per_point = int(tuple(viewpoint.shape) != (S, 3))
+    pp, vo = _ptr(points, torch.float32, f"{who}: points"), _ptr(vertex_offsets, torch.int64, f"{who}: vertex_offsets")
+    normals = torch.empty(N, 3, dtype=torch.float32, device=points.device)
+    if N:
+        _lib.check(lib.sd3d_point_normals(pp, _ptr(nbr, torch.int32, f"{who}: nbr"), vo, N, S, k,
+                                          None if viewpoint is None else _ptr(viewpoint, torch.float32, f"{who}: viewpoint"), per_point,
+                                          _ptr(normals), _stream()), who)
+    return normals
+
+
+def graph_superpoints(points, normals, ea, eb, vertex_offsets, edge_offsets, oriented: bool, k_thresh: float, min_verts: int,
+                      debug: bool = False):
+    """Graph segmentation of a batch of concatenated clouds over a given edge list (`sd3d_graph_superpoints`): points, normals fp32
+    [N, 3], ea, eb int32 [E] with indices local to each scene, vertex_offsets / edge_offsets int64 [n_scenes + 1] on the device ->
+    (labels int64 [N], info int32 [n_scenes, 2] = {superpoints, ignored edges} per scene, on the device), and with `debug` also
+    (weight bits int32 [E], sweep_stats int64 [n_scenes, 2]).  Enqueues only."""
+    lib = _lib.load()
+    who = "graph_superpoints"
+    for t, name in ((points, "points"), (normals, "normals")):
+        if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be fp32 [N, 3], got {t.dtype} {list(t.shape)}")
+    N, E = points.shape[0], ea.numel()
+    if normals.shape[0] != N:
+        raise ValueError(f"{who}: normals must have one row per point, got {normals.shape[0]} for {N}")
+    if ea.dim() != 1 or eb.dim() != 1 or eb.numel() != E or ea.dtype != torch.int32 or eb.dtype != torch.int32:
+        raise ValueError(f"{who}: ea and eb must both be int32 [E], got {ea.dtype} {list(ea.shape)} and {eb.dtype} {list(eb.shape)}")
+    S = _scene_count(vertex_offsets, who)
+    if edge_offsets.numel() != S + 1:
+        raise ValueError(f"{who}: vertex_offsets and edge_offsets must both be int64 [n_scenes + 1]")
+    if E >= 1 << 31 or N >= 1 << 31:
+        raise ValueError(f"{who}: need N < 2^31 and E < 2^31 over the batch, got N = {N}, E = {E}")
+    if not (np.isfinite(k_thresh) and k_thresh >= 0):
+        raise ValueError(f"{who}: k_thresh must be finite and >= 0, got {k_thresh}")
+    if int(min_verts) != min_verts or min_verts < 1:
+        raise ValueError(f"{who}: min_verts must be an integer >= 1, got {min_verts}")
+    pp, np_ = _ptr(points, torch.float32, f"{who}: points"), _ptr(normals, torch.float32, f"{who}: normals")
+    ap, bp = _ptr(ea, torch.int32, f"{who}: ea"), _ptr(eb, torch.int32, f"{who}: eb")
+    vo, eo = _ptr(vertex_offsets, torch.int64, f"{who}: vertex_offsets"), _ptr(edge_offsets, torch.int64, f"{who}: edge_offsets")
+    dev = points.device
+    labels = torch.empty(N, dtype=torch.int64, device=dev)
+    info = torch.empty(S, 2, dtype=torch.int32, device=dev)
+    extra = ()
+    if debug:
+        extra = (torch.empty(E, dtype=torch.int32, device=dev), torch.empty(S, 2, dtype=torch.int64, device=dev))
+    need = lib.sd3d_graph_superpoints_ws_bytes(N, E, S)
+    if need == 0:
+        raise ValueError(f"{who}: sizes out of range (N = {N}, E = {E}, n_scenes = {S})")
+    ws = _WS_GSP.get(need, dev)
+    _lib.check(lib.sd3d_graph_superpoints(pp if N else None, np_ if N else None, ap if E else None, bp if E else None, vo, eo, N, E, S,
+                                          int(bool(oriented)), float(k_thresh), int(min_verts), _ptr(labels) if N else None, _ptr(info),
+                                          *((_ptr(t) if t.numel() else None for t in extra) if debug else (None, None)),
+                                          ws.data_ptr(), ws.numel(), _stream()), who)
+    return (labels, info) + tuple(extra)
