@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 18
+#define SD3D_ABI_VERSION 19
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1257,6 +1257,65 @@ int sd3d_knn_graph(const float* points, const int64_t* vertex_offsets, int64_t n
                    float* d2_out, void* ws, size_t ws_bytes, void* stream);
 int sd3d_point_normals(const float* points, const int32_t* nbr, const int64_t* vertex_offsets, int64_t n_points, int n_scenes, int k,
                        const float* viewpoint, int viewpoint_per_point, float* normals, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fusion of posed RGB-D frames into the scene's point cloud (csrc/fuse_views.hip): the producer of `points [N, 6]` (xyz, rgb on the
+ * 0-255 scale), the input of the superpoint, lifting and query stages.  The reference has no counterpart (it reads a `points/` file per scene,
+ * made offline from a mesh); tests/fuse_views_ref.py restates the rule below in numpy and the kernels EQUAL it, bit for bit.  The
+ * calls only enqueue work.  Every decision is an integer one or a single rounded fp32 operation and the per-cell state is a set of
+ * integer sums, so the result is a pure function of the SET of (view, pixel) observations: the same bits however the views are cut
+ * into sd3d_fuse_accumulate calls, in whatever order they arrive, and on whatever stream.
+ *
+ *   Inputs.  depth [V, Hd, Wd], uint16 times depth_scale (depth_u16 != 0) or float metres; intrinsics float [V, 4] = fx, fy, cx, cy in
+ *     pixels of the depth image, pixel centres at integer coordinates; cam_to_world float [V, 12] = the rows of [R | t]; colors uint8
+ *     [V, Hc, Wc, 3] at any resolution.
+ *   1. Pixels.  Depth pixel (vi, ui) of view v takes part iff vi % stride == 0 and ui % stride == 0.  It reads the colour pixel
+ *      (((2 vi + 1) Hc) / (2 Hd), ((2 ui + 1) Wc) / (2 Wd)), integer divisions: the sampling rule of sd3d_lift_query_centres.
+ *   2. Depth.  d = (float)raw * depth_scale, one rounded fp32 multiply (float depth is used as it is).  The pixel is valid iff d > 0,
+ *      d >= near and d <= far, compared in fp32; a NaN fails.
+ *   3. Edges (flying pixels at depth discontinuities; skipped when use_edges == 0).  For each of the 4 neighbours (vi +- 1, ui),
+ *      (vi, ui +- 1) that lies inside the image, whatever the stride: dn = the neighbour's depth by step 2; it is a jump iff !(dn > 0)
+ *      or |dn - d| > edge_abs + edge_rel * d, the right-hand side one rounded multiply then one rounded add, the difference one
+ *      rounded subtract.  A pixel with any jump is dropped.
+ *   4. Back-projection.  Step 5 of sd3d_lift_query_centres, the same device function (csrc/backproject.h): x = (ui - cx) * d / fx, y
+ *      likewise, w_i = ((R_i0 x + R_i1 y) + R_i2 d) + R_i3, every operation rounded on its own, left to right, no fused multiply-add.
+ *      Unless all three w_i are finite with |w_i| < 2^SD3D_FUSE_WORLD_BITS the pixel is dropped and counted in out_of_range.
+ *   5. Cell.  c_i = floorf(w_i * inv_voxel), one rounded fp32 multiply; inv_voxel = (float)(1.0 / voxel), divided on the host in
+ *      double.  Unless -2^SD3D_FUSE_CELL_BITS <= c_i < 2^SD3D_FUSE_CELL_BITS on all axes, compared as floats before anything becomes
+ *      an integer, the pixel is dropped and counted in out_of_range.  key = ((c_x + 2^20) << 42) | ((c_y + 2^20) << 21) | (c_z + 2^20).
+ *      floor, not truncation: negative coordinates are ordinary.
+ *   6. Per cell, integers only.  n += 1; S_i += (int64)rint((double)w_i * 2^SD3D_FUSE_FIXED_BITS); C_j += colour byte j (r, g, b).  All
+ *      seven sums are 64-bit: 2^28 observations of one cell cannot overflow them.
+ *   7. Output.  The cells with n >= min_obs in ascending key order: xyz_i = (float)((double)S_i / (double)n / 2^SD3D_FUSE_FIXED_BITS),
+ *      rgb_j = (float)((double)C_j / (double)n), obs = n.
+ *
+ *   The state is an open-addressing table of `capacity` slots (a power of two, SD3D_FUSE_MIN_CAPACITY .. SD3D_FUSE_MAX_CAPACITY) of
+ *   SD3D_FUSE_SLOT_WORDS 64-bit words = 64 bytes {key, S_x, S_y, S_z, n, C_r, C_g, C_b}, in a caller-owned workspace of
+ *   sd3d_fuse_ws_bytes(capacity) bytes (0 for a bad capacity), 256-byte aligned, that also holds five 64-bit counters and the scratch
+ *   of the emit.  A cell whose probe sequence finds no slot within SD3D_FUSE_PROBE_LIMIT slots is dropped and its pixels are counted
+ *   in `overflow`: nothing is written outside the table, and the caller treats overflow > 0 as an error.  The table does not grow.
+ *
+ *   sd3d_fuse_reset: empties the table and zeroes the counters.  Required once before the first accumulate.
+ *   sd3d_fuse_accumulate: steps 1 to 6 for V views, one launch.
+ *   sd3d_fuse_emit: step 7.  points float [out_cap, 6], obs int32 [out_cap], keys_out int64 [out_cap] or NULL: the first
+ *     min(N, out_cap) rows are written.  info int64 [SD3D_FUSE_INFO_WORDS] on the device = N, cells (occupied slots), pixels_used
+ *     (observations added to a cell), out_of_range, overflow.  The table is left as it is: accumulate may go on.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_FUSE_FIXED_BITS 20          /* fixed-point fraction bits of the position sums */
+#define SD3D_FUSE_WORLD_BITS 14          /* world coordinates at or beyond 2^14 m are dropped */
+#define SD3D_FUSE_CELL_BITS 20           /* cell indices lie in [-2^20, 2^20): 21 bits per axis of the key */
+#define SD3D_FUSE_SLOT_WORDS 8           /* 64-bit words per slot of the table */
+#define SD3D_FUSE_PROBE_LIMIT 64         /* slots a cell tries before it counts as overflow */
+#define SD3D_FUSE_INFO_WORDS 5           /* N, cells, pixels_used, out_of_range, overflow */
+#define SD3D_FUSE_MIN_CAPACITY 16
+#define SD3D_FUSE_MAX_CAPACITY (1 << 24)
+size_t sd3d_fuse_ws_bytes(int64_t capacity);
+int sd3d_fuse_reset(void* ws, size_t ws_bytes, int64_t capacity, void* stream);
+int sd3d_fuse_accumulate(const void* depth, int depth_u16, float depth_scale, const float* intrinsics, const float* cam_to_world,
+                         const void* colors, int V, int Hd, int Wd, int Hc, int Wc, int stride, float near, float far, float edge_abs,
+                         float edge_rel, int use_edges, float inv_voxel, void* ws, size_t ws_bytes, int64_t capacity, void* stream);
+int sd3d_fuse_emit(void* ws, size_t ws_bytes, int64_t capacity, int min_obs, float* points, int32_t* obs, int64_t* keys_out,
+                   int64_t out_cap, int64_t* info, void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,7 @@
 //   sd3d_lift_query_gather   lq_gather_kernel   16 bytes of a feats row per lane.
 // All values are written with plain vector stores; no atomics but the LDS ones of the histograms.
 #include "common.h"
+#include "backproject.h"
 #include "../../include/segdino3d_hip.h"
 #include <hip/hip_fp16.h>
 
@@ -275,22 +276,15 @@ __global__ __launch_bounds__(LQ_THREADS) void lq_centre_kernel(const D* __restri
     const int k_med = (hi << 8) | s_sel[0];
 
     // ---- gate, back-project, fixed-point sums
-    const float* kk = intr + (int64_t)v * 4;
-    const float fx = kk[0], fy = kk[1], cx = kk[2], cy = kk[3];
-    const float* m = c2w + (int64_t)v * 12;
-    const float r00 = m[0], r01 = m[1], r02 = m[2], t0 = m[3], r10 = m[4], r11 = m[5], r12 = m[6], t1 = m[7], r20 = m[8], r21 = m[9],
-                r22 = m[10], t2 = m[11];
+    const Sd3dCamera cam = sd3d_load_camera(intr, c2w, v);
     const int64_t slack = 1000ll * g.gate_mm + (int64_t)g.gate_permille * k_med;
     const float lim = (float)(1 << SD3D_LIFTQ_WORLD_BITS), fixed = (float)(1 << SD3D_LIFTQ_FIXED_BITS);
     long long sx = 0, sy = 0, sz = 0;
     int cnt = 0;
     lq_sweep<D, FAST>(mask, depth, g, b, [&](int vi, int ui, float d, int k) {
         if (1000ll * abs(k - k_med) > slack) return;
-        // every operation rounded on its own, left to right: no contraction into FMAs, so this is the restatement's float32 arithmetic
-        const float x = __fdiv_rn(__fmul_rn(__fsub_rn((float)ui, cx), d), fx), y = __fdiv_rn(__fmul_rn(__fsub_rn((float)vi, cy), d), fy);
-        const float wx = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(r00, x), __fmul_rn(r01, y)), __fmul_rn(r02, d)), t0);
-        const float wy = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(r10, x), __fmul_rn(r11, y)), __fmul_rn(r12, d)), t1);
-        const float wz = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(r20, x), __fmul_rn(r21, y)), __fmul_rn(r22, d)), t2);
+        float wx, wy, wz;
+        sd3d_backproject(cam, vi, ui, d, wx, wy, wz);                                  // step 5: backproject.h, shared with fuse_views.hip
         if (!(fabsf(wx) < lim && fabsf(wy) < lim && fabsf(wz) < lim)) return;          // NaN and infinities stop here
         sx += (long long)rintf(wx * fixed);
         sy += (long long)rintf(wy * fixed);

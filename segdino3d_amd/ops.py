@@ -2612,3 +2612,101 @@ def graph_superpoints(points, normals, ea, eb, vertex_offsets, edge_offsets, ori
                                           *((_ptr(t) if t.numel() else None for t in extra) if debug else (None, None)),
                                           ws.data_ptr(), ws.numel(), _stream()), who)
     return (labels, info) + tuple(extra)
+
+
+# --------------------------------------------------------------------------------------------
+# fusion of posed RGB-D frames into a point cloud (csrc/fuse_views.hip; the rule: include/segdino3d_hip.h, segdino3d_amd/fuse_views.py)
+# --------------------------------------------------------------------------------------------
+FUSE_MIN_CAPACITY = 16
+FUSE_MAX_CAPACITY = 1 << 24
+FUSE_MAX_DIM = 16384
+FUSE_INFO = ("n", "cells", "pixels_used", "out_of_range", "overflow")
+
+
+def fuse_workspace(capacity: int, device):
+    """The caller-owned state of one fusion: an emptied table of `capacity` slots (a power of two) with zeroed counters, as a uint8
+    device tensor (`sd3d_fuse_ws_bytes`, `sd3d_fuse_reset`).  Enqueues only."""
+    lib = _lib.load()
+    if int(capacity) != capacity or not FUSE_MIN_CAPACITY <= capacity <= FUSE_MAX_CAPACITY or capacity & (capacity - 1):
+        raise ValueError(f"fuse_workspace: capacity must be a power of two in [{FUSE_MIN_CAPACITY}, 2^24], got {capacity}")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"fuse_workspace: expected the HIP device, got {device} (no CPU fallback)")
+    ws = torch.empty(lib.sd3d_fuse_ws_bytes(int(capacity)), dtype=torch.uint8, device=device)
+    fuse_reset(ws, capacity)
+    return ws
+
+
+def fuse_reset(ws, capacity: int):
+    """Empties the table and zeroes the counters (`sd3d_fuse_reset`).  Enqueues only."""
+    lib = _lib.load()
+    _lib.check(lib.sd3d_fuse_reset(_ptr(ws, torch.uint8, "fuse_reset: ws"), ws.numel(), int(capacity), _stream()), "fuse_reset")
+
+
+def fuse_accumulate(depth, depth_scale, intrinsics, cam_to_world, colors, ws, capacity: int, inv_voxel: float, stride=1, near=0.1, far=6.0,
+                    edge_abs=0.02, edge_rel=0.02):
+    """Steps 1 to 6 of the fusion rule for V views into the table of `ws` (`sd3d_fuse_accumulate`): depth uint16 [V, Hd, Wd] with
+    `depth_scale` or fp32 metres, intrinsics fp32 [V, 4], cam_to_world fp32 [V, 3, 4], colors uint8 [V, Hc, Wc, 3]; `inv_voxel` is
+    rounded to fp32 here; `edge_rel=None` turns the edge test off.  Enqueues only."""
+    lib = _lib.load()
+    who = "fuse_accumulate"
+    if depth.dim() != 3:
+        raise ValueError(f"{who}: depth must be [V, Hd, Wd], got {list(depth.shape)}")
+    V, Hd, Wd = depth.shape
+    if not (1 <= Hd <= FUSE_MAX_DIM and 1 <= Wd <= FUSE_MAX_DIM):
+        raise ValueError(f"{who}: depth images must be 1 .. {FUSE_MAX_DIM} a side, got {Hd} x {Wd}")
+    if depth.dtype == torch.uint16:
+        if depth_scale is None or not float(depth_scale) > 0.0:
+            raise ValueError(f"{who}: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
+        u16, scale = 1, float(depth_scale)
+    elif depth.dtype == torch.float32:
+        if depth_scale is not None:
+            raise ValueError(f"{who}: fp32 depth is in metres and takes no depth_scale")
+        u16, scale = 0, 1.0
+    else:
+        raise TypeError(f"{who}: depth must be uint16 or fp32, got {depth.dtype}")
+    _want_shape(intrinsics, [(V, 4)], f"{who}: intrinsics")
+    _want_shape(cam_to_world, [(V, 3, 4)], f"{who}: cam_to_world")
+    if colors.dtype != torch.uint8:
+        raise TypeError(f"{who}: colors must be uint8, got {colors.dtype}")
+    if colors.dim() != 4 or colors.shape[0] != V or colors.shape[3] != 3 or not (1 <= colors.shape[1] <= FUSE_MAX_DIM and
+                                                                                  1 <= colors.shape[2] <= FUSE_MAX_DIM):
+        raise ValueError(f"{who}: colors must be [V = {V}, Hc, Wc, 3] with 1 .. {FUSE_MAX_DIM} a side, got {list(colors.shape)}")
+    Hc, Wc = colors.shape[1:3]
+    if int(stride) != stride or not 1 <= stride <= FUSE_MAX_DIM:
+        raise ValueError(f"{who}: stride must be an integer in [1, {FUSE_MAX_DIM}], got {stride}")
+    if not (float(near) >= 0.0 and float(far) >= float(near)):
+        raise ValueError(f"{who}: need 0 <= near <= far, got near = {near}, far = {far}")
+    use_edges = edge_rel is not None
+    if use_edges and not (float(edge_abs) >= 0.0 and float(edge_rel) >= 0.0):
+        raise ValueError(f"{who}: edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {edge_abs}, {edge_rel}")
+    inv32 = float(np.float32(inv_voxel))
+    if not (inv32 > 0.0 and np.isfinite(inv32)):
+        raise ValueError(f"{who}: inv_voxel must be positive and finite in fp32, got {inv_voxel}")
+    dp, ip = _ptr(depth, None, f"{who}: depth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
+    cp, kp = _ptr(cam_to_world, torch.float32, f"{who}: cam_to_world"), _ptr(colors, torch.uint8, f"{who}: colors")
+    wp = _ptr(ws, torch.uint8, f"{who}: ws")
+    if V == 0:
+        return
+    _lib.check(lib.sd3d_fuse_accumulate(dp, u16, scale, ip, cp, kp, V, Hd, Wd, Hc, Wc, int(stride), float(near), float(far),
+                                        float(edge_abs) if use_edges else 0.0, float(edge_rel) if use_edges else 0.0, int(use_edges), inv32,
+                                        wp, ws.numel(), int(capacity), _stream()), who)
+
+
+def fuse_emit(ws, capacity: int, min_obs: int, out_cap: int, want_keys: bool = False):
+    """Step 7 (`sd3d_fuse_emit`) -> (points fp32 [out_cap, 6], obs int32 [out_cap], keys int64 [out_cap] or None, info int64 [5] =
+    FUSE_INFO on the device): the first min(info[0], out_cap) rows are written, in ascending key order.  Enqueues only."""
+    lib = _lib.load()
+    if int(min_obs) != min_obs or not 1 <= min_obs <= 0x7FFFFFFF:
+        raise ValueError(f"fuse_emit: min_obs must be an integer >= 1, got {min_obs}")
+    out_cap = int(out_cap)
+    if out_cap < 0:
+        raise ValueError(f"fuse_emit: out_cap >= 0, got {out_cap}")
+    dev = ws.device
+    points = torch.empty(out_cap, 6, dtype=torch.float32, device=dev)
+    obs = torch.empty(out_cap, dtype=torch.int32, device=dev)
+    keys = torch.empty(out_cap, dtype=torch.int64, device=dev) if want_keys else None
+    info = torch.empty(len(FUSE_INFO), dtype=torch.int64, device=dev)
+    _lib.check(lib.sd3d_fuse_emit(_ptr(ws, torch.uint8, "fuse_emit: ws"), ws.numel(), int(capacity), int(min_obs),
+                                  _ptr(points) if out_cap else None, _ptr(obs) if out_cap else None,
+                                  _ptr(keys) if want_keys and out_cap else None, out_cap, _ptr(info), _stream()), "fuse_emit")
+    return points, obs, keys, info
