@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 19
+#define SD3D_ABI_VERSION 20
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1316,6 +1316,52 @@ int sd3d_fuse_accumulate(const void* depth, int depth_u16, float depth_scale, co
                          float edge_rel, int use_edges, float inv_voxel, void* ws, size_t ws_bytes, int64_t capacity, void* stream);
 int sd3d_fuse_emit(void* ws, size_t ws_bytes, int64_t capacity, int min_obs, float* points, int32_t* obs, int64_t* keys_out,
                    int64_t out_cap, int64_t* info, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Nearest point (csrc/transfer.hip): carrying what a forward computed per point onto other points and onto the depth frames.  The
+ * results of a forward are indexed by the points it ran on; a labelling tool, a robot or an evaluation needs them on the pixels of
+ * the frames, on a mesh's vertices or on another cloud.  The reference has no counterpart (it evaluates on the points it loaded);
+ * tests/transfer_ref.py restates the rule below in numpy and the kernels EQUAL it, bit for bit.  The calls only enqueue work.  The
+ * answer is a minimum over a set, so it is a pure function of the source cloud and the query: the same bits however the views are
+ * cut into calls and on whatever stream.  No float atomics.
+ *
+ *   Source cloud P float [N, 3], N < 2^31; radius 0 < r <= 4 (the limits of sd3d_knn_graph); r2 = (float)(r r).
+ *   1. Valid points.  A source point or a query is valid iff all three coordinates satisfy |c| < 2^14, compared as floats: a NaN or
+ *      an infinity fails.  An invalid query answers -1; an invalid source point is never a candidate.
+ *   2. Distance.  For query q and valid source j: dx = P[j].x - q.x (dy, dz alike), d2 = (dx dx + dy dy) + dz dz, every operation
+ *      rounded on its own in fp32, no fused multiply-add; j is a candidate iff d2 <= r2.
+ *   3. Answer.  The candidate with the smallest key (bits of d2 << 32) | j: the nearest, ties to the lower index.  idx int32 (-1 when
+ *      there is no candidate) and d2 float (+inf when there is none).
+ *   4. Pixel queries.  Pixel (vi, ui) of view v: d by step 2 of the fusion rule ((float)raw * depth_scale; valid iff d > 0, d >= near,
+ *      d <= far); no edge test and no stride; w = the back-projection of csrc/backproject.h, every operation rounded on its own; w is
+ *      then a query as in steps 1 to 3.  A pixel whose depth is invalid answers -1.
+ *   5. Labels.  labels int32 [L, N], 0 <= L <= SD3D_NEAREST_MAX_LABELS: labels_out[l, query] = labels[l, idx], or `fill` where idx < 0,
+ *      written by the kernel that found idx.
+ *   6. Instance map.  masks uint8 [I, N] (non-zero = set), scores float [I]: map[n] = the i with masks[i, n] set and
+ *      scores[i] >= score_thr that has the largest score, compared in fp32; ties go to the lower i; a NaN score never wins;
+ *      map[n] = -1 if there is none.
+ *
+ *   sd3d_point_index_build: the hashed grid of sd3d_knn_graph over P (one definition: csrc/point_grid.h) into a caller-owned workspace
+ *     of sd3d_point_index_ws_bytes(N) bytes (0 for a bad N), 256-byte aligned.  Built once per cloud and radius; the queries only read
+ *     it and must be given the same n_points and radius.  The grid chooses the pairs that are evaluated and cannot change the answer
+ *     (the argument: csrc/transfer.hip).
+ *   sd3d_nearest_points: queries float [M, 3], M < 2^31.  idx_out int32 [M], d2_out float [M], labels_out int32 [L, M]: each optional
+ *     (labels_out is required when n_labels > 0).
+ *   sd3d_nearest_pixels: depth [V, Hd, Wd], uint16 times depth_scale (depth_u16 != 0) or float metres; intrinsics float [V, 4];
+ *     cam_to_world float [V, 12]; images up to 16384 a side; one launch over the V views, at most 2^31 - 1 tiles of 8 x 32 pixels.
+ *     idx_out int32 [V, Hd, Wd], d2_out float [V, Hd, Wd], labels_out int32 [L, V, Hd, Wd], indexed in 64 bits.
+ *   sd3d_instance_map: map int32 [N].
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_NEAREST_MAX_LABELS 8
+size_t sd3d_point_index_ws_bytes(int64_t n_points);
+int sd3d_point_index_build(const float* points, int64_t n_points, float radius, void* ws, size_t ws_bytes, void* stream);
+int sd3d_nearest_points(const float* queries, int64_t n_queries, const void* index_ws, size_t ws_bytes, int64_t n_points, float radius,
+                        const int32_t* labels, int n_labels, int fill, int32_t* idx_out, float* d2_out, int32_t* labels_out, void* stream);
+int sd3d_nearest_pixels(const void* depth, int depth_u16, float depth_scale, const float* intrinsics, const float* cam_to_world, int V,
+                        int Hd, int Wd, float near, float far, const void* index_ws, size_t ws_bytes, int64_t n_points, float radius,
+                        const int32_t* labels, int n_labels, int fill, int32_t* idx_out, float* d2_out, int32_t* labels_out, void* stream);
+int sd3d_instance_map(const void* masks, const float* scores, int n_instances, int64_t n_points, float score_thr, int32_t* map,
+                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@
 
 // Written with the operators: the header's __fmul_rn / __fadd_rn may fuse once inlined under the default contraction mode.
 #pragma clang fp contract(off)
+#include "point_grid.h"                                 // the grid sd3d_knn_graph searches, shared with transfer.hip
 
 #define SP_BATCH 512                                    // edges per sweep batch = lanes of the sweep workgroup
 #define SP_TABLE 2048                                   // hash slots: at most 2 SP_BATCH distinct start-roots, load <= 1 / 2
@@ -79,15 +80,6 @@ static SpWs sp_ws(void* ws, int64_t N, int64_t E, int S, bool mesh) {
 }
 
 // ---------------------------------------------------------------------------------------------- scenes, faces
-// the scene of element i < off[S]: the last s with off[s] <= i (off ascends from 0; empty scenes repeat a value)
-__device__ __forceinline__ int sp_scene_of(const int64_t* __restrict__ off, int S, int64_t i) {
-    int lo = 0, hi = S - 1;                                                           // at most 17 rounds
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 __device__ __forceinline__ int64_t sp_clamp(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // the global vertex indices of face f -> whether all three lie in the face's scene (offsets that do not fit the arrays are clamped)
@@ -650,81 +642,23 @@ extern "C" int sd3d_graph_superpoints(const float* points, const float* normals,
 // they are evaluated like any other and refused by d2 or by their scene.  Two of the 27 cells may share a bucket: a repeated bucket
 // is dropped before the walk, and every point lies in exactly one bucket, so no candidate is visited twice.
 //
+// The cell, the bucket, the workspace and the two kernels that build the index stand in point_grid.h, which transfer.hip shares:
 //   knn_key_kernel      one thread per point: its bucket as the sort key; an invalid point gets the key B and sorts behind all others.
 //   knn_gather_kernel   sort_pairs_u64 with "value = original index", then per sorted position (x, y, z, index) side by side and the
 //                       first / one-past-last position of every bucket (zeroed before: an empty bucket is [0, 0)).
-//   knn_search_kernel   one wave per point, in bucket order, so that the waves of a workgroup read the same buckets.  Lanes 0 .. 26 look up
+// Here:
+//   knn_search_kernel  one wave per point, in bucket order, so that the waves of a workgroup read the same buckets.  Lanes 0 .. 26 look up
 //                       the 27 buckets; the wave walks their concatenated ranges 64 points at a time, one distance per lane; lane l
 //                       keeps entry l of the sorted list of the best keys (k <= 64 = the lanes of a wave: no LDS table), and a candidate
 //                       below the k-th key is inserted by one ballot and one shift.  Trip counts: ceil(T / 64) walks for the T points
 //                       of the searched buckets, at most 64 insertions per walk, 5 rounds per range lookup, 17 per scene lookup.
-#define KNN_BIAS (1 << 24)
 #define KNN_WAVES 4                                     // waves = points per workgroup
 
-struct KnnWs {
-    uint64_t *keys_a, *keys_b;                          // [N]
-    uint32_t *vals_a, *vals_b;                          // [N]
-    float4* sorted;                                     // [N]
-    int32_t *cell_lo, *cell_hi;                         // [B]
-    void* sort_ws;
-    size_t sort_bytes, total_bytes;
-};
-static int knn_bucket_bits(int64_t N) {
-    int bits = 10;
-    while (bits < 26 && (1ll << bits) < 2 * N) ++bits;
-    return bits;
-}
-static KnnWs knn_ws(void* ws, int64_t N) {
-    KnnWs w;
-    char* p = (char*)ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* q = p + o; o += align_up(bytes, 256); return (void*)q; };
-    const size_t n = (size_t)(N > 0 ? N : 1), b = (size_t)1 << knn_bucket_bits(N);
-    w.keys_a = (uint64_t*)take(n * 8); w.keys_b = (uint64_t*)take(n * 8);
-    w.vals_a = (uint32_t*)take(n * 4); w.vals_b = (uint32_t*)take(n * 4);
-    w.sorted = (float4*)take(n * 16);
-    w.cell_lo = (int32_t*)take(b * 4); w.cell_hi = (int32_t*)take(b * 4);
-    w.sort_bytes = sort_ws_bytes((int64_t)n); w.sort_ws = take(w.sort_bytes);
-    w.total_bytes = o;
-    return w;
-}
-
-__device__ __forceinline__ bool knn_valid(float x, float y, float z) {
-    return fabsf(x) < 16384.0f && fabsf(y) < 16384.0f && fabsf(z) < 16384.0f;         // a NaN or an infinity is not
-}
-__device__ __forceinline__ int knn_cell(float c, int H) { return ((int)rintf(c * 1024.0f) + KNN_BIAS) / H; }     // 0 <= q + 2^24 <= 2^25
-__device__ __forceinline__ uint32_t knn_bucket(int cx, int cy, int cz, int s, int bucket_bits) {
-    const uint32_t h = hash_u64(((uint64_t)(uint32_t)cx << 32) | (uint32_t)cy);
-    return hash_u64(((uint64_t)h << 32) ^ ((uint64_t)(uint32_t)s << 40) ^ (uint32_t)cz) & ((1u << bucket_bits) - 1u);
-}
 __device__ __forceinline__ uint64_t knn_shfl(uint64_t v, int src) {
     return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src);
 }
 __device__ __forceinline__ uint64_t knn_shfl_up1(uint64_t v) {
     return ((uint64_t)(uint32_t)__shfl_up((int)(v >> 32), 1) << 32) | (uint32_t)__shfl_up((int)(uint32_t)v, 1);
-}
-
-__global__ __launch_bounds__(256) void knn_key_kernel(const float* __restrict__ pts, const int64_t* __restrict__ voff, int S, int64_t N, int H,
-                                                      int bucket_bits, uint64_t* __restrict__ keys) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const float x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
-    uint64_t key = 1ull << bucket_bits;
-    if (knn_valid(x, y, z)) key = knn_bucket(knn_cell(x, H), knn_cell(y, H), knn_cell(z, H), sp_scene_of(voff, S, i), bucket_bits);
-    keys[i] = key;
-}
-
-__global__ __launch_bounds__(256) void knn_gather_kernel(const float* __restrict__ pts, const uint64_t* __restrict__ keys,
-                                                         const uint32_t* __restrict__ idx, int64_t N, int bucket_bits,
-                                                         float4* __restrict__ sorted, int32_t* __restrict__ cell_lo, int32_t* __restrict__ cell_hi) {
-    const int64_t pos = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (pos >= N) return;
-    const int64_t i = (int64_t)idx[pos];
-    sorted[pos] = make_float4(pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2], __uint_as_float((uint32_t)i));
-    const uint64_t key = keys[pos];
-    if (key >> bucket_bits) return;                                                   // an invalid point: in no bucket
-    if (pos == 0 || keys[pos - 1] != key) cell_lo[key] = (int32_t)pos;
-    if (pos == N - 1 || keys[pos + 1] != key) cell_hi[key] = (int32_t)(pos + 1);
 }
 
 __global__ __launch_bounds__(64 * KNN_WAVES) void knn_search_kernel(const float4* __restrict__ sorted, const uint64_t* __restrict__ keys,
@@ -814,17 +748,10 @@ extern "C" int sd3d_knn_graph(const float* points, const int64_t* vertex_offsets
     if (ws_bytes < w.total_bytes) return sd3d_set_error(SD3D_ERR_WS, "knn_graph: workspace too small");
     if (N == 0) return SD3D_OK;
     const float r2 = radius * radius;
-    const int H = (int)ceilf(radius * 1024.0f) + 2;                                   // radius 2^10 is exact; 3 <= H <= 4098
+    const int H = knn_cell_units(radius);
     const int bucket_bits = knn_bucket_bits(N);
-    const dim3 b256(256), gv((unsigned)cdiv(N, 256));
-    if (hipMemsetAsync(w.cell_lo, 0, (size_t)4 << bucket_bits, st) != hipSuccess || hipMemsetAsync(w.cell_hi, 0, (size_t)4 << bucket_bits, st) != hipSuccess)
-        return sd3d_set_error(SD3D_ERR_LAUNCH, "knn_graph: memset");
-    hipLaunchKernelGGL(knn_key_kernel, gv, b256, 0, st, points, vertex_offsets, S, N, H, bucket_bits, w.keys_a);
-    int landed = 0;
-    if (int rc = sort_pairs_u64(w.keys_a, nullptr, w.keys_b, w.vals_b, N, 0, bucket_bits + 1, w.sort_ws, w.sort_bytes, st, w.vals_a, &landed)) return rc;
-    const uint64_t* keys = landed ? w.keys_a : w.keys_b;
-    const uint32_t* idx = landed ? w.vals_a : w.vals_b;
-    hipLaunchKernelGGL(knn_gather_kernel, gv, b256, 0, st, points, keys, idx, N, bucket_bits, w.sorted, w.cell_lo, w.cell_hi);
+    const uint64_t* keys = nullptr;
+    if (int rc = knn_build_index(points, vertex_offsets, S, N, H, bucket_bits, w, st, &keys)) return rc;
     hipLaunchKernelGGL(knn_search_kernel, dim3((unsigned)cdiv(N, KNN_WAVES)), dim3(64 * KNN_WAVES), 0, st, w.sorted, keys, w.cell_lo, w.cell_hi,
                        vertex_offsets, S, N, H, bucket_bits, k, r2, nbr, d2_out);
     SD3D_CHECK_LAUNCH();

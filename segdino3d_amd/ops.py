@@ -2710,3 +2710,128 @@ def fuse_emit(ws, capacity: int, min_obs: int, out_cap: int, want_keys: bool = F
                                   _ptr(points) if out_cap else None, _ptr(obs) if out_cap else None,
                                   _ptr(keys) if want_keys and out_cap else None, out_cap, _ptr(info), _stream()), "fuse_emit")
     return points, obs, keys, info
+
+
+# --------------------------------------------------------------------------------------------
+# nearest point: results of a forward carried onto other points and onto frames (csrc/transfer.hip; the rule: include/segdino3d_hip.h,
+# segdino3d_amd/transfer.py)
+# --------------------------------------------------------------------------------------------
+NEAREST_MAX_LABELS = 8
+
+
+def _nearest_radius(radius, who):
+    if not (np.isfinite(radius) and 0 < radius <= KNN_MAX_RADIUS):
+        raise ValueError(f"{who}: radius must lie in (0, {KNN_MAX_RADIUS}], got {radius}")
+    return float(radius)
+
+
+def point_index_build(points, radius: float):
+    """The grid of `knn_graph` over one cloud (`sd3d_point_index_build`): points fp32 [N, 3] -> the caller-owned index, a uint8 device
+    tensor that `nearest_points` / `nearest_pixels` read with the same `N` and `radius`.  Enqueues only."""
+    lib = _lib.load()
+    who = "point_index_build"
+    radius = _nearest_radius(radius, who)
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError(f"{who}: points must be fp32 [N, 3], got {points.dtype} {list(points.shape)}")
+    N = points.shape[0]
+    if N >= 1 << 31:
+        raise ValueError(f"{who}: need N < 2^31, got {N}")
+    pp = _ptr(points, torch.float32, f"{who}: points")
+    ws = torch.empty(lib.sd3d_point_index_ws_bytes(N), dtype=torch.uint8, device=points.device)
+    _lib.check(lib.sd3d_point_index_build(pp if N else None, N, radius, ws.data_ptr(), ws.numel(), _stream()), who)
+    return ws
+
+
+def _nearest_outputs(shape, N, labels, fill, return_index, return_d2, dev, who):
+    """-> (L, labels pointer, fill, idx, d2, out): the optional outputs of one query call over `shape` queries."""
+    L = 0
+    if labels is not None:
+        if labels.dim() != 2 or labels.shape[1] != N or not 1 <= labels.shape[0] <= NEAREST_MAX_LABELS:
+            raise ValueError(f"{who}: labels must be int32 [L, N = {N}] with 1 <= L <= {NEAREST_MAX_LABELS}, got {list(labels.shape)}")
+        L = labels.shape[0]
+    if int(fill) != fill or not -(1 << 31) <= fill < 1 << 31:
+        raise ValueError(f"{who}: fill must be an int32, got {fill}")
+    lp = _ptr(labels, torch.int32, f"{who}: labels") if L else None
+    idx = torch.empty(shape, dtype=torch.int32, device=dev) if return_index else None
+    d2 = torch.empty(shape, dtype=torch.float32, device=dev) if return_d2 else None
+    out = torch.empty((L,) + tuple(shape), dtype=torch.int32, device=dev) if L else None
+    return L, lp, int(fill), idx, d2, out
+
+
+def nearest_points(queries, index, n_points: int, radius: float, labels=None, fill: int = -1, return_index: bool = True,
+                   return_d2: bool = False):
+    """The nearest source point within `radius` of each query (`sd3d_nearest_points`): queries fp32 [M, 3], `index` from
+    `point_index_build`, labels int32 [L, N] or None -> (idx int32 [M] or None, d2 fp32 [M] or None, out int32 [L, M] or None).
+    Enqueues only."""
+    lib = _lib.load()
+    who = "nearest_points"
+    radius = _nearest_radius(radius, who)
+    if queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
+        raise ValueError(f"{who}: queries must be fp32 [M, 3], got {queries.dtype} {list(queries.shape)}")
+    M, N = queries.shape[0], int(n_points)
+    if M >= 1 << 31:
+        raise ValueError(f"{who}: need M < 2^31, got {M}")
+    qp, wp = _ptr(queries, torch.float32, f"{who}: queries"), _ptr(index, torch.uint8, f"{who}: index")
+    L, lp, fill, idx, d2, out = _nearest_outputs((M,), N, labels, fill, return_index, return_d2, queries.device, who)
+    if M:
+        _lib.check(lib.sd3d_nearest_points(qp, M, wp, index.numel(), N, radius, lp if N else None, L, fill, _ptr(idx), _ptr(d2), _ptr(out),
+                                           _stream()), who)
+    return idx, d2, out
+
+
+def nearest_pixels(depth, depth_scale, intrinsics, cam_to_world, index, n_points: int, radius: float, labels=None, fill: int = -1,
+                   return_index: bool = True, return_d2: bool = False, near=0.1, far=6.0):
+    """The nearest source point within `radius` of each back-projected depth pixel (`sd3d_nearest_pixels`): depth uint16 [V, Hd, Wd] with
+    `depth_scale` or fp32 metres, intrinsics fp32 [V, 4], cam_to_world fp32 [V, 3, 4] -> (idx int32 [V, Hd, Wd] or None, d2 fp32
+    [V, Hd, Wd] or None, out int32 [L, V, Hd, Wd] or None).  One launch; enqueues only."""
+    lib = _lib.load()
+    who = "nearest_pixels"
+    radius = _nearest_radius(radius, who)
+    if depth.dim() != 3:
+        raise ValueError(f"{who}: depth must be [V, Hd, Wd], got {list(depth.shape)}")
+    V, Hd, Wd = depth.shape
+    if not (1 <= Hd <= FUSE_MAX_DIM and 1 <= Wd <= FUSE_MAX_DIM):
+        raise ValueError(f"{who}: depth images must be 1 .. {FUSE_MAX_DIM} a side, got {Hd} x {Wd}")
+    if depth.dtype == torch.uint16:
+        if depth_scale is None or not float(depth_scale) > 0.0:
+            raise ValueError(f"{who}: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
+        u16, scale = 1, float(depth_scale)
+    elif depth.dtype == torch.float32:
+        if depth_scale is not None:
+            raise ValueError(f"{who}: fp32 depth is in metres and takes no depth_scale")
+        u16, scale = 0, 1.0
+    else:
+        raise TypeError(f"{who}: depth must be uint16 or fp32, got {depth.dtype}")
+    _want_shape(intrinsics, [(V, 4)], f"{who}: intrinsics")
+    _want_shape(cam_to_world, [(V, 3, 4)], f"{who}: cam_to_world")
+    if not (float(near) >= 0.0 and float(far) >= float(near)):
+        raise ValueError(f"{who}: need 0 <= near <= far, got near = {near}, far = {far}")
+    N = int(n_points)
+    dp, ip = _ptr(depth, None, f"{who}: depth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
+    cp, wp = _ptr(cam_to_world, torch.float32, f"{who}: cam_to_world"), _ptr(index, torch.uint8, f"{who}: index")
+    L, lp, fill, idx, d2, out = _nearest_outputs((V, Hd, Wd), N, labels, fill, return_index, return_d2, depth.device, who)
+    if V:
+        _lib.check(lib.sd3d_nearest_pixels(dp, u16, scale, ip, cp, V, Hd, Wd, float(near), float(far), wp, index.numel(), N, radius,
+                                           lp if N else None, L, fill, _ptr(idx), _ptr(d2), _ptr(out), _stream()), who)
+    return idx, d2, out
+
+
+def instance_map(masks, scores, score_thr: float = 0.0):
+    """Overlapping instance masks as one map (`sd3d_instance_map`): masks bool / uint8 [I, N], scores fp32 [I] -> int32 [N], per point
+    the instance of the largest score >= `score_thr` whose mask holds it (ties: the lower index), -1 if none.  Enqueues only."""
+    lib = _lib.load()
+    who = "instance_map"
+    if masks.dim() != 2 or masks.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{who}: masks must be bool or uint8 [I, N], got {masks.dtype} {list(masks.shape)}")
+    I, N = masks.shape
+    if scores.dtype != torch.float32 or tuple(scores.shape) != (I,):
+        raise TypeError(f"{who}: scores must be fp32 [I = {I}], got {scores.dtype} {list(scores.shape)}")
+    if score_thr != score_thr:
+        raise ValueError(f"{who}: score_thr must not be a NaN")
+    if N >= 1 << 31:
+        raise ValueError(f"{who}: need N < 2^31, got {N}")
+    mp, sp = _ptr(masks, None, f"{who}: masks"), _ptr(scores, torch.float32, f"{who}: scores")
+    out = torch.empty(N, dtype=torch.int32, device=masks.device)
+    if N:
+        _lib.check(lib.sd3d_instance_map(mp if I else None, sp if I else None, I, N, float(score_thr), _ptr(out), _stream()), who)
+    return out
