@@ -674,7 +674,7 @@ int sd3d_linear_wgrad(const float* g, int ld_g, const float* x, int ld_x, int64_
  *   sd3d_bn_apply:         y = act((x - mean) * rstd * gamma + beta + res)            (res nullable)
  *   sd3d_bn_backward:      g = dy masked by y > 0 when act == relu; dbeta = sum g; dgamma = sum g * xhat;
  *                          dx = gamma * rstd * (g - dbeta / M - xhat * dgamma / M); dres = g (nullable)
- * Reductions run in a fixed order (bit-reproducible).  ws: sd3d_bn_ws_bytes(M, C). */
+ * Reductions run in a fixed order (bit-reproducible) and in double.  ws: sd3d_bn_ws_bytes(M, C), aligned to 8 bytes. */
 size_t sd3d_bn_ws_bytes(int64_t M, int C);
 /* sd3d_bn_stats_running also advances nn.BatchNorm1d's buffers in place (any of the three may be NULL: then it only computes
  * the statistics): running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with the UNBIASED batch variance

@@ -2,8 +2,11 @@
 // residual add and ReLU folded in (ME.MinkowskiBatchNorm = nn.BatchNorm1d over the voxel rows, minkunet.py:302-304;
 // BasicBlock :234-250), and the backward of the fused devoxelise + superpoint mean (minkunet.py:668-676).
 // All of it is streaming work over [M, C] row-major fp32 tensors: HBM-bound, float4 accesses, one pass per tensor.
-// Column reductions are two-level with a fixed order (per-block partial sums, then one block adds the partials in
-// double precision), so statistics and gradients are reproducible bit for bit.
+// Column reductions are two-level with a fixed order (per-block partial sums, then one block adds the partials), so
+// statistics and gradients are reproducible bit for bit.  Every sum is kept in double from the first addend on: the
+// variance comes out as E[d^2] - E[d]^2 with d = x - pivot, which cancels (pivot - mean)^2 / var of the sums' digits -
+// with fp32 sums a first row 8 spreads off the mean cost the variance 3e-5 of its value (a 256-row chain at C = 1024,
+// 256 row lanes at C = 4).  The loads set the pace of these kernels, not the additions.
 #include "common.h"
 #include "../../include/segdino3d_hip.h"
 
@@ -17,27 +20,30 @@ struct ColParams {
     const float* x; int ld_x;          // MODE 1: BatchNorm input
     const float* mean; const float* rstd;
     int64_t M; int C; int act;
-    float* partial;                    // [nblk][2][C]
+    double* partial;                   // [nblk][2][C]
 };
 
 template <int MODE>
 __global__ __launch_bounds__(256) void col_partial_kernel(const ColParams p) {
-    extern __shared__ float sm[];                              // [rpi][2][C]
+    extern __shared__ double sm[];                             // [rpi][2][C]
     const int c4n = p.C >> 2, rpi = 256 / c4n;
     const int tid = threadIdx.x;
     const int col = (tid % c4n) * 4, rl = tid / c4n;
     const int64_t r0 = (int64_t)blockIdx.x * CS_ROWS;
     const int64_t r1 = r0 + CS_ROWS < p.M ? r0 + CS_ROWS : p.M;
-    f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
     if (rl < rpi) {
+        double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
         f32x4 piv = {0.f, 0.f, 0.f, 0.f}, mu = piv, rs = piv;
         if (MODE == 0) piv = *(const f32x4*)(p.a + col);
         else { mu = *(const f32x4*)(p.mean + col); rs = *(const f32x4*)(p.rstd + col); }
         for (int64_t r = r0 + rl; r < r1; r += rpi) {
             const f32x4 v = *(const f32x4*)(p.a + r * p.ld_a + col);
             if (MODE == 0) {
-                const f32x4 d = v - piv;
-                s1 += d; s2 += d * d;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const double d = (double)v[e] - (double)piv[e];
+                    s1[e] += d; s2[e] = fma(d, d, s2[e]);
+                }
             } else {
                 f32x4 g = v;
                 if (p.act == 1) {
@@ -46,25 +52,29 @@ __global__ __launch_bounds__(256) void col_partial_kernel(const ColParams p) {
                     for (int e = 0; e < 4; ++e) g[e] = yy[e] > 0.f ? g[e] : 0.f;
                 }
                 const f32x4 xh = (*(const f32x4*)(p.x + r * p.ld_x + col) - mu) * rs;
-                s1 += g; s2 += g * xh;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { s1[e] += (double)g[e]; s2[e] = fma((double)g[e], (double)xh[e], s2[e]); }
             }
         }
-        *(f32x4*)(sm + (rl * 2 + 0) * p.C + col) = s1;
-        *(f32x4*)(sm + (rl * 2 + 1) * p.C + col) = s2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            sm[(rl * 2 + 0) * p.C + col + e] = s1[e];
+            sm[(rl * 2 + 1) * p.C + col + e] = s2[e];
+        }
     }
     __syncthreads();
     for (int i = tid; i < 2 * p.C; i += 256) {                 // fixed order over the row lanes
-        float a = 0.f;
+        double a = 0.0;
         for (int r = 0; r < rpi; ++r) a += sm[r * 2 * p.C + i];
         p.partial[(int64_t)blockIdx.x * 2 * p.C + i] = a;
     }
 }
 
 // MODE 0 -> mean, biased variance, rstd;  MODE 1 -> dbeta = sum g, dgamma = sum g xhat.
-// One workgroup per 16 columns; the per-block partials of a column are dealt to 16 threads (interleaved), each adds its share
-// in double, and the 16 shares are added in a fixed order - hundreds of partials per column without a serial chain of loads.
+// One workgroup per 16 columns; the per-block partials of a column are dealt to 16 threads (interleaved), each adds its share,
+// and the 16 shares are added in a fixed order - hundreds of partials per column without a serial chain of loads.
 template <int MODE>
-__global__ __launch_bounds__(256) void col_final_kernel(const float* __restrict__ partial, int nblk, int C, int64_t M, float eps,
+__global__ __launch_bounds__(256) void col_final_kernel(const double* __restrict__ partial, int nblk, int C, int64_t M, float eps,
                                                         const float* __restrict__ x_first, float* __restrict__ o0, float* __restrict__ o1,
                                                         float* __restrict__ o2, float* __restrict__ run_mean = nullptr,
                                                         float* __restrict__ run_var = nullptr, long long* __restrict__ n_tracked = nullptr,
@@ -74,7 +84,7 @@ __global__ __launch_bounds__(256) void col_final_kernel(const float* __restrict_
     const int c = blockIdx.x * 16 + cl;
     double a = 0.0, b = 0.0;
     if (c < C)
-        for (int i = part; i < nblk; i += 16) { a += (double)partial[(int64_t)i * 2 * C + c]; b += (double)partial[(int64_t)i * 2 * C + C + c]; }
+        for (int i = part; i < nblk; i += 16) { a += partial[(int64_t)i * 2 * C + c]; b += partial[(int64_t)i * 2 * C + C + c]; }
     sa[part][cl] = a; sb[part][cl] = b;
     __syncthreads();
     if (part != 0 || c >= C) return;
@@ -166,15 +176,16 @@ static int col_blocks(int64_t M) { return (int)cdiv(M, CS_ROWS); }
 #define ST ((hipStream_t)stream)
 extern "C" {
 
-size_t sd3d_bn_ws_bytes(int64_t M, int C) { return align_up((size_t)col_blocks(M) * 2 * C * sizeof(float), 256); }
+size_t sd3d_bn_ws_bytes(int64_t M, int C) { return align_up((size_t)col_blocks(M) * 2 * C * sizeof(double), 256); }
 
 int sd3d_bn_stats_running(const float* x, int ld, int64_t M, int C, float eps, float* mean, float* var, float* rstd, float* running_mean,
                           float* running_var, int64_t* num_batches_tracked, float momentum, void* ws, size_t ws_bytes, void* stream) {
     if (M <= 0 || C <= 0 || (C & 3) || C > 1024 || (ld & 3)) return sd3d_set_error(SD3D_ERR_ARG, "bn_stats: C must be a multiple of 4, <= 1024");
     if (ws_bytes < sd3d_bn_ws_bytes(M, C)) return sd3d_set_error(SD3D_ERR_WS, "bn_stats: workspace too small");
-    ColParams p{}; p.a = x; p.ld_a = ld; p.M = M; p.C = C; p.partial = (float*)ws;
+    if ((uintptr_t)ws & 7) return sd3d_set_error(SD3D_ERR_ARG, "bn_stats: the workspace holds doubles, align it to 8 bytes");
+    ColParams p{}; p.a = x; p.ld_a = ld; p.M = M; p.C = C; p.partial = (double*)ws;
     const int nblk = col_blocks(M), rpi = 256 / (C >> 2);
-    col_partial_kernel<0><<<nblk, 256, (size_t)rpi * 2 * C * sizeof(float), ST>>>(p);
+    col_partial_kernel<0><<<nblk, 256, (size_t)rpi * 2 * C * sizeof(double), ST>>>(p);
     col_final_kernel<0><<<(unsigned)cdiv(C, 16), 256, 0, ST>>>(p.partial, nblk, C, M, eps, x, mean, var, rstd, running_mean, running_var,
                                                                (long long*)num_batches_tracked, momentum);
     SD3D_CHECK_LAUNCH();
@@ -198,10 +209,11 @@ int sd3d_bn_backward(const float* dy, int ld_dy, const float* y, int ld_y, const
         (act == 1 && (!y || (ld_y & 3))))
         return sd3d_set_error(SD3D_ERR_ARG, "bn_backward: bad shape");
     if (ws_bytes < sd3d_bn_ws_bytes(M, C)) return sd3d_set_error(SD3D_ERR_WS, "bn_backward: workspace too small");
+    if ((uintptr_t)ws & 7) return sd3d_set_error(SD3D_ERR_ARG, "bn_backward: the workspace holds doubles, align it to 8 bytes");
     ColParams p{}; p.a = dy; p.ld_a = ld_dy; p.y = y; p.ld_y = ld_y; p.x = x; p.ld_x = ld_x; p.mean = mean; p.rstd = rstd;
-    p.M = M; p.C = C; p.act = act; p.partial = (float*)ws;
+    p.M = M; p.C = C; p.act = act; p.partial = (double*)ws;
     const int nblk = col_blocks(M), rpi = 256 / (C >> 2);
-    col_partial_kernel<1><<<nblk, 256, (size_t)rpi * 2 * C * sizeof(float), ST>>>(p);
+    col_partial_kernel<1><<<nblk, 256, (size_t)rpi * 2 * C * sizeof(double), ST>>>(p);
     col_final_kernel<1><<<(unsigned)cdiv(C, 16), 256, 0, ST>>>(p.partial, nblk, C, M, 0.f, nullptr, dbeta, dgamma, nullptr);
     bn_bwd_apply_kernel<<<(unsigned)cdiv(M * (C >> 2), 256), 256, 0, ST>>>(dy, ld_dy, y, ld_y, x, ld_x, mean, rstd, gamma, dbeta, dgamma, M, C, act,
                                                                           dx, ld_dx, dres, ld_dres);

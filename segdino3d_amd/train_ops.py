@@ -23,8 +23,18 @@ from . import _lib, ops
 _WS = ops._PerThread()
 
 
+def _want_training_lists(pairs: "ops.PairLists", who: str):
+    """The weight gradient walks plain offset-major lists and needs every pair's output row: chained lists carry flag bits in `tile_k`
+    and no [K, M] position table, lean lists no position table either - neither can be served (training builds plain full lists)."""
+    if pairs.center == ops.PAIR_CHAINED:
+        raise ValueError(f"{who}: chained pair lists cannot be used for the weight gradient; build plain lists (center=-1)")
+    if pairs.out_idx is None and (pairs.pos is None or pairs.pos.numel() == 0):
+        raise ValueError(f"{who}: pair lists without a position table (lean lists) have no output rows; build full lists")
+
+
 def pair_out_rows(pairs: "ops.PairLists") -> torch.Tensor:
     """out_idx[p] = output row of pair p (-1 on padding); cached on the lists."""
+    _want_training_lists(pairs, "pair_out_rows")
     if pairs.out_idx is None:
         lib = _lib.load()
         out = torch.empty(pairs.p_cap, dtype=torch.int32, device=pairs.pos.device)
@@ -38,6 +48,7 @@ def pair_wgrad(dy: torch.Tensor, x: torch.Tensor, pairs: "ops.PairLists", dw: to
     """dw[k] (+)= dy[out rows of offset k]^T @ x[in rows of offset k]; dy [M, Cout], x [V_in, Cin] -> dw [K, Cout, Cin].
     bf16_operands: both operands rounded to bf16 before the (fp32-accumulated) product.
     bias (K = 1, a Linear): returns (dw, db) with db [Cout] = column sums of dy, out of the same launch (SD3D_WGRAD_BIAS)."""
+    _want_training_lists(pairs, "pair_wgrad")
     lib = _lib.load()
     pdy, ldy = ops._rows(dy, "dy")
     px, ldx = ops._rows(x, "x")
@@ -67,6 +78,7 @@ def pair_wgrad(dy: torch.Tensor, x: torch.Tensor, pairs: "ops.PairLists", dw: to
 def pair_wgrad_native(dy: torch.Tensor, x: torch.Tensor, pairs: "ops.PairLists") -> torch.Tensor:
     """The weight gradient in the PARAMETER's layout [K, Cin, Cout] (`ME.MinkowskiConvolution.kernel`): the same kernel with the two
     operands - and their index lists - exchanged (dW^T[k][ci][co] = sum_p x[in(p)][ci] dy[out(p)][co]); no transposed copy afterwards."""
+    _want_training_lists(pairs, "pair_wgrad_native")
     lib = _lib.load()
     pdy, ldy = ops._rows(dy, "dy")
     px, ldx = ops._rows(x, "x")
