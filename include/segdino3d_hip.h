@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 20
+#define SD3D_ABI_VERSION 21
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1316,6 +1316,73 @@ int sd3d_fuse_accumulate(const void* depth, int depth_u16, float depth_scale, co
                          float edge_rel, int use_edges, float inv_voxel, void* ws, size_t ws_bytes, int64_t capacity, void* stream);
 int sd3d_fuse_emit(void* ws, size_t ws_bytes, int64_t capacity, int min_obs, float* points, int32_t* obs, int64_t* keys_out,
                    int64_t out_cap, int64_t* info, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * TSDF fusion of posed RGB-D frames and a surface-net mesh (csrc/tsdf.hip): the producer of a mesh - vertices [V, 6] in the layout of
+ * `points`, faces [F, 3] - for sd3d_mesh_superpoints, the superpoint rule the network saw in training.  The reference has no
+ * counterpart (it reads meshes made offline); tests/tsdf_ref.py restates the rule below in numpy and the kernels EQUAL it, bit for
+ * bit.  The per-voxel state is integer sums and a view contributes to a voxel only through a block it touched, so the volume and the
+ * mesh are a function of the SET of views: the bits do not depend on how the views are cut into calls, on their order, or on the
+ * stream.  Every decision is an integer one or a single rounded fp32 operation (no fused multiply-add).
+ *
+ *   1. Valid pixel.  Steps 1 to 3 of the fusion above with stride 1: d = (float)raw * depth_scale; valid iff d > 0, near <= d <= far
+ *      and no 4-neighbour inside the image is a jump (!(dn > 0) or |dn - d| > edge_abs + edge_rel * d); colour pixel
+ *      ((2 vi + 1) Hc) / (2 Hd), ((2 ui + 1) Wc) / (2 Wd).
+ *   2. Touched blocks.  For a valid pixel and j = -2 .. 2: d_j = d + (float)j * half_step (one rounded add), w = the back-projection
+ *      of (vi, ui, d_j) by csrc/backproject.h; unless |w_i| < 2^SD3D_FUSE_WORLD_BITS and c_i = floorf(w_i * inv_voxel) lies in
+ *      [-2^20, 2^20) on all axes (as floats) the sample is counted in out_of_range; else the view TOUCHES block b_i = c_i >> 3
+ *      (arithmetic), key = ((b_x + 2^17) << 36) | ((b_y + 2^17) << 18) | (b_z + 2^17).  A block that finds no slot within
+ *      SD3D_TSDF_PROBE_LIMIT slots counts into overflow (once per image tile that holds it).
+ *   3. Integration, per (view, touched block) and per voxel c of the block: p_i = ((float)c_i + 0.5f) * voxel; camera point
+ *      ((r0 p_x + r1 p_y) + r2 p_z) + t per row of world_to_cam; z > 0; uf = floorf(((fx * x) / z + cx) + 0.5f), vf likewise;
+ *      0 <= uf < Wd and 0 <= vf < Hd as floats; the pixel is valid by step 1 with depth d; sdf = d - z; skipped if sdf < -trunc;
+ *      q = (int)rintf(fminf(sdf, trunc) * qscale); W += 1, T += q, C_j += colour byte j - 32-bit integers, |q| <= 4097, so up to
+ *      SD3D_TSDF_MAX_VIEWS views of one volume keep |T| < 2^30.
+ *   4. A voxel is observed iff W >= min_weight, inside iff T < 0.
+ *   5. Vertices.  Cell c (corner voxels c + {0,1}^3) is active iff its eight corners are observed and not all of one sign.  Its 12
+ *      edges in the order x-edges (y, z) = (0,0) (0,1) (1,0) (1,1), y-edges (x, z) likewise, z-edges (x, y) likewise, each from its
+ *      lower end a to its upper end b; an edge whose ends differ in sign crosses at s = f_a / (f_a - f_b), f = (float)((double)T /
+ *      (double)W).  m = the fp32 sums of the crossings' cell coordinates in that order, divided once by their number; vertex_i =
+ *      ((float)c_i + (0.5f + m_i)) * voxel; rgb_j = (float)((double)sum C_j / (double)sum W) over the eight corners.  Vertices in
+ *      ascending cell key ((c_x + 2^20) << 42) | ((c_y + 2^20) << 21) | (c_z + 2^20).
+ *   6. Faces.  A grid edge a -> a + e_k with both ends observed and of different sign emits a quad iff the four cells around it are
+ *      active: with (u, w) = (k + 1, k + 2) mod 3, q0 = a - e_u - e_w, q1 = a - e_w, q2 = a, q3 = a - e_u; triangles (q0 q1 q2),
+ *      (q0 q2 q3) if a is inside, (q0 q2 q1), (q0 q3 q2) otherwise: the right-hand normal points from the inside end to the outside
+ *      end.  Faces in ascending (key of a, k), as indices into the vertex order.
+ *
+ *   The state is a caller-owned workspace of sd3d_tsdf_ws_bytes(capacity) bytes (0 for a bad capacity), 256-byte aligned, each part
+ *   rounded up to 256 bytes: 7 64-bit counters | block keys uint64 [capacity] (SD3D_EMPTY_KEY = free) | touched uint64 [capacity] |
+ *   slot list uint32 [capacity] | voxels int32 [capacity][SD3D_TSDF_VOXEL_WORDS][512] = W, T, C_r, C_g, C_b with voxel (lx, ly, lz) at
+ *   lx * 64 + ly * 8 + lz | cell table int32 [capacity][512].  `capacity` counts BLOCKS, a power of two.
+ *
+ *   sd3d_tsdf_reset: empties the table.  Required once before the first touch.
+ *   sd3d_tsdf_touch: steps 1 and 2 for V <= SD3D_TSDF_MAX_CALL_VIEWS views; writes vdepth float [V, Hd, Wd], the depth of each valid
+ *     pixel and 0 elsewhere.  half_step = trunc / 2.
+ *   sd3d_tsdf_integrate: step 3 for the same V views, which must follow their touch; reads its vdepth.  qscale = 4096 / trunc.
+ *   sd3d_tsdf_mesh: steps 4 to 6.  vertices float [max_vertices, 6], keys_out int64 [max_vertices] or NULL, faces int32
+ *     [6 * max_vertices, 3] (a cell's low corner starts three grid edges: no more than three quads a vertex); scratch of
+ *     sd3d_tsdf_mesh_ws_bytes(max_vertices) bytes.  info int64 [SD3D_TSDF_INFO_WORDS] on the device = vertices (found; only the first
+ *     max_vertices are written, and then the faces are incomplete: the caller treats vertices > max_vertices as an error), faces,
+ *     blocks, voxels_observed, updates, out_of_range, overflow.  The volume is left as it is: touch / integrate may go on.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_TSDF_VOXEL_WORDS 5          /* 32-bit words per voxel: W, T, C_r, C_g, C_b */
+#define SD3D_TSDF_PROBE_LIMIT 64         /* slots a block tries before it counts as overflow */
+#define SD3D_TSDF_INFO_WORDS 7           /* vertices, faces, blocks, voxels_observed, updates, out_of_range, overflow */
+#define SD3D_TSDF_MAX_CALL_VIEWS 64      /* views of one touch / integrate pair: a bit each in a block's `touched` word */
+#define SD3D_TSDF_MAX_VIEWS (1 << 17)    /* views of one volume: 2^17 * 4097 < 2^30 */
+#define SD3D_TSDF_MIN_CAPACITY 16
+#define SD3D_TSDF_MAX_CAPACITY (1 << 20)
+#define SD3D_TSDF_MAX_VERTICES (1 << 26)
+size_t sd3d_tsdf_ws_bytes(int64_t capacity);
+int sd3d_tsdf_reset(void* ws, size_t ws_bytes, int64_t capacity, void* stream);
+int sd3d_tsdf_touch(const void* depth, int depth_u16, float depth_scale, const float* intrinsics, const float* cam_to_world, int V, int Hd,
+                    int Wd, float near, float far, float edge_abs, float edge_rel, int use_edges, float inv_voxel, float half_step,
+                    float* vdepth, void* ws, size_t ws_bytes, int64_t capacity, void* stream);
+int sd3d_tsdf_integrate(const float* vdepth, const float* intrinsics, const float* world_to_cam, const void* colors, int V, int Hd, int Wd,
+                        int Hc, int Wc, float voxel, float trunc, float qscale, void* ws, size_t ws_bytes, int64_t capacity, void* stream);
+size_t sd3d_tsdf_mesh_ws_bytes(int64_t max_vertices);
+int sd3d_tsdf_mesh(void* ws, size_t ws_bytes, int64_t capacity, int min_weight, float voxel, int64_t max_vertices, void* scratch,
+                   size_t scratch_bytes, float* vertices, int64_t* keys_out, int32_t* faces, int64_t* info, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Nearest point (csrc/transfer.hip): carrying what a forward computed per point onto other points and onto the depth frames.  The

@@ -1,0 +1,640 @@
+// TSDF fusion of posed RGB-D frames and a surface-net mesh of the fused volume (the producer of a MESH - vertices [V, 6] and faces
+// [F, 3] - from frames, so that superpoints.mesh_superpoints, the rule the network saw in training, has an input without an offline
+// tool).  The reference reads meshes made offline and ships no code that makes one: tests/tsdf_ref.py, a numpy restatement of the
+// rule in segdino3d_amd/tsdf.py and include/segdino3d_hip.h, is what these kernels are pinned against, bit for bit.
+//
+// The rule in short (segdino3d_amd/tsdf.py has it in full); every decision is an integer one or a single rounded fp32 operation:
+//   1. valid pixel, its depth d and its colour pixel: steps 1 to 3 of fuse_views.hip with stride 1 (restated here: ONE rule, two
+//      places, because sharing the code would mean recompiling fuse_views.hip's kernel around a new header);
+//   2. a view TOUCHES the blocks (8 x 8 x 8 voxels) that hold the back-projections (backproject.h) of the five depths d + j h,
+//      j = -2 .. 2, h = trunc / 2, of its valid pixels; range failures are counted in out_of_range;
+//   3. per (view, touched block) and per voxel of the block: the centre is projected through the fp32 world_to_cam, rounded to the
+//      nearest pixel, which must be valid; sdf = d - z, skipped below -trunc, clamped at trunc, quantised to q = rint(t * 4096 / trunc);
+//      W += 1, T += q, C_j += colour byte j.  Integers only: the volume is a function of the SET of views;
+//   4. a voxel is observed iff W >= min_weight, inside iff T < 0;
+//   5. one vertex per active cell (eight observed corners of both signs): the mean of the edge crossings, in ascending cell key;
+//   6. one quad (two triangles) per sign-changing grid edge whose four cells are active, in ascending (key of the lower end, axis).
+//
+// State (caller-owned, sd3d_tsdf_ws_bytes): counters | block keys u64 [capacity] (open addressing, SD3D_EMPTY_KEY = free) | touched
+// u64 [capacity] (bit v = view v of the running call touched the block) | list u32 [capacity] (the slots with a non-zero `touched`) |
+// voxels int32 [capacity][5][512] = W, T, C_r, C_g, C_b, voxel (lx, ly, lz) at lx * 64 + ly * 8 + lz | cell table int32 [capacity][512],
+// the vertex index of each cell of the block, -1 for none, written by sd3d_tsdf_mesh.  12 KiB + 20 bytes a block.
+//
+//   sd3d_tsdf_reset      memsets.
+//   sd3d_tsdf_touch      ts_touch_kernel      a workgroup of 256 lanes takes a tile of 8 x 32 pixels of one view, as fv_accumulate_kernel
+//                                             does.  Each lane writes its pixel's validated depth (d, or 0) for the integration to read,
+//                                             and puts the blocks of its five samples into an LDS set (64-bit compare-and-swap);
+//                                             then one lane per distinct block of the tile claims the block in the global table
+//                                             (atomicCAS, linear probing, SD3D_TSDF_PROBE_LIMIT slots), sets the view's bit in `touched`,
+//                                             and lists the slot if it was the first to set a bit.  Both atomics come after a plain
+//                                             look: a key never leaves its slot and a bit stays set until the integration.  The look
+//                                             did not move the time (profiles/tsdf_mesh.md); it spares the L2 the repeats.
+//   sd3d_tsdf_integrate  ts_integrate_kernel  block-major: a workgroup takes a listed slot, two voxels per lane, and walks the views whose
+//                                             bit is set with the sums in registers; one read-modify-write of the block's 10 KiB per
+//                                             call, no atomics on voxels (the slot belongs to one workgroup), then clears `touched`.
+//   sd3d_tsdf_mesh       ts_cells_kernel      a workgroup per occupied slot: finds the 7 neighbour blocks that hold the far corners of
+//                                             its cells, decides each cell, computes the vertex of an active one and appends (cell key,
+//                                             vertex, slot * 512 + cell) to a list - one position atomic per workgroup and round, one
+//                                             per cell cost three times the kernel's time; clears the block's cell table;
+//                        sort_pairs_u64       the cell keys, the unused tail of the list last;
+//                        ts_vertices_kernel   sorted position j -> vertices[j], keys[j], cell table [cell] = j;
+//                        ts_quads_kernel      a lane per vertex j, twice: its cell's low corner `a` has three grid edges a -> a + e_k; the
+//                                             first run counts the quads they emit, scan_exclusive_i32 turns the counts into offsets (the
+//                                             order (key of a, axis) IS the order (j, axis): no second sort), the second run writes them.
+#include "common.h"
+// The kernels here must EQUAL a float32 evaluation of the restatement: nothing in this file may be contracted into a fused
+// multiply-add.  The pragma covers backproject.h as it is compiled here and every expression below.
+#pragma clang fp contract(off)
+#include "backproject.h"
+#include "../../include/segdino3d_hip.h"
+
+#define TS_THREADS 256
+#define TS_TILE_W 32
+#define TS_TILE_H 8
+#define TS_LDS_SLOTS 2048                               // 5 samples of 256 pixels = 1280 keys at most: the LDS probe always ends
+#define TS_LDS_LIST (5 * TS_THREADS)
+#define TS_MAX_DIM 16384                                // image extents; (2 v + 1) * H stays below 2^30
+#define TS_VOX 512                                      // voxels of a block
+#define TS_WORDS SD3D_TSDF_VOXEL_WORDS
+#define TS_BLOCK_BIAS (1 << 17)                         // block indices lie in [-2^17, 2^17): 18 bits per axis of the block key
+#define TS_CELL_BIAS (1 << 20)
+typedef unsigned long long ts_u64;
+
+// the counters at the head of the workspace, 64-bit each
+enum { TS_BLOCKS = 0, TS_UPDATES = 1, TS_RANGE = 2, TS_OVERFLOW = 3, TS_NLIST = 4, TS_NVERT = 5, TS_OBSERVED = 6, TS_COUNTERS = 7 };
+
+struct TsGeom {
+    int Hd, Wd, Hc, Wc, tiles_x, tiles_per_view, use_edges;
+    float depth_scale, near, far, edge_abs, edge_rel, inv_voxel, voxel, h, trunc, qscale;
+    uint32_t mask;                                      // capacity - 1
+    ts_u64 vmask;                                       // a bit per view of the call
+};
+
+__device__ __forceinline__ float ts_metres(uint16_t raw, float scale) { return (float)raw * scale; }
+__device__ __forceinline__ float ts_metres(float d, float) { return d; }
+__device__ __forceinline__ bool ts_jump(float dn, float d, float thr) { return !(dn > 0.0f) || fabsf(dn - d) > thr; }
+
+__device__ __forceinline__ ts_u64 ts_block_key(int bx, int by, int bz) {
+    return ((ts_u64)(uint32_t)(bx + TS_BLOCK_BIAS) << 36) | ((ts_u64)(uint32_t)(by + TS_BLOCK_BIAS) << 18) | (ts_u64)(uint32_t)(bz + TS_BLOCK_BIAS);
+}
+__device__ __forceinline__ void ts_block_coords(ts_u64 key, int& bx, int& by, int& bz) {
+    bx = (int)((key >> 36) & 0x3FFFFull) - TS_BLOCK_BIAS;
+    by = (int)((key >> 18) & 0x3FFFFull) - TS_BLOCK_BIAS;
+    bz = (int)(key & 0x3FFFFull) - TS_BLOCK_BIAS;
+}
+// the slot of a block, or -1: a read-only probe of a table nobody is inserting into
+__device__ __forceinline__ int ts_find(const ts_u64* __restrict__ keys, uint32_t mask, int bx, int by, int bz) {
+    if (bx < -TS_BLOCK_BIAS || bx >= TS_BLOCK_BIAS || by < -TS_BLOCK_BIAS || by >= TS_BLOCK_BIAS || bz < -TS_BLOCK_BIAS || bz >= TS_BLOCK_BIAS)
+        return -1;
+    const ts_u64 key = ts_block_key(bx, by, bz);
+    uint32_t slot = hash_u64(key) & mask;
+    for (int probe = 0; probe < SD3D_TSDF_PROBE_LIMIT; ++probe) {
+        const ts_u64 k = keys[slot];
+        if (k == key) return (int)slot;
+        if (k == SD3D_EMPTY_KEY) return -1;
+        slot = (slot + 1) & mask;
+    }
+    return -1;
+}
+
+// ---------------------------------------------------------------------------------------------- steps 1 and 2
+template <typename D>
+__global__ __launch_bounds__(TS_THREADS) void ts_touch_kernel(const D* __restrict__ depth, const float* __restrict__ intr,
+                                                              const float* __restrict__ c2w, TsGeom g, ts_u64* __restrict__ keys,
+                                                              ts_u64* __restrict__ touched, uint32_t* __restrict__ list,
+                                                              ts_u64* __restrict__ counters, float* __restrict__ vdepth) {
+    __shared__ ts_u64 s_key[TS_LDS_SLOTS];
+    __shared__ int s_list[TS_LDS_LIST], s_nkeys;
+    const int t = threadIdx.x, lane = t & 63;
+    const int v = blockIdx.x / g.tiles_per_view, tile = blockIdx.x - v * g.tiles_per_view;
+    const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
+    for (int i = t; i < TS_LDS_SLOTS; i += TS_THREADS) s_key[i] = SD3D_EMPTY_KEY;
+    if (t == 0) s_nkeys = 0;
+    __syncthreads();
+
+    const int vi = ty * TS_TILE_H + (t >> 5), ui = tx * TS_TILE_W + (t & 31);
+    int dropped = 0;
+    if (vi < g.Hd && ui < g.Wd) {
+        const D* img = depth + (int64_t)v * g.Hd * g.Wd;
+        const D* row = img + (int64_t)vi * g.Wd;
+        const float d = ts_metres(row[ui], g.depth_scale);
+        bool ok = d > 0.0f && d >= g.near && d <= g.far;                              // a NaN fails
+        if (ok && g.use_edges) {
+            const float thr = g.edge_abs + g.edge_rel * d;                            // two roundings: contraction is off
+            if (vi > 0) ok = ok && !ts_jump(ts_metres(row[ui - g.Wd], g.depth_scale), d, thr);
+            if (vi + 1 < g.Hd) ok = ok && !ts_jump(ts_metres(row[ui + g.Wd], g.depth_scale), d, thr);
+            if (ui > 0) ok = ok && !ts_jump(ts_metres(row[ui - 1], g.depth_scale), d, thr);
+            if (ui + 1 < g.Wd) ok = ok && !ts_jump(ts_metres(row[ui + 1], g.depth_scale), d, thr);
+        }
+        vdepth[((int64_t)v * g.Hd + vi) * g.Wd + ui] = ok ? d : 0.0f;                 // what step 3 reads: d of a valid pixel, else 0
+        if (ok) {
+            const Sd3dCamera cam = sd3d_load_camera(intr, c2w, v);
+            const float lim = (float)(1 << SD3D_FUSE_WORLD_BITS), cells = (float)TS_CELL_BIAS;
+            ts_u64 last = SD3D_EMPTY_KEY;
+            for (int j = -2; j <= 2; ++j) {
+                const float dj = d + (float)j * g.h;                                  // j * h is exact: one rounded add
+                float w[3];
+                sd3d_backproject(cam, vi, ui, dj, w[0], w[1], w[2]);
+                bool in = fabsf(w[0]) < lim && fabsf(w[1]) < lim && fabsf(w[2]) < lim;    // NaN and infinities stop here
+                float c[3] = {0.0f, 0.0f, 0.0f};
+                if (in) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        c[i] = floorf(w[i] * g.inv_voxel);
+                        in = in && c[i] >= -cells && c[i] < cells;                     // as floats, before anything becomes an integer
+                    }
+                }
+                if (!in) { ++dropped; continue; }
+                const ts_u64 key = ts_block_key((int)c[0] >> 3, (int)c[1] >> 3, (int)c[2] >> 3);      // arithmetic shifts
+                if (key == last) continue;
+                last = key;
+                int slot = (int)(hash_u64(key) >> 21);                                 // the top 11 bits; the global table takes the low ones
+                for (;;) {                                                            // at most 1280 keys in 2048 slots: it ends
+                    const ts_u64 prev = atomicCAS(&s_key[slot], (ts_u64)SD3D_EMPTY_KEY, key);
+                    if (prev == SD3D_EMPTY_KEY) { s_list[atomicAdd(&s_nkeys, 1)] = slot; break; }      // < TS_LDS_LIST: one per (lane, j)
+                    if (prev == key) break;
+                    slot = (slot + 1) & (TS_LDS_SLOTS - 1);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- one global claim per distinct block of the tile
+    const int nkeys = s_nkeys;
+    int fresh = 0, lost = 0;
+    for (int i = t; i < nkeys; i += TS_THREADS) {
+        const ts_u64 key = s_key[s_list[i]];
+        uint32_t slot = hash_u64(key) & g.mask;
+        int gslot = -1;
+        for (int probe = 0; probe < SD3D_TSDF_PROBE_LIMIT; ++probe) {
+            // a look first: most tiles meet blocks that are there already, and a key never leaves its slot
+            ts_u64 prev = __atomic_load_n(&keys[slot], __ATOMIC_RELAXED);
+            if (prev == SD3D_EMPTY_KEY) {
+                prev = atomicCAS(&keys[slot], (ts_u64)SD3D_EMPTY_KEY, key);
+                if (prev == SD3D_EMPTY_KEY) ++fresh;
+            }
+            if (prev == SD3D_EMPTY_KEY || prev == key) { gslot = (int)slot; break; }
+            slot = (slot + 1) & g.mask;
+        }
+        if (gslot < 0) { ++lost; continue; }
+        // 0 <= gslot <= mask: inside the table; v < 64.  A bit that is seen set was set by this view in this call: nothing to do
+        if ((__atomic_load_n(&touched[gslot], __ATOMIC_RELAXED) >> v) & 1ull) continue;
+        const ts_u64 before = atomicOr(&touched[gslot], 1ull << v);
+        if (before == 0) {
+            const ts_u64 at = atomicAdd(&counters[TS_NLIST], 1ull);                    // once per slot and call: at < capacity
+            if (at <= g.mask) list[at] = (uint32_t)gslot;
+        }
+    }
+    fresh = wave_sum(fresh); lost = wave_sum(lost); dropped = wave_sum(dropped);
+    if (lane == 0) {
+        if (fresh) atomicAdd(&counters[TS_BLOCKS], (ts_u64)fresh);
+        if (lost) atomicAdd(&counters[TS_OVERFLOW], (ts_u64)lost);
+        if (dropped) atomicAdd(&counters[TS_RANGE], (ts_u64)dropped);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- step 3
+__global__ __launch_bounds__(TS_THREADS) void ts_integrate_kernel(const float* __restrict__ vdepth, const float* __restrict__ intr,
+                                                                  const float* __restrict__ w2c, const uint8_t* __restrict__ colors, TsGeom g,
+                                                                  const ts_u64* __restrict__ keys, ts_u64* __restrict__ touched,
+                                                                  const uint32_t* __restrict__ list, int32_t* __restrict__ vox,
+                                                                  ts_u64* __restrict__ counters) {
+    const int t = threadIdx.x;
+    ts_u64 n64 = counters[TS_NLIST];
+    const int nlist = (int)(n64 > (ts_u64)g.mask + 1 ? (ts_u64)g.mask + 1 : n64);
+    int updates = 0;
+    for (int it = blockIdx.x; it < nlist; it += gridDim.x) {                           // uniform over the workgroup
+        const uint32_t slot = list[it] & g.mask;
+        ts_u64 views = touched[slot] & g.vmask;                                       // v < V: inside vdepth, intr, w2c and colors
+        int bx, by, bz;
+        ts_block_coords(keys[slot], bx, by, bz);
+        float p[2][3];
+        int acc[2][TS_WORDS];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int l = t + k * TS_THREADS;
+            p[k][0] = ((float)(bx * 8 + (l >> 6)) + 0.5f) * g.voxel;
+            p[k][1] = ((float)(by * 8 + ((l >> 3) & 7)) + 0.5f) * g.voxel;
+            p[k][2] = ((float)(bz * 8 + (l & 7)) + 0.5f) * g.voxel;
+#pragma unroll
+            for (int w = 0; w < TS_WORDS; ++w) acc[k][w] = 0;
+        }
+        while (views) {
+            const int v = __ffsll((long long)views) - 1;
+            views &= views - 1;
+            const float* kk = intr + v * 4;
+            const float* m = w2c + v * 12;
+            const float fx = kk[0], fy = kk[1], cx = kk[2], cy = kk[3];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const float x = ((m[0] * p[k][0] + m[1] * p[k][1]) + m[2] * p[k][2]) + m[3];
+                const float y = ((m[4] * p[k][0] + m[5] * p[k][1]) + m[6] * p[k][2]) + m[7];
+                const float z = ((m[8] * p[k][0] + m[9] * p[k][1]) + m[10] * p[k][2]) + m[11];
+                if (!(z > 0.0f)) continue;
+                const float uf = floorf(((fx * x) / z + cx) + 0.5f), vf = floorf(((fy * y) / z + cy) + 0.5f);
+                if (!(uf >= 0.0f && uf < (float)g.Wd && vf >= 0.0f && vf < (float)g.Hd)) continue;      // as floats; a NaN fails
+                const int ui = (int)uf, vi = (int)vf;
+                const float d = vdepth[((int64_t)v * g.Hd + vi) * g.Wd + ui];
+                if (!(d > 0.0f)) continue;
+                const float sdf = d - z;
+                if (sdf < -g.trunc) continue;
+                const int q = (int)rintf(fminf(sdf, g.trunc) * g.qscale);
+                const int yc = (int)(((uint32_t)(2 * vi + 1) * (uint32_t)g.Hc) / (uint32_t)(2 * g.Hd));       // < Hc
+                const int xc = (int)(((uint32_t)(2 * ui + 1) * (uint32_t)g.Wc) / (uint32_t)(2 * g.Wd));       // < Wc
+                const uint8_t* px = colors + (((int64_t)v * g.Hc + yc) * g.Wc + xc) * 3;
+                acc[k][0] += 1; acc[k][1] += q; acc[k][2] += px[0]; acc[k][3] += px[1]; acc[k][4] += px[2];
+                ++updates;
+            }
+        }
+        int32_t* b = vox + (size_t)slot * (TS_WORDS * TS_VOX);
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (acc[k][0]) {
+#pragma unroll
+                for (int w = 0; w < TS_WORDS; ++w) b[w * TS_VOX + t + k * TS_THREADS] += acc[k][w];
+            }
+        __syncthreads();                                                              // every lane has read `touched`
+        if (t == 0) touched[slot] = 0;
+    }
+    __shared__ int s_upd[TS_THREADS / 64];
+    updates = wave_sum(updates);
+    if ((t & 63) == 0) s_upd[t >> 6] = updates;
+    __syncthreads();
+    if (t == 0) {
+        const int tot = s_upd[0] + s_upd[1] + s_upd[2] + s_upd[3];
+        if (tot) atomicAdd(&counters[TS_UPDATES], (ts_u64)tot);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- steps 4 and 5
+struct TsMesh {
+    const ts_u64* keys;
+    const int32_t* vox;
+    int32_t* cellvert;
+    uint32_t mask;
+    int min_weight;
+    float voxel;
+    int64_t max_vertices;
+};
+
+__global__ __launch_bounds__(TS_THREADS) void ts_cells_kernel(TsMesh m, uint64_t* __restrict__ ckeys, float* __restrict__ cvert,
+                                                              uint32_t* __restrict__ cref, ts_u64* __restrict__ counters) {
+    __shared__ int s_nbr[8], s_wcnt[4];
+    __shared__ ts_u64 s_base;
+    const int t = threadIdx.x, slot = blockIdx.x, wave = t >> 6, lane = t & 63;
+    const ts_u64 bkey = m.keys[slot];
+    if (bkey == SD3D_EMPTY_KEY) return;                                               // uniform
+    int bx, by, bz;
+    ts_block_coords(bkey, bx, by, bz);
+    if (t < 8) s_nbr[t] = t == 0 ? slot : ts_find(m.keys, m.mask, bx + (t >> 2), by + ((t >> 1) & 1), bz + (t & 1));
+    __syncthreads();
+    int observed = 0;
+    for (int k = 0; k < 2; ++k) {
+        const int l = t + k * TS_THREADS, lx = l >> 6, ly = (l >> 3) & 7, lz = l & 7;
+        m.cellvert[(size_t)slot * TS_VOX + l] = -1;
+        int W[8], T[8];
+        bool all = true;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {                                                 // corner c = (dx, dy, dz) = bits 2, 1, 0
+            const int x = lx + (c >> 2), y = ly + ((c >> 1) & 1), z = lz + (c & 1);
+            const int nb = s_nbr[((x >> 3) << 2) | ((y >> 3) << 1) | (z >> 3)];
+            W[c] = 0; T[c] = 0;
+            if (nb >= 0) {
+                const int32_t* b = m.vox + (size_t)nb * (TS_WORDS * TS_VOX) + (((x & 7) << 6) | ((y & 7) << 3) | (z & 7));
+                W[c] = b[0]; T[c] = b[TS_VOX];
+            }
+            all = all && W[c] >= m.min_weight;
+        }
+        if (W[0] >= m.min_weight) ++observed;
+        int inside = 0;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) inside += T[c] < 0;
+        const bool active = all && inside != 0 && inside != 8;
+        ts_u64 ckey = 0;
+        float o[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (active) {
+        float f[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) f[c] = (float)((double)T[c] / (double)W[c]);
+        float s[3] = {0.0f, 0.0f, 0.0f};
+        int n = 0;
+#pragma unroll
+        for (int axis = 0; axis < 3; ++axis) {                                        // x-edges, y-edges, z-edges
+            const int sh = 2 - axis, u = (axis == 0) ? 1 : 0, w = (axis == 2) ? 1 : 2;      // the two remaining axes, the earlier one major
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int cu = e >> 1, cw = e & 1;
+                const int a = (cu << (2 - u)) | (cw << (2 - w)), b = a | (1 << sh);
+                if ((T[a] < 0) == (T[b] < 0)) continue;
+                float pos[3];
+                pos[axis] = f[a] / (f[a] - f[b]);
+                pos[u] = (float)cu;
+                pos[w] = (float)cw;
+                s[0] += pos[0]; s[1] += pos[1]; s[2] += pos[2];
+                ++n;
+            }
+        }
+        long long sw = 0, cc[3] = {0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const int x = lx + (c >> 2), y = ly + ((c >> 1) & 1), z = lz + (c & 1);
+            const int nb = s_nbr[((x >> 3) << 2) | ((y >> 3) << 1) | (z >> 3)];       // >= 0: the corner is observed
+            const int32_t* b = m.vox + (size_t)nb * (TS_WORDS * TS_VOX) + (((x & 7) << 6) | ((y & 7) << 3) | (z & 7));
+            sw += W[c]; cc[0] += b[2 * TS_VOX]; cc[1] += b[3 * TS_VOX]; cc[2] += b[4 * TS_VOX];
+        }
+        const int c3[3] = {bx * 8 + lx, by * 8 + ly, bz * 8 + lz};
+        ckey = ((ts_u64)(uint32_t)(c3[0] + TS_CELL_BIAS) << 42) | ((ts_u64)(uint32_t)(c3[1] + TS_CELL_BIAS) << 21) |
+               (ts_u64)(uint32_t)(c3[2] + TS_CELL_BIAS);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) o[i] = ((float)c3[i] + (0.5f + s[i] / (float)n)) * m.voxel;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) o[3 + i] = (float)((double)cc[i] / (double)sw);
+        }
+        // one global atomic per workgroup and round: a list position for every active cell (the order is the sort's business)
+        const ts_u64 bal = __ballot(active);
+        if (lane == 0) s_wcnt[wave] = __popcll(bal);
+        __syncthreads();
+        if (t == 0) {
+            const int tot = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+            s_base = tot ? atomicAdd(&counters[TS_NVERT], (ts_u64)tot) : 0ull;
+        }
+        __syncthreads();
+        if (active) {
+            ts_u64 at = s_base + (ts_u64)__popcll(bal & ((1ull << lane) - 1ull));
+            for (int w = 0; w < wave; ++w) at += (ts_u64)s_wcnt[w];
+            if ((int64_t)at < m.max_vertices) {                                       // beyond: counted, not written; the host raises
+                ckeys[at] = ckey;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) cvert[at * 6 + i] = o[i];
+                cref[at] = (uint32_t)slot * TS_VOX + (uint32_t)l;
+            }
+        }
+        __syncthreads();                                                              // s_wcnt and s_base are free again
+    }
+    observed = wave_sum(observed);
+    if (lane == 0) s_wcnt[wave] = observed;
+    __syncthreads();
+    if (t == 0) {
+        const int tot = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+        if (tot) atomicAdd(&counters[TS_OBSERVED], (ts_u64)tot);
+    }
+}
+
+__global__ __launch_bounds__(256) void ts_vertices_kernel(const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ sidx,
+                                                          const float* __restrict__ cvert, const uint32_t* __restrict__ cref, int64_t max_vertices,
+                                                          int64_t cells, float* __restrict__ vertices, int64_t* __restrict__ keys_out,
+                                                          uint32_t* __restrict__ sref, int32_t* __restrict__ cellvert,
+                                                          const ts_u64* __restrict__ counters, int32_t* __restrict__ nlive) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j == 0) {
+        const ts_u64 n = counters[TS_NVERT];
+        *nlive = (int32_t)(n > (ts_u64)max_vertices ? (ts_u64)max_vertices : n);
+    }
+    if (j >= max_vertices) return;
+    const uint64_t key = skeys[j];
+    if (key == SD3D_EMPTY_KEY) return;                                                // the cells come first
+    const int64_t idx = sidx[j];
+    if (idx >= max_vertices) return;                                                  // never from the sort: a permutation
+    const uint32_t ref = cref[idx];
+    if ((int64_t)ref >= cells) return;                                                // never: slot * 512 + cell of an occupied slot
+#pragma unroll
+    for (int i = 0; i < 6; ++i) vertices[j * 6 + i] = cvert[idx * 6 + i];
+    if (keys_out) keys_out[j] = (int64_t)key;
+    sref[j] = ref;
+    cellvert[ref] = (int32_t)j;
+}
+
+// ---------------------------------------------------------------------------------------------- step 6
+// the reference (slot * 512 + voxel) of voxel (lx, ly, lz), each in [-1, 8], relative to block (bx, by, bz) at `slot`; -1 if its block
+// is not in the table
+__device__ __forceinline__ int64_t ts_ref(const TsMesh& m, int slot, int bx, int by, int bz, int lx, int ly, int lz) {
+    int s = slot;
+    if (((lx | ly | lz) & ~7) != 0) s = ts_find(m.keys, m.mask, bx + (lx >> 3), by + (ly >> 3), bz + (lz >> 3));     // >> 3 of -1 is -1
+    return s < 0 ? -1 : (int64_t)s * TS_VOX + (((lx & 7) << 6) | ((ly & 7) << 3) | (lz & 7));
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void ts_quads_kernel(TsMesh m, const uint32_t* __restrict__ sref, const int32_t* __restrict__ nlive,
+                                                       int32_t* __restrict__ count, const int32_t* __restrict__ offset,
+                                                       const int32_t* __restrict__ nquads, int32_t* __restrict__ faces,
+                                                       const ts_u64* __restrict__ counters, int64_t* __restrict__ info) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (WRITE && j == 0) {
+        info[0] = (int64_t)counters[TS_NVERT]; info[1] = 2 * (int64_t)*nquads; info[2] = (int64_t)counters[TS_BLOCKS];
+        info[3] = (int64_t)counters[TS_OBSERVED]; info[4] = (int64_t)counters[TS_UPDATES]; info[5] = (int64_t)counters[TS_RANGE];
+        info[6] = (int64_t)counters[TS_OVERFLOW];
+    }
+    if (j >= *nlive) return;                                                          // nlive <= max_vertices
+    const uint32_t ref = sref[j];
+    const int slot = (int)(ref >> 9), l = (int)(ref & 511), lx = l >> 6, ly = (l >> 3) & 7, lz = l & 7;
+    int bx, by, bz;
+    ts_block_coords(m.keys[slot], bx, by, bz);
+    const bool a_in = m.vox[(size_t)ref + (size_t)slot * ((TS_WORDS - 1) * TS_VOX) + TS_VOX] < 0;      // T of voxel a (observed: its cell is active)
+    int n = 0;
+    int32_t* out = WRITE ? faces + (int64_t)offset[j] * 6 : nullptr;
+    for (int axis = 0; axis < 3; ++axis) {
+        const int u = (axis + 1) % 3, w = (axis + 2) % 3;                              // e_u x e_w = e_axis
+        int d[3] = {0, 0, 0};
+        d[axis] = 1;
+        const int64_t rb = ts_ref(m, slot, bx, by, bz, lx + d[0], ly + d[1], lz + d[2]);
+        if (rb < 0) continue;
+        const int32_t* vb = m.vox + (rb >> 9) * (TS_WORDS * TS_VOX) + (rb & 511);
+        if (vb[0] < m.min_weight || (vb[TS_VOX] < 0) == a_in) continue;
+        int du[3] = {0, 0, 0}, dw[3] = {0, 0, 0};
+        du[u] = 1; dw[w] = 1;
+        const int64_t r0 = ts_ref(m, slot, bx, by, bz, lx - du[0] - dw[0], ly - du[1] - dw[1], lz - du[2] - dw[2]);
+        const int64_t r1 = ts_ref(m, slot, bx, by, bz, lx - dw[0], ly - dw[1], lz - dw[2]);
+        const int64_t r3 = ts_ref(m, slot, bx, by, bz, lx - du[0], ly - du[1], lz - du[2]);
+        if (r0 < 0 || r1 < 0 || r3 < 0) continue;
+        const int32_t q0 = m.cellvert[r0], q1 = m.cellvert[r1], q2 = (int32_t)j, q3 = m.cellvert[r3];
+        if (q0 < 0 || q1 < 0 || q3 < 0) continue;
+        if (WRITE) {
+            // q0 q1 q2 q3 turns about +e_axis; the normal points from the inside end to the outside end
+            int32_t* f = out + n * 6;
+            f[0] = q0; f[3] = q0;
+            if (a_in) { f[1] = q1; f[2] = q2; f[4] = q2; f[5] = q3; }
+            else      { f[1] = q2; f[2] = q1; f[4] = q3; f[5] = q2; }
+        }
+        ++n;
+    }
+    if (!WRITE) count[j] = n;
+}
+
+// ---------------------------------------------------------------------------------------------- C entry points
+struct TsWs {
+    ts_u64 *counters, *keys, *touched;
+    uint32_t* list;
+    int32_t *vox, *cellvert;
+    size_t total;
+};
+static TsWs ts_ws(void* ws, int64_t capacity) {
+    TsWs w;
+    char* p = (char*)ws;
+    size_t o = 0;
+    const size_t m = (size_t)capacity;
+    auto take = [&](size_t bytes) { char* q = p + o; o += align_up(bytes, 256); return (void*)q; };
+    w.counters = (ts_u64*)take(TS_COUNTERS * 8);
+    w.keys = (ts_u64*)take(m * 8);
+    w.touched = (ts_u64*)take(m * 8);
+    w.list = (uint32_t*)take(m * 4);
+    w.vox = (int32_t*)take(m * TS_WORDS * TS_VOX * 4);
+    w.cellvert = (int32_t*)take(m * TS_VOX * 4);
+    w.total = o;
+    return w;
+}
+static bool ts_capacity_ok(int64_t c) { return c >= SD3D_TSDF_MIN_CAPACITY && c <= SD3D_TSDF_MAX_CAPACITY && (c & (c - 1)) == 0; }
+static int ts_check_ws(const char* who, void* ws, size_t ws_bytes, int64_t capacity, TsWs& w) {
+    char msg[160];                                      // sd3d_set_error copies it
+    if (!ts_capacity_ok(capacity)) {
+        snprintf(msg, sizeof msg, "%s: capacity must be a power of two in [2^4, 2^20]", who);
+        return sd3d_set_error(SD3D_ERR_ARG, msg);
+    }
+    if (!ws || ((uintptr_t)ws & 255) != 0) {
+        snprintf(msg, sizeof msg, "%s: ws is required and must be 256-byte aligned", who);
+        return sd3d_set_error(SD3D_ERR_ARG, msg);
+    }
+    w = ts_ws(ws, capacity);
+    if (ws_bytes < w.total) {
+        snprintf(msg, sizeof msg, "%s: workspace too small (sd3d_tsdf_ws_bytes)", who);
+        return sd3d_set_error(SD3D_ERR_WS, msg);
+    }
+    return SD3D_OK;
+}
+
+extern "C" size_t sd3d_tsdf_ws_bytes(int64_t capacity) { return ts_capacity_ok(capacity) ? ts_ws(nullptr, capacity).total : 0; }
+
+extern "C" int sd3d_tsdf_reset(void* ws, size_t ws_bytes, int64_t capacity, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    TsWs w;
+    if (int rc = ts_check_ws("tsdf_reset", ws, ws_bytes, capacity, w)) return rc;
+    const size_t m = (size_t)capacity;
+    if (hipMemsetAsync(w.counters, 0, TS_COUNTERS * 8, st) != hipSuccess || hipMemsetAsync(w.keys, 0xFF, m * 8, st) != hipSuccess ||
+        hipMemsetAsync(w.touched, 0, m * 8, st) != hipSuccess || hipMemsetAsync(w.vox, 0, m * TS_WORDS * TS_VOX * 4, st) != hipSuccess)
+        return sd3d_set_error(SD3D_ERR_LAUNCH, "tsdf_reset: memset");
+    return SD3D_OK;
+}
+
+static int ts_geom(const char* who, int V, int Hd, int Wd, int Hc, int Wc, int64_t capacity, TsGeom& g) {
+    char msg[160];
+    if (V < 0 || V > SD3D_TSDF_MAX_CALL_VIEWS || Hd < 1 || Hd > TS_MAX_DIM || Wd < 1 || Wd > TS_MAX_DIM || Hc < 1 || Hc > TS_MAX_DIM || Wc < 1 ||
+        Wc > TS_MAX_DIM) {
+        snprintf(msg, sizeof msg, "%s: 0 <= V <= 64 views a call, images up to 16384 a side", who);
+        return sd3d_set_error(SD3D_ERR_ARG, msg);
+    }
+    g.Hd = Hd; g.Wd = Wd; g.Hc = Hc; g.Wc = Wc;
+    g.tiles_x = (Wd + TS_TILE_W - 1) / TS_TILE_W;
+    g.tiles_per_view = g.tiles_x * ((Hd + TS_TILE_H - 1) / TS_TILE_H);
+    g.mask = (uint32_t)(capacity - 1);
+    g.vmask = V >= 64 ? ~0ull : (1ull << V) - 1ull;
+    return SD3D_OK;
+}
+
+extern "C" int sd3d_tsdf_touch(const void* depth, int depth_u16, float depth_scale, const float* intrinsics, const float* cam_to_world, int V,
+                               int Hd, int Wd, float near, float far, float edge_abs, float edge_rel, int use_edges, float inv_voxel,
+                               float half_step, float* vdepth, void* ws, size_t ws_bytes, int64_t capacity, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    TsGeom g = {};
+    if (int rc = ts_geom("tsdf_touch", V, Hd, Wd, 1, 1, capacity, g)) return rc;
+    if ((depth_u16 && !(depth_scale > 0.0f)) || !(near >= 0.0f) || !(far >= near) || (use_edges && (!(edge_abs >= 0.0f) || !(edge_rel >= 0.0f))) ||
+        !(inv_voxel > 0.0f) || !(inv_voxel <= 3.0e38f) || !(half_step > 0.0f) || !(half_step <= 3.0e38f))
+        return sd3d_set_error(SD3D_ERR_ARG, "tsdf_touch: depth_scale > 0 for uint16 depth, 0 <= near <= far, edge_abs, edge_rel >= 0, inv_voxel and "
+                                            "half_step > 0 and finite");
+    TsWs w;
+    if (int rc = ts_check_ws("tsdf_touch", ws, ws_bytes, capacity, w)) return rc;
+    if (hipMemsetAsync(&w.counters[TS_NLIST], 0, 8, st) != hipSuccess) return sd3d_set_error(SD3D_ERR_LAUNCH, "tsdf_touch: memset");
+    if (V == 0) return SD3D_OK;
+    if (!depth || !intrinsics || !cam_to_world || !vdepth) return sd3d_set_error(SD3D_ERR_ARG, "tsdf_touch: NULL argument");
+    g.use_edges = use_edges ? 1 : 0;
+    g.depth_scale = depth_u16 ? depth_scale : 1.0f;
+    g.near = near; g.far = far; g.edge_abs = edge_abs; g.edge_rel = edge_rel; g.inv_voxel = inv_voxel; g.h = half_step;
+    const dim3 grid((unsigned)((int64_t)V * g.tiles_per_view)), block(TS_THREADS);    // <= 64 * 2^18 tiles
+    if (depth_u16)
+        hipLaunchKernelGGL(ts_touch_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)depth, intrinsics, cam_to_world, g, w.keys, w.touched,
+                           w.list, w.counters, vdepth);
+    else
+        hipLaunchKernelGGL(ts_touch_kernel<float>, grid, block, 0, st, (const float*)depth, intrinsics, cam_to_world, g, w.keys, w.touched, w.list,
+                           w.counters, vdepth);
+    SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
+}
+
+extern "C" int sd3d_tsdf_integrate(const float* vdepth, const float* intrinsics, const float* world_to_cam, const void* colors, int V, int Hd,
+                                   int Wd, int Hc, int Wc, float voxel, float trunc, float qscale, void* ws, size_t ws_bytes, int64_t capacity,
+                                   void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    TsGeom g = {};
+    if (int rc = ts_geom("tsdf_integrate", V, Hd, Wd, Hc, Wc, capacity, g)) return rc;
+    if (!(voxel > 0.0f) || !(trunc >= voxel) || !(trunc <= 3.0e38f) || !(qscale > 0.0f) || !(qscale <= 3.0e38f))
+        return sd3d_set_error(SD3D_ERR_ARG, "tsdf_integrate: 0 < voxel <= trunc, qscale > 0, all finite");
+    TsWs w;
+    if (int rc = ts_check_ws("tsdf_integrate", ws, ws_bytes, capacity, w)) return rc;
+    if (V == 0) return SD3D_OK;
+    if (!vdepth || !intrinsics || !world_to_cam || !colors) return sd3d_set_error(SD3D_ERR_ARG, "tsdf_integrate: NULL argument");
+    g.voxel = voxel; g.trunc = trunc; g.qscale = qscale;
+    const int64_t groups = capacity < 16384 ? capacity : 16384;
+    hipLaunchKernelGGL(ts_integrate_kernel, dim3((unsigned)groups), dim3(TS_THREADS), 0, st, vdepth, intrinsics, world_to_cam,
+                       (const uint8_t*)colors, g, w.keys, w.touched, w.list, w.vox, w.counters);
+    SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
+}
+
+// cell keys a, b uint64 [n] | indices a, b uint32 [n] | vertices float [n][6] | cell refs uint32 [n] | sorted refs uint32 [n] | counts,
+// offsets int32 [n] | nlive, nquads int32 | sort scratch | scan scratch
+struct TsScratch {
+    uint64_t *keys_a, *keys_b;
+    uint32_t *idx_a, *idx_b, *cref, *sref;
+    float* cvert;
+    int32_t *count, *offset, *ints;
+    void *sort_ws, *scan_ws;
+    size_t sort_bytes, scan_bytes, total;
+};
+static TsScratch ts_scratch(void* ws, int64_t n) {
+    TsScratch s;
+    char* p = (char*)ws;
+    size_t o = 0;
+    const size_t m = (size_t)n;
+    auto take = [&](size_t bytes) { char* q = p + o; o += align_up(bytes, 256); return (void*)q; };
+    s.keys_a = (uint64_t*)take(m * 8); s.keys_b = (uint64_t*)take(m * 8);
+    s.idx_a = (uint32_t*)take(m * 4); s.idx_b = (uint32_t*)take(m * 4);
+    s.cvert = (float*)take(m * 24);
+    s.cref = (uint32_t*)take(m * 4); s.sref = (uint32_t*)take(m * 4);
+    s.count = (int32_t*)take(m * 4); s.offset = (int32_t*)take(m * 4);
+    s.ints = (int32_t*)take(8);
+    s.sort_bytes = sort_ws_bytes(n); s.sort_ws = take(s.sort_bytes);
+    s.scan_bytes = scan_ws_bytes(n); s.scan_ws = take(s.scan_bytes);
+    s.total = o;
+    return s;
+}
+static bool ts_vertices_ok(int64_t n) { return n >= 1 && n <= SD3D_TSDF_MAX_VERTICES; }
+extern "C" size_t sd3d_tsdf_mesh_ws_bytes(int64_t max_vertices) { return ts_vertices_ok(max_vertices) ? ts_scratch(nullptr, max_vertices).total : 0; }
+
+extern "C" int sd3d_tsdf_mesh(void* ws, size_t ws_bytes, int64_t capacity, int min_weight, float voxel, int64_t max_vertices, void* scratch,
+                              size_t scratch_bytes, float* vertices, int64_t* keys_out, int32_t* faces, int64_t* info, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    TsWs w;
+    if (int rc = ts_check_ws("tsdf_mesh", ws, ws_bytes, capacity, w)) return rc;
+    if (min_weight < 1 || !(voxel > 0.0f) || !ts_vertices_ok(max_vertices) || !vertices || !faces || !info)
+        return sd3d_set_error(SD3D_ERR_ARG, "tsdf_mesh: min_weight >= 1, voxel > 0, 1 <= max_vertices <= 2^26, vertices, faces and info required");
+    if (!scratch || ((uintptr_t)scratch & 255) != 0) return sd3d_set_error(SD3D_ERR_ARG, "tsdf_mesh: scratch is required and must be 256-byte aligned");
+    const TsScratch s = ts_scratch(scratch, max_vertices);
+    if (scratch_bytes < s.total) return sd3d_set_error(SD3D_ERR_WS, "tsdf_mesh: scratch too small (sd3d_tsdf_mesh_ws_bytes)");
+    if (hipMemsetAsync(&w.counters[TS_NVERT], 0, 2 * 8, st) != hipSuccess ||                                   // vertices and observed voxels
+        hipMemsetAsync(s.keys_a, 0xFF, (size_t)max_vertices * 8, st) != hipSuccess)
+        return sd3d_set_error(SD3D_ERR_LAUNCH, "tsdf_mesh: memset");
+    TsMesh m;
+    m.keys = w.keys; m.vox = w.vox; m.cellvert = w.cellvert; m.mask = (uint32_t)(capacity - 1); m.min_weight = min_weight; m.voxel = voxel;
+    m.max_vertices = max_vertices;
+    hipLaunchKernelGGL(ts_cells_kernel, dim3((unsigned)capacity), dim3(TS_THREADS), 0, st, m, s.keys_a, s.cvert, s.cref, w.counters);
+    int landed = 0;
+    if (int rc = sort_pairs_u64(s.keys_a, nullptr, s.keys_b, s.idx_b, max_vertices, 0, 64, s.sort_ws, s.sort_bytes, st, s.idx_a, &landed)) return rc;
+    const dim3 grid((unsigned)cdiv(max_vertices, 256)), block(256);
+    int32_t *nlive = s.ints, *nquads = s.ints + 1;
+    hipLaunchKernelGGL(ts_vertices_kernel, grid, block, 0, st, landed ? s.keys_a : s.keys_b, landed ? s.idx_a : s.idx_b, s.cvert, s.cref,
+                       max_vertices, capacity * TS_VOX, vertices, keys_out, s.sref, w.cellvert, w.counters, nlive);
+    hipLaunchKernelGGL(ts_quads_kernel<false>, grid, block, 0, st, m, s.sref, nlive, s.count, nullptr, nullptr, nullptr, w.counters, nullptr);
+    if (int rc = scan_exclusive_i32(s.count, s.offset, max_vertices, nlive, nquads, s.scan_ws, s.scan_bytes, st)) return rc;
+    hipLaunchKernelGGL(ts_quads_kernel<true>, grid, block, 0, st, m, s.sref, nlive, nullptr, s.offset, nquads, faces, w.counters, info);
+    SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
+}

@@ -37,8 +37,8 @@ The table has `capacity` slots and does not grow.  A cell that finds no slot wit
 counted in `overflow`; `result()` then raises: a scene that does not fit is an error, not a thinner cloud.  Use a larger `capacity`
 (64 bytes a slot) or a larger `voxel`.
 
-Out of scope: reading image files, TSDF integration and meshing, growing the table, per-point normals (`superpoints.point_superpoints`
-computes its own)."""
+Out of scope: reading image files, growing the table, per-point normals (`superpoints.point_superpoints` computes its own); a mesh
+from the same frames is `tsdf.py`."""
 from __future__ import annotations
 
 from collections import namedtuple

@@ -2713,6 +2713,163 @@ def fuse_emit(ws, capacity: int, min_obs: int, out_cap: int, want_keys: bool = F
 
 
 # --------------------------------------------------------------------------------------------
+# TSDF fusion and the surface-net mesh (csrc/tsdf.hip; the rule: include/segdino3d_hip.h, segdino3d_amd/tsdf.py)
+# --------------------------------------------------------------------------------------------
+TSDF_MIN_CAPACITY = 16
+TSDF_MAX_CAPACITY = 1 << 20
+TSDF_MAX_CALL_VIEWS = 64
+TSDF_MAX_VERTICES = 1 << 26
+TSDF_VOXEL_WORDS = 5
+TSDF_INFO = ("vertices", "faces", "blocks", "voxels_observed", "updates", "out_of_range", "overflow")
+
+
+def _tsdf_capacity(capacity, who):
+    if int(capacity) != capacity or not TSDF_MIN_CAPACITY <= capacity <= TSDF_MAX_CAPACITY or capacity & (capacity - 1):
+        raise ValueError(f"{who}: capacity must be a power of two in [{TSDF_MIN_CAPACITY}, 2^20] (blocks of 8 x 8 x 8 voxels), got {capacity}")
+    return int(capacity)
+
+
+def tsdf_workspace(capacity: int, device):
+    """The caller-owned state of one volume: an emptied block table of `capacity` blocks (a power of two) with zeroed voxels and
+    counters, as a uint8 device tensor (`sd3d_tsdf_ws_bytes`, `sd3d_tsdf_reset`).  Enqueues only."""
+    lib = _lib.load()
+    capacity = _tsdf_capacity(capacity, "tsdf_workspace")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"tsdf_workspace: expected the HIP device, got {device} (no CPU fallback)")
+    ws = torch.empty(lib.sd3d_tsdf_ws_bytes(capacity), dtype=torch.uint8, device=device)
+    tsdf_reset(ws, capacity)
+    return ws
+
+
+def tsdf_reset(ws, capacity: int):
+    """Empties the block table and zeroes the voxels and the counters (`sd3d_tsdf_reset`).  Enqueues only."""
+    lib = _lib.load()
+    _lib.check(lib.sd3d_tsdf_reset(_ptr(ws, torch.uint8, "tsdf_reset: ws"), ws.numel(), _tsdf_capacity(capacity, "tsdf_reset"), _stream()),
+               "tsdf_reset")
+
+
+def tsdf_state_views(ws, capacity: int):
+    """The parts of a volume's workspace as views of it, by the layout include/segdino3d_hip.h gives: (counters int64 [7], block keys
+    int64 [capacity], voxels int32 [capacity, 5, 512])."""
+    capacity = _tsdf_capacity(capacity, "tsdf_state_views")
+    up = lambda n: -(-n // 256) * 256                                                    # noqa: E731
+    o_keys = up(7 * 8)
+    o_vox = o_keys + 2 * up(capacity * 8) + up(capacity * 4)
+    n_vox = capacity * TSDF_VOXEL_WORDS * 512 * 4
+    if ws.dtype != torch.uint8 or ws.numel() < o_vox + n_vox:
+        raise RuntimeError("tsdf_state_views: workspace too small (sd3d_tsdf_ws_bytes)")
+    return (ws[:56].view(torch.int64), ws[o_keys:o_keys + capacity * 8].view(torch.int64),
+            ws[o_vox:o_vox + n_vox].view(torch.int32).view(capacity, TSDF_VOXEL_WORDS, 512))
+
+
+def _tsdf_depth(depth, depth_scale, who):
+    if depth.dim() != 3:
+        raise ValueError(f"{who}: depth must be [V, Hd, Wd], got {list(depth.shape)}")
+    V, Hd, Wd = depth.shape
+    if V > TSDF_MAX_CALL_VIEWS:
+        raise ValueError(f"{who}: at most {TSDF_MAX_CALL_VIEWS} views a call, got {V}")
+    if not (1 <= Hd <= FUSE_MAX_DIM and 1 <= Wd <= FUSE_MAX_DIM):
+        raise ValueError(f"{who}: depth images must be 1 .. {FUSE_MAX_DIM} a side, got {Hd} x {Wd}")
+    if depth.dtype == torch.uint16:
+        if depth_scale is None or not float(depth_scale) > 0.0:
+            raise ValueError(f"{who}: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
+        return 1, float(depth_scale)
+    if depth.dtype == torch.float32:
+        if depth_scale is not None:
+            raise ValueError(f"{who}: fp32 depth is in metres and takes no depth_scale")
+        return 0, 1.0
+    raise TypeError(f"{who}: depth must be uint16 or fp32, got {depth.dtype}")
+
+
+def _tsdf_f32(x, name, who):
+    x32 = float(np.float32(x))
+    if not (x32 > 0.0 and np.isfinite(x32)):
+        raise ValueError(f"{who}: {name} must be positive and finite in fp32, got {x}")
+    return x32
+
+
+def tsdf_touch(depth, depth_scale, intrinsics, cam_to_world, ws, capacity: int, inv_voxel: float, half_step: float, near=0.1, far=6.0,
+               edge_abs=0.02, edge_rel=0.02):
+    """Steps 1 and 2 of the TSDF rule for V <= 64 views (`sd3d_tsdf_touch`): marks the blocks each view touches in the table of `ws`
+    and -> vdepth fp32 [V, Hd, Wd], the depth of each valid pixel and 0 elsewhere, for `tsdf_integrate` of the same views.
+    `inv_voxel` and `half_step` (= trunc / 2) are rounded to fp32 here; `edge_rel=None` turns the edge test off.  Enqueues only."""
+    lib = _lib.load()
+    who = "tsdf_touch"
+    u16, scale = _tsdf_depth(depth, depth_scale, who)
+    V, Hd, Wd = depth.shape
+    _want_shape(intrinsics, [(V, 4)], f"{who}: intrinsics")
+    _want_shape(cam_to_world, [(V, 3, 4)], f"{who}: cam_to_world")
+    if not (float(near) >= 0.0 and float(far) >= float(near)):
+        raise ValueError(f"{who}: need 0 <= near <= far, got near = {near}, far = {far}")
+    use_edges = edge_rel is not None
+    if use_edges and not (float(edge_abs) >= 0.0 and float(edge_rel) >= 0.0):
+        raise ValueError(f"{who}: edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {edge_abs}, {edge_rel}")
+    inv32, h32 = _tsdf_f32(inv_voxel, "inv_voxel", who), _tsdf_f32(half_step, "half_step", who)
+    dp, ip = _ptr(depth, None, f"{who}: depth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
+    cp, wp = _ptr(cam_to_world, torch.float32, f"{who}: cam_to_world"), _ptr(ws, torch.uint8, f"{who}: ws")
+    vdepth = torch.empty(V, Hd, Wd, dtype=torch.float32, device=depth.device)
+    _lib.check(lib.sd3d_tsdf_touch(dp if V else None, u16, scale, ip if V else None, cp if V else None, V, Hd, Wd, float(near), float(far),
+                                   float(edge_abs) if use_edges else 0.0, float(edge_rel) if use_edges else 0.0, int(use_edges), inv32, h32,
+                                   _ptr(vdepth) if V else None, wp, ws.numel(), _tsdf_capacity(capacity, who), _stream()), who)
+    return vdepth
+
+
+def tsdf_integrate(vdepth, intrinsics, world_to_cam, colors, ws, capacity: int, voxel: float, trunc: float, qscale: float):
+    """Step 3 of the TSDF rule (`sd3d_tsdf_integrate`) for the views of the `tsdf_touch` that made `vdepth` fp32 [V, Hd, Wd]:
+    intrinsics fp32 [V, 4], world_to_cam fp32 [V, 3, 4], colors uint8 [V, Hc, Wc, 3]; `voxel`, `trunc` and `qscale` (= 4096 / trunc) are
+    rounded to fp32 here.  Enqueues only."""
+    lib = _lib.load()
+    who = "tsdf_integrate"
+    u16, _ = _tsdf_depth(vdepth, None, who)
+    if u16:
+        raise TypeError(f"{who}: vdepth must be the fp32 output of tsdf_touch")
+    V, Hd, Wd = vdepth.shape
+    _want_shape(intrinsics, [(V, 4)], f"{who}: intrinsics")
+    _want_shape(world_to_cam, [(V, 3, 4)], f"{who}: world_to_cam")
+    if colors.dtype != torch.uint8:
+        raise TypeError(f"{who}: colors must be uint8, got {colors.dtype}")
+    if colors.dim() != 4 or colors.shape[0] != V or colors.shape[3] != 3 or not (1 <= colors.shape[1] <= FUSE_MAX_DIM and
+                                                                                  1 <= colors.shape[2] <= FUSE_MAX_DIM):
+        raise ValueError(f"{who}: colors must be [V = {V}, Hc, Wc, 3] with 1 .. {FUSE_MAX_DIM} a side, got {list(colors.shape)}")
+    Hc, Wc = colors.shape[1:3]
+    v32, t32, q32 = _tsdf_f32(voxel, "voxel", who), _tsdf_f32(trunc, "trunc", who), _tsdf_f32(qscale, "qscale", who)
+    if not t32 >= v32:
+        raise ValueError(f"{who}: need voxel <= trunc, got {voxel}, {trunc}")
+    dp, ip = _ptr(vdepth, torch.float32, f"{who}: vdepth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
+    mp, kp = _ptr(world_to_cam, torch.float32, f"{who}: world_to_cam"), _ptr(colors, torch.uint8, f"{who}: colors")
+    wp = _ptr(ws, torch.uint8, f"{who}: ws")
+    if V == 0:
+        return
+    _lib.check(lib.sd3d_tsdf_integrate(dp, ip, mp, kp, V, Hd, Wd, Hc, Wc, v32, t32, q32, wp, ws.numel(), _tsdf_capacity(capacity, who),
+                                       _stream()), who)
+
+
+def tsdf_mesh(ws, capacity: int, min_weight: int, voxel: float, max_vertices: int, want_keys: bool = False):
+    """Steps 4 to 6 of the TSDF rule (`sd3d_tsdf_mesh`) -> (vertices fp32 [max_vertices, 6], keys int64 [max_vertices] or None, faces
+    int32 [6 * max_vertices, 3], info int64 [7] = TSDF_INFO on the device): the first min(info[0], max_vertices) vertices and the
+    first info[1] faces are written.  The volume is left as it is.  Enqueues only."""
+    lib = _lib.load()
+    who = "tsdf_mesh"
+    if int(min_weight) != min_weight or not 1 <= min_weight <= 0x7FFFFFFF:
+        raise ValueError(f"{who}: min_weight must be an integer >= 1, got {min_weight}")
+    if int(max_vertices) != max_vertices or not 1 <= max_vertices <= TSDF_MAX_VERTICES:
+        raise ValueError(f"{who}: max_vertices must be an integer in [1, 2^26], got {max_vertices}")
+    max_vertices = int(max_vertices)
+    v32 = _tsdf_f32(voxel, "voxel", who)
+    wp = _ptr(ws, torch.uint8, f"{who}: ws")
+    dev = ws.device
+    scratch = torch.empty(lib.sd3d_tsdf_mesh_ws_bytes(max_vertices), dtype=torch.uint8, device=dev)
+    vertices = torch.empty(max_vertices, 6, dtype=torch.float32, device=dev)
+    keys = torch.empty(max_vertices, dtype=torch.int64, device=dev) if want_keys else None
+    faces = torch.empty(6 * max_vertices, 3, dtype=torch.int32, device=dev)
+    info = torch.empty(len(TSDF_INFO), dtype=torch.int64, device=dev)
+    _lib.check(lib.sd3d_tsdf_mesh(wp, ws.numel(), _tsdf_capacity(capacity, who), int(min_weight), v32, max_vertices, scratch.data_ptr(),
+                                  scratch.numel(), _ptr(vertices), _ptr(keys) if want_keys else None, _ptr(faces), _ptr(info), _stream()),
+               who)
+    return vertices, keys, faces, info
+
+
+# --------------------------------------------------------------------------------------------
 # nearest point: results of a forward carried onto other points and onto frames (csrc/transfer.hip; the rule: include/segdino3d_hip.h,
 # segdino3d_amd/transfer.py)
 # --------------------------------------------------------------------------------------------
