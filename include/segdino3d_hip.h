@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 21
+#define SD3D_ABI_VERSION 22
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1429,6 +1429,47 @@ int sd3d_nearest_pixels(const void* depth, int depth_u16, float depth_scale, con
                         const int32_t* labels, int n_labels, int fill, int32_t* idx_out, float* d2_out, int32_t* labels_out, void* stream);
 int sd3d_instance_map(const void* masks, const float* scores, int n_instances, int64_t n_points, float score_thr, int32_t* map,
                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Camera tracking against the TSDF volume (csrc/track.hip): frame-to-model alignment of a depth frame on the signed distance field
+ * of sd3d_tsdf_*, which turns an ordered stream of UNPOSED frames into the poses the fusion above starts from.  The reference has no
+ * counterpart (its poses were made offline); tests/track_ref.py restates the rule below in numpy and the kernels EQUAL it, bit for
+ * bit.  segdino3d_amd/track.py has the rule in full.  The calls only enqueue work.
+ *
+ *   State: cam_to_world [R | t] as double [12]; steps 1 to 4 read its fp32 rounding.  One ITERATION at stride s:
+ *   1. Samples: depth pixels (vi, ui) with vi % s == 0 and ui % s == 0, valid by step 1 of the TSDF rule (edge test at full resolution).
+ *   2. p by csrc/backproject.h, y_i = (R_i0 p_x + R_i1 p_y) + R_i2 p_z, w_i = y_i + t_i; dropped unless all |w_i| < 2^14 and all
+ *      |y_i| <= ymax (ymax = far sqrt(3): what bounds the sums).
+ *   3. g_i = w_i * inv_voxel - 0.5f, c_i = floorf(g_i), f_i = g_i - c_i; the eight voxels c + {0,1}^3 must lie in [-2^20, 2^20) (as
+ *      floats) and have W >= min_weight; value (float)((double)T / (double)W) * (1 / 4096); phi = the trilinear interpolant, lerped
+ *      along x, then y, then z as a + (b - a) * f; n = its analytic gradient: the same lerps over the four corner differences per axis.
+ *   4. q = y * inv_voxel; J = (q x n, n), the cross product term by term; Jq_k = (int)rintf(J_k * 1024), rq = (int)rintf(phi * 16384);
+ *      int64 sums A += Jq Jq^T (21, the upper triangle row-major), b += Jq rq (6), count += 1, e += rq rq.
+ *   5. One lane, double, + - * / only: A_kk *= 1 + (double)damping, an A_kk of exactly 0 becomes 1 (x_k = 0); L D L^T without
+ *      pivoting; x = -(A^-1 b) / 16.  The iteration is LOST iff count < min_samples, a pivot is not > 0, x is not finite,
+ *      |x_rot|^2 > max_rot^2 or |x_trans voxel|^2 > max_trans^2.
+ *   6. a = x_rot / 2, dR = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a); R <- dR R (three-term sums, left to right); t <- t + x_trans
+ *      voxel.  After a lost iteration the later iterations of the frame do nothing.
+ *
+ *   The state is caller-owned, sd3d_track_state_bytes() bytes, 8-byte aligned: pose double [12] | the pose before the frame double
+ *   [12] | lost, count, e | the SD3D_TRACK_SUMS sums in flight at word 32 | those of the last iteration that ran at word 64 (A, b,
+ *   count, e).  The caller writes the first pose into words 0 .. 11.
+ *   sd3d_track_begin: remembers the pose, clears lost and the sums.
+ *   sd3d_track_iterate: one iteration of ONE frame (depth [Hd, Wd], intrinsics float [4]) against the volume in `ws` (read only).
+ *     Refuses (4096 ymax inv_voxel + 2)^2 * samples >= 2^63.
+ *   sd3d_track_end: a lost frame puts the pose back.  pose double [12] (NaN when lost), cam_to_world and world_to_cam float [12] as
+ *     sd3d_tsdf_touch / sd3d_tsdf_integrate take them (world_to_cam = [R^T | -(R^T t)], in double, each entry rounded once), info
+ *     int64 [SD3D_TRACK_INFO_WORDS] = lost, count and e of the last iteration that ran.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_TRACK_SUMS 29
+#define SD3D_TRACK_INFO_WORDS 3
+size_t sd3d_track_state_bytes(void);
+int sd3d_track_begin(void* state, size_t state_bytes, void* stream);
+int sd3d_track_iterate(const void* depth, int depth_u16, float depth_scale, const float* intrinsics, int Hd, int Wd, int stride, float near,
+                       float far, float edge_abs, float edge_rel, int use_edges, float inv_voxel, float voxel, float ymax, int min_weight,
+                       int min_samples, float damping, float max_rot, float max_trans, void* state, size_t state_bytes, void* ws,
+                       size_t ws_bytes, int64_t capacity, void* stream);
+int sd3d_track_end(void* state, size_t state_bytes, double* pose, float* cam_to_world, float* world_to_cam, int64_t* info, void* stream);
 
 #ifdef __cplusplus
 }

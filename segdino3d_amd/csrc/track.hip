@@ -1,0 +1,347 @@
+// Camera tracking against the TSDF volume (frame-to-model alignment on the signed distance field itself, as Bylow et al. and the
+// SDF-Tracker do): what turns an ordered stream of UNPOSED depth frames into the poses lift2d.Views and tsdf.TsdfVolume start from.
+// The reference reads poses made offline and ships no tracker: tests/track_ref.py, a numpy restatement of the rule in
+// segdino3d_amd/track.py and include/segdino3d_hip.h, is what these kernels are pinned against, bit for bit.
+//
+// The rule in short (segdino3d_amd/track.py has it in full).  State: cam_to_world [R | t] as float64 [3, 4]; the kernels read its fp32
+// rounding.  One iteration at stride s:
+//   1. a sample is a depth pixel (vi, ui), vi % s == 0 and ui % s == 0, valid by step 1 of the TSDF rule (full-resolution edge test);
+//   2. p by backproject.h, y = R p (relative to the camera centre), w = y + t; all |w_i| < 2^14 and all |y_i| <= ymax or dropped;
+//   3. g = w * inv_voxel - 0.5, c = floor(g), f = g - c; the eight voxels c + {0,1}^3 in range and W >= min_weight or dropped; each
+//      value float32((double) T / (double) W) * (1 / 4096); phi = the trilinear interpolant (x, then y, then z, a + (b - a) * f), n
+//      its analytic gradient (the same lerps over the four corner differences along each axis);
+//   4. q = y * inv_voxel, J = (q x n, n), Jq = rint(J * 1024), rq = rint(phi * 16384); int64 sums A += Jq Jq^T (21), b += Jq rq (6),
+//      count += 1, e += rq rq: a function of the SET of samples;
+//   5. one lane, float64, + - * / only: A_kk *= 1 + damping (an A_kk of exactly 0 becomes 1), L D L^T without pivoting, x = -(A^-1 b)
+//      / 16; lost iff count < min_samples, a pivot <= 0, x not finite, |x_rot|^2 > max_rot^2 or |x_trans voxel|^2 > max_trans^2;
+//   6. a = x_rot / 2, dR = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a) (Cayley), R <- dR R, t <- t + x_trans voxel.
+// A frame: begin (remember the state), a fixed schedule of iterations, end (a lost frame puts the state back and emits NaN).
+//
+// State (caller-owned, sd3d_track_state_bytes, 128 words of 8 bytes): the pose double [12] | the pose before the frame double [12] |
+// lost | count and e of the last iteration that ran | 5 spare | the 29 sums int64 being accumulated | 3 spare | at word 64 the 29
+// sums of the last iteration that ran, kept for inspection and the tests.
+//
+//   sd3d_track_begin    tk_begin_kernel       one lane.
+//   sd3d_track_iterate  tk_accumulate_kernel  a workgroup of 256 lanes takes a tile of 8 x 32 SAMPLES (the grid is the strided one), a
+//                                             lane a sample.  Neighbouring samples land in the same few blocks: each lane puts the
+//                                             blocks of its eight corners into an LDS set (64-bit compare-and-swap, as ts_touch_kernel
+//                                             does), the workgroup then probes the global table ONCE per distinct block, and each
+//                                             lane reads its sixteen words through the slots it remembered.  The 29 int64 sums go
+//                                             through wave_sum and LDS to one 64-bit atomic add each per workgroup: integers, so the
+//                                             order of the workgroups cannot change a bit.
+//                       tk_solve_kernel       one lane: steps 5 and 6; zeroes the sums for the next iteration.
+//   sd3d_track_end      tk_end_kernel         one lane: the pose as float64 and as the fp32 cam_to_world / world_to_cam the TSDF
+//                                             integration takes, lost, count, e.
+#include "common.h"
+// The kernels here must EQUAL a float32 / float64 evaluation of the restatement: nothing in this file may be contracted into a fused
+// multiply-add.  The pragma covers backproject.h as it is compiled here and every expression below.
+#pragma clang fp contract(off)
+#include "backproject.h"
+#include "tsdf_table.h"
+
+#define TK_THREADS 256
+#define TK_TILE_W 32
+#define TK_TILE_H 8
+#define TK_LDS_SLOTS 4096                               // 8 corners of 256 samples = 2048 keys at most: the LDS probe always ends
+#define TK_MAX_DIM 16384                                // image extents and the stride
+#define TK_SUMS SD3D_TRACK_SUMS
+
+// the words of the state, 8 bytes each
+enum { TK_CUR = 0, TK_SAVED = 12, TK_LOST = 24, TK_COUNT = 25, TK_E = 26, TK_SUM0 = 32, TK_LAST = 64, TK_WORDS = 128 };
+
+struct TkGeom {
+    int Hd, Wd, stride, tiles_x, use_edges, min_weight;
+    float depth_scale, near, far, edge_abs, edge_rel, inv_voxel, ymax;
+    uint32_t mask;                                      // capacity - 1
+};
+
+__device__ __forceinline__ float tk_metres(uint16_t raw, float scale) { return (float)raw * scale; }
+__device__ __forceinline__ float tk_metres(float d, float) { return d; }
+__device__ __forceinline__ bool tk_jump(float dn, float d, float thr) { return !(dn > 0.0f) || fabsf(dn - d) > thr; }
+__device__ __forceinline__ float tk_lerp(float a, float b, float f) { return a + (b - a) * f; }
+
+// ---------------------------------------------------------------------------------------------- steps 1 to 4
+template <typename D>
+__global__ __launch_bounds__(TK_THREADS) void tk_accumulate_kernel(const D* __restrict__ depth, const float* __restrict__ intr, TkGeom g,
+                                                                   const ts_u64* __restrict__ keys, const int32_t* __restrict__ vox,
+                                                                   ts_u64* __restrict__ state) {
+    __shared__ ts_u64 s_key[TK_LDS_SLOTS];
+    __shared__ int s_slot[TK_LDS_SLOTS];
+    __shared__ long long s_part[TK_THREADS / 64][TK_SUMS];
+    if (state[TK_LOST] != 0) return;                                                  // uniform: a lost frame's iterations do nothing
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int ty = blockIdx.x / g.tiles_x, tx = blockIdx.x - ty * g.tiles_x;
+    for (int i = t; i < TK_LDS_SLOTS; i += TK_THREADS) s_key[i] = SD3D_EMPTY_KEY;
+    __syncthreads();
+
+    // sample (sy, sx) of the strided grid is pixel (sy * stride, sx * stride): both below 2^14 * 2^14 / stride + 8 * stride < 2^31
+    const int vi = (ty * TK_TILE_H + (t >> 5)) * g.stride, ui = (tx * TK_TILE_W + (t & 31)) * g.stride;
+    bool ok = false;
+    float y[3] = {0.0f, 0.0f, 0.0f}, f[3] = {0.0f, 0.0f, 0.0f};
+    int c[3] = {0, 0, 0}, ls[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (vi < g.Hd && ui < g.Wd) {
+        const D* row = depth + (int64_t)vi * g.Wd;
+        const float d = tk_metres(row[ui], g.depth_scale);
+        ok = d > 0.0f && d >= g.near && d <= g.far;                                   // a NaN fails
+        if (ok && g.use_edges) {
+            const float thr = g.edge_abs + g.edge_rel * d;                            // two roundings: contraction is off
+            if (vi > 0) ok = ok && !tk_jump(tk_metres(row[ui - g.Wd], g.depth_scale), d, thr);
+            if (vi + 1 < g.Hd) ok = ok && !tk_jump(tk_metres(row[ui + g.Wd], g.depth_scale), d, thr);
+            if (ui > 0) ok = ok && !tk_jump(tk_metres(row[ui - 1], g.depth_scale), d, thr);
+            if (ui + 1 < g.Wd) ok = ok && !tk_jump(tk_metres(row[ui + 1], g.depth_scale), d, thr);
+        }
+        if (ok) {
+            const double* cur = (const double*)state + TK_CUR;                        // the fp32 rounding of the state; t apart: y = R p
+            const Sd3dCamera cam = {intr[0], intr[1], intr[2], intr[3], (float)cur[0], (float)cur[1], (float)cur[2], 0.0f,
+                                    (float)cur[4], (float)cur[5], (float)cur[6], 0.0f, (float)cur[8], (float)cur[9], (float)cur[10], 0.0f};
+            const float tr[3] = {(float)cur[3], (float)cur[7], (float)cur[11]};
+            sd3d_backproject(cam, vi, ui, d, y[0], y[1], y[2]);                        // + 0.0f changes no value the rule reads
+            const float lim = (float)(1 << SD3D_FUSE_WORLD_BITS), cells = (float)TS_CELL_BIAS;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float w = y[i] + tr[i];
+                ok = ok && fabsf(w) < lim && fabsf(y[i]) <= g.ymax;                    // NaN and infinities stop here
+                const float gg = w * g.inv_voxel - 0.5f, cf = floorf(gg);
+                f[i] = gg - cf;
+                ok = ok && cf >= -cells && cf + 1.0f < cells;                          // as floats, before anything becomes an integer
+                c[i] = ok ? (int)cf : 0;
+            }
+        }
+        if (ok) {
+            ts_u64 last = SD3D_EMPTY_KEY;
+            int last_slot = 0;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {                                             // corner m = (dx, dy, dz) = bits 2, 1, 0
+                const ts_u64 key = ts_block_key((c[0] + (m >> 2)) >> 3, (c[1] + ((m >> 1) & 1)) >> 3, (c[2] + (m & 1)) >> 3);
+                if (key != last) {
+                    int slot = (int)(hash_u64(key) >> 20);                             // the top 12 bits; the global table takes the low ones
+                    for (;;) {                                                        // at most 2048 keys in 4096 slots: it ends
+                        const ts_u64 prev = atomicCAS(&s_key[slot], (ts_u64)SD3D_EMPTY_KEY, key);
+                        if (prev == SD3D_EMPTY_KEY || prev == key) break;
+                        slot = (slot + 1) & (TK_LDS_SLOTS - 1);
+                    }
+                    last = key;
+                    last_slot = slot;
+                }
+                ls[m] = last_slot;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- one probe of the global table per distinct block of the tile
+    for (int i = t; i < TK_LDS_SLOTS; i += TK_THREADS) {
+        const ts_u64 key = s_key[i];
+        if (key != SD3D_EMPTY_KEY) s_slot[i] = ts_find_key(keys, g.mask, key);
+    }
+    __syncthreads();
+
+    long long acc[TK_SUMS];
+#pragma unroll
+    for (int k = 0; k < TK_SUMS; ++k) acc[k] = 0;
+    if (ok) {
+        float v[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int slot = s_slot[ls[m]];                                           // -1, or inside the table: 0 <= slot <= mask
+            int W = 0, T = 0;
+            if (slot >= 0) {
+                const int32_t* b = vox + (size_t)slot * (TS_WORDS * TS_VOX) +
+                                   ((((c[0] + (m >> 2)) & 7) << 6) | (((c[1] + ((m >> 1) & 1)) & 7) << 3) | ((c[2] + (m & 1)) & 7));
+                W = b[0]; T = b[TS_VOX];
+            }
+            ok = ok && W >= g.min_weight;                                             // min_weight >= 1: an absent block fails too
+            v[m] = W > 0 ? (float)((double)T / (double)W) * (1.0f / 4096.0f) : 0.0f;
+        }
+        if (ok) {
+            const float fx = f[0], fy = f[1], fz = f[2];
+            const float phi = tk_lerp(tk_lerp(tk_lerp(v[0], v[4], fx), tk_lerp(v[2], v[6], fx), fy),
+                                      tk_lerp(tk_lerp(v[1], v[5], fx), tk_lerp(v[3], v[7], fx), fy), fz);
+            const float nx = tk_lerp(tk_lerp(v[4] - v[0], v[6] - v[2], fy), tk_lerp(v[5] - v[1], v[7] - v[3], fy), fz);
+            const float ny = tk_lerp(tk_lerp(v[2] - v[0], v[6] - v[4], fx), tk_lerp(v[3] - v[1], v[7] - v[5], fx), fz);
+            const float nz = tk_lerp(tk_lerp(v[1] - v[0], v[5] - v[4], fx), tk_lerp(v[3] - v[2], v[7] - v[6], fx), fy);
+            const float q0 = y[0] * g.inv_voxel, q1 = y[1] * g.inv_voxel, q2 = y[2] * g.inv_voxel;
+            const float J[6] = {q1 * nz - q2 * ny, q2 * nx - q0 * nz, q0 * ny - q1 * nx, nx, ny, nz};
+            long long Jq[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) Jq[k] = (long long)(int)rintf(J[k] * 1024.0f);      // |J_k| 1024 < 2^31: the entry point checked ymax
+            const long long rq = (long long)(int)rintf(phi * 16384.0f);
+            int n = 0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int j = i; j < 6; ++j) acc[n++] = Jq[i] * Jq[j];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) acc[21 + k] = Jq[k] * rq;
+            acc[27] = 1;
+            acc[28] = rq * rq;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < TK_SUMS; ++k) {
+        const long long s = wave_sum(acc[k]);
+        if (lane == 0) s_part[wave][k] = s;
+    }
+    __syncthreads();
+    if (t < TK_SUMS) {
+        const long long s = (s_part[0][t] + s_part[1][t]) + (s_part[2][t] + s_part[3][t]);
+        if (s != 0) atomicAdd(&state[TK_SUM0 + t], (ts_u64)s);                         // two's complement: the wrap of the add is the sum
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- steps 5 and 6
+__global__ void tk_solve_kernel(ts_u64* __restrict__ state, int min_samples, float damping, float voxel, float max_rot, float max_trans) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || state[TK_LOST] != 0) return;
+    long long s[TK_SUMS];
+    for (int k = 0; k < TK_SUMS; ++k) { s[k] = (long long)state[TK_SUM0 + k]; state[TK_SUM0 + k] = 0; state[TK_LAST + k] = (ts_u64)s[k]; }
+    state[TK_COUNT] = (ts_u64)s[27];
+    state[TK_E] = (ts_u64)s[28];
+    bool lost = s[27] < (long long)min_samples;
+    double A[6][6], b[6], L[6][6], Dg[6], z[6], x[6];
+    int n = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) { A[i][j] = (double)s[n]; A[j][i] = A[i][j]; ++n; }
+    for (int i = 0; i < 6; ++i) { b[i] = (double)s[21 + i]; Dg[i] = 0.0; z[i] = 0.0; x[i] = 0.0; }
+    const double scale = 1.0 + (double)damping;
+    // a diagonal sum of exactly 0: no sample moves with that variable, its row, column and b are 0 too; 1 leaves x_i = 0
+    for (int i = 0; i < 6; ++i) A[i][i] = A[i][i] == 0.0 ? 1.0 : A[i][i] * scale;
+    for (int j = 0; j < 6 && !lost; ++j) {
+        double dj = A[j][j];
+        for (int m = 0; m < j; ++m) dj = dj - L[j][m] * (L[j][m] * Dg[m]);
+        if (!(dj > 0.0)) { lost = true; break; }
+        Dg[j] = dj;
+        for (int i = j + 1; i < 6; ++i) {
+            double tt = A[i][j];
+            for (int m = 0; m < j; ++m) tt = tt - L[j][m] * (L[i][m] * Dg[m]);
+            L[i][j] = tt / dj;
+        }
+    }
+    if (!lost) {
+        for (int i = 0; i < 6; ++i) {
+            double tt = b[i];
+            for (int m = 0; m < i; ++m) tt = tt - L[i][m] * z[m];
+            z[i] = tt;
+        }
+        for (int i = 5; i >= 0; --i) {
+            double tt = z[i] / Dg[i];
+            for (int m = i + 1; m < 6; ++m) tt = tt - L[m][i] * x[m];
+            x[i] = tt;
+        }
+        const double vox = (double)voxel;
+        for (int i = 0; i < 6; ++i) {
+            x[i] = -(x[i] * 0.0625);
+            lost = lost || !(fabs(x[i]) <= 1.7976931348623157e308);                    // a NaN or an infinity
+        }
+        const double tv[3] = {x[3] * vox, x[4] * vox, x[5] * vox};
+        const double rot2 = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2], tr2 = (tv[0] * tv[0] + tv[1] * tv[1]) + tv[2] * tv[2];
+        lost = lost || rot2 > (double)max_rot * (double)max_rot || tr2 > (double)max_trans * (double)max_trans;
+    }
+    if (lost) { state[TK_LOST] = 1; return; }
+    double* P = (double*)state + TK_CUR;
+    const double a[3] = {x[0] * 0.5, x[1] * 0.5, x[2] * 0.5};
+    const double aa = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
+    const double den = 1.0 + aa, one = 1.0 - aa;
+    const double p01 = 2.0 * (a[0] * a[1]), p02 = 2.0 * (a[0] * a[2]), p12 = 2.0 * (a[1] * a[2]);
+    const double dR[3][3] = {{(one + 2.0 * (a[0] * a[0])) / den, (p01 - 2.0 * a[2]) / den, (p02 + 2.0 * a[1]) / den},
+                             {(p01 + 2.0 * a[2]) / den, (one + 2.0 * (a[1] * a[1])) / den, (p12 - 2.0 * a[0]) / den},
+                             {(p02 - 2.0 * a[1]) / den, (p12 + 2.0 * a[0]) / den, (one + 2.0 * (a[2] * a[2])) / den}};
+    double out[12];
+    const double vox = (double)voxel;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) out[i * 4 + j] = (dR[i][0] * P[j] + dR[i][1] * P[4 + j]) + dR[i][2] * P[8 + j];
+        out[i * 4 + 3] = P[i * 4 + 3] + x[3 + i] * vox;
+    }
+    for (int i = 0; i < 12; ++i) P[i] = out[i];
+}
+
+__global__ void tk_begin_kernel(ts_u64* __restrict__ state) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    for (int i = 0; i < 12; ++i) state[TK_SAVED + i] = state[TK_CUR + i];
+    state[TK_LOST] = 0; state[TK_COUNT] = 0; state[TK_E] = 0;
+    for (int k = 0; k < TK_SUMS; ++k) { state[TK_SUM0 + k] = 0; state[TK_LAST + k] = 0; }
+}
+
+__global__ void tk_end_kernel(ts_u64* __restrict__ state, double* __restrict__ pose, float* __restrict__ c2w, float* __restrict__ w2c,
+                              int64_t* __restrict__ info) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const bool lost = state[TK_LOST] != 0;
+    info[0] = lost ? 1 : 0; info[1] = (int64_t)state[TK_COUNT]; info[2] = (int64_t)state[TK_E];
+    if (lost) {
+        for (int i = 0; i < 12; ++i) state[TK_CUR + i] = state[TK_SAVED + i];            // the next frame tries again from the last good pose
+        const double nan = __longlong_as_double(0x7FF8000000000000ll);
+        for (int i = 0; i < 12; ++i) { pose[i] = nan; c2w[i] = (float)nan; w2c[i] = (float)nan; }
+        return;
+    }
+    const double* P = (const double*)state + TK_CUR;
+    for (int i = 0; i < 12; ++i) { pose[i] = P[i]; c2w[i] = (float)P[i]; }
+    for (int i = 0; i < 3; ++i) {                                                     // world_to_cam = [R^T | -(R^T t)], each entry rounded once
+        for (int j = 0; j < 3; ++j) w2c[i * 4 + j] = (float)P[j * 4 + i];
+        w2c[i * 4 + 3] = (float)(-((P[i] * P[3] + P[4 + i] * P[7]) + P[8 + i] * P[11]));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- C entry points
+static int tk_check_state(const char* who, void* state, size_t state_bytes) {
+    char msg[160];
+    if (!state || ((uintptr_t)state & 7) != 0 || state_bytes < (size_t)TK_WORDS * 8) {
+        snprintf(msg, sizeof msg, "%s: state is required, 8-byte aligned and sd3d_track_state_bytes() long", who);
+        return sd3d_set_error(SD3D_ERR_ARG, msg);
+    }
+    return SD3D_OK;
+}
+
+extern "C" size_t sd3d_track_state_bytes(void) { return (size_t)TK_WORDS * 8; }
+
+extern "C" int sd3d_track_begin(void* state, size_t state_bytes, void* stream) {
+    if (int rc = tk_check_state("track_begin", state, state_bytes)) return rc;
+    hipLaunchKernelGGL(tk_begin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (ts_u64*)state);
+    SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
+}
+
+extern "C" int sd3d_track_iterate(const void* depth, int depth_u16, float depth_scale, const float* intrinsics, int Hd, int Wd, int stride,
+                                  float near, float far, float edge_abs, float edge_rel, int use_edges, float inv_voxel, float voxel, float ymax,
+                                  int min_weight, int min_samples, float damping, float max_rot, float max_trans, void* state,
+                                  size_t state_bytes, void* ws, size_t ws_bytes, int64_t capacity, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (Hd < 1 || Hd > TK_MAX_DIM || Wd < 1 || Wd > TK_MAX_DIM || stride < 1 || stride > TK_MAX_DIM)
+        return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: images up to 16384 a side, 1 <= stride <= 16384");
+    if ((depth_u16 && !(depth_scale > 0.0f)) || !(near >= 0.0f) || !(far >= near) || (use_edges && (!(edge_abs >= 0.0f) || !(edge_rel >= 0.0f))) ||
+        !(inv_voxel > 0.0f) || !(inv_voxel <= 3.0e38f) || !(voxel > 0.0f) || !(voxel <= 3.0e38f))
+        return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: depth_scale > 0 for uint16 depth, 0 <= near <= far, edge_abs, edge_rel >= 0, inv_voxel "
+                                            "and voxel > 0 and finite");
+    if (min_weight < 1 || min_samples < 1 || !(damping >= 0.0f) || !(damping <= 1.0f) || !(max_rot > 0.0f) || !(max_rot <= 3.0e38f) ||
+        !(max_trans > 0.0f) || !(max_trans <= 3.0e38f))
+        return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: min_weight, min_samples >= 1, 0 <= damping <= 1, max_rot and max_trans > 0 and finite");
+    // the width of the sums: |Jq_k| <= 4096 Q + 2 with Q = ymax * inv_voxel (track.py, "Widths"), over at most `samples` rows
+    const int64_t nx = cdiv(Wd, stride), ny = cdiv(Hd, stride);
+    const double jq = 4096.0 * ((double)ymax * (double)inv_voxel) * 1.001 + 2.0;
+    if (!(ymax > 0.0f) || !(jq < 2147483648.0) || !(jq * jq * (double)(nx * ny) < 9.0e18))
+        return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: ymax > 0 and (4096 ymax inv_voxel + 2)^2 * samples < 2^63 (the int64 sums)");
+    if (int rc = tk_check_state("track_iterate", state, state_bytes)) return rc;
+    TsWs w;
+    if (int rc = ts_check_ws("track_iterate", ws, ws_bytes, capacity, w)) return rc;
+    if (!depth || !intrinsics) return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: NULL argument");
+    TkGeom g = {};
+    g.Hd = Hd; g.Wd = Wd; g.stride = stride; g.use_edges = use_edges ? 1 : 0; g.min_weight = min_weight;
+    g.depth_scale = depth_u16 ? depth_scale : 1.0f;
+    g.near = near; g.far = far; g.edge_abs = edge_abs; g.edge_rel = edge_rel; g.inv_voxel = inv_voxel; g.ymax = ymax;
+    g.mask = (uint32_t)(capacity - 1);
+    g.tiles_x = (int)cdiv(nx, TK_TILE_W);
+    const dim3 grid((unsigned)(g.tiles_x * cdiv(ny, TK_TILE_H))), block(TK_THREADS);  // <= 2^9 * 2^11 tiles
+    if (depth_u16)
+        hipLaunchKernelGGL(tk_accumulate_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)depth, intrinsics, g, w.keys, w.vox, (ts_u64*)state);
+    else
+        hipLaunchKernelGGL(tk_accumulate_kernel<float>, grid, block, 0, st, (const float*)depth, intrinsics, g, w.keys, w.vox, (ts_u64*)state);
+    hipLaunchKernelGGL(tk_solve_kernel, dim3(1), dim3(64), 0, st, (ts_u64*)state, min_samples, damping, voxel, max_rot, max_trans);
+    SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
+}
+
+extern "C" int sd3d_track_end(void* state, size_t state_bytes, double* pose, float* cam_to_world, float* world_to_cam, int64_t* info,
+                              void* stream) {
+    if (int rc = tk_check_state("track_end", state, state_bytes)) return rc;
+    if (!pose || !cam_to_world || !world_to_cam || !info) return sd3d_set_error(SD3D_ERR_ARG, "track_end: NULL argument");
+    hipLaunchKernelGGL(tk_end_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (ts_u64*)state, pose, cam_to_world, world_to_cam, info);
+    SD3D_CHECK_LAUNCH();
+    return SD3D_OK;
+}

@@ -2870,6 +2870,107 @@ def tsdf_mesh(ws, capacity: int, min_weight: int, voxel: float, max_vertices: in
 
 
 # --------------------------------------------------------------------------------------------
+# camera tracking against the TSDF volume (csrc/track.hip; the rule: include/segdino3d_hip.h, segdino3d_amd/track.py)
+# --------------------------------------------------------------------------------------------
+TRACK_SUMS = 29
+TRACK_INFO = ("lost", "count", "e")
+TRACK_MAX_STRIDE = 16384
+
+
+def track_state(device):
+    """The caller-owned state of one tracker (`sd3d_track_state_bytes`), zeroed, as a uint8 device tensor; `track_pose_view` is the
+    pose inside it.  Enqueues only."""
+    lib = _lib.load()
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"track_state: expected the HIP device, got {device} (no CPU fallback)")
+    return torch.zeros(lib.sd3d_track_state_bytes(), dtype=torch.uint8, device=device)
+
+
+def track_pose_view(state):
+    """The current cam_to_world float64 [3, 4] of a tracker's state, as a view of it: the caller writes the first pose here."""
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 1 or state.numel() < 96:
+        raise TypeError("track_pose_view: state must be the uint8 tensor of track_state")
+    return state[:96].view(torch.float64).view(3, 4)
+
+
+def track_sums_view(state):
+    """The 29 integer sums of the last iteration that ran (A: 21, the upper triangle row-major; b: 6; count; e) as an int64 [29] view
+    of a tracker's state: for inspection and the tests."""
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 1 or state.numel() < (64 + TRACK_SUMS) * 8:
+        raise TypeError("track_sums_view: state must be the uint8 tensor of track_state")
+    return state[512:512 + TRACK_SUMS * 8].view(torch.int64)
+
+
+def track_begin(state):
+    """Opens a frame (`sd3d_track_begin`): remembers the pose, clears `lost` and the sums.  Enqueues only."""
+    lib = _lib.load()
+    _lib.check(lib.sd3d_track_begin(_ptr(state, torch.uint8, "track_begin: state"), state.numel(), _stream()), "track_begin")
+
+
+def track_iterate(depth, depth_scale, intrinsics, state, ws, capacity: int, stride: int, inv_voxel: float, voxel: float, ymax: float,
+                  track_min_weight: int = 1, min_samples: int = 64, damping: float = 1e-6, max_rot: float = 0.5, max_trans: float = 0.32,
+                  near=0.1, far=6.0, edge_abs=0.02, edge_rel=0.02):
+    """One iteration of the tracking rule (`sd3d_track_iterate`) for ONE frame - depth uint16 [Hd, Wd] with `depth_scale` or fp32
+    metres, intrinsics fp32 [4] - against the volume in `ws` (read only): the accumulate launch and the one-lane solve + update.  The
+    float parameters are rounded to fp32 here.  Enqueues only."""
+    lib = _lib.load()
+    who = "track_iterate"
+    if depth.dim() != 2:
+        raise ValueError(f"{who}: depth must be [Hd, Wd], one frame, got {list(depth.shape)}")
+    u16, scale = _tsdf_depth(depth[None], depth_scale, who)
+    Hd, Wd = depth.shape
+    _want_shape(intrinsics, [(4,)], f"{who}: intrinsics")
+    if int(stride) != stride or not 1 <= stride <= TRACK_MAX_STRIDE:
+        raise ValueError(f"{who}: stride must be an integer in [1, {TRACK_MAX_STRIDE}], got {stride}")
+    if not (float(near) >= 0.0 and float(far) >= float(near)):
+        raise ValueError(f"{who}: need 0 <= near <= far, got near = {near}, far = {far}")
+    use_edges = edge_rel is not None
+    if use_edges and not (float(edge_abs) >= 0.0 and float(edge_rel) >= 0.0):
+        raise ValueError(f"{who}: edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {edge_abs}, {edge_rel}")
+    if int(track_min_weight) != track_min_weight or not 1 <= track_min_weight <= 0x7FFFFFFF:
+        raise ValueError(f"{who}: track_min_weight must be an integer >= 1, got {track_min_weight}")
+    if int(min_samples) != min_samples or not 1 <= min_samples <= 0x7FFFFFFF:
+        raise ValueError(f"{who}: min_samples must be an integer >= 1, got {min_samples}")
+    if not 0.0 <= float(damping) <= 1.0:
+        raise ValueError(f"{who}: damping must lie in [0, 1], got {damping}")
+    inv32, v32, y32 = _tsdf_f32(inv_voxel, "inv_voxel", who), _tsdf_f32(voxel, "voxel", who), _tsdf_f32(ymax, "ymax", who)
+    r32, t32 = _tsdf_f32(max_rot, "max_rot", who), _tsdf_f32(max_trans, "max_trans", who)
+    samples = -(-Hd // int(stride)) * -(-Wd // int(stride))
+    jq = 4096.0 * (y32 * inv32) * 1.001 + 2.0
+    if not (jq < 2.0 ** 31 and jq * jq * samples < 9.0e18):
+        raise ValueError(f"{who}: (4096 ymax inv_voxel + 2)^2 * samples must stay below 2^63 (the int64 sums), got ymax = {ymax}, "
+                         f"inv_voxel = {inv_voxel}, {samples} samples")
+    dp, ip = _ptr(depth, None, f"{who}: depth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
+    sp, wp = _ptr(state, torch.uint8, f"{who}: state"), _ptr(ws, torch.uint8, f"{who}: ws")
+    _lib.check(lib.sd3d_track_iterate(dp, u16, scale, ip, Hd, Wd, int(stride), float(near), float(far), float(edge_abs) if use_edges else 0.0,
+                                      float(edge_rel) if use_edges else 0.0, int(use_edges), inv32, v32, y32, int(track_min_weight),
+                                      int(min_samples), float(np.float32(damping)), r32, t32, sp, state.numel(), wp, ws.numel(),
+                                      _tsdf_capacity(capacity, who), _stream()), who)
+
+
+def track_end(state, pose=None, cam_to_world=None, world_to_cam=None, info=None):
+    """Closes a frame (`sd3d_track_end`) -> (pose float64 [3, 4], NaN when lost; cam_to_world and world_to_cam fp32 [3, 4] as
+    `tsdf_touch` / `tsdf_integrate` take them; info int64 [3] = TRACK_INFO), written into the given tensors or into new ones.  A lost
+    frame puts the state's pose back.  Enqueues only."""
+    lib = _lib.load()
+    who = "track_end"
+    sp = _ptr(state, torch.uint8, f"{who}: state")
+    dev = state.device
+    pose = torch.empty(3, 4, dtype=torch.float64, device=dev) if pose is None else pose
+    cam_to_world = torch.empty(3, 4, dtype=torch.float32, device=dev) if cam_to_world is None else cam_to_world
+    world_to_cam = torch.empty(3, 4, dtype=torch.float32, device=dev) if world_to_cam is None else world_to_cam
+    info = torch.empty(len(TRACK_INFO), dtype=torch.int64, device=dev) if info is None else info
+    for t, name in ((pose, "pose"), (cam_to_world, "cam_to_world"), (world_to_cam, "world_to_cam")):
+        _want_shape(t, [(3, 4)], f"{who}: {name}")
+    _want_shape(info, [(len(TRACK_INFO),)], f"{who}: info")
+    _lib.check(lib.sd3d_track_end(sp, state.numel(), _ptr(pose, torch.float64, f"{who}: pose"),
+                                  _ptr(cam_to_world, torch.float32, f"{who}: cam_to_world"),
+                                  _ptr(world_to_cam, torch.float32, f"{who}: world_to_cam"), _ptr(info, torch.int64, f"{who}: info"),
+                                  _stream()), who)
+    return pose, cam_to_world, world_to_cam, info
+
+
+# --------------------------------------------------------------------------------------------
 # nearest point: results of a forward carried onto other points and onto frames (csrc/transfer.hip; the rule: include/segdino3d_hip.h,
 # segdino3d_amd/transfer.py)
 # --------------------------------------------------------------------------------------------

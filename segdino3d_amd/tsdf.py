@@ -146,6 +146,41 @@ class TsdfVolume:
             ops.tsdf_integrate(vdepth, intr, views.world_to_cam[s], colors[s], self._ws, self.capacity, self.voxel, self.trunc, self.qscale)
         self.n_views += K
 
+    def add_posed(self, depth, depth_scale, intrinsics, cam_to_world, world_to_cam, colors) -> None:
+        """`add` for frames whose poses are already ON THE DEVICE (`track.Tracker` makes them there): depth [V, Hd, Wd] uint16 with
+        `depth_scale` or fp32 metres, intrinsics fp32 [V, 4], the fp32 `cam_to_world` and `world_to_cam` [V, 3, 4], colors uint8
+        [V, Hc, Wc, 3].  Nothing is read back, so no view can be dropped here: a view with a non-finite pose goes through the same two
+        launches, every one of its samples fails `|w| < 2^14` at step 2 and is counted in `out_of_range`, and it writes no voxel.
+        Every view counts towards the 2^17 of a volume.  Enqueues only."""
+        who = "TsdfVolume.add_posed"
+        for t, name in ((depth, "depth"), (intrinsics, "intrinsics"), (cam_to_world, "cam_to_world"), (world_to_cam, "world_to_cam"),
+                        (colors, "colors")):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{who}: {name}: expected a tensor, got {type(t).__name__}")
+            if not t.is_cuda:
+                raise RuntimeError(f"{who}: {name}: expected a tensor on the HIP device, got {t.device} (no CPU fallback)")
+        if depth.dim() != 3:
+            raise ValueError(f"{who}: depth must be [V, Hd, Wd], got {list(depth.shape)}")
+        K = depth.shape[0]
+        if colors.dtype != torch.uint8:
+            raise TypeError(f"{who}: colors must be uint8, got {colors.dtype}")
+        if colors.dim() != 4 or colors.shape[0] != K or colors.shape[3] != 3 or colors.shape[1] < 1 or colors.shape[2] < 1:
+            raise ValueError(f"{who}: colors must be [V = {K}, Hc, Wc, 3], got {list(colors.shape)}")
+        if K == 0:
+            return
+        if self.n_views + K > MAX_VIEWS:
+            raise ValueError(f"{who}: more than 2^17 views in one volume ({self.n_views} + {K}): the 32-bit sums of one voxel "
+                             "are sized for that many; fuse the scene in parts")
+        if self._ws is None:
+            self._ws = ops.tsdf_workspace(self.capacity, colors.device)
+        r, step = self.rule, ops.TSDF_MAX_CALL_VIEWS
+        for i in range(0, K, step):
+            s = slice(i, i + step)
+            vdepth = ops.tsdf_touch(depth[s], depth_scale, intrinsics[s], cam_to_world[s], self._ws, self.capacity, self.inv_voxel,
+                                    self.half_step, r["near"], r["far"], r["edge_abs"], r["edge_rel"])
+            ops.tsdf_integrate(vdepth, intrinsics[s], world_to_cam[s], colors[s], self._ws, self.capacity, self.voxel, self.trunc, self.qscale)
+        self.n_views += K
+
     def mesh(self, return_info: bool = False, return_keys: bool = False, max_vertices: int | None = None):
         """-> vertices fp32 [V, 6] on the device (xyz, rgb 0-255) and faces int32 [F, 3], then a `TsdfInfo` with `return_info`, then the
         cell keys int64 [V] (ascending) with `return_keys`.  Raises RuntimeError when blocks were dropped for want of a slot or the
