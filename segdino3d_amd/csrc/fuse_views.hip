@@ -5,10 +5,7 @@
 // The rule, per depth pixel (vi, ui) of view v; every decision is an integer one or a single rounded fp32 operation:
 //   1. the pixel takes part iff vi % stride == 0 and ui % stride == 0; it reads colour pixel ((2 vi + 1) Hc) / (2 Hd),
 //      ((2 ui + 1) Wc) / (2 Wd) (integer divisions);
-//   2. d = (float)raw * depth_scale, one rounded multiply (fp32 depth as it is); valid iff d > 0, d >= near and d <= far;
-//   3. unless edges are off: each of the 4 neighbours (vi +- 1, ui), (vi, ui +- 1) inside the image, whatever the stride, with depth
-//      dn by step 2, is a jump iff !(dn > 0) or |dn - d| > edge_abs + edge_rel * d (one rounded multiply, one rounded add, one rounded
-//      subtract); a pixel with any jump is dropped;
+//   2, 3. the depth d of the pixel, its validity and the edge test: depth_pixel.h, which states both steps;
 //   4. w = the back-projection of backproject.h (step 5 of lift_queries); unless all three components are finite with
 //      |w| < 2^SD3D_FUSE_WORLD_BITS the pixel is dropped and counted in out_of_range;
 //   5. c_i = floorf(w_i * inv_voxel), one rounded multiply; unless -2^SD3D_FUSE_CELL_BITS <= c_i < 2^SD3D_FUSE_CELL_BITS on all
@@ -36,37 +33,28 @@
 //   sd3d_fuse_emit        fv_emit_keys_kernel   slot -> its key if n >= min_obs, SD3D_EMPTY_KEY otherwise; counts N and the cells;
 //                         sort_pairs_u64        all `capacity` keys (the count is only known on the device), the empty ones last;
 //                         fv_emit_write_kernel  sorted position j < N -> points, obs, keys; lane 0 copies the counters.
-// The edge test reads its neighbours from global memory: a row of a tile is 64 contiguous bytes and the rows above and below are the
-// neighbouring lanes' own pixels, so they come from the L1; nothing of the halo is staged in LDS.
 #include "common.h"
 // The kernels here must EQUAL a float32 evaluation of the restatement, so nothing in this file may be contracted into a fused
 // multiply-add: hipcc contracts by default, and HIP's __fmul_rn / __fadd_rn / __fsub_rn are the plain operators, which it contracts
-// too.  The pragma covers backproject.h as it is compiled here and every expression below.
+// too.  The pragma covers depth_pixel.h and backproject.h as they are compiled here and every expression below.
 #pragma clang fp contract(off)
-#include "backproject.h"
-#include "../../include/segdino3d_hip.h"
+#include "depth_pixel.h"
 
 #define FV_THREADS 256
 #define FV_TILE_W 32
 #define FV_TILE_H 8
 #define FV_LDS_SLOTS 512                                // twice the pixels of a tile: the LDS probe always ends
-#define FV_MAX_DIM 16384                                // image extents; (2 v + 1) * H stays below 2^30
 #define FV_W SD3D_FUSE_SLOT_WORDS
 typedef unsigned long long fv_u64;
 
 struct FvGeom {
-    int Hd, Wd, Hc, Wc, stride, Hs, Ws, tiles_x, tiles_per_view, use_edges;
-    float depth_scale, near, far, edge_abs, edge_rel, inv_voxel;
+    Sd3dDepthRule px;
+    int Hc, Wc, stride, Hs, Ws, tiles_x, tiles_per_view;
+    float inv_voxel;
     uint32_t mask;                                      // capacity - 1
 };
 // the counters at the head of the workspace, 64-bit each
 enum { FV_N = 0, FV_CELLS = 1, FV_USED = 2, FV_RANGE = 3, FV_OVERFLOW = 4, FV_COUNTERS = 5 };
-
-__device__ __forceinline__ float fv_metres(uint16_t raw, float scale) { return (float)raw * scale; }
-__device__ __forceinline__ float fv_metres(float d, float) { return d; }
-
-// step 3 for one neighbour inside the image
-__device__ __forceinline__ bool fv_jump(float dn, float d, float thr) { return !(dn > 0.0f) || fabsf(dn - d) > thr; }
 
 template <typename D>
 __global__ __launch_bounds__(FV_THREADS) void fv_accumulate_kernel(const D* __restrict__ depth, const float* __restrict__ intr,
@@ -93,48 +81,24 @@ __global__ __launch_bounds__(FV_THREADS) void fv_accumulate_kernel(const D* __re
     int dropped = 0;
     if (vs < g.Hs && us < g.Ws) {
         const int vi = vs * g.stride, ui = us * g.stride;                             // < Hd, < Wd: Hs = ceil(Hd / stride)
-        const D* img = depth + (int64_t)v * g.Hd * g.Wd;
-        const D* row = img + (int64_t)vi * g.Wd;
-        const float d = fv_metres(row[ui], g.depth_scale);
-        bool ok = d > 0.0f && d >= g.near && d <= g.far;                              // a NaN fails
-        if (ok && g.use_edges) {
-            const float thr = g.edge_abs + g.edge_rel * d;                            // two roundings: contraction is off
-            if (vi > 0) ok = ok && !fv_jump(fv_metres(row[ui - g.Wd], g.depth_scale), d, thr);
-            if (vi + 1 < g.Hd) ok = ok && !fv_jump(fv_metres(row[ui + g.Wd], g.depth_scale), d, thr);
-            if (ui > 0) ok = ok && !fv_jump(fv_metres(row[ui - 1], g.depth_scale), d, thr);
-            if (ui + 1 < g.Wd) ok = ok && !fv_jump(fv_metres(row[ui + 1], g.depth_scale), d, thr);
-        }
-        if (ok) {
+        float d;
+        if (sd3d_depth_pixel(depth + (int64_t)v * g.px.Hd * g.px.Wd, g.px, vi, ui, d)) {
             const Sd3dCamera cam = sd3d_load_camera(intr, c2w, v);
-            float w[3];
+            float w[3], c[3];
             sd3d_backproject(cam, vi, ui, d, w[0], w[1], w[2]);
-            const float lim = (float)(1 << SD3D_FUSE_WORLD_BITS), cells = (float)(1 << SD3D_FUSE_CELL_BITS);
-            ok = fabsf(w[0]) < lim && fabsf(w[1]) < lim && fabsf(w[2]) < lim;         // NaN and infinities stop here
-            float c[3] = {0.0f, 0.0f, 0.0f};
-            if (ok) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    c[i] = floorf(w[i] * g.inv_voxel);
-                    ok = ok && c[i] >= -cells && c[i] < cells;                         // as floats, before anything becomes an integer
-                }
-            }
-            if (!ok) {
+            if (!sd3d_world_cell(w, g.inv_voxel, (float)(1 << SD3D_FUSE_CELL_BITS), c)) {
                 dropped = 1;
             } else {
                 const fv_u64 off = 1ull << SD3D_FUSE_CELL_BITS;
                 const fv_u64 key = ((fv_u64)((long long)c[0] + (long long)off) << 42) | ((fv_u64)((long long)c[1] + (long long)off) << 21) |
                                    (fv_u64)((long long)c[2] + (long long)off);
-                const int yc = (int)(((uint32_t)(2 * vi + 1) * (uint32_t)g.Hc) / (uint32_t)(2 * g.Hd));       // < Hc
-                const int xc = (int)(((uint32_t)(2 * ui + 1) * (uint32_t)g.Wc) / (uint32_t)(2 * g.Wd));       // < Wc
+                const int yc = (int)(((uint32_t)(2 * vi + 1) * (uint32_t)g.Hc) / (uint32_t)(2 * g.px.Hd));       // < Hc
+                const int xc = (int)(((uint32_t)(2 * ui + 1) * (uint32_t)g.Wc) / (uint32_t)(2 * g.px.Wd));       // < Wc
                 const uint8_t* px = colors + (((int64_t)v * g.Hc + yc) * g.Wc + xc) * 3;
                 const uint32_t cr = px[0], cg = px[1], cb = px[2];
-                int slot = (int)(hash_u64(key) >> 23);                                 // the top 9 bits; the global table takes the low ones
-                for (;;) {                                                            // at most 256 keys in 512 slots: it ends
-                    const fv_u64 prev = atomicCAS(&s_key[slot], (fv_u64)SD3D_EMPTY_KEY, key);
-                    if (prev == SD3D_EMPTY_KEY) { s_list[atomicAdd(&s_ncells, 1)] = slot; break; }
-                    if (prev == key) break;
-                    slot = (slot + 1) & (FV_LDS_SLOTS - 1);
-                }
+                bool fresh;
+                const int slot = sd3d_lds_claim<FV_LDS_SLOTS>(s_key, key, fresh);       // at most 256 keys in 512 slots: it ends
+                if (fresh) s_list[atomicAdd(&s_ncells, 1)] = slot;
                 const double fixed = (double)(1 << SD3D_FUSE_FIXED_BITS);
 #pragma unroll
                 for (int i = 0; i < 3; ++i) atomicAdd(&s_sum[slot][i], (fv_u64)(long long)rint((double)w[i] * fixed));
@@ -286,33 +250,27 @@ extern "C" int sd3d_fuse_accumulate(const void* depth, int depth_u16, float dept
                                     float edge_abs, float edge_rel, int use_edges, float inv_voxel, void* ws, size_t ws_bytes,
                                     int64_t capacity, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (V < 0 || Hd < 1 || Hd > FV_MAX_DIM || Wd < 1 || Wd > FV_MAX_DIM || Hc < 1 || Hc > FV_MAX_DIM || Wc < 1 || Wc > FV_MAX_DIM || stride < 1 ||
-        stride > FV_MAX_DIM || (depth_u16 && !(depth_scale > 0.0f)) || !(near >= 0.0f) || !(far >= near) ||
-        (use_edges && (!(edge_abs >= 0.0f) || !(edge_rel >= 0.0f))) || !(inv_voxel > 0.0f) || !(inv_voxel <= 3.0e38f))
-        return sd3d_set_error(SD3D_ERR_ARG, "fuse_accumulate: V >= 0, images up to 16384 a side, 1 <= stride <= 16384, depth_scale > 0 for uint16 "
-                                            "depth, 0 <= near <= far, edge_abs, edge_rel >= 0, inv_voxel > 0 and finite");
+    FvGeom g;
+    if (int rc = sd3d_depth_rule("fuse_accumulate", depth_u16, depth_scale, Hd, Wd, near, far, edge_abs, edge_rel, use_edges, g.px)) return rc;
+    if (V < 0 || Hc < 1 || Hc > SD3D_MAX_IMAGE_DIM || Wc < 1 || Wc > SD3D_MAX_IMAGE_DIM || stride < 1 || stride > SD3D_MAX_IMAGE_DIM ||
+        !(inv_voxel > 0.0f) || !(inv_voxel <= 3.0e38f))
+        return sd3d_set_error(SD3D_ERR_ARG, "fuse_accumulate: V >= 0, colour images up to 16384 a side, 1 <= stride <= 16384, inv_voxel > 0 and "
+                                            "finite");
     FvWs w;
     if (int rc = fv_check_ws("fuse_accumulate", ws, ws_bytes, capacity, w)) return rc;
     if (V == 0) return SD3D_OK;
     if (!depth || !intrinsics || !cam_to_world || !colors) return sd3d_set_error(SD3D_ERR_ARG, "fuse_accumulate: NULL argument");
-    FvGeom g;
-    g.Hd = Hd; g.Wd = Wd; g.Hc = Hc; g.Wc = Wc; g.stride = stride;
+    g.Hc = Hc; g.Wc = Wc; g.stride = stride;
     g.Hs = (Hd + stride - 1) / stride; g.Ws = (Wd + stride - 1) / stride;
     g.tiles_x = (g.Ws + FV_TILE_W - 1) / FV_TILE_W;
     g.tiles_per_view = g.tiles_x * ((g.Hs + FV_TILE_H - 1) / FV_TILE_H);
-    g.use_edges = use_edges ? 1 : 0;
-    g.depth_scale = depth_u16 ? depth_scale : 1.0f;
-    g.near = near; g.far = far; g.edge_abs = edge_abs; g.edge_rel = edge_rel; g.inv_voxel = inv_voxel;
+    g.inv_voxel = inv_voxel;
     g.mask = (uint32_t)(capacity - 1);
     const int64_t blocks = (int64_t)V * g.tiles_per_view;
     if (blocks > 0x7FFFFFFFll) return sd3d_set_error(SD3D_ERR_ARG, "fuse_accumulate: more than 2^31 - 1 tiles in one call; cut the views into several");
     const dim3 grid((unsigned)blocks), block(FV_THREADS);
-    if (depth_u16)
-        hipLaunchKernelGGL(fv_accumulate_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)depth, intrinsics, cam_to_world,
-                           (const uint8_t*)colors, g, w.table, w.counters);
-    else
-        hipLaunchKernelGGL(fv_accumulate_kernel<float>, grid, block, 0, st, (const float*)depth, intrinsics, cam_to_world,
-                           (const uint8_t*)colors, g, w.table, w.counters);
+    SD3D_LAUNCH_DEPTH(fv_accumulate_kernel, grid, block, st, depth_u16, depth, intrinsics, cam_to_world, (const uint8_t*)colors, g, w.table,
+                      w.counters);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }

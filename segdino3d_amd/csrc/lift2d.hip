@@ -15,13 +15,12 @@
 // made on floats first (a NaN fails it); the tap coordinates of sd3d_lift_accumulate are clamped as floats before they become
 // integers, so a mask the caller made up cannot produce an address outside the maps either.
 #include "common.h"
-#include "../../include/segdino3d_hip.h"
+#include "depth_pixel.h"                                // the depth conversion alone, under the default contraction
 #include <hip/hip_fp16.h>
 #include <stdio.h>
 
 #define LIFT_MAX_POINTS 0x7F000000ll
 #define LIFT_MAX_VIEWS (1 << 20)                        // words per point stay below the 65535 of gridDim.y
-#define LIFT_MAX_DIM 16384                              // image extents: exact in fp32, (view * H + y) * W + x in 64 bits
 
 struct LiftRule {
     float near, tol_abs, tol_rel, lo, hi_x, hi_y, depth_scale;
@@ -43,9 +42,6 @@ __device__ __forceinline__ LiftProj lift_project(const float* __restrict__ m, co
     return p;
 }
 
-__device__ __forceinline__ float lift_depth(const uint16_t* d, int64_t i, float scale) { return (float)d[i] * scale; }
-__device__ __forceinline__ float lift_depth(const float* d, int64_t i, float) { return d[i]; }
-
 template <typename D>
 __global__ __launch_bounds__(256) void lift_visibility_kernel(const float* __restrict__ points, int64_t ld, int64_t N,
                                                               const float* __restrict__ w2c, const float* __restrict__ intr,
@@ -63,7 +59,7 @@ __global__ __launch_bounds__(256) void lift_visibility_kernel(const float* __res
         const float uf = floorf(p.u + 0.5f), vf = floorf(p.v + 0.5f);
         if (!(uf >= r.lo && uf < r.hi_x && vf >= r.lo && vf < r.hi_y)) continue;          // NaN and huge values stop here
         const int ui = (int)uf, vi = (int)vf;                                             // 0 <= ui < Wd, 0 <= vi < Hd
-        const float d = lift_depth(depth, ((int64_t)v * Hd + vi) * Wd + ui, r.depth_scale);
+        const float d = sd3d_depth_metres(depth[((int64_t)v * Hd + vi) * Wd + ui], r.depth_scale);
         if (!(d > 0.0f)) continue;
         if (fabsf(d - p.z) <= r.tol_abs + r.tol_rel * d) word |= 1u << (v - vbeg);
     }
@@ -187,7 +183,7 @@ __global__ __launch_bounds__(256) void lift_finish_kernel(const float* __restric
 
 // ---------------------------------------------------------------------------------------------- C entry points
 static bool lift_bad_views(int64_t N, int64_t ld, int V, int Hd, int Wd) {
-    return N < 0 || N > LIFT_MAX_POINTS || ld < 3 || V < 1 || V > LIFT_MAX_VIEWS || Hd < 1 || Hd > LIFT_MAX_DIM || Wd < 1 || Wd > LIFT_MAX_DIM;
+    return N < 0 || N > LIFT_MAX_POINTS || ld < 3 || V < 1 || V > LIFT_MAX_VIEWS || Hd < 1 || Hd > SD3D_MAX_IMAGE_DIM || Wd < 1 || Wd > SD3D_MAX_IMAGE_DIM;
 }
 
 extern "C" int sd3d_lift_visibility(const float* points, int64_t ld, int64_t N, const float* world_to_cam, const float* intrinsics,
@@ -237,7 +233,7 @@ extern "C" int sd3d_lift_accumulate(const float* points, int64_t ld, int64_t N, 
                                     int Hd, int Wd, const uint32_t* bits, const void* maps, int maps_f16, int Hf, int Wf, int C, int v0,
                                     int v1, float* sum, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (lift_bad_views(N, ld, V, Hd, Wd) || Hf < 1 || Hf > LIFT_MAX_DIM || Wf < 1 || Wf > LIFT_MAX_DIM || v0 < 0 || v1 > V || v0 > v1)
+    if (lift_bad_views(N, ld, V, Hd, Wd) || Hf < 1 || Hf > SD3D_MAX_IMAGE_DIM || Wf < 1 || Wf > SD3D_MAX_IMAGE_DIM || v0 < 0 || v1 > V || v0 > v1)
         return sd3d_set_error(SD3D_ERR_ARG, "lift_accumulate: 0 <= N <= 0x7F000000 points (ld >= 3), 1..2^20 views, images and maps up to "
                                             "16384 a side, 0 <= v0 <= v1 <= V");
     if (C < 64 || C > 1024 || C % 64 != 0) return sd3d_set_error(SD3D_ERR_ARG, "lift_accumulate: C must be a multiple of 64 up to 1024");

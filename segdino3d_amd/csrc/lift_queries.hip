@@ -33,12 +33,10 @@
 //   sd3d_lift_query_gather   lq_gather_kernel   16 bytes of a feats row per lane.
 // All values are written with plain vector stores; no atomics but the LDS ones of the histograms.
 #include "common.h"
-#include "backproject.h"
-#include "../../include/segdino3d_hip.h"
+#include "depth_pixel.h"                                // the depth conversion alone (and backproject.h), under the default contraction
 #include <hip/hip_fp16.h>
 
 #define LQ_THREADS 256
-#define LQ_MAX_DIM 16384                                // image extents; (2 v + 1) * H stays below 2^30
 #define LQ_MAX_PIXELS (1 << 28)                         // 2^28 pixels * 2^(14 + 20) per addend < 2^63
 #define LQ_MAX_ROWS 0x7F000000ll
 
@@ -59,14 +57,12 @@ struct LqBox {                                          // depth pixels, inclusi
     uint64_t magic_cols;                                // lq_magic(columns a sweep walks per row)
 };
 
-__device__ __forceinline__ float lq_metres(uint16_t raw, float scale) { return __fmul_rn((float)raw, scale); }
-__device__ __forceinline__ float lq_metres(float d, float) { return d; }
 // 16 depth pixels from a 16-byte aligned address -> metres
 __device__ __forceinline__ void lq_load16(const uint16_t* p, float scale, float (&d)[16]) {
     const uint4 a = ((const uint4*)p)[0], b = ((const uint4*)p)[1];
     const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
-    for (int j = 0; j < 16; ++j) d[j] = lq_metres((uint16_t)((w[j >> 1] >> (16 * (j & 1))) & 0xFFFFu), scale);
+    for (int j = 0; j < 16; ++j) d[j] = sd3d_depth_metres((uint16_t)((w[j >> 1] >> (16 * (j & 1))) & 0xFFFFu), scale);
 }
 __device__ __forceinline__ void lq_load16(const float* p, float, float (&d)[16]) {
 #pragma unroll
@@ -83,17 +79,6 @@ __device__ __forceinline__ int lq_key(float d, int far_mm) {
     if (!(t < 65536.0f)) return 0;
     const int k = (int)floorf(t);
     return k >= 1 && k <= far_mm ? k : 0;
-}
-
-__device__ __forceinline__ int lq_wave_min(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
-    return v;
-}
-__device__ __forceinline__ int lq_wave_max(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
-    return v;
 }
 
 // f(vi, ui, d, k) for every depth pixel of `box` whose mask sample is set and whose key is valid.
@@ -142,7 +127,7 @@ __device__ __forceinline__ void lq_sweep(const uint8_t* __restrict__ mask, const
 #pragma unroll
             for (int j = 0; j < LQ_COLS; ++j) {
                 if (!mk[j]) continue;
-                const float d = lq_metres(dv[j], g.depth_scale);
+                const float d = sd3d_depth_metres(dv[j], g.depth_scale);
                 const int k = lq_key(d, g.far_mm);
                 if (k) f(vi, ug + j, d, k);
             }
@@ -230,7 +215,7 @@ __global__ __launch_bounds__(LQ_THREADS) void lq_centre_kernel(const D* __restri
             ymin = min(ymin, y); ymax = max(ymax, y); xmin = min(xmin, x); xmax = max(xmax, x);
         }
     }
-    ymin = lq_wave_min(ymin); xmin = lq_wave_min(xmin); ymax = lq_wave_max(ymax); xmax = lq_wave_max(xmax);
+    ymin = wave_min(ymin); xmin = wave_min(xmin); ymax = wave_max(ymax); xmax = wave_max(xmax);
     if (lane == 0) {
         atomicMin(&s_box[0], ymin); atomicMin(&s_box[1], xmin); atomicMax(&s_box[2], ymax); atomicMax(&s_box[3], xmax);
     }
@@ -368,8 +353,8 @@ extern "C" int sd3d_lift_query_centres(const void* depth, int depth_u16, float d
                                        int far_mm, int gate_mm, int gate_permille, float* centre, int32_t* count, int32_t* median_mm,
                                        void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (V < 0 || Q < 0 || (int64_t)V * Q > LQ_MAX_ROWS || Hd < 1 || Hd > LQ_MAX_DIM || Wd < 1 || Wd > LQ_MAX_DIM || Hm < 1 ||
-        Hm > LQ_MAX_DIM || Wm < 1 || Wm > LQ_MAX_DIM || (int64_t)Hd * Wd > LQ_MAX_PIXELS || (int64_t)Hm * Wm > LQ_MAX_PIXELS || far_mm < 1 ||
+    if (V < 0 || Q < 0 || (int64_t)V * Q > LQ_MAX_ROWS || Hd < 1 || Hd > SD3D_MAX_IMAGE_DIM || Wd < 1 || Wd > SD3D_MAX_IMAGE_DIM || Hm < 1 ||
+        Hm > SD3D_MAX_IMAGE_DIM || Wm < 1 || Wm > SD3D_MAX_IMAGE_DIM || (int64_t)Hd * Wd > LQ_MAX_PIXELS || (int64_t)Hm * Wm > LQ_MAX_PIXELS || far_mm < 1 ||
         far_mm > 65535 || gate_mm < 0 || gate_mm > 65535 || gate_permille < 0 || gate_permille > 65535 || (depth_u16 && !(depth_scale > 0.0f)))
         return sd3d_set_error(SD3D_ERR_ARG, "lift_query_centres: V * Q <= 0x7F000000 rows, images and masks up to 16384 a side and 2^28 pixels, "
                                             "1 <= far_mm <= 65535, 0 <= gate_mm, gate_permille <= 65535, depth_scale > 0 for uint16 depth");

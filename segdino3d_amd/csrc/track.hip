@@ -5,7 +5,7 @@
 //
 // The rule in short (segdino3d_amd/track.py has it in full).  State: cam_to_world [R | t] as float64 [3, 4]; the kernels read its fp32
 // rounding.  One iteration at stride s:
-//   1. a sample is a depth pixel (vi, ui), vi % s == 0 and ui % s == 0, valid by step 1 of the TSDF rule (full-resolution edge test);
+//   1. a sample is a depth pixel (vi, ui), vi % s == 0 and ui % s == 0, valid by step 1 of the TSDF rule (depth_pixel.h; full-resolution edge test);
 //   2. p by backproject.h, y = R p (relative to the camera centre), w = y + t; all |w_i| < 2^14 and all |y_i| <= ymax or dropped;
 //   3. g = w * inv_voxel - 0.5, c = floor(g), f = g - c; the eight voxels c + {0,1}^3 in range and W >= min_weight or dropped; each
 //      value float32((double) T / (double) W) * (1 / 4096); phi = the trilinear interpolant (x, then y, then z, a + (b - a) * f), n
@@ -34,30 +34,27 @@
 //                                             integration takes, lost, count, e.
 #include "common.h"
 // The kernels here must EQUAL a float32 / float64 evaluation of the restatement: nothing in this file may be contracted into a fused
-// multiply-add.  The pragma covers backproject.h as it is compiled here and every expression below.
+// multiply-add.  The pragma covers depth_pixel.h and backproject.h as they are compiled here and every expression below.
 #pragma clang fp contract(off)
-#include "backproject.h"
+#include "depth_pixel.h"
 #include "tsdf_table.h"
 
 #define TK_THREADS 256
 #define TK_TILE_W 32
 #define TK_TILE_H 8
 #define TK_LDS_SLOTS 4096                               // 8 corners of 256 samples = 2048 keys at most: the LDS probe always ends
-#define TK_MAX_DIM 16384                                // image extents and the stride
 #define TK_SUMS SD3D_TRACK_SUMS
 
 // the words of the state, 8 bytes each
 enum { TK_CUR = 0, TK_SAVED = 12, TK_LOST = 24, TK_COUNT = 25, TK_E = 26, TK_SUM0 = 32, TK_LAST = 64, TK_WORDS = 128 };
 
 struct TkGeom {
-    int Hd, Wd, stride, tiles_x, use_edges, min_weight;
-    float depth_scale, near, far, edge_abs, edge_rel, inv_voxel, ymax;
+    Sd3dDepthRule px;
+    int stride, tiles_x, min_weight;
+    float inv_voxel, ymax;
     uint32_t mask;                                      // capacity - 1
 };
 
-__device__ __forceinline__ float tk_metres(uint16_t raw, float scale) { return (float)raw * scale; }
-__device__ __forceinline__ float tk_metres(float d, float) { return d; }
-__device__ __forceinline__ bool tk_jump(float dn, float d, float thr) { return !(dn > 0.0f) || fabsf(dn - d) > thr; }
 __device__ __forceinline__ float tk_lerp(float a, float b, float f) { return a + (b - a) * f; }
 
 // ---------------------------------------------------------------------------------------------- steps 1 to 4
@@ -79,17 +76,9 @@ __global__ __launch_bounds__(TK_THREADS) void tk_accumulate_kernel(const D* __re
     bool ok = false;
     float y[3] = {0.0f, 0.0f, 0.0f}, f[3] = {0.0f, 0.0f, 0.0f};
     int c[3] = {0, 0, 0}, ls[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (vi < g.Hd && ui < g.Wd) {
-        const D* row = depth + (int64_t)vi * g.Wd;
-        const float d = tk_metres(row[ui], g.depth_scale);
-        ok = d > 0.0f && d >= g.near && d <= g.far;                                   // a NaN fails
-        if (ok && g.use_edges) {
-            const float thr = g.edge_abs + g.edge_rel * d;                            // two roundings: contraction is off
-            if (vi > 0) ok = ok && !tk_jump(tk_metres(row[ui - g.Wd], g.depth_scale), d, thr);
-            if (vi + 1 < g.Hd) ok = ok && !tk_jump(tk_metres(row[ui + g.Wd], g.depth_scale), d, thr);
-            if (ui > 0) ok = ok && !tk_jump(tk_metres(row[ui - 1], g.depth_scale), d, thr);
-            if (ui + 1 < g.Wd) ok = ok && !tk_jump(tk_metres(row[ui + 1], g.depth_scale), d, thr);
-        }
+    if (vi < g.px.Hd && ui < g.px.Wd) {
+        float d;
+        ok = sd3d_depth_pixel(depth, g.px, vi, ui, d);
         if (ok) {
             const double* cur = (const double*)state + TK_CUR;                        // the fp32 rounding of the state; t apart: y = R p
             const Sd3dCamera cam = {intr[0], intr[1], intr[2], intr[3], (float)cur[0], (float)cur[1], (float)cur[2], 0.0f,
@@ -97,6 +86,7 @@ __global__ __launch_bounds__(TK_THREADS) void tk_accumulate_kernel(const D* __re
             const float tr[3] = {(float)cur[3], (float)cur[7], (float)cur[11]};
             sd3d_backproject(cam, vi, ui, d, y[0], y[1], y[2]);                        // + 0.0f changes no value the rule reads
             const float lim = (float)(1 << SD3D_FUSE_WORLD_BITS), cells = (float)TS_CELL_BIAS;
+            // not sd3d_world_cell: a different rule, the cell of w - voxel / 2 with its upper neighbour in range too, and ymax
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const float w = y[i] + tr[i];
@@ -114,14 +104,9 @@ __global__ __launch_bounds__(TK_THREADS) void tk_accumulate_kernel(const D* __re
             for (int m = 0; m < 8; ++m) {                                             // corner m = (dx, dy, dz) = bits 2, 1, 0
                 const ts_u64 key = ts_block_key((c[0] + (m >> 2)) >> 3, (c[1] + ((m >> 1) & 1)) >> 3, (c[2] + (m & 1)) >> 3);
                 if (key != last) {
-                    int slot = (int)(hash_u64(key) >> 20);                             // the top 12 bits; the global table takes the low ones
-                    for (;;) {                                                        // at most 2048 keys in 4096 slots: it ends
-                        const ts_u64 prev = atomicCAS(&s_key[slot], (ts_u64)SD3D_EMPTY_KEY, key);
-                        if (prev == SD3D_EMPTY_KEY || prev == key) break;
-                        slot = (slot + 1) & (TK_LDS_SLOTS - 1);
-                    }
+                    bool fresh;                                                       // not used: the set is walked slot by slot below
+                    last_slot = sd3d_lds_claim<TK_LDS_SLOTS>(s_key, key, fresh);       // at most 2048 keys in 4096 slots: it ends
                     last = key;
-                    last_slot = slot;
                 }
                 ls[m] = last_slot;
             }
@@ -303,12 +288,10 @@ extern "C" int sd3d_track_iterate(const void* depth, int depth_u16, float depth_
                                   int min_weight, int min_samples, float damping, float max_rot, float max_trans, void* state,
                                   size_t state_bytes, void* ws, size_t ws_bytes, int64_t capacity, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (Hd < 1 || Hd > TK_MAX_DIM || Wd < 1 || Wd > TK_MAX_DIM || stride < 1 || stride > TK_MAX_DIM)
-        return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: images up to 16384 a side, 1 <= stride <= 16384");
-    if ((depth_u16 && !(depth_scale > 0.0f)) || !(near >= 0.0f) || !(far >= near) || (use_edges && (!(edge_abs >= 0.0f) || !(edge_rel >= 0.0f))) ||
-        !(inv_voxel > 0.0f) || !(inv_voxel <= 3.0e38f) || !(voxel > 0.0f) || !(voxel <= 3.0e38f))
-        return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: depth_scale > 0 for uint16 depth, 0 <= near <= far, edge_abs, edge_rel >= 0, inv_voxel "
-                                            "and voxel > 0 and finite");
+    TkGeom g = {};
+    if (int rc = sd3d_depth_rule("track_iterate", depth_u16, depth_scale, Hd, Wd, near, far, edge_abs, edge_rel, use_edges, g.px)) return rc;
+    if (stride < 1 || stride > SD3D_MAX_IMAGE_DIM || !(inv_voxel > 0.0f) || !(inv_voxel <= 3.0e38f) || !(voxel > 0.0f) || !(voxel <= 3.0e38f))
+        return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: 1 <= stride <= 16384, inv_voxel and voxel > 0 and finite");
     if (min_weight < 1 || min_samples < 1 || !(damping >= 0.0f) || !(damping <= 1.0f) || !(max_rot > 0.0f) || !(max_rot <= 3.0e38f) ||
         !(max_trans > 0.0f) || !(max_trans <= 3.0e38f))
         return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: min_weight, min_samples >= 1, 0 <= damping <= 1, max_rot and max_trans > 0 and finite");
@@ -321,17 +304,11 @@ extern "C" int sd3d_track_iterate(const void* depth, int depth_u16, float depth_
     TsWs w;
     if (int rc = ts_check_ws("track_iterate", ws, ws_bytes, capacity, w)) return rc;
     if (!depth || !intrinsics) return sd3d_set_error(SD3D_ERR_ARG, "track_iterate: NULL argument");
-    TkGeom g = {};
-    g.Hd = Hd; g.Wd = Wd; g.stride = stride; g.use_edges = use_edges ? 1 : 0; g.min_weight = min_weight;
-    g.depth_scale = depth_u16 ? depth_scale : 1.0f;
-    g.near = near; g.far = far; g.edge_abs = edge_abs; g.edge_rel = edge_rel; g.inv_voxel = inv_voxel; g.ymax = ymax;
+    g.stride = stride; g.min_weight = min_weight; g.inv_voxel = inv_voxel; g.ymax = ymax;
     g.mask = (uint32_t)(capacity - 1);
     g.tiles_x = (int)cdiv(nx, TK_TILE_W);
     const dim3 grid((unsigned)(g.tiles_x * cdiv(ny, TK_TILE_H))), block(TK_THREADS);  // <= 2^9 * 2^11 tiles
-    if (depth_u16)
-        hipLaunchKernelGGL(tk_accumulate_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)depth, intrinsics, g, w.keys, w.vox, (ts_u64*)state);
-    else
-        hipLaunchKernelGGL(tk_accumulate_kernel<float>, grid, block, 0, st, (const float*)depth, intrinsics, g, w.keys, w.vox, (ts_u64*)state);
+    SD3D_LAUNCH_DEPTH(tk_accumulate_kernel, grid, block, st, depth_u16, depth, intrinsics, g, w.keys, w.vox, (ts_u64*)state);
     hipLaunchKernelGGL(tk_solve_kernel, dim3(1), dim3(64), 0, st, (ts_u64*)state, min_samples, damping, voxel, max_rot, max_trans);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;

@@ -8,7 +8,8 @@
 //   2. dx = P[j].x - q.x (dy, dz alike), d2 = (dx dx + dy dy) + dz dz, one fp32 rounding per operation; j is a candidate iff d2 <= r2;
 //   3. the answer is the candidate with the smallest key (bits of d2 << 32) | j: the nearest, ties to the lower index; -1 / +inf if
 //      there is none;
-//   4. a pixel query is the back-projection of backproject.h of a depth pixel whose depth passes step 2 of the fusion rule;
+//   4. a pixel query is the back-projection of backproject.h of a depth pixel whose depth passes step 2 of the fusion rule
+//      (depth_pixel.h, the edge test off);
 //   5. out[l, query] = labels[l, idx], or `fill` where idx < 0, written by the kernel that found idx.
 // The answer is a minimum over a SET of keys, so it is a pure function of the cloud and the query: nothing depends on the order in
 // which candidates are met, on how the views are cut into calls, or on the stream.  No atomics touch global memory.
@@ -42,20 +43,17 @@
 // All values are written with plain vector stores.
 #include "common.h"
 // The kernels here must EQUAL a float32 evaluation of the restatement, so nothing in this file may be contracted into a fused
-// multiply-add (see fuse_views.hip).  The pragma covers backproject.h and point_grid.h as they are compiled here.
+// multiply-add (see fuse_views.hip).  The pragma covers depth_pixel.h, backproject.h and point_grid.h as they are compiled here.
 #pragma clang fp contract(off)
-#include "backproject.h"
+#include "depth_pixel.h"
 #include "point_grid.h"
-#include "../../include/segdino3d_hip.h"
 #include <climits>
-#include <cstdio>
 
 #define TQ_THREADS 256
 #define TQ_TILE_W 32
 #define TQ_TILE_H 8
 #define TQ_CELLS 512                                    // cells of a tile's box whose bucket ranges are staged in LDS
 #define TQ_POINTS 1536                                  // source points of a tile's box staged in LDS (16 bytes each)
-#define TQ_MAX_DIM 16384                                // image extents, as for the fusion
 #define TQ_NO_KEY 0xFFFFFFFFFFFFFFFFull
 #define TQ_MAP_ROWS 8                                   // mask rows the instance map reads before it uses any
 
@@ -75,12 +73,9 @@ struct TqOut {
     int32_t fill;
 };
 struct TqGeom {
-    int Hd, Wd, tiles_x, tiles_per_view;
-    float depth_scale, near, far;
+    int tiles_x, tiles_per_view;                        // before the rule: what the kernel reads is then one run of 28 bytes
+    Sd3dDepthRule px;                                   // use_edges = 0: step 2 alone
 };
-
-__device__ __forceinline__ float tq_metres(uint16_t raw, float scale) { return (float)raw * scale; }
-__device__ __forceinline__ float tq_metres(float d, float) { return d; }
 
 // the points p[0 .. n) against the query: step 2 and the running minimum of step 3 (P = a global or an LDS pointer, after inlining)
 template <typename P>
@@ -94,17 +89,6 @@ __device__ __forceinline__ void tq_scan(P p, int n, float qx, float qy, float qz
             best = key < best ? key : best;
         }
     }
-}
-
-__device__ __forceinline__ int tq_wave_min(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
-    return v;
-}
-__device__ __forceinline__ int tq_wave_max(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
-    return v;
 }
 
 // the range of bucket b, inside [0, N] whatever the workspace holds
@@ -158,13 +142,13 @@ __global__ __launch_bounds__(TQ_THREADS) void tq_pixel_kernel(const D* __restric
 
     // ---- step 4: this lane's pixel as a query, and the tile's box of cells
     const int vi = ty * TQ_TILE_H + (t >> 5), ui = tx * TQ_TILE_W + (t & 31);
-    const bool inside = vi < g.Hd && ui < g.Wd;
+    const bool inside = vi < g.px.Hd && ui < g.px.Wd;
     bool ok = false;
     float w[3] = {0.0f, 0.0f, 0.0f};
     int c[3] = {0, 0, 0};
     if (inside) {
-        const float d = tq_metres(depth[((int64_t)v * g.Hd + vi) * g.Wd + ui], g.depth_scale);
-        ok = d > 0.0f && d >= g.near && d <= g.far;                                   // a NaN fails
+        float d;
+        ok = sd3d_depth_pixel<false>(depth + (int64_t)v * g.px.Hd * g.px.Wd, g.px, vi, ui, d);
         if (ok) {
             const Sd3dCamera cam = sd3d_load_camera(intr, c2w, v);
             sd3d_backproject(cam, vi, ui, d, w[0], w[1], w[2]);
@@ -179,7 +163,7 @@ __global__ __launch_bounds__(TQ_THREADS) void tq_pixel_kernel(const D* __restric
     // take their turns one by one)
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const int lo = tq_wave_min(ok ? c[i] : INT_MAX), hi = tq_wave_max(ok ? c[i] : INT_MIN);
+        const int lo = wave_min(ok ? c[i] : INT_MAX), hi = wave_max(ok ? c[i] : INT_MIN);
         if (lane == 0 && lo <= hi) {
             atomicMin(&s_min[i], lo);
             atomicMax(&s_max[i], hi);
@@ -243,7 +227,7 @@ __global__ __launch_bounds__(TQ_THREADS) void tq_pixel_kernel(const D* __restric
             }
         }
     }
-    if (inside) tq_emit(o, ((int64_t)v * g.Hd + vi) * g.Wd + ui, best);
+    if (inside) tq_emit(o, ((int64_t)v * g.px.Hd + vi) * g.px.Wd + ui, best);
 }
 
 // map[n] = the i with masks[i, n] set and scores[i] >= thr of the largest score, ties to the lower i, -1 if none; `vec`: N % 4 == 0 and
@@ -362,14 +346,11 @@ extern "C" int sd3d_nearest_pixels(const void* depth, int depth_u16, float depth
     TqIndex ix;
     TqOut o;
     if (int rc = tq_index("nearest_pixels", index_ws, ws_bytes, n_points, radius, ix)) return rc;
-    if (V < 0 || Hd < 1 || Hd > TQ_MAX_DIM || Wd < 1 || Wd > TQ_MAX_DIM || (depth_u16 && !(depth_scale > 0.0f)) || !(near >= 0.0f) || !(far >= near))
-        return sd3d_set_error(SD3D_ERR_ARG, "nearest_pixels: V >= 0, images up to 16384 a side, depth_scale > 0 for uint16 depth, 0 <= near <= far");
     TqGeom g;
-    g.Hd = Hd; g.Wd = Wd;
+    if (int rc = sd3d_depth_rule("nearest_pixels", depth_u16, depth_scale, Hd, Wd, near, far, 0.0f, 0.0f, 0, g.px)) return rc;
+    if (V < 0) return sd3d_set_error(SD3D_ERR_ARG, "nearest_pixels: V >= 0");
     g.tiles_x = (Wd + TQ_TILE_W - 1) / TQ_TILE_W;
     g.tiles_per_view = g.tiles_x * ((Hd + TQ_TILE_H - 1) / TQ_TILE_H);
-    g.depth_scale = depth_u16 ? depth_scale : 1.0f;
-    g.near = near; g.far = far;
     // V Hd Wd < 2^31 2^28 and L <= 8: the int64 indices of the outputs cannot overflow; the grid is what limits one call
     const int64_t blocks = (int64_t)V * g.tiles_per_view, M = (int64_t)V * Hd * Wd;
     if (blocks > 0x7FFFFFFFll) return sd3d_set_error(SD3D_ERR_ARG, "nearest_pixels: more than 2^31 - 1 tiles in one call; cut the views into several");
@@ -377,10 +358,7 @@ extern "C" int sd3d_nearest_pixels(const void* depth, int depth_u16, float depth
     if (V == 0) return SD3D_OK;
     if (!depth || !intrinsics || !cam_to_world) return sd3d_set_error(SD3D_ERR_ARG, "nearest_pixels: NULL argument");
     const dim3 grid((unsigned)blocks), block(TQ_THREADS);
-    if (depth_u16)
-        hipLaunchKernelGGL(tq_pixel_kernel<uint16_t>, grid, block, 0, (hipStream_t)stream, (const uint16_t*)depth, intrinsics, cam_to_world, g, ix, o);
-    else
-        hipLaunchKernelGGL(tq_pixel_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)depth, intrinsics, cam_to_world, g, ix, o);
+    SD3D_LAUNCH_DEPTH(tq_pixel_kernel, grid, block, (hipStream_t)stream, depth_u16, depth, intrinsics, cam_to_world, g, ix, o);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }

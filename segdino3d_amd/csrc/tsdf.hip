@@ -4,8 +4,8 @@
 // rule in segdino3d_amd/tsdf.py and include/segdino3d_hip.h, is what these kernels are pinned against, bit for bit.
 //
 // The rule in short (segdino3d_amd/tsdf.py has it in full); every decision is an integer one or a single rounded fp32 operation:
-//   1. valid pixel, its depth d and its colour pixel: steps 1 to 3 of fuse_views.hip with stride 1 (restated here: ONE rule, two
-//      places, because sharing the code would mean recompiling fuse_views.hip's kernel around a new header);
+//   1. valid pixel, its depth d and its colour pixel: steps 1 to 3 of fuse_views.hip with stride 1; steps 2 and 3 are the code of
+//      depth_pixel.h, which states them;
 //   2. a view TOUCHES the blocks (8 x 8 x 8 voxels) that hold the back-projections (backproject.h) of the five depths d + j h,
 //      j = -2 .. 2, h = trunc / 2, of its valid pixels; range failures are counted in out_of_range;
 //   3. per (view, touched block) and per voxel of the block: the centre is projected through the fp32 world_to_cam, rounded to the
@@ -43,10 +43,9 @@
 //                                             order (key of a, axis) IS the order (j, axis): no second sort), the second run writes them.
 #include "common.h"
 // The kernels here must EQUAL a float32 evaluation of the restatement: nothing in this file may be contracted into a fused
-// multiply-add.  The pragma covers backproject.h as it is compiled here and every expression below.
+// multiply-add.  The pragma covers depth_pixel.h and backproject.h as they are compiled here and every expression below.
 #pragma clang fp contract(off)
-#include "backproject.h"
-#include "../../include/segdino3d_hip.h"
+#include "depth_pixel.h"
 #include "tsdf_table.h"                                 // block keys, the read-only probe and the workspace: shared with track.hip
 
 #define TS_THREADS 256
@@ -54,19 +53,14 @@
 #define TS_TILE_H 8
 #define TS_LDS_SLOTS 2048                               // 5 samples of 256 pixels = 1280 keys at most: the LDS probe always ends
 #define TS_LDS_LIST (5 * TS_THREADS)
-#define TS_MAX_DIM 16384                                // image extents; (2 v + 1) * H stays below 2^30
 
 struct TsGeom {
-    int Hd, Wd, Hc, Wc, tiles_x, tiles_per_view, use_edges;
-    float depth_scale, near, far, edge_abs, edge_rel, inv_voxel, voxel, h, trunc, qscale;
+    Sd3dDepthRule px;                                   // the integration reads its Hd and Wd alone
+    int Hc, Wc, tiles_x, tiles_per_view;
+    float inv_voxel, voxel, h, trunc, qscale;
     uint32_t mask;                                      // capacity - 1
     ts_u64 vmask;                                       // a bit per view of the call
 };
-
-__device__ __forceinline__ float ts_metres(uint16_t raw, float scale) { return (float)raw * scale; }
-__device__ __forceinline__ float ts_metres(float d, float) { return d; }
-__device__ __forceinline__ bool ts_jump(float dn, float d, float thr) { return !(dn > 0.0f) || fabsf(dn - d) > thr; }
-
 
 // ---------------------------------------------------------------------------------------------- steps 1 and 2
 template <typename D>
@@ -85,47 +79,24 @@ __global__ __launch_bounds__(TS_THREADS) void ts_touch_kernel(const D* __restric
 
     const int vi = ty * TS_TILE_H + (t >> 5), ui = tx * TS_TILE_W + (t & 31);
     int dropped = 0;
-    if (vi < g.Hd && ui < g.Wd) {
-        const D* img = depth + (int64_t)v * g.Hd * g.Wd;
-        const D* row = img + (int64_t)vi * g.Wd;
-        const float d = ts_metres(row[ui], g.depth_scale);
-        bool ok = d > 0.0f && d >= g.near && d <= g.far;                              // a NaN fails
-        if (ok && g.use_edges) {
-            const float thr = g.edge_abs + g.edge_rel * d;                            // two roundings: contraction is off
-            if (vi > 0) ok = ok && !ts_jump(ts_metres(row[ui - g.Wd], g.depth_scale), d, thr);
-            if (vi + 1 < g.Hd) ok = ok && !ts_jump(ts_metres(row[ui + g.Wd], g.depth_scale), d, thr);
-            if (ui > 0) ok = ok && !ts_jump(ts_metres(row[ui - 1], g.depth_scale), d, thr);
-            if (ui + 1 < g.Wd) ok = ok && !ts_jump(ts_metres(row[ui + 1], g.depth_scale), d, thr);
-        }
-        vdepth[((int64_t)v * g.Hd + vi) * g.Wd + ui] = ok ? d : 0.0f;                 // what step 3 reads: d of a valid pixel, else 0
+    if (vi < g.px.Hd && ui < g.px.Wd) {
+        float d;
+        const bool ok = sd3d_depth_pixel(depth + (int64_t)v * g.px.Hd * g.px.Wd, g.px, vi, ui, d);
+        vdepth[((int64_t)v * g.px.Hd + vi) * g.px.Wd + ui] = ok ? d : 0.0f;           // what step 3 reads: d of a valid pixel, else 0
         if (ok) {
             const Sd3dCamera cam = sd3d_load_camera(intr, c2w, v);
-            const float lim = (float)(1 << SD3D_FUSE_WORLD_BITS), cells = (float)TS_CELL_BIAS;
             ts_u64 last = SD3D_EMPTY_KEY;
             for (int j = -2; j <= 2; ++j) {
                 const float dj = d + (float)j * g.h;                                  // j * h is exact: one rounded add
-                float w[3];
+                float w[3], c[3];
                 sd3d_backproject(cam, vi, ui, dj, w[0], w[1], w[2]);
-                bool in = fabsf(w[0]) < lim && fabsf(w[1]) < lim && fabsf(w[2]) < lim;    // NaN and infinities stop here
-                float c[3] = {0.0f, 0.0f, 0.0f};
-                if (in) {
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        c[i] = floorf(w[i] * g.inv_voxel);
-                        in = in && c[i] >= -cells && c[i] < cells;                     // as floats, before anything becomes an integer
-                    }
-                }
-                if (!in) { ++dropped; continue; }
+                if (!sd3d_world_cell(w, g.inv_voxel, (float)TS_CELL_BIAS, c)) { ++dropped; continue; }
                 const ts_u64 key = ts_block_key((int)c[0] >> 3, (int)c[1] >> 3, (int)c[2] >> 3);      // arithmetic shifts
                 if (key == last) continue;
                 last = key;
-                int slot = (int)(hash_u64(key) >> 21);                                 // the top 11 bits; the global table takes the low ones
-                for (;;) {                                                            // at most 1280 keys in 2048 slots: it ends
-                    const ts_u64 prev = atomicCAS(&s_key[slot], (ts_u64)SD3D_EMPTY_KEY, key);
-                    if (prev == SD3D_EMPTY_KEY) { s_list[atomicAdd(&s_nkeys, 1)] = slot; break; }      // < TS_LDS_LIST: one per (lane, j)
-                    if (prev == key) break;
-                    slot = (slot + 1) & (TS_LDS_SLOTS - 1);
-                }
+                bool fresh;
+                const int slot = sd3d_lds_claim<TS_LDS_SLOTS>(s_key, key, fresh);       // at most 1280 keys in 2048 slots: it ends
+                if (fresh) s_list[atomicAdd(&s_nkeys, 1)] = slot;                      // < TS_LDS_LIST: one per (lane, j)
             }
         }
     }
@@ -204,15 +175,15 @@ __global__ __launch_bounds__(TS_THREADS) void ts_integrate_kernel(const float* _
                 const float z = ((m[8] * p[k][0] + m[9] * p[k][1]) + m[10] * p[k][2]) + m[11];
                 if (!(z > 0.0f)) continue;
                 const float uf = floorf(((fx * x) / z + cx) + 0.5f), vf = floorf(((fy * y) / z + cy) + 0.5f);
-                if (!(uf >= 0.0f && uf < (float)g.Wd && vf >= 0.0f && vf < (float)g.Hd)) continue;      // as floats; a NaN fails
+                if (!(uf >= 0.0f && uf < (float)g.px.Wd && vf >= 0.0f && vf < (float)g.px.Hd)) continue;      // as floats; a NaN fails
                 const int ui = (int)uf, vi = (int)vf;
-                const float d = vdepth[((int64_t)v * g.Hd + vi) * g.Wd + ui];
+                const float d = vdepth[((int64_t)v * g.px.Hd + vi) * g.px.Wd + ui];
                 if (!(d > 0.0f)) continue;
                 const float sdf = d - z;
                 if (sdf < -g.trunc) continue;
                 const int q = (int)rintf(fminf(sdf, g.trunc) * g.qscale);
-                const int yc = (int)(((uint32_t)(2 * vi + 1) * (uint32_t)g.Hc) / (uint32_t)(2 * g.Hd));       // < Hc
-                const int xc = (int)(((uint32_t)(2 * ui + 1) * (uint32_t)g.Wc) / (uint32_t)(2 * g.Wd));       // < Wc
+                const int yc = (int)(((uint32_t)(2 * vi + 1) * (uint32_t)g.Hc) / (uint32_t)(2 * g.px.Hd));    // < Hc
+                const int xc = (int)(((uint32_t)(2 * ui + 1) * (uint32_t)g.Wc) / (uint32_t)(2 * g.px.Wd));    // < Wc
                 const uint8_t* px = colors + (((int64_t)v * g.Hc + yc) * g.Wc + xc) * 3;
                 acc[k][0] += 1; acc[k][1] += q; acc[k][2] += px[0]; acc[k][3] += px[1]; acc[k][4] += px[2];
                 ++updates;
@@ -447,14 +418,15 @@ extern "C" int sd3d_tsdf_reset(void* ws, size_t ws_bytes, int64_t capacity, void
     return SD3D_OK;
 }
 
+// what the touch and the integration share; of g.px the extents alone (the touch fills the rest with sd3d_depth_rule)
 static int ts_geom(const char* who, int V, int Hd, int Wd, int Hc, int Wc, int64_t capacity, TsGeom& g) {
     char msg[160];
-    if (V < 0 || V > SD3D_TSDF_MAX_CALL_VIEWS || Hd < 1 || Hd > TS_MAX_DIM || Wd < 1 || Wd > TS_MAX_DIM || Hc < 1 || Hc > TS_MAX_DIM || Wc < 1 ||
-        Wc > TS_MAX_DIM) {
+    if (V < 0 || V > SD3D_TSDF_MAX_CALL_VIEWS || Hd < 1 || Hd > SD3D_MAX_IMAGE_DIM || Wd < 1 || Wd > SD3D_MAX_IMAGE_DIM || Hc < 1 ||
+        Hc > SD3D_MAX_IMAGE_DIM || Wc < 1 || Wc > SD3D_MAX_IMAGE_DIM) {
         snprintf(msg, sizeof msg, "%s: 0 <= V <= 64 views a call, images up to 16384 a side", who);
         return sd3d_set_error(SD3D_ERR_ARG, msg);
     }
-    g.Hd = Hd; g.Wd = Wd; g.Hc = Hc; g.Wc = Wc;
+    g.px.Hd = Hd; g.px.Wd = Wd; g.Hc = Hc; g.Wc = Wc;
     g.tiles_x = (Wd + TS_TILE_W - 1) / TS_TILE_W;
     g.tiles_per_view = g.tiles_x * ((Hd + TS_TILE_H - 1) / TS_TILE_H);
     g.mask = (uint32_t)(capacity - 1);
@@ -467,26 +439,19 @@ extern "C" int sd3d_tsdf_touch(const void* depth, int depth_u16, float depth_sca
                                float half_step, float* vdepth, void* ws, size_t ws_bytes, int64_t capacity, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     TsGeom g = {};
+    if (int rc = sd3d_depth_rule("tsdf_touch", depth_u16, depth_scale, Hd, Wd, near, far, edge_abs, edge_rel, use_edges, g.px)) return rc;
     if (int rc = ts_geom("tsdf_touch", V, Hd, Wd, 1, 1, capacity, g)) return rc;
-    if ((depth_u16 && !(depth_scale > 0.0f)) || !(near >= 0.0f) || !(far >= near) || (use_edges && (!(edge_abs >= 0.0f) || !(edge_rel >= 0.0f))) ||
-        !(inv_voxel > 0.0f) || !(inv_voxel <= 3.0e38f) || !(half_step > 0.0f) || !(half_step <= 3.0e38f))
-        return sd3d_set_error(SD3D_ERR_ARG, "tsdf_touch: depth_scale > 0 for uint16 depth, 0 <= near <= far, edge_abs, edge_rel >= 0, inv_voxel and "
-                                            "half_step > 0 and finite");
+    if (!(inv_voxel > 0.0f) || !(inv_voxel <= 3.0e38f) || !(half_step > 0.0f) || !(half_step <= 3.0e38f))
+        return sd3d_set_error(SD3D_ERR_ARG, "tsdf_touch: inv_voxel and half_step > 0 and finite");
     TsWs w;
     if (int rc = ts_check_ws("tsdf_touch", ws, ws_bytes, capacity, w)) return rc;
     if (hipMemsetAsync(&w.counters[TS_NLIST], 0, 8, st) != hipSuccess) return sd3d_set_error(SD3D_ERR_LAUNCH, "tsdf_touch: memset");
     if (V == 0) return SD3D_OK;
     if (!depth || !intrinsics || !cam_to_world || !vdepth) return sd3d_set_error(SD3D_ERR_ARG, "tsdf_touch: NULL argument");
-    g.use_edges = use_edges ? 1 : 0;
-    g.depth_scale = depth_u16 ? depth_scale : 1.0f;
-    g.near = near; g.far = far; g.edge_abs = edge_abs; g.edge_rel = edge_rel; g.inv_voxel = inv_voxel; g.h = half_step;
+    g.inv_voxel = inv_voxel; g.h = half_step;
     const dim3 grid((unsigned)((int64_t)V * g.tiles_per_view)), block(TS_THREADS);    // <= 64 * 2^18 tiles
-    if (depth_u16)
-        hipLaunchKernelGGL(ts_touch_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)depth, intrinsics, cam_to_world, g, w.keys, w.touched,
-                           w.list, w.counters, vdepth);
-    else
-        hipLaunchKernelGGL(ts_touch_kernel<float>, grid, block, 0, st, (const float*)depth, intrinsics, cam_to_world, g, w.keys, w.touched, w.list,
-                           w.counters, vdepth);
+    SD3D_LAUNCH_DEPTH(ts_touch_kernel, grid, block, st, depth_u16, depth, intrinsics, cam_to_world, g, w.keys, w.touched, w.list, w.counters,
+                      vdepth);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }

@@ -26,6 +26,16 @@ __device__ __forceinline__ float wave_min(float v) {
     for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
     return v;
 }
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
+    return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
+    return v;
+}
 // Inclusive prefix sum over the wave; `lane` is the caller's lane id (threadIdx.x & 63).
 __device__ __forceinline__ int wave_scan_incl(int v, int lane) {
 #pragma unroll

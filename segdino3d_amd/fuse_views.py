@@ -46,7 +46,7 @@ from collections import namedtuple
 import torch
 
 from . import ops
-from .lift2d import Views
+from .lift2d import Views, check_depth_range
 
 RULE_DEFAULTS = dict(near=0.1, far=6.0, stride=1, edge_abs=0.02, edge_rel=0.02, min_obs=2)
 MIN_VOXEL = 2.0 ** -6               # |w| < 2^14 then keeps every cell index inside [-2^20, 2^20)
@@ -66,10 +66,7 @@ def _rule(rule: dict) -> dict:
         raise ValueError(f"stride must be an integer >= 1, got {r['stride']}")
     if int(r["min_obs"]) != r["min_obs"] or r["min_obs"] < 1:
         raise ValueError(f"min_obs must be an integer >= 1, got {r['min_obs']}")
-    if not (float(r["near"]) >= 0.0 and float(r["far"]) >= float(r["near"])):
-        raise ValueError(f"need 0 <= near <= far, got near = {r['near']}, far = {r['far']}")
-    if r["edge_rel"] is not None and not (float(r["edge_abs"]) >= 0.0 and float(r["edge_rel"]) >= 0.0):
-        raise ValueError(f"edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {r['edge_abs']}, {r['edge_rel']}")
+    check_depth_range(r)
     return r
 
 
@@ -84,9 +81,8 @@ class PointCloudFuser:
         self.rule = _rule(rule)
         if not float(voxel) >= MIN_VOXEL or float(voxel) == float("inf"):
             raise ValueError(f"PointCloudFuser: voxel must be finite and >= 2^-6 m (cell indices must fit 21 bits), got {voxel}")
-        if int(capacity) != capacity or capacity & (capacity - 1) or not ops.FUSE_MIN_CAPACITY <= capacity <= ops.FUSE_MAX_CAPACITY:
-            raise ValueError(f"PointCloudFuser: capacity must be a power of two in [{ops.FUSE_MIN_CAPACITY}, 2^24], got {capacity}")
-        self.voxel, self.capacity = float(voxel), int(capacity)
+        self.voxel = float(voxel)
+        self.capacity = ops._pow2_capacity(capacity, ops.FUSE_MIN_CAPACITY, ops.FUSE_MAX_CAPACITY, "PointCloudFuser")
         self.inv_voxel = 1.0 / self.voxel               # float64 here; ops.fuse_accumulate rounds it to fp32
         self.n_views, self.n_pixels = 0, 0
         self._ws = None
@@ -95,17 +91,7 @@ class PointCloudFuser:
     def add(self, views: Views, colors) -> None:
         if not isinstance(views, Views):
             raise TypeError(f"PointCloudFuser.add: views must be a lift2d.Views, got {type(views).__name__}")
-        if not isinstance(colors, torch.Tensor):
-            raise TypeError(f"PointCloudFuser.add: colors: expected a tensor, got {type(colors).__name__}")
-        if not colors.is_cuda:
-            raise RuntimeError(f"PointCloudFuser.add: colors: expected a tensor on the HIP device, got {colors.device} (no CPU fallback)")
-        if colors.dtype != torch.uint8:
-            raise TypeError(f"PointCloudFuser.add: colors must be uint8, got {colors.dtype}")
-        if colors.dim() != 4 or colors.shape[3] != 3 or colors.shape[1] < 1 or colors.shape[2] < 1:
-            raise ValueError(f"PointCloudFuser.add: colors must be [V, Hc, Wc, 3], got {list(colors.shape)}")
-        if colors.shape[0] not in (views.n_given, len(views)):
-            raise ValueError(f"PointCloudFuser.add: expected one colour image per view ({views.n_given} given, {len(views)} kept), "
-                             f"got {list(colors.shape)}")
+        views.check_colors(colors, "PointCloudFuser.add")
         K = len(views)
         if K == 0:
             return

@@ -110,6 +110,33 @@ class Views:
             raise ValueError(f"feature maps: expected one per view ({self.n_given} given, {len(self.kept)} kept), got {maps.shape[0]}")
         return maps
 
+    def check_colors(self, colors, who) -> None:
+        """`colors` as the fusion stages take them: uint8 [V, Hc, Wc, 3] on the device, one per given or per kept view."""
+        check_colors(colors, who)
+        if colors.shape[0] not in (self.n_given, len(self)):
+            raise ValueError(f"{who}: expected one colour image per view ({self.n_given} given, {len(self)} kept), got {list(colors.shape)}")
+
+
+def check_colors(colors, who, V=None) -> None:
+    """Colour images uint8 [V, Hc, Wc, 3] on the device; with `V` their number is checked too."""
+    if not isinstance(colors, torch.Tensor):
+        raise TypeError(f"{who}: colors: expected a tensor, got {type(colors).__name__}")
+    if not colors.is_cuda:
+        raise RuntimeError(f"{who}: colors: expected a tensor on the HIP device, got {colors.device} (no CPU fallback)")
+    if colors.dtype != torch.uint8:
+        raise TypeError(f"{who}: colors must be uint8, got {colors.dtype}")
+    if colors.dim() != 4 or (V is not None and colors.shape[0] != V) or colors.shape[3] != 3 or colors.shape[1] < 1 or colors.shape[2] < 1:
+        raise ValueError(f"{who}: colors must be [{'V' if V is None else f'V = {V}'}, Hc, Wc, 3], got {list(colors.shape)}")
+
+
+def check_depth_range(r: dict) -> None:
+    """The depth-pixel parameters of a stage's rule (csrc/depth_pixel.h): `near`, `far` and, where the stage has the edge test,
+    `edge_abs`, `edge_rel` (`None` turns it off)."""
+    if not (float(r["near"]) >= 0.0 and float(r["far"]) >= float(r["near"])):
+        raise ValueError(f"need 0 <= near <= far, got near = {r['near']}, far = {r['far']}")
+    if r.get("edge_rel") is not None and not (float(r["edge_abs"]) >= 0.0 and float(r["edge_rel"]) >= 0.0):
+        raise ValueError(f"edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {r['edge_abs']}, {r['edge_rel']}")
+
 
 def _rule(rule: dict) -> dict:
     bad = set(rule) - set(RULE_DEFAULTS)

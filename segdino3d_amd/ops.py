@@ -2142,16 +2142,7 @@ def lift_visibility(points, world_to_cam, intrinsics, depth, depth_scale=None, n
     pp, ld, N, V = _lift_views(points, world_to_cam, intrinsics, "lift_visibility")
     if depth.dim() != 3 or depth.shape[0] != V or depth.shape[1] < 1 or depth.shape[2] < 1:
         raise ValueError(f"lift_visibility: depth must be [V = {V}, Hd, Wd], got {list(depth.shape)}")
-    if depth.dtype == torch.uint16:
-        if depth_scale is None or not float(depth_scale) > 0.0:
-            raise ValueError("lift_visibility: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
-        u16, scale = 1, float(depth_scale)
-    elif depth.dtype == torch.float32:
-        if depth_scale is not None:
-            raise ValueError("lift_visibility: fp32 depth is in metres and takes no depth_scale")
-        u16, scale = 0, 1.0
-    else:
-        raise TypeError(f"lift_visibility: depth must be uint16 or fp32, got {depth.dtype}")
+    u16, scale = _depth_arg(depth, depth_scale, "lift_visibility", max_dim=None)
     if int(border) != border or border < 0 or not near >= 0.0 or not tol_abs >= 0.0 or not tol_rel >= 0.0:
         raise ValueError("lift_visibility: border must be an integer >= 0; near, tol_abs and tol_rel must be >= 0")
     W = (V + 31) // 32
@@ -2246,16 +2237,7 @@ def lift_query_centres(depth, depth_scale, intrinsics, cam_to_world, masks, far_
     V, Hd, Wd = depth.shape
     if Hd < 1 or Wd < 1 or Hd * Wd > LIFTQ_MAX_PIXELS:
         raise ValueError(f"lift_query_centres: depth images must have 1 .. 2^28 pixels (the int64 sums cannot overflow then), got {Hd} x {Wd}")
-    if depth.dtype == torch.uint16:
-        if depth_scale is None or not float(depth_scale) > 0.0:
-            raise ValueError("lift_query_centres: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
-        u16, scale = 1, float(depth_scale)
-    elif depth.dtype == torch.float32:
-        if depth_scale is not None:
-            raise ValueError("lift_query_centres: fp32 depth is in metres and takes no depth_scale")
-        u16, scale = 0, 1.0
-    else:
-        raise TypeError(f"lift_query_centres: depth must be uint16 or fp32, got {depth.dtype}")
+    u16, scale = _depth_arg(depth, depth_scale, "lift_query_centres", max_dim=None)
     _want_shape(intrinsics, [(V, 4)], "lift_query_centres: intrinsics")
     _want_shape(cam_to_world, [(V, 3, 4)], "lift_query_centres: cam_to_world")
     if masks.dtype not in (torch.bool, torch.uint8):
@@ -2623,12 +2605,64 @@ FUSE_MAX_DIM = 16384
 FUSE_INFO = ("n", "cells", "pixels_used", "out_of_range", "overflow")
 
 
+# The argument checks the stages that start from a depth pixel share (csrc/depth_pixel.h has the C side), one per rule.
+def _depth_arg(depth, depth_scale, who, dims=3, max_dim=FUSE_MAX_DIM):
+    """depth of rank `dims`, uint16 with a `depth_scale` or fp32 metres without one -> (u16, scale) as the C calls take them."""
+    if depth.dim() != dims:
+        raise ValueError(f"{who}: depth must be {'[V, Hd, Wd]' if dims == 3 else '[Hd, Wd], one frame'}, got {list(depth.shape)}")
+    Hd, Wd = depth.shape[-2:]
+    if max_dim is not None and not (1 <= Hd <= max_dim and 1 <= Wd <= max_dim):
+        raise ValueError(f"{who}: depth images must be 1 .. {max_dim} a side, got {Hd} x {Wd}")
+    if depth.dtype == torch.uint16:
+        if depth_scale is None or not float(depth_scale) > 0.0:
+            raise ValueError(f"{who}: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
+        return 1, float(depth_scale)
+    if depth.dtype == torch.float32:
+        if depth_scale is not None:
+            raise ValueError(f"{who}: fp32 depth is in metres and takes no depth_scale")
+        return 0, 1.0
+    raise TypeError(f"{who}: depth must be uint16 or fp32, got {depth.dtype}")
+
+
+def _range_args(near, far, edge_abs, edge_rel, who):
+    """-> (near, far, edge_abs, edge_rel, use_edges) as the C calls take them; `edge_rel=None` turns the edge test off."""
+    if not (float(near) >= 0.0 and float(far) >= float(near)):
+        raise ValueError(f"{who}: need 0 <= near <= far, got near = {near}, far = {far}")
+    if edge_rel is None:
+        return float(near), float(far), 0.0, 0.0, 0
+    if not (float(edge_abs) >= 0.0 and float(edge_rel) >= 0.0):
+        raise ValueError(f"{who}: edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {edge_abs}, {edge_rel}")
+    return float(near), float(far), float(edge_abs), float(edge_rel), 1
+
+
+def _colors_arg(colors, V, who):
+    """colors uint8 [V, Hc, Wc, 3] -> (Hc, Wc)."""
+    if colors.dtype != torch.uint8:
+        raise TypeError(f"{who}: colors must be uint8, got {colors.dtype}")
+    if colors.dim() != 4 or colors.shape[0] != V or colors.shape[3] != 3 or not (1 <= colors.shape[1] <= FUSE_MAX_DIM and
+                                                                                  1 <= colors.shape[2] <= FUSE_MAX_DIM):
+        raise ValueError(f"{who}: colors must be [V = {V}, Hc, Wc, 3] with 1 .. {FUSE_MAX_DIM} a side, got {list(colors.shape)}")
+    return colors.shape[1], colors.shape[2]
+
+
+def _pow2_capacity(capacity, lo, hi, who, what=""):
+    if int(capacity) != capacity or not lo <= capacity <= hi or capacity & (capacity - 1):
+        raise ValueError(f"{who}: capacity must be a power of two in [{lo}, 2^{hi.bit_length() - 1}]{what}, got {capacity}")
+    return int(capacity)
+
+
+def _positive_f32(x, name, who):
+    x32 = float(np.float32(x))
+    if not (x32 > 0.0 and np.isfinite(x32)):
+        raise ValueError(f"{who}: {name} must be positive and finite in fp32, got {x}")
+    return x32
+
+
 def fuse_workspace(capacity: int, device):
     """The caller-owned state of one fusion: an emptied table of `capacity` slots (a power of two) with zeroed counters, as a uint8
     device tensor (`sd3d_fuse_ws_bytes`, `sd3d_fuse_reset`).  Enqueues only."""
     lib = _lib.load()
-    if int(capacity) != capacity or not FUSE_MIN_CAPACITY <= capacity <= FUSE_MAX_CAPACITY or capacity & (capacity - 1):
-        raise ValueError(f"fuse_workspace: capacity must be a power of two in [{FUSE_MIN_CAPACITY}, 2^24], got {capacity}")
+    capacity = _pow2_capacity(capacity, FUSE_MIN_CAPACITY, FUSE_MAX_CAPACITY, "fuse_workspace")
     if torch.device(device).type != "cuda":
         raise RuntimeError(f"fuse_workspace: expected the HIP device, got {device} (no CPU fallback)")
     ws = torch.empty(lib.sd3d_fuse_ws_bytes(int(capacity)), dtype=torch.uint8, device=device)
@@ -2649,47 +2683,22 @@ def fuse_accumulate(depth, depth_scale, intrinsics, cam_to_world, colors, ws, ca
     rounded to fp32 here; `edge_rel=None` turns the edge test off.  Enqueues only."""
     lib = _lib.load()
     who = "fuse_accumulate"
-    if depth.dim() != 3:
-        raise ValueError(f"{who}: depth must be [V, Hd, Wd], got {list(depth.shape)}")
+    u16, scale = _depth_arg(depth, depth_scale, who)
     V, Hd, Wd = depth.shape
-    if not (1 <= Hd <= FUSE_MAX_DIM and 1 <= Wd <= FUSE_MAX_DIM):
-        raise ValueError(f"{who}: depth images must be 1 .. {FUSE_MAX_DIM} a side, got {Hd} x {Wd}")
-    if depth.dtype == torch.uint16:
-        if depth_scale is None or not float(depth_scale) > 0.0:
-            raise ValueError(f"{who}: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
-        u16, scale = 1, float(depth_scale)
-    elif depth.dtype == torch.float32:
-        if depth_scale is not None:
-            raise ValueError(f"{who}: fp32 depth is in metres and takes no depth_scale")
-        u16, scale = 0, 1.0
-    else:
-        raise TypeError(f"{who}: depth must be uint16 or fp32, got {depth.dtype}")
     _want_shape(intrinsics, [(V, 4)], f"{who}: intrinsics")
     _want_shape(cam_to_world, [(V, 3, 4)], f"{who}: cam_to_world")
-    if colors.dtype != torch.uint8:
-        raise TypeError(f"{who}: colors must be uint8, got {colors.dtype}")
-    if colors.dim() != 4 or colors.shape[0] != V or colors.shape[3] != 3 or not (1 <= colors.shape[1] <= FUSE_MAX_DIM and
-                                                                                  1 <= colors.shape[2] <= FUSE_MAX_DIM):
-        raise ValueError(f"{who}: colors must be [V = {V}, Hc, Wc, 3] with 1 .. {FUSE_MAX_DIM} a side, got {list(colors.shape)}")
-    Hc, Wc = colors.shape[1:3]
+    Hc, Wc = _colors_arg(colors, V, who)
     if int(stride) != stride or not 1 <= stride <= FUSE_MAX_DIM:
         raise ValueError(f"{who}: stride must be an integer in [1, {FUSE_MAX_DIM}], got {stride}")
-    if not (float(near) >= 0.0 and float(far) >= float(near)):
-        raise ValueError(f"{who}: need 0 <= near <= far, got near = {near}, far = {far}")
-    use_edges = edge_rel is not None
-    if use_edges and not (float(edge_abs) >= 0.0 and float(edge_rel) >= 0.0):
-        raise ValueError(f"{who}: edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {edge_abs}, {edge_rel}")
-    inv32 = float(np.float32(inv_voxel))
-    if not (inv32 > 0.0 and np.isfinite(inv32)):
-        raise ValueError(f"{who}: inv_voxel must be positive and finite in fp32, got {inv_voxel}")
+    rng = _range_args(near, far, edge_abs, edge_rel, who)
+    inv32 = _positive_f32(inv_voxel, "inv_voxel", who)
     dp, ip = _ptr(depth, None, f"{who}: depth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
     cp, kp = _ptr(cam_to_world, torch.float32, f"{who}: cam_to_world"), _ptr(colors, torch.uint8, f"{who}: colors")
     wp = _ptr(ws, torch.uint8, f"{who}: ws")
     if V == 0:
         return
-    _lib.check(lib.sd3d_fuse_accumulate(dp, u16, scale, ip, cp, kp, V, Hd, Wd, Hc, Wc, int(stride), float(near), float(far),
-                                        float(edge_abs) if use_edges else 0.0, float(edge_rel) if use_edges else 0.0, int(use_edges), inv32,
-                                        wp, ws.numel(), int(capacity), _stream()), who)
+    _lib.check(lib.sd3d_fuse_accumulate(dp, u16, scale, ip, cp, kp, V, Hd, Wd, Hc, Wc, int(stride), *rng, inv32, wp, ws.numel(), int(capacity),
+                                        _stream()), who)
 
 
 def fuse_emit(ws, capacity: int, min_obs: int, out_cap: int, want_keys: bool = False):
@@ -2724,9 +2733,7 @@ TSDF_INFO = ("vertices", "faces", "blocks", "voxels_observed", "updates", "out_o
 
 
 def _tsdf_capacity(capacity, who):
-    if int(capacity) != capacity or not TSDF_MIN_CAPACITY <= capacity <= TSDF_MAX_CAPACITY or capacity & (capacity - 1):
-        raise ValueError(f"{who}: capacity must be a power of two in [{TSDF_MIN_CAPACITY}, 2^20] (blocks of 8 x 8 x 8 voxels), got {capacity}")
-    return int(capacity)
+    return _pow2_capacity(capacity, TSDF_MIN_CAPACITY, TSDF_MAX_CAPACITY, who, " (blocks of 8 x 8 x 8 voxels)")
 
 
 def tsdf_workspace(capacity: int, device):
@@ -2763,29 +2770,11 @@ def tsdf_state_views(ws, capacity: int):
 
 
 def _tsdf_depth(depth, depth_scale, who):
-    if depth.dim() != 3:
-        raise ValueError(f"{who}: depth must be [V, Hd, Wd], got {list(depth.shape)}")
-    V, Hd, Wd = depth.shape
-    if V > TSDF_MAX_CALL_VIEWS:
-        raise ValueError(f"{who}: at most {TSDF_MAX_CALL_VIEWS} views a call, got {V}")
-    if not (1 <= Hd <= FUSE_MAX_DIM and 1 <= Wd <= FUSE_MAX_DIM):
-        raise ValueError(f"{who}: depth images must be 1 .. {FUSE_MAX_DIM} a side, got {Hd} x {Wd}")
-    if depth.dtype == torch.uint16:
-        if depth_scale is None or not float(depth_scale) > 0.0:
-            raise ValueError(f"{who}: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
-        return 1, float(depth_scale)
-    if depth.dtype == torch.float32:
-        if depth_scale is not None:
-            raise ValueError(f"{who}: fp32 depth is in metres and takes no depth_scale")
-        return 0, 1.0
-    raise TypeError(f"{who}: depth must be uint16 or fp32, got {depth.dtype}")
-
-
-def _tsdf_f32(x, name, who):
-    x32 = float(np.float32(x))
-    if not (x32 > 0.0 and np.isfinite(x32)):
-        raise ValueError(f"{who}: {name} must be positive and finite in fp32, got {x}")
-    return x32
+    """`_depth_arg` and the view limit of one touch / integrate call (a bit per view in the `touched` words)."""
+    u16, scale = _depth_arg(depth, depth_scale, who)
+    if depth.shape[0] > TSDF_MAX_CALL_VIEWS:
+        raise ValueError(f"{who}: at most {TSDF_MAX_CALL_VIEWS} views a call, got {depth.shape[0]}")
+    return u16, scale
 
 
 def tsdf_touch(depth, depth_scale, intrinsics, cam_to_world, ws, capacity: int, inv_voxel: float, half_step: float, near=0.1, far=6.0,
@@ -2799,17 +2788,12 @@ def tsdf_touch(depth, depth_scale, intrinsics, cam_to_world, ws, capacity: int, 
     V, Hd, Wd = depth.shape
     _want_shape(intrinsics, [(V, 4)], f"{who}: intrinsics")
     _want_shape(cam_to_world, [(V, 3, 4)], f"{who}: cam_to_world")
-    if not (float(near) >= 0.0 and float(far) >= float(near)):
-        raise ValueError(f"{who}: need 0 <= near <= far, got near = {near}, far = {far}")
-    use_edges = edge_rel is not None
-    if use_edges and not (float(edge_abs) >= 0.0 and float(edge_rel) >= 0.0):
-        raise ValueError(f"{who}: edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {edge_abs}, {edge_rel}")
-    inv32, h32 = _tsdf_f32(inv_voxel, "inv_voxel", who), _tsdf_f32(half_step, "half_step", who)
+    rng = _range_args(near, far, edge_abs, edge_rel, who)
+    inv32, h32 = _positive_f32(inv_voxel, "inv_voxel", who), _positive_f32(half_step, "half_step", who)
     dp, ip = _ptr(depth, None, f"{who}: depth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
     cp, wp = _ptr(cam_to_world, torch.float32, f"{who}: cam_to_world"), _ptr(ws, torch.uint8, f"{who}: ws")
     vdepth = torch.empty(V, Hd, Wd, dtype=torch.float32, device=depth.device)
-    _lib.check(lib.sd3d_tsdf_touch(dp if V else None, u16, scale, ip if V else None, cp if V else None, V, Hd, Wd, float(near), float(far),
-                                   float(edge_abs) if use_edges else 0.0, float(edge_rel) if use_edges else 0.0, int(use_edges), inv32, h32,
+    _lib.check(lib.sd3d_tsdf_touch(dp if V else None, u16, scale, ip if V else None, cp if V else None, V, Hd, Wd, *rng, inv32, h32,
                                    _ptr(vdepth) if V else None, wp, ws.numel(), _tsdf_capacity(capacity, who), _stream()), who)
     return vdepth
 
@@ -2826,13 +2810,8 @@ def tsdf_integrate(vdepth, intrinsics, world_to_cam, colors, ws, capacity: int, 
     V, Hd, Wd = vdepth.shape
     _want_shape(intrinsics, [(V, 4)], f"{who}: intrinsics")
     _want_shape(world_to_cam, [(V, 3, 4)], f"{who}: world_to_cam")
-    if colors.dtype != torch.uint8:
-        raise TypeError(f"{who}: colors must be uint8, got {colors.dtype}")
-    if colors.dim() != 4 or colors.shape[0] != V or colors.shape[3] != 3 or not (1 <= colors.shape[1] <= FUSE_MAX_DIM and
-                                                                                  1 <= colors.shape[2] <= FUSE_MAX_DIM):
-        raise ValueError(f"{who}: colors must be [V = {V}, Hc, Wc, 3] with 1 .. {FUSE_MAX_DIM} a side, got {list(colors.shape)}")
-    Hc, Wc = colors.shape[1:3]
-    v32, t32, q32 = _tsdf_f32(voxel, "voxel", who), _tsdf_f32(trunc, "trunc", who), _tsdf_f32(qscale, "qscale", who)
+    Hc, Wc = _colors_arg(colors, V, who)
+    v32, t32, q32 = _positive_f32(voxel, "voxel", who), _positive_f32(trunc, "trunc", who), _positive_f32(qscale, "qscale", who)
     if not t32 >= v32:
         raise ValueError(f"{who}: need voxel <= trunc, got {voxel}, {trunc}")
     dp, ip = _ptr(vdepth, torch.float32, f"{who}: vdepth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
@@ -2855,7 +2834,7 @@ def tsdf_mesh(ws, capacity: int, min_weight: int, voxel: float, max_vertices: in
     if int(max_vertices) != max_vertices or not 1 <= max_vertices <= TSDF_MAX_VERTICES:
         raise ValueError(f"{who}: max_vertices must be an integer in [1, 2^26], got {max_vertices}")
     max_vertices = int(max_vertices)
-    v32 = _tsdf_f32(voxel, "voxel", who)
+    v32 = _positive_f32(voxel, "voxel", who)
     wp = _ptr(ws, torch.uint8, f"{who}: ws")
     dev = ws.device
     scratch = torch.empty(lib.sd3d_tsdf_mesh_ws_bytes(max_vertices), dtype=torch.uint8, device=dev)
@@ -2915,26 +2894,20 @@ def track_iterate(depth, depth_scale, intrinsics, state, ws, capacity: int, stri
     float parameters are rounded to fp32 here.  Enqueues only."""
     lib = _lib.load()
     who = "track_iterate"
-    if depth.dim() != 2:
-        raise ValueError(f"{who}: depth must be [Hd, Wd], one frame, got {list(depth.shape)}")
-    u16, scale = _tsdf_depth(depth[None], depth_scale, who)
+    u16, scale = _depth_arg(depth, depth_scale, who, dims=2)
     Hd, Wd = depth.shape
     _want_shape(intrinsics, [(4,)], f"{who}: intrinsics")
     if int(stride) != stride or not 1 <= stride <= TRACK_MAX_STRIDE:
         raise ValueError(f"{who}: stride must be an integer in [1, {TRACK_MAX_STRIDE}], got {stride}")
-    if not (float(near) >= 0.0 and float(far) >= float(near)):
-        raise ValueError(f"{who}: need 0 <= near <= far, got near = {near}, far = {far}")
-    use_edges = edge_rel is not None
-    if use_edges and not (float(edge_abs) >= 0.0 and float(edge_rel) >= 0.0):
-        raise ValueError(f"{who}: edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {edge_abs}, {edge_rel}")
+    rng = _range_args(near, far, edge_abs, edge_rel, who)
     if int(track_min_weight) != track_min_weight or not 1 <= track_min_weight <= 0x7FFFFFFF:
         raise ValueError(f"{who}: track_min_weight must be an integer >= 1, got {track_min_weight}")
     if int(min_samples) != min_samples or not 1 <= min_samples <= 0x7FFFFFFF:
         raise ValueError(f"{who}: min_samples must be an integer >= 1, got {min_samples}")
     if not 0.0 <= float(damping) <= 1.0:
         raise ValueError(f"{who}: damping must lie in [0, 1], got {damping}")
-    inv32, v32, y32 = _tsdf_f32(inv_voxel, "inv_voxel", who), _tsdf_f32(voxel, "voxel", who), _tsdf_f32(ymax, "ymax", who)
-    r32, t32 = _tsdf_f32(max_rot, "max_rot", who), _tsdf_f32(max_trans, "max_trans", who)
+    inv32, v32, y32 = _positive_f32(inv_voxel, "inv_voxel", who), _positive_f32(voxel, "voxel", who), _positive_f32(ymax, "ymax", who)
+    r32, t32 = _positive_f32(max_rot, "max_rot", who), _positive_f32(max_trans, "max_trans", who)
     samples = -(-Hd // int(stride)) * -(-Wd // int(stride))
     jq = 4096.0 * (y32 * inv32) * 1.001 + 2.0
     if not (jq < 2.0 ** 31 and jq * jq * samples < 9.0e18):
@@ -2942,10 +2915,9 @@ def track_iterate(depth, depth_scale, intrinsics, state, ws, capacity: int, stri
                          f"inv_voxel = {inv_voxel}, {samples} samples")
     dp, ip = _ptr(depth, None, f"{who}: depth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
     sp, wp = _ptr(state, torch.uint8, f"{who}: state"), _ptr(ws, torch.uint8, f"{who}: ws")
-    _lib.check(lib.sd3d_track_iterate(dp, u16, scale, ip, Hd, Wd, int(stride), float(near), float(far), float(edge_abs) if use_edges else 0.0,
-                                      float(edge_rel) if use_edges else 0.0, int(use_edges), inv32, v32, y32, int(track_min_weight),
-                                      int(min_samples), float(np.float32(damping)), r32, t32, sp, state.numel(), wp, ws.numel(),
-                                      _tsdf_capacity(capacity, who), _stream()), who)
+    _lib.check(lib.sd3d_track_iterate(dp, u16, scale, ip, Hd, Wd, int(stride), *rng, inv32, v32, y32, int(track_min_weight), int(min_samples),
+                                      float(np.float32(damping)), r32, t32, sp, state.numel(), wp, ws.numel(), _tsdf_capacity(capacity, who),
+                                      _stream()), who)
 
 
 def track_end(state, pose=None, cam_to_world=None, world_to_cam=None, info=None):
@@ -3045,31 +3017,17 @@ def nearest_pixels(depth, depth_scale, intrinsics, cam_to_world, index, n_points
     lib = _lib.load()
     who = "nearest_pixels"
     radius = _nearest_radius(radius, who)
-    if depth.dim() != 3:
-        raise ValueError(f"{who}: depth must be [V, Hd, Wd], got {list(depth.shape)}")
+    u16, scale = _depth_arg(depth, depth_scale, who)
     V, Hd, Wd = depth.shape
-    if not (1 <= Hd <= FUSE_MAX_DIM and 1 <= Wd <= FUSE_MAX_DIM):
-        raise ValueError(f"{who}: depth images must be 1 .. {FUSE_MAX_DIM} a side, got {Hd} x {Wd}")
-    if depth.dtype == torch.uint16:
-        if depth_scale is None or not float(depth_scale) > 0.0:
-            raise ValueError(f"{who}: uint16 depth needs a depth_scale > 0 (ScanNet: 0.001)")
-        u16, scale = 1, float(depth_scale)
-    elif depth.dtype == torch.float32:
-        if depth_scale is not None:
-            raise ValueError(f"{who}: fp32 depth is in metres and takes no depth_scale")
-        u16, scale = 0, 1.0
-    else:
-        raise TypeError(f"{who}: depth must be uint16 or fp32, got {depth.dtype}")
     _want_shape(intrinsics, [(V, 4)], f"{who}: intrinsics")
     _want_shape(cam_to_world, [(V, 3, 4)], f"{who}: cam_to_world")
-    if not (float(near) >= 0.0 and float(far) >= float(near)):
-        raise ValueError(f"{who}: need 0 <= near <= far, got near = {near}, far = {far}")
+    near, far = _range_args(near, far, None, None, who)[:2]
     N = int(n_points)
     dp, ip = _ptr(depth, None, f"{who}: depth"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
     cp, wp = _ptr(cam_to_world, torch.float32, f"{who}: cam_to_world"), _ptr(index, torch.uint8, f"{who}: index")
     L, lp, fill, idx, d2, out = _nearest_outputs((V, Hd, Wd), N, labels, fill, return_index, return_d2, depth.device, who)
     if V:
-        _lib.check(lib.sd3d_nearest_pixels(dp, u16, scale, ip, cp, V, Hd, Wd, float(near), float(far), wp, index.numel(), N, radius,
+        _lib.check(lib.sd3d_nearest_pixels(dp, u16, scale, ip, cp, V, Hd, Wd, near, far, wp, index.numel(), N, radius,
                                            lp if N else None, L, fill, _ptr(idx), _ptr(d2), _ptr(out), _stream()), who)
     return idx, d2, out
 

@@ -77,6 +77,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .lift2d import check_colors
 from .tsdf import TsdfVolume
 
 DEFAULT_SCHEDULE = ((4, 3), (2, 3), (1, 3))
@@ -193,14 +194,7 @@ class Tracker:
         V, H, W = depth.shape
         if tuple(intrinsics.shape) != (V, 4):
             raise ValueError(f"{who}: intrinsics must be [V = {V}, 4], got {list(intrinsics.shape)}")
-        if not isinstance(colors, torch.Tensor):
-            raise TypeError(f"{who}: colors: expected a tensor, got {type(colors).__name__}")
-        if not colors.is_cuda:
-            raise RuntimeError(f"{who}: colors: expected a tensor on the HIP device, got {colors.device} (no CPU fallback)")
-        if colors.dtype != torch.uint8:
-            raise TypeError(f"{who}: colors must be uint8, got {colors.dtype}")
-        if colors.dim() != 4 or colors.shape[0] != V or colors.shape[3] != 3 or colors.shape[1] < 1 or colors.shape[2] < 1:
-            raise ValueError(f"{who}: colors must be [V = {V}, Hc, Wc, 3], got {list(colors.shape)}")
+        check_colors(colors, who, V)
         if V == 0:
             return
         self._p.check_width(who, H, W)

@@ -40,7 +40,7 @@ import numbers
 import torch
 
 from . import ops
-from .lift2d import Views
+from .lift2d import Views, check_depth_range
 
 RULE_DEFAULTS = dict(near=0.1, far=6.0)
 
@@ -50,8 +50,7 @@ def _rule(rule: dict) -> dict:
     if bad:
         raise TypeError(f"unknown pixel-query parameter(s) {sorted(bad)}; known: {sorted(RULE_DEFAULTS)}")
     r = {**RULE_DEFAULTS, **rule}
-    if not (float(r["near"]) >= 0.0 and float(r["far"]) >= float(r["near"])):
-        raise ValueError(f"need 0 <= near <= far, got near = {r['near']}, far = {r['far']}")
+    check_depth_range(r)
     return r
 
 

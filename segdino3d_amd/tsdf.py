@@ -65,7 +65,7 @@ from collections import namedtuple
 import torch
 
 from . import ops
-from .lift2d import Views
+from .lift2d import Views, check_colors, check_depth_range
 
 RULE_DEFAULTS = dict(near=0.1, far=6.0, edge_abs=0.02, edge_rel=0.02, min_weight=2)
 MIN_VOXEL = 2.0 ** -6               # |w| < 2^14 then keeps every voxel index inside [-2^20, 2^20)
@@ -85,10 +85,7 @@ def _rule(rule: dict) -> dict:
     r = {**RULE_DEFAULTS, **rule}
     if int(r["min_weight"]) != r["min_weight"] or r["min_weight"] < 1:
         raise ValueError(f"min_weight must be an integer >= 1, got {r['min_weight']}")
-    if not (float(r["near"]) >= 0.0 and float(r["far"]) >= float(r["near"])):
-        raise ValueError(f"need 0 <= near <= far, got near = {r['near']}, far = {r['far']}")
-    if r["edge_rel"] is not None and not (float(r["edge_abs"]) >= 0.0 and float(r["edge_rel"]) >= 0.0):
-        raise ValueError(f"edge_abs and edge_rel must be >= 0 (edge_rel=None: no edge test), got {r['edge_abs']}, {r['edge_rel']}")
+    check_depth_range(r)
     return r
 
 
@@ -105,9 +102,8 @@ class TsdfVolume:
             raise ValueError(f"TsdfVolume: voxel must be finite and >= 2^-6 m (voxel indices must fit 21 bits), got {voxel}")
         if not float(voxel) <= float(trunc) <= 8.0 * float(voxel):
             raise ValueError(f"TsdfVolume: need voxel <= trunc <= 8 * voxel (the band is at most one block), got voxel = {voxel}, trunc = {trunc}")
-        if int(capacity) != capacity or capacity & (capacity - 1) or not ops.TSDF_MIN_CAPACITY <= capacity <= ops.TSDF_MAX_CAPACITY:
-            raise ValueError(f"TsdfVolume: capacity must be a power of two in [{ops.TSDF_MIN_CAPACITY}, 2^20] blocks, got {capacity}")
-        self.voxel, self.trunc, self.capacity = float(voxel), float(trunc), int(capacity)
+        self.voxel, self.trunc = float(voxel), float(trunc)
+        self.capacity = ops._pow2_capacity(capacity, ops.TSDF_MIN_CAPACITY, ops.TSDF_MAX_CAPACITY, "TsdfVolume", " blocks")
         # float64 here; ops rounds each to fp32 once
         self.inv_voxel, self.half_step, self.qscale = 1.0 / self.voxel, self.trunc / 2.0, 4096.0 / self.trunc
         self.n_views = 0
@@ -117,17 +113,7 @@ class TsdfVolume:
     def add(self, views: Views, colors) -> None:
         if not isinstance(views, Views):
             raise TypeError(f"TsdfVolume.add: views must be a lift2d.Views, got {type(views).__name__}")
-        if not isinstance(colors, torch.Tensor):
-            raise TypeError(f"TsdfVolume.add: colors: expected a tensor, got {type(colors).__name__}")
-        if not colors.is_cuda:
-            raise RuntimeError(f"TsdfVolume.add: colors: expected a tensor on the HIP device, got {colors.device} (no CPU fallback)")
-        if colors.dtype != torch.uint8:
-            raise TypeError(f"TsdfVolume.add: colors must be uint8, got {colors.dtype}")
-        if colors.dim() != 4 or colors.shape[3] != 3 or colors.shape[1] < 1 or colors.shape[2] < 1:
-            raise ValueError(f"TsdfVolume.add: colors must be [V, Hc, Wc, 3], got {list(colors.shape)}")
-        if colors.shape[0] not in (views.n_given, len(views)):
-            raise ValueError(f"TsdfVolume.add: expected one colour image per view ({views.n_given} given, {len(views)} kept), "
-                             f"got {list(colors.shape)}")
+        views.check_colors(colors, "TsdfVolume.add")
         K = len(views)
         if K == 0:
             return
@@ -153,8 +139,7 @@ class TsdfVolume:
         launches, every one of its samples fails `|w| < 2^14` at step 2 and is counted in `out_of_range`, and it writes no voxel.
         Every view counts towards the 2^17 of a volume.  Enqueues only."""
         who = "TsdfVolume.add_posed"
-        for t, name in ((depth, "depth"), (intrinsics, "intrinsics"), (cam_to_world, "cam_to_world"), (world_to_cam, "world_to_cam"),
-                        (colors, "colors")):
+        for t, name in ((depth, "depth"), (intrinsics, "intrinsics"), (cam_to_world, "cam_to_world"), (world_to_cam, "world_to_cam")):
             if not isinstance(t, torch.Tensor):
                 raise TypeError(f"{who}: {name}: expected a tensor, got {type(t).__name__}")
             if not t.is_cuda:
@@ -162,10 +147,7 @@ class TsdfVolume:
         if depth.dim() != 3:
             raise ValueError(f"{who}: depth must be [V, Hd, Wd], got {list(depth.shape)}")
         K = depth.shape[0]
-        if colors.dtype != torch.uint8:
-            raise TypeError(f"{who}: colors must be uint8, got {colors.dtype}")
-        if colors.dim() != 4 or colors.shape[0] != K or colors.shape[3] != 3 or colors.shape[1] < 1 or colors.shape[2] < 1:
-            raise ValueError(f"{who}: colors must be [V = {K}, Hc, Wc, 3], got {list(colors.shape)}")
+        check_colors(colors, who, K)
         if K == 0:
             return
         if self.n_views + K > MAX_VIEWS:

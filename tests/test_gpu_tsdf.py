@@ -275,3 +275,25 @@ def test_device_argument_errors():
         ops.tsdf_workspace(1000, d)
     vertices, faces = vol.mesh()
     assert tuple(vertices.shape) == (0, 6) and tuple(faces.shape) == (0, 3)           # nothing was added by the refused calls
+
+
+# ---------------------------------------------------------------------------------------------- steps 2 and 3 of the pixel rule, directly
+@pytest.mark.parametrize("edges", C.PIXEL_RULE_EDGES, ids=("edges", "no-edges"))
+@pytest.mark.parametrize("kind", ("u16", "f32"))
+@pytest.mark.parametrize("H, W", C.PIXEL_RULE_SIZES)
+def test_touch_vdepth_equals_the_pixel_rule(H, W, kind, edges):
+    """`vdepth` of ops.tsdf_touch is the front end every depth-pixel stage shares (csrc/depth_pixel.h): d where the pixel is valid by
+    steps 2 and 3, else 0.  Bit for bit against valid_pixels of tests/fuse_views_ref.py on images with a zero, a NaN (fp32), a pixel
+    exactly at `near` and one exactly at `far`, and a step edge; tests/test_tsdf_ref.py checks that each image has pixels of both
+    kinds."""
+    from segdino3d_amd import ops
+    d = dev()
+    c = C.pixel_rule_case(H, W, kind)
+    ok = C.pixel_rule_valid(c, **edges)
+    assert ok.any() and not ok.all()
+    want = np.where(ok, c["metres"], np.float32(0))
+    c2w, _ = K.R.cam_to_world(c["poses"])
+    ws = ops.tsdf_workspace(1 << 10, d)
+    got = ops.tsdf_touch(_t(c["depth"], d), c["scale"], _t(c["intr"], d), _t(c2w, d), ws, 1 << 10, 50.0, 0.04, c["near"], c["far"], **edges)
+    assert got.dtype == torch.float32 and tuple(got.shape) == (1, H, W)
+    assert np.array_equal(got.cpu().numpy()[0].view(np.uint32), want.view(np.uint32)), (H, W, kind, edges)

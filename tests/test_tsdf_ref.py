@@ -98,3 +98,29 @@ def test_nothing_to_fuse():
     dark = {**c, "depth_u16": np.zeros_like(c["depth_u16"])}
     vol, mesh = C.ref(dark, min_weight=1)
     assert len(vol.keys) == 0 and vol.updates == 0 and mesh.vertices.shape == (0, 6)
+
+
+# ---------------------------------------------------------------------------------------------- the pixel-rule images decide something
+@pytest.mark.parametrize("edges", C.PIXEL_RULE_EDGES, ids=("edges", "no-edges"))
+@pytest.mark.parametrize("kind", ("u16", "f32"))
+@pytest.mark.parametrize("H, W", C.PIXEL_RULE_SIZES)
+def test_pixel_rule_images_have_valid_and_invalid_pixels(H, W, kind, edges):
+    """What tests/test_gpu_tsdf.py compares `vdepth` against cannot be all zeros or all depth: every image has pixels of both kinds,
+    the planted zero (and NaN) is invalid, the pixels exactly at `near` and `far` are valid where no edge test can drop them, and
+    the planted step drops pixels only with the edge test on."""
+    c = C.pixel_rule_case(H, W, kind)
+    ok = C.pixel_rule_valid(c, **edges)
+    assert ok.shape == (H, W) and ok.any() and not ok.all()
+    assert not ok[1, 1] and c["metres"][1, 1] == 0
+    if kind == "f32":
+        assert np.isnan(c["metres"][0, 3]) and not ok[0, 3]
+    assert (c["metres"][ok] >= np.float32(c["near"])).all() and (c["metres"][ok] <= np.float32(c["far"])).all()
+    off = C.pixel_rule_valid(c, edge_abs=0.02, edge_rel=None)
+    assert off[2, 2] and off[3, 4] and c["metres"][2, 2] == np.float32(c["near"]) and c["metres"][3, 4] == np.float32(c["far"])
+    below, above = c["metres"] < np.float32(c["near"]), c["metres"] > np.float32(c["far"])
+    assert (below & (c["metres"] > 0)).any() and above.any() and not off[below | above].any()
+    on = C.pixel_rule_valid(c, edge_abs=0.02, edge_rel=0.02)
+    assert (off & ~on).any() and not (on & ~off).any()                                 # the edge test only drops pixels
+    assert on[2, 2] and on[3, 4]                                                       # >= near and <= far hold in both variants
+    step = off[:, 7 if W > 7 else 4] & ~on[:, 7 if W > 7 else 4]                       # a column beside the planted step
+    assert step.any()

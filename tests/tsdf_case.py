@@ -5,6 +5,7 @@ import functools
 import numpy as np
 
 import fuse_views_case as K
+import fuse_views_ref as FR
 import tsdf_ref as R
 
 DEPTH_SCALE = K.DEPTH_SCALE
@@ -45,6 +46,36 @@ def block_face_wall(on_centres=False):
 
 
 BLOCK_FACE_RULE = dict(voxel=2.0 ** -5, trunc=0.125, min_weight=1)
+
+# one partial tile of the kernels' 8 x 32 pixels; a row that crosses the 32-wide tile edge and the 64 lanes of a wave
+PIXEL_RULE_SIZES = ((5, 7), (9, 65))
+PIXEL_RULE_EDGES = (dict(edge_abs=0.02, edge_rel=0.02), dict(edge_abs=0.02, edge_rel=None))
+
+
+def pixel_rule_case(H, W, kind):
+    """One view of `K.noisy` (holes and steps at random) with what steps 2 and 3 of the pixel rule must decide planted into it: a
+    zero at (1, 1), a pixel exactly at `near` at (2, 2) and one exactly at `far` at (3, 4), each with its four neighbours at the same
+    depth, a step edge of 0.6 m before and after columns 5 and 6 (but for (3, 5), which belongs to a flat cross) and, for fp32, a NaN
+    at (0, 3).  `near` and `far` ARE the metres of the two planted pixels.  -> the case with `depth` and `scale` of `kind`, `near`,
+    `far` and `metres` fp32 [H, W]."""
+    c = K.noisy(H, W, seed=H)
+    raw = np.array(c["depth_u16"])                                                     # 900 .. 1700 mm
+    raw[0, :, 5:7] += 600
+    for (y, x), mm in (((2, 2), 905), ((3, 4), 1500)):                                 # each in a flat cross: no edge test drops it
+        raw[0, y - 1:y + 2, x] = raw[0, y, x - 1:x + 2] = mm
+    raw[0, 1, 1] = 0
+    if kind == "u16":
+        depth, scale = raw, DEPTH_SCALE
+    else:
+        depth, scale = raw.astype(np.float32) * np.float32(DEPTH_SCALE), None
+        depth[0, 0, 3] = np.nan
+    metres = FR.depth_metres(depth, scale)[0]
+    return {**c, "depth": depth, "scale": scale, "metres": metres, "near": float(metres[2, 2]), "far": float(metres[3, 4])}
+
+
+def pixel_rule_valid(c, edge_abs, edge_rel):
+    """The restatement's steps 2 and 3 on a `pixel_rule_case` -> bool [H, W]."""
+    return FR.valid_pixels(c["metres"], c["near"], c["far"], edge_abs, edge_rel)
 
 
 def edge_use(faces):
