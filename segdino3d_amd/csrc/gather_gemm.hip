@@ -388,6 +388,7 @@ extern "C" int sd3d_dense_plan_code(int64_t rows, int Cin, int Cout) {
     const int64_t tiles = cdiv(rows, 32);
     const int64_t steps = Cin / 32;
     if (tiles >= 64 && steps >= 2) return 0;
+    if (sub <= 0) return 1;                                            // no columns: nothing will be launched (`sub % nt` would divide by zero)
     int nt = sub >= 4 ? 4 : sub;
     while (nt > 1 && tiles * cdiv(sub, nt) < 2048) --nt;
     if (sub % nt) { for (int c = nt; c >= 1; --c) if (sub % c == 0) { nt = c; break; } }

@@ -863,7 +863,9 @@ def linear_group(jobs, force_small=False):
             return [gather_gemm(x, w, x2=x2, shift=b, act=act, res=res, nt=small_rows_code(w.shape[-1]), exact=True)]
         return [gather_gemm(x, w, x2=x2, shift=b, act=act, res=res)]
     bf16 = getattr(_BF16_TLS, "on", False)
-    small = [force_small or (x.shape[0] < 2048 and not (bf16 and x.shape[0] >= BF16_MIN_ROWS) and x.shape[0] > 0) for (x, *_r) in jobs]
+    # (an empty job - no rows or no output columns - goes out alone: sd3d_linear_group refuses it, sd3d_gather_gemm launches nothing for it)
+    small = [(force_small or (x.shape[0] < 2048 and not (bf16 and x.shape[0] >= BF16_MIN_ROWS) and x.shape[0] > 0)) and w.shape[0] > 0
+             for (x, w, *_r) in jobs]
     # a few thousand rows each (one query per superpoint): the lock-step kernel of the single launch, several jobs per launch
     large = not bf16 and not force_small and all(w.dim() == 2 and w.shape[1] % 32 == 0 and dense_code(x.shape[0], w.shape[1], w.shape[0]) == 0
                                                    for (x, w, *_r) in jobs)
