@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 22
+#define SD3D_ABI_VERSION 23
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -101,14 +101,8 @@ int sd3d_unique_sorted(const uint64_t* keys, const uint32_t* src_idx, int64_t n_
                        uint64_t* ukeys, int32_t* seg_start, int32_t* map, int32_t* n_unique_dev, void* ws,
                        size_t ws_bytes, const float* clip_stats, float clip_inv_voxel, int clip_level, int clip_min_shape,
                        void* stream);
-/* ALL coarser levels of a scene from its sorted level-0 unique keys in four launches: level l = 1..n_extra keeps the runs of
- * (Morton >> 3 l).  ukeys[l - 1] [<= n_cap], parents[l - 1] [<= n_cap]: the level-l id of every level-(l - 1) voxel, counts[l - 1] = voxels
- * of level l - the arrays sd3d_unique_sorted(shift 3, map) produces when called level after level, without the extent clip. */
-size_t sd3d_unique_levels_ws_bytes(int64_t n_cap, int n_extra);
-int sd3d_unique_levels(const uint64_t* keys, int64_t n_cap, const int32_t* n_dev, int n_extra, uint64_t* const* ukeys,
-                       int32_t* const* parents, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
-/* One scene's voxelisation chain from ONE call (sd3d_scene_stats, sd3d_voxel_keys, the radix sort of the keys, sd3d_unique_sorted with
- * segment starts and the point -> voxel map, sd3d_unique_levels, the superpoint ids' sort keys): ~28 launches that take the GPU ~0.25 ms
+/* One scene's voxelisation chain from ONE call (sd3d_scene_stats, sd3d_voxel_keys, the radix sort of the keys, sd3d_voxel_levels_all,
+ * the superpoint ids' sort keys): ~28 launches that take the GPU ~0.25 ms
  * but cost a Python host ~0.5 ms when issued one by one in front of everything else of the scene.  Same kernels, same order, same
  * outputs as the separate calls (`minkunet.py:624-630`: batch_sparse_collate + TensorField.sparse() + inverse_mapping).
  *   readback [n_levels + 2] is zeroed here and receives {voxels of level 0 .. n_levels - 1, flags, largest superpoint id}
@@ -131,10 +125,11 @@ typedef struct sd3d_voxelise_desc {
 } sd3d_voxelise_desc;
 size_t sd3d_voxelise_scene_ws_bytes(int64_t n, int n_levels);
 int sd3d_voxelise_scene(const sd3d_voxelise_desc* d, int* sorted_in_a, void* stream);
-/* sd3d_unique_sorted(shift 0, seg_start, map) + sd3d_unique_levels in ONE set of four launches, from the sorted POINT keys: ukeys[l] [<= n]
+/* EVERY level of a scene in ONE set of four launches, from the sorted POINT keys (level l keeps the runs of Morton >> 3 l): ukeys[l] [<= n]
  * (l = 0 .. n_levels - 1, level 0 included), seg_start [<= n + 1], map[src_idx ? src_idx[j] : j] = level-0 id, parents[l] [<= n] (l < n_levels - 1:
- * level-(l + 1) id of every level-l voxel), counts[l] = voxels of level l.  1 <= n_levels <= 8, no extent clip; entry for entry the arrays of the
- * two separate calls.  Workspace: sd3d_unique_levels_ws_bytes(n, n_levels). */
+ * level-(l + 1) id of every level-l voxel), counts[l] = voxels of level l.  1 <= n_levels <= 8, no extent clip; entry for entry the arrays of
+ * sd3d_unique_sorted(shift 0, seg_start, map) followed by sd3d_unique_sorted(shift 3, map) level after level. */
+size_t sd3d_voxel_levels_all_ws_bytes(int64_t n, int n_levels);
 int sd3d_voxel_levels_all(const uint64_t* sorted_keys, const uint32_t* src_idx, int64_t n, int n_levels, uint64_t* const* ukeys, int32_t* seg_start,
                           int32_t* map, int32_t* const* parents, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
 /* Open-addressing hash table key -> voxel id; capacity = power of two > n. */
@@ -150,7 +145,7 @@ int sd3d_kernel_map(const uint64_t* out_keys, int64_t n_out, const uint64_t* tab
                     int64_t capacity, const int8_t* offsets, int K, int mirrored, int32_t* nbr, int32_t* pair_count, void* stream);
 /* The 3^3 kernel maps of EVERY level of a scene (and the 5^3 map of the finest level) from one call, without hash tables: through the
  * hierarchy of the sorted keys (level l + 1 = unique(key >> 3): the children of a coarse voxel are consecutive rows, the neighbour of a
- * voxel lies in one of the 27 cells around its parent).  keys[l] / n[l]: the levels' sorted keys (finest first, as sd3d_unique_levels
+ * voxel lies in one of the 27 cells around its parent).  keys[l] / n[l]: the levels' sorted keys (finest first, as sd3d_voxel_levels_all
  * leaves them), parent[l][j] = row of voxel j's parent on level l + 1 (NULL for the coarsest level; no extent clip: every parent
  * exists), nbr3[l] [27, n_l] outputs, nbr5 [125, n_0] output or NULL, offsets3 / offsets5 device int8 [K, 3] in the enumeration order
  * of the weights, inv27 (HOST) maps (dx + 1) + 3 (dy + 1) + 9 (dz + 1) to the row of offsets3.  pair_counts: NULL or device int32
@@ -171,18 +166,12 @@ int sd3d_kernel_maps_hier(int n_levels, const uint64_t* const* keys, const int32
  * maps the child's Z-order position (x | y<<1 | z<<2) to the weight index. */
 int sd3d_stride_maps(const uint64_t* fine_keys, const int32_t* parent, int64_t n_fine, int64_t n_coarse,
                      const int32_t* perm8, int32_t* nbr_down, int32_t* nbr_up, void* stream);
-/* Unweighted per-voxel average of the assembled point feature row (ME quantisation mode used by the
- * reference).  mode 0: rgb|f2d, 1: rgb, 2: rgb|xyz-mean|f2d.  out [n_vox, ld_out], zero padded. */
-int sd3d_voxel_mean(const float* points, int ld_points, const float* feats2d, int F, int mode, const float* stats,
-                    int64_t n_points, const uint32_t* sorted_idx, const int32_t* seg_start, int64_t n_vox, float* out,
-                    int ld_out, void* stream);
-/* start[s] = first position of superpoint id s in the sorted id array, start[S] = n. */
-int sd3d_segment_starts(const uint64_t* sorted_ids, int64_t n, int64_t S, int32_t* start, void* stream);
 
-/* ---- several scenes as ONE block-diagonal sparse tensor (the collation of `utils/dataset_utils.py:215-230` collate_fn_3D +
+/* ---- 1..16 scenes as ONE block-diagonal sparse tensor (the collation of `utils/dataset_utils.py:215-230` collate_fn_3D +
  * ME.utils.batch_sparse_collate, minkunet.py:624-627): the scene index sits in the key bits above the 48-bit Z-order code
  * (sd3d_voxel_keys batch_index), so ONE sort / unique / hash / kernel-map pass serves every scene of the batch and rows of
- * different scenes never become neighbours.  Per voxel / superpoint the arithmetic is the single-scene kernels'. ---- */
+ * different scenes never become neighbours.  One scene is a batch of one: per voxel / superpoint the arithmetic (point order,
+ * sums) does not depend on the number of scenes. ---- */
 #define SD3D_MAX_BATCH 16
 typedef struct sd3d_scene_src {
     const float* points;     /* [n_points, ld_points] xyz rgb of this scene */
@@ -192,12 +181,15 @@ typedef struct sd3d_scene_src {
     int64_t n_points;
     int32_t ld_points, pad_;
 } sd3d_scene_src;
-/* sd3d_voxel_mean over the voxels of all scenes: voxel v belongs to scene (ukeys[v] >> 48) & 0xFF; sorted_idx holds
- * batch-global point numbers.  `scenes` is a HOST array (copied into the launch). */
+/* Unweighted per-voxel average of the assembled point feature row (ME quantisation mode used by the reference) over the voxels
+ * of all scenes.  mode 0: rgb|f2d, 1: rgb, 2: rgb|xyz-mean|f2d.  out [n_vox, ld_out], zero padded.  Voxel v belongs to scene
+ * (ukeys[v] >> 48) & 0xFF; sorted_idx holds batch-global point numbers.  With n_scenes == 1 every voxel belongs to scene 0:
+ * ukeys may be NULL and is not read.  `scenes` is a HOST array (copied into the launch); every scene needs points and stats. */
 int sd3d_voxel_mean_batch(const sd3d_scene_src* scenes, int n_scenes, int F, int mode, const uint64_t* ukeys,
                           const uint32_t* sorted_idx, const int32_t* seg_start, int64_t n_vox, float* out, int ld_out, void* stream);
-/* sd3d_segment_starts for sorted (scene << 32 | id) keys: dense id = id_off[scene] + id, S = number of dense ids of the batch.
- * `id_off` is a HOST array of n_scenes entries. */
+/* start[s] = first position of dense superpoint id s in the sorted (scene << 32 | id) keys, start[S] = n: dense id = id_off[scene] + id,
+ * S = number of dense ids of the batch.  `id_off` is a HOST array of n_scenes entries.  One scene (n_scenes = 1, id_off = {0}): the keys
+ * are plain ids below 2^32 - the product checks ids into [0, 2^31 - 2] and the dataset targets sort over at most 32 bits. */
 int sd3d_segment_starts_batch(const uint64_t* sorted_ids, int64_t n, int64_t S, const int32_t* id_off, int n_scenes, int32_t* start,
                               void* stream);
 /* Fused `x.slice(field)` + torch_scatter.scatter_mean of features [S,C] and of the floor-quantised
@@ -476,15 +468,13 @@ int sd3d_attention_batch(int n, const sd3d_attn_job* jobs, int H, int head_dim, 
  * states [ceil(Lq/32)][H][ksplit][64 + 1024] (m[32], l[32], O[32 dv][32 q], log2 domain) at ws + part_off_out_host[i] floats. */
 int sd3d_attention_batch_parts(int n, const sd3d_attn_job* jobs, int H, float scale, int bf16, void* ws, size_t ws_bytes,
                                int32_t* ksplit_out_host, int64_t* part_off_out_host, void* stream);
-/* _forward_head mask part (:567-572): bits = sigmoid(logits) < thr, dead rows reset to open. */
-int sd3d_mask_bits(const float* logits, int ld, int64_t Q, int S, float thr, uint32_t* bits, int nwords, void* stream);
 /* (dist < thr) of torch.cdist(p=1) (:721) as bits near[M, ceil(S/32)]. */
 int sd3d_near_bits(const float* sp_pos, int64_t S, const float* centers, int64_t M, float thr, uint32_t* near, int nwords,
                    void* stream);
-/* mask_ = ((~attn_mask).float() @ near.float()) == 0, plus the always-open dummy key (:722-726). */
-int sd3d_dinox_mask_bits(const uint32_t* blocked, const uint32_t* near, int nwords, int64_t Q, int64_t M, uint32_t* out,
-                         int nwords_out, void* stream);
-/* sd3d_mask_bits / sd3d_dinox_mask_bits for the matrices of n <= SD3D_MAX_BATCH scenes in one launch each (host arrays of n entries). */
+/* The matrices of 1 <= n <= SD3D_MAX_BATCH scenes in one launch each (host arrays of n entries; one scene is n = 1).
+ * mask_bits, the _forward_head mask part (:567-572): bits[i] [Q_i, nwords_i = ceil(S_i/32)] = sigmoid(logits[i]) < thr, dead rows reset to open.
+ * dinox_mask_bits: out[i] [Q_i, nwords_out_i = ceil((Mq_i+1)/32)] = ((~blocked[i]).float() @ near[i].float()) == 0, plus the always-open dummy
+ * key (:722-726); refused when two (under 2048 query rows in all) or eight query rows of the widest scene exceed 64 KiB of LDS. */
 int sd3d_mask_bits_batch(int n, const float* const* logits, const int* ld, const int64_t* Q, const int* S, uint32_t* const* bits,
                          const int* nwords, float thr, void* stream);
 int sd3d_dinox_mask_bits_batch(int n, const uint32_t* const* blocked, const uint32_t* const* near, const int* nwords, const int64_t* Q,
@@ -540,21 +530,18 @@ int sd3d_gather_sigmoid(const float* masks, int ld, int S, const int32_t* qidx, 
 int sd3d_nms_decay(const float* inter, int ld, const float* area, const int32_t* labels, int n, int gaussian,
                    float sigma, const float* score_in, float* comp_ws, float* score_out, void* stream);
 /* superpoint -> point broadcast + threshold + point count + optional box filter (:453-454, :464, :348-371).
- * out [n, N] bytes (0/1); count[n] counts BEFORE the box filter; boxes [n,6] or NULL.  Superpoint ids must be
- * < ld_sig (the padded row width of sig); ws holds the thresholded rows as a bit table. */
-size_t sd3d_expand_masks_ws_bytes(int n, int ld_sig);
-int sd3d_expand_masks(const float* sig, int ld_sig, const uint32_t* src_row, int n, const int64_t* superpoints,
-                      const float* points, int ld_points, int64_t N, float sp_thr, const float* boxes, float loose_ratio,
-                      uint8_t* out, int32_t* count, void* ws, size_t ws_bytes, void* stream);
-/* The same in two steps, for callers that apply the score / point-count thresholds BEFORE expanding (count[] comes from step 1):
+ * Mask bytes are 0/1; count[n] counts BEFORE the box filter; boxes [n,6] or NULL.  Superpoint ids must be
+ * < ld_sig (the padded row width of sig); ws holds the thresholded rows as a bit table.
+ * Two steps, so that the caller applies the score / point-count thresholds BEFORE expanding (count[] comes from step 1):
  * sd3d_mask_rowbits thresholds the rows into the bit table in `ws` (sd3d_expand_masks_ws_bytes) and makes count[n];
  * sd3d_expand_rows writes out[j] = row rows[j] for a list of m rows from the SAME ws (boxes [n, 6] indexed by the row number, or NULL):
- * the [n, N] byte table of sd3d_expand_masks (90 MB at 600 x 150 k) is never made, only the kept rows. */
+ * the whole [n, N] byte table (90 MB at 600 x 150 k; the list 0 .. n - 1) is never made, only the kept rows. */
+size_t sd3d_expand_masks_ws_bytes(int n, int ld_sig);
 int sd3d_mask_rowbits(const float* sig, int ld_sig, const uint32_t* src_row, int n, const int64_t* superpoints, int64_t N, float sp_thr,
                       int32_t* count, void* ws, size_t ws_bytes, void* stream);
 int sd3d_expand_rows(const void* ws, int n, int ld_sig, const int32_t* rows, int m, const int64_t* superpoints, const float* points,
                      int ld_points, int64_t N, const float* boxes, float loose_ratio, uint8_t* out, void* stream);
-/* Bit-packed copy of selected rows of the [n, N] byte masks of sd3d_expand_masks, for the device -> host copy of
+/* Bit-packed copy of selected rows of the [n, N] byte masks of sd3d_expand_rows, for the device -> host copy of
  * `pts_instance_mask[0]` (baseline3d.py:453-454; evaluator_3d.py:178 reads it on the host): out [n_rows, nb = ceil(N/8)] bytes,
  * bit j of byte b = masks[rows[i]][8 b + j] != 0 (numpy bitorder "little"); rows NULL = rows 0..n_rows-1. */
 int sd3d_pack_mask_rows(const uint8_t* masks, int64_t N, const int32_t* rows, int n_rows, uint8_t* out, int64_t nb, void* stream);

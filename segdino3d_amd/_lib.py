@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _lib = None
 
@@ -45,16 +45,13 @@ SIGNATURES = {
     "sd3d_scene_stats": (_i, [_p, _i, _l, _p, _p, _z, _p]),
     "sd3d_voxel_keys": (_i, [_p, _i, _l, _f, _p, _i, _i, _p, _p, _p, _p, _p]),
     "sd3d_unique_ws_bytes": (_z, [_l]),
-    "sd3d_unique_levels_ws_bytes": (_z, [_l, _i]),
-    "sd3d_unique_levels": (_i, [_p, _l, _p, _i, _p, _p, _p, _p, _z, _p]),
+    "sd3d_voxel_levels_all_ws_bytes": (_z, [_l, _i]),
     "sd3d_unique_sorted": (_i, [_p, _p, _l, _p, _i, _p, _p, _p, _p, _p, _z, _p, _f, _i, _i, _p]),
     "sd3d_hash_build": (_i, [_p, _l, _p, _p, _l, _p]),
     "sd3d_kernel_map": (_i, [_p, _l, _p, _p, _l, _p, _i, _i, _p, _p, _p]),
     "sd3d_kernel_maps_hier_ws_bytes": (_z, [_i, _p]),
     "sd3d_kernel_maps_hier": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "sd3d_stride_maps": (_i, [_p, _p, _l, _l, _p, _p, _p, _p]),
-    "sd3d_voxel_mean": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _p, _l, _p, _i, _p]),
-    "sd3d_segment_starts": (_i, [_p, _l, _l, _p, _p]),
     "sd3d_voxel_mean_batch": (_i, [_p, _i, _i, _i, _p, _p, _p, _l, _p, _i, _p]),
     "sd3d_segment_starts_batch": (_i, [_p, _l, _l, _p, _i, _p, _p]),
     "sd3d_pool_superpoints": (_i, [_p, _i, _i, _p, _p, _f, _p, _p, _l, _p, _p, _p]),
@@ -73,9 +70,7 @@ SIGNATURES = {
     "sd3d_box_refine": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _l, _p, _p, _p, _p]),
     "sd3d_mask_bits_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _p]),
     "sd3d_dinox_mask_bits_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "sd3d_mask_bits": (_i, [_p, _i, _l, _i, _f, _p, _i, _p]),
     "sd3d_near_bits": (_i, [_p, _l, _p, _l, _f, _p, _i, _p]),
-    "sd3d_dinox_mask_bits": (_i, [_p, _p, _i, _l, _l, _p, _i, _p]),
     "sd3d_scale_shift_act_add": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _l, _i, _p, _i, _p, _i, _p]),
     "sd3d_class_scores": (_i, [_p, _i, _l, _i, _p, _p, _p]),
     "sd3d_mask_scores": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
@@ -100,7 +95,6 @@ SIGNATURES = {
     "sd3d_expand_masks_ws_bytes": (_z, [_i, _i]),
     "sd3d_mask_rowbits": (_i, [_p, _i, _p, _i, _p, _l, _f, _p, _p, _z, _p]),
     "sd3d_expand_rows": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _l, _p, _f, _p, _p]),
-    "sd3d_expand_masks": (_i, [_p, _i, _p, _i, _p, _p, _i, _l, _f, _p, _f, _p, _p, _p, _z, _p]),
     "sd3d_row_argmax": (_i, [_p, _i, _l, _p, _i, _p, _p]),
     "sd3d_gather_i64": (_i, [_p, _p, _l, _i, _p, _p]),
     "sd3d_panoptic": (_i, [_p, _l, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p]),

@@ -347,12 +347,7 @@ __device__ __forceinline__ void mask_bits_body(const float* __restrict__ logits,
         }
     }
 }
-__global__ __launch_bounds__(256) void mask_bits_kernel(const float* __restrict__ logits, int ld, int64_t Q, int S, float thr,
-                                                        uint32_t* __restrict__ bits, int nwords) {
-    __shared__ int open_s[4];
-    mask_bits_body(logits, ld, S, thr, bits, nwords, blockIdx.x, open_s);
-}
-// the same for the logit matrices of several scenes (one workgroup per query row of any scene)
+// the logit matrices of 1..16 scenes in one launch (one workgroup per query row of any scene)
 struct MaskBitsBatch { int n; int row0[SD3D_MAX_BATCH + 1]; const float* logits[SD3D_MAX_BATCH]; uint32_t* bits[SD3D_MAX_BATCH];
                        int ld[SD3D_MAX_BATCH], S[SD3D_MAX_BATCH], nwords[SD3D_MAX_BATCH]; };
 __global__ __launch_bounds__(256) void mask_bits_batch_kernel(const MaskBitsBatch b, float thr) {
@@ -377,15 +372,6 @@ extern "C" int sd3d_mask_bits_batch(int n, const float* const* logits, const int
     b.row0[n] = rows;
     if (rows <= 0) return SD3D_OK;
     hipLaunchKernelGGL(mask_bits_batch_kernel, dim3((unsigned)rows), dim3(256), 0, st, b, thr);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
-}
-
-extern "C" int sd3d_mask_bits(const float* logits, int ld, int64_t Q, int S, float thr, uint32_t* bits, int nwords, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (Q <= 0) return SD3D_OK;
-    if (nwords != (S + 31) / 32) return sd3d_set_error(SD3D_ERR_ARG, "mask_bits: nwords != ceil(S/32)");
-    hipLaunchKernelGGL(mask_bits_kernel, dim3((unsigned)Q), dim3(256), 0, st, logits, ld, Q, S, thr, bits, nwords);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }
@@ -506,13 +492,6 @@ __device__ __forceinline__ void dinox_mask_bits_body(const uint32_t* __restrict_
         }
     }
 }
-template <int QB>
-__global__ __launch_bounds__(512) void dinox_mask_bits_kernel(const uint32_t* __restrict__ blocked, const uint32_t* __restrict__ near,
-                                                              int nwords, int64_t Q, int64_t Mq, uint32_t* __restrict__ out,
-                                                              int nwords_out) {
-    extern __shared__ uint32_t open_w[];                       // ~blocked[q0 .. q0 + QB)[:]
-    dinox_mask_bits_body<QB>(blocked, near, nwords, Q, Mq, out, nwords_out, (int64_t)blockIdx.x * QB, open_w);
-}
 struct DinoxBitsBatch { int n; int wg0[SD3D_MAX_BATCH + 1]; const uint32_t* blocked[SD3D_MAX_BATCH]; const uint32_t* near[SD3D_MAX_BATCH];
                         uint32_t* out[SD3D_MAX_BATCH]; int nwords[SD3D_MAX_BATCH], Q[SD3D_MAX_BATCH], Mq[SD3D_MAX_BATCH], nwords_out[SD3D_MAX_BATCH]; };
 template <int QB>
@@ -547,6 +526,7 @@ extern "C" int sd3d_dinox_mask_bits_batch(int n, const uint32_t* const* blocked,
     b.wg0[n] = wgs;
     if (wgs <= 0) return SD3D_OK;
     const size_t sm = (size_t)qb * wmax * sizeof(uint32_t);
+    if (sm > 64 * 1024) return sd3d_set_error(SD3D_ERR_ARG, "dinox_mask_bits_batch: more than 65536 superpoints");
     if (qb == 8) hipLaunchKernelGGL(dinox_mask_bits_batch_kernel<8>, dim3((unsigned)wgs), dim3(256), sm, st, b);
     else hipLaunchKernelGGL(dinox_mask_bits_batch_kernel<2>, dim3((unsigned)wgs), dim3(512), sm, st, b);
     SD3D_CHECK_LAUNCH();
@@ -557,19 +537,6 @@ extern "C" int sd3d_near_bits(const float* pos, int64_t S, const float* ctr, int
     hipStream_t st = (hipStream_t)stream;
     if (Mq <= 0 || S <= 0) return SD3D_OK;
     hipLaunchKernelGGL(near_bits_kernel, dim3((unsigned)cdiv(Mq * nwords, 256)), dim3(256), 0, st, pos, S, ctr, Mq, thr, near, nwords);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
-}
-extern "C" int sd3d_dinox_mask_bits(const uint32_t* blocked, const uint32_t* near, int nwords, int64_t Q, int64_t Mq, uint32_t* out, int nwords_out,
-                                    void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (Q <= 0) return SD3D_OK;
-    if (nwords_out != (int)((Mq + 1 + 31) / 32)) return sd3d_set_error(SD3D_ERR_ARG, "dinox_mask_bits: nwords_out != ceil((M+1)/32)");
-    const int qb = dinox_qb(Q);
-    const size_t sm = (size_t)qb * nwords * sizeof(uint32_t);
-    if (sm > 64 * 1024) return sd3d_set_error(SD3D_ERR_ARG, "dinox_mask_bits: more than 65536 superpoints");
-    if (qb == 8) hipLaunchKernelGGL(dinox_mask_bits_kernel<8>, dim3((unsigned)cdiv(Q, 8)), dim3(256), sm, st, blocked, near, nwords, Q, Mq, out, nwords_out);
-    else hipLaunchKernelGGL(dinox_mask_bits_kernel<2>, dim3((unsigned)cdiv(Q, 2)), dim3(512), sm, st, blocked, near, nwords, Q, Mq, out, nwords_out);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }

@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256) void mq_member_keys_kernel(const int32_t* __re
     keys[r] = live ? ((uint64_t)(uint32_t)label[r] << 32) | (uint32_t)rank_row[r] : ((uint64_t)Mc << 32) | (uint32_t)r;
 }
 // seg[2 s], seg[2 s + 1] = where the members of seed rank s begin and end in the sorted keys (zeroed before: no members).  One thread per
-// sorted position.  (sd3d_segment_starts fills the starts of absent ids in a serial loop per gap: the seeds are a few hundred of 16384
+// sorted position.  (sd3d_segment_starts_batch fills the starts of absent ids in a serial loop per gap: the seeds are a few hundred of 16384
 // ranks, most of them early, and the one thread behind the last seed took 0.19 ms.)
 __global__ __launch_bounds__(256) void mq_bounds_kernel(const uint64_t* __restrict__ sorted, int64_t Mc, int32_t* __restrict__ seg) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -135,15 +135,12 @@ __global__ __launch_bounds__(64 * NMS_RL) void nms_coef_kernel(const float* __re
 // Point masks (:453-454, :464-465, :348-371).  For final row r (src row = src[r] of sig), point p:
 //   bit = sig[src[r]][superpoints[p]] > sp_thr ; count[r] = number of bits BEFORE the box filter;
 //   out[r][p] = bit && inside(points[p], center[r] +- size[r] * (1 + loose) / 2)   (if boxes given)
-// One thread handles 4 consecutive points for EM_ROWS consecutive rows: the superpoint ids and the
-// coordinates are read once per EM_ROWS rows, each row costs 4 gathered floats (L2-resident sig row)
-// and one uchar4 store.  grid = (point quads / 256, row groups).
-// Two passes.  (1) em_rowbits_kernel thresholds the [n, S] sigmoid rows into a bit table transposed to
-// [S][W] words (bit r of word r/32 = row r is on for superpoint s): 226 KB for 600 x 3000, L2-resident.
-// (2) em_expand_kernel: a thread owns 4 consecutive points and one 32-row word; it reads the word of
-// each point's superpoint once and emits 32 uchar4 stores (one per row) - the kernel is bound by the
-// n x N bytes it writes (the first version gathered one float per (row, point): 90 M random 4-byte loads,
-// 0.62 ms for 600 x 150 k).
+// Two steps with the score / point-count thresholds between them.  (1) em_hist_kernel counts the points of every superpoint and
+// em_rowbits_kernel thresholds the [n, S] sigmoid rows into a bit table transposed to [S][W] words (bit r of word r/32 = row r is on
+// for superpoint s: 226 KB for 600 x 3000, L2-resident) and makes count[].  (2) em_expand_rows_kernel writes the bytes of a LIST of
+// rows from that table: a thread owns 4 consecutive points, reads the word of each point's superpoint and emits one uchar4 store per
+// listed row - bound by the m x N bytes it writes (gathering one float per (row, point) was 90 M random 4-byte loads, 0.62 ms for
+// 600 x 150 k).  The whole [n, N] table is the list 0 .. n - 1; the product never asks for it.
 __global__ __launch_bounds__(256) void em_hist_kernel(const int64_t* __restrict__ superpoints, int64_t N, int S, int32_t* __restrict__ npts) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= N) return;
@@ -176,67 +173,7 @@ __global__ __launch_bounds__(256) void em_rowbits_kernel(const float* __restrict
     }
 }
 
-#define EM_WORDS 4               // 32-row words per workgroup: superpoint ids / coordinates are re-read W / 4 times
-__global__ __launch_bounds__(256) void em_expand_kernel(const uint32_t* __restrict__ bits, int W, int n, int S,
-                                                        const int64_t* __restrict__ superpoints, const float* __restrict__ pts,
-                                                        int ld_pts, int64_t N, const float* __restrict__ boxes, float loose,
-                                                        uint8_t* __restrict__ out) {
-    const int g0 = blockIdx.y * EM_WORDS;
-    const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    const bool vec = ((N & 3) == 0);
-    const int np = p0 < N ? (int)min((int64_t)4, N - p0) : 0;
-    uint32_t w[EM_WORDS][4];
-    uint32_t any_pt = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int64_t sp = e < np ? superpoints[p0 + e] : -1;
-        const bool ok = sp >= 0 && sp < S;
-#pragma unroll
-        for (int u = 0; u < EM_WORDS; ++u) {
-            w[u][e] = (ok && g0 + u < W) ? bits[sp * W + g0 + u] : 0u;
-            any_pt |= w[u][e];
-        }
-    }
-    float xyz[4][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-    if (boxes && any_pt) {                                  // coordinates only where some row is on
-        for (int e = 0; e < np; ++e)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) xyz[e][a] = pts[(p0 + e) * ld_pts + a];
-    }
-#pragma unroll
-    for (int u = 0; u < EM_WORDS; ++u) {
-        const uint32_t any_w = w[u][0] | w[u][1] | w[u][2] | w[u][3];
-        for (int rr = 0; rr < 32; ++rr) {
-            const int r = (g0 + u) * 32 + rr;
-            if (r >= n) break;                              // uniform per block
-            uint8_t res[4] = {0, 0, 0, 0};
-            if ((any_w >> rr) & 1u) {
-                float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-                if (boxes) {
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        const float c = boxes[r * 6 + a], s = boxes[r * 6 + 3 + a] * (1.f + loose);
-                        lo[a] = c - s / 2.f;
-                        hi[a] = c + s / 2.f;
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    bool b = (w[u][e] >> rr) & 1u;
-                    if (b && boxes) {
-#pragma unroll
-                        for (int a = 0; a < 3; ++a) b &= (xyz[e][a] >= lo[a]) & (xyz[e][a] <= hi[a]);
-                    }
-                    res[e] = b;
-                }
-            }
-            if (np == 4 && vec) *(uchar4*)(out + (int64_t)r * N + p0) = make_uchar4(res[0], res[1], res[2], res[3]);
-            else for (int e = 0; e < np; ++e) out[(int64_t)r * N + p0 + e] = res[e];
-        }
-    }
-}
-
-// The same expansion for a LIST of rows (the instances that survive the score / point-count thresholds: 100 - 250 of the 600 candidates):
+// The listed rows are the instances that survive the score / point-count thresholds (100 - 250 of the 600 candidates):
 // out[j][p] = row rows[j] of the bit table at point p (and inside its box).  The thresholds only need count[], which em_rowbits_kernel
 // makes at superpoint granularity - so the [600, N] byte table (90 MB written, then 20 - 40 MB of it gathered) never has to exist.
 // A thread owns 4 consecutive points and 32 listed rows; a row's word is re-read only when it differs from the previous row's.
@@ -458,8 +395,8 @@ extern "C" int sd3d_nms_decay(const float* inter, int ld, const float* area, con
 }
 // (+ n ints behind npts: a caller that places `count` there - ops.MaskBits - gets both zeroed by ONE memset launch)
 extern "C" size_t sd3d_expand_masks_ws_bytes(int n, int ld_sig) { return ((size_t)ld_sig * ((n + 31) / 32 + 1) + (size_t)n) * sizeof(uint32_t) + 256; }
-// bits [ld_sig][W] words + npts [ld_sig] ints live in `ws` (sd3d_expand_masks_ws_bytes): phase 1 of expand_masks, and all of it when the
-// caller expands a list of rows later (sd3d_expand_rows on the same ws)
+// bits [ld_sig][W] words + npts [ld_sig] ints live in `ws` (sd3d_expand_masks_ws_bytes); the caller expands a list of rows later
+// (sd3d_expand_rows on the same ws)
 extern "C" int sd3d_mask_rowbits(const float* sig, int ld_sig, const uint32_t* src, int n, const int64_t* superpoints, int64_t N, float sp_thr,
                                  int32_t* count, void* ws, size_t ws_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -488,19 +425,6 @@ extern "C" int sd3d_expand_rows(const void* ws, int n, int ld_sig, const int32_t
     const int W = (n + 31) / 32;
     hipLaunchKernelGGL(em_expand_rows_kernel, dim3((unsigned)cdiv(N, 1024), (unsigned)cdiv(m, 32)), dim3(256), 0, st, (const uint32_t*)ws, W, ld_sig,
                        rows, m, superpoints, pts, ld_pts, N, boxes, loose, out);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
-}
-extern "C" int sd3d_expand_masks(const float* sig, int ld_sig, const uint32_t* src, int n, const int64_t* superpoints, const float* pts, int ld_pts,
-                                 int64_t N, float sp_thr, const float* boxes, float loose, uint8_t* out, int32_t* count, void* ws, size_t ws_bytes,
-                                 void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (n <= 0 || N <= 0) return SD3D_OK;
-    const int rc = sd3d_mask_rowbits(sig, ld_sig, src, n, superpoints, N, sp_thr, count, ws, ws_bytes, st);
-    if (rc) return rc;
-    const int W = (n + 31) / 32, S = ld_sig;
-    hipLaunchKernelGGL(em_expand_kernel, dim3((unsigned)cdiv(N, 1024), (unsigned)cdiv(W, EM_WORDS)), dim3(256), 0, st, (const uint32_t*)ws, W, n, S,
-                       superpoints, pts, ld_pts, N, boxes, loose, out);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }

@@ -415,7 +415,8 @@ extern "C" int sd3d_targets_build(int64_t n, const int32_t* header, int n_classe
     if (int rc = sd3d_sort_pairs_u64_ex(w.keys_a, nullptr, w.keys_b, w.vals_b, w.vals_a, n, 0, bits, w.sort_ws, w.sort_ws_bytes, &landed, stream)) return rc;
     const uint64_t* sorted = landed ? w.keys_a : w.keys_b;
     const uint32_t* sidx = landed ? w.vals_a : w.vals_b;
-    if (int rc = sd3d_segment_starts(sorted, n, S, seg_start, stream)) return rc;
+    const int32_t id_off = 0;                                   // one scene: the sorted keys are plain ids (at most 32 bits, above)
+    if (int rc = sd3d_segment_starts_batch(sorted, n, S, &id_off, 1, seg_start, stream)) return rc;
     hipLaunchKernelGGL(tg_votes_kernel, dim3((unsigned)cdiv(S, 4)), dim3(256), 0, st, sidx, seg_start, S, w.vote, w.sem, spec.C, sp_inst, sp_sem);
     SD3D_CHECK_LAUNCH();
 

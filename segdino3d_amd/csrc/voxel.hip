@@ -228,82 +228,21 @@ extern "C" int sd3d_unique_sorted(const uint64_t* keys, const uint32_t* src_idx,
 }
 
 // ---------------------------------------------------------------------------------------------
-// All coarser levels of a scene from its sorted level-0 keys in FOUR launches (mark, the two scan launches over the levels' flag rows
-// back to back, emit) instead of four per level: level l's voxels are the runs of (Morton >> 3 l); a run boundary at level l + 1 is one at
-// level l, so id_l(i) = (number of level-l heads among rows <= i) - 1 and the parent of level-(l - 1) voxel id_{l-1}(i) is id_l(i).  The
-// keys, parents and counts are those of sd3d_unique_sorted called level after level (shift 3 each); no extent clip (MinkowskiEngine
+// EVERY level of a scene - the level-0 unique (keys, segment starts, point -> voxel map) and all coarser levels (keys, parents) -
+// from the sorted POINT keys in four launches (mark, the two scan launches over the levels' flag rows back to back, emit) instead of four
+// per level: level l's voxels are the runs of (Morton >> 3 l), and a run boundary at level l + 1 is one at level l, so
+// id_l(i) = (number of level-l heads among rows <= i) - 1 and the parent of level-(l - 1) voxel id_{l-1}(i) is id_l(i).  The arrays are
+// those of sd3d_unique_sorted called level after level (shift 0, then 3 each), entry for entry; no extent clip (MinkowskiEngine
 // semantics).  The chain before a scene's first host synchronisation is bound by its number of dependent launches, not by their work.
 // ---------------------------------------------------------------------------------------------
-#define UL_MAX 7
-struct ULParams {
-    const uint64_t* keys; int64_t cap; const int* n_dev; int nl;
-    uint64_t* ukeys[UL_MAX]; int32_t* parent[UL_MAX]; int32_t* counts;
-};
-__global__ __launch_bounds__(256) void mark_levels(const ULParams P, int* __restrict__ flags) {
-    const int64_t n = P.n_dev ? min((int64_t)*P.n_dev, P.cap) : P.cap;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int l = blockIdx.y + 1;
-    if (i >= P.cap) return;
-    if (i == 0 && n <= 0) P.counts[l - 1] = 0;                 // an empty / fully filtered scene: emit_levels has no row n - 1 to write the count from
-    int f = 0;
-    if (i < n) f = (i == 0) || level_key(P.keys[i], 3 * l) != level_key(P.keys[i - 1], 3 * l);
-    flags[(int64_t)blockIdx.y * P.cap + i] = f;
-}
-__global__ __launch_bounds__(256) void emit_levels(const ULParams P, const int* __restrict__ flags, const int* __restrict__ excl) {
-    const int64_t n = P.n_dev ? min((int64_t)*P.n_dev, P.cap) : P.cap;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int l = blockIdx.y + 1;
-    if (i >= n) return;
-    const int64_t row = (int64_t)blockIdx.y * P.cap;
-    const int f = flags[row + i];
-    const int id = excl[row + i] - excl[row] + f - 1;          // (the scan ran over all rows back to back: subtract the row's base)
-    if (f) P.ukeys[l - 1][id] = level_key(P.keys[i], 3 * l);
-    if (l == 1) {
-        P.parent[0][i] = id;
-    } else {
-        const int64_t prow = row - P.cap;
-        if (flags[prow + i]) P.parent[l - 1][excl[prow + i] - excl[prow]] = id;
-    }
-    if (i == n - 1) P.counts[l - 1] = id + 1;
-}
-static size_t unique_levels_ws_bytes(int64_t n_cap, int n_extra) {
-    const int64_t tot = n_cap * n_extra;
+#define UL_MAX 7                                                // coarser levels
+static size_t voxel_levels_all_ws_bytes(int64_t n, int n_levels) {
+    const int64_t tot = n * n_levels;
     return 2 * align_up((size_t)tot * sizeof(int), 256) + scan_ws_bytes(tot) + 256;
 }
-extern "C" size_t sd3d_unique_levels_ws_bytes(int64_t n_cap, int n_extra) {
-    return unique_levels_ws_bytes(n_cap > 0 ? n_cap : 1, n_extra > 0 ? n_extra : 1);
+extern "C" size_t sd3d_voxel_levels_all_ws_bytes(int64_t n, int n_levels) {
+    return voxel_levels_all_ws_bytes(n > 0 ? n : 1, n_levels > 0 ? n_levels : 1);
 }
-extern "C" int sd3d_unique_levels(const uint64_t* keys, int64_t n_cap, const int* n_dev, int n_extra, uint64_t* const* ukeys, int32_t* const* parents,
-                                  int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (n_cap <= 0 || n_extra < 1 || n_extra > UL_MAX) return sd3d_set_error(SD3D_ERR_ARG, "unique_levels: n_cap > 0 and 1..7 coarser levels");
-    if (!keys || !ukeys || !parents || !counts) return sd3d_set_error(SD3D_ERR_ARG, "unique_levels: null pointer");
-    if (ws_bytes < unique_levels_ws_bytes(n_cap, n_extra)) return sd3d_set_error(SD3D_ERR_WS, "unique_levels workspace too small");
-    ULParams P;
-    P.keys = keys; P.cap = n_cap; P.n_dev = n_dev; P.nl = n_extra; P.counts = counts;
-    for (int l = 0; l < UL_MAX; ++l) { P.ukeys[l] = l < n_extra ? ukeys[l] : nullptr; P.parent[l] = l < n_extra ? parents[l] : nullptr; }
-    for (int l = 0; l < n_extra; ++l) if (!P.ukeys[l] || !P.parent[l]) return sd3d_set_error(SD3D_ERR_ARG, "unique_levels: null output");
-    const int64_t tot = n_cap * n_extra;
-    const size_t a = align_up((size_t)tot * sizeof(int), 256);
-    int* flags = (int*)ws;
-    int* excl = (int*)((char*)ws + a);
-    int* total = (int*)((char*)ws + 2 * a);
-    void* sws = (char*)ws + 2 * a + 256;
-    const dim3 grid((unsigned)cdiv(n_cap, 256), (unsigned)n_extra);
-    hipLaunchKernelGGL(mark_levels, grid, dim3(256), 0, st, P, flags);
-    const int rc = scan_exclusive_i32(flags, excl, tot, nullptr, total, sws, ws_bytes - 2 * a - 256, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(emit_levels, grid, dim3(256), 0, st, P, (const int*)flags, (const int*)excl);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Round 5: EVERY level of a scene - the level-0 unique (keys, segment starts, point -> voxel map) and all coarser levels (keys, parents) -
-// from the sorted POINT keys in four launches (mark, two scan launches, emit) instead of four for level 0 plus four for the rest: a
-// run boundary of (Morton >> 3 l) over the sorted point keys is a run boundary over the unique keys of any finer level, so the
-// arrays are those of sd3d_unique_sorted(shift 0) followed by sd3d_unique_levels, entry for entry.  No extent clip.
-// ---------------------------------------------------------------------------------------------
 struct VLParams {
     const uint64_t* keys; const uint32_t* src_idx; int64_t n; int nl;                   // sorted point keys, their points; nl levels (level 0 included)
     uint64_t* ukeys[UL_MAX + 1]; int32_t* parent[UL_MAX]; int32_t* seg_start; int32_t* map; int32_t* counts;
@@ -336,7 +275,7 @@ static int launch_voxel_levels_all(const uint64_t* keys, const uint32_t* src_idx
                                    int32_t* map, int32_t* const* parents, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t st) {
     if (n <= 0 || n_levels < 1 || n_levels > UL_MAX + 1) return sd3d_set_error(SD3D_ERR_ARG, "voxel_levels_all: n > 0 and 1..8 levels");
     if (!keys || !ukeys || !seg_start || !map || !counts || (n_levels > 1 && !parents)) return sd3d_set_error(SD3D_ERR_ARG, "voxel_levels_all: null pointer");
-    if (ws_bytes < unique_levels_ws_bytes(n, n_levels)) return sd3d_set_error(SD3D_ERR_WS, "voxel_levels_all workspace too small");
+    if (ws_bytes < voxel_levels_all_ws_bytes(n, n_levels)) return sd3d_set_error(SD3D_ERR_WS, "voxel_levels_all workspace too small");
     VLParams P;
     P.keys = keys; P.src_idx = src_idx; P.n = n; P.nl = n_levels; P.seg_start = seg_start; P.map = map; P.counts = counts;
     for (int l = 0; l <= UL_MAX; ++l) P.ukeys[l] = l < n_levels ? ukeys[l] : nullptr;
@@ -365,7 +304,7 @@ extern "C" int sd3d_voxel_levels_all(const uint64_t* sorted_keys, const uint32_t
 extern "C" size_t sd3d_voxelise_scene_ws_bytes(int64_t n, int n_levels) {
     n = n > 0 ? n : 1;
     size_t b = sd3d_scene_stats_ws_bytes();
-    const size_t c[3] = {sort_ws_bytes(n), unique_ws_bytes(n), unique_levels_ws_bytes(n, n_levels > 1 ? n_levels : 1)};
+    const size_t c[3] = {sort_ws_bytes(n), unique_ws_bytes(n), voxel_levels_all_ws_bytes(n, n_levels > 1 ? n_levels : 1)};
     for (size_t v : c) b = v > b ? v : b;
     return b;
 }
@@ -919,40 +858,22 @@ __device__ __forceinline__ void voxel_mean_body(const float* __restrict__ pts, i
     }
 }
 
-__global__ __launch_bounds__(256) void voxel_mean_kernel(const float* __restrict__ pts, int ld_pts,
-                                                         const float* __restrict__ f2d, int F, int mode,
-                                                         const float* __restrict__ stats, float inv_n,
-                                                         const uint32_t* __restrict__ sidx, const int32_t* __restrict__ seg_start,
-                                                         int64_t n_vox, float* __restrict__ out, int ld_out) {
-    const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (v >= n_vox) return;
-    voxel_mean_body(pts, ld_pts, f2d, F, mode, stats, inv_n, 0, sidx, seg_start, v, out, ld_out);
-}
-
-// Several scenes voxelised as ONE block-diagonal tensor (batch index in the key bits above the Z-order code): a voxel finds its
-// scene's source arrays from its key.  Per voxel the arithmetic is the single-scene kernel's (same point order, same sums).
+// 1..16 scenes voxelised as ONE block-diagonal tensor (batch index in the key bits above the Z-order code): a voxel finds its
+// scene's source arrays from its key.  One scene is scene 0 and its keys are not read (the branch is uniform across the launch).
 struct VMBatch { int n; sd3d_scene_src s[SD3D_MAX_BATCH]; };
 __global__ __launch_bounds__(256) void voxel_mean_batch_kernel(const VMBatch b, int F, int mode, const uint64_t* __restrict__ ukeys,
                                                                const uint32_t* __restrict__ sidx, const int32_t* __restrict__ seg_start,
                                                                int64_t n_vox, float* __restrict__ out, int ld_out) {
     const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (v >= n_vox) return;
-    int bi = (int)((ukeys[v] >> SD3D_MORTON_BITS) & 0xFF);
-    bi = __builtin_amdgcn_readfirstlane(bi < b.n ? bi : 0);
+    int bi = 0;
+    if (b.n > 1) {
+        bi = (int)((ukeys[v] >> SD3D_MORTON_BITS) & 0xFF);
+        bi = __builtin_amdgcn_readfirstlane(bi < b.n ? bi : 0);
+    }
     const sd3d_scene_src& sc = b.s[bi];
     voxel_mean_body(sc.points, sc.ld_points, sc.feats2d, F, mode, sc.stats, 1.0f / (float)sc.n_points, sc.point_off, sidx, seg_start, v,
                     out, ld_out);
-}
-
-extern "C" int sd3d_voxel_mean(const float* pts, int ld_pts, const float* f2d, int F, int mode, const float* stats, int64_t n_points,
-                               const uint32_t* sidx, const int32_t* seg_start, int64_t n_vox, float* out, int ld_out, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (n_vox <= 0) return SD3D_OK;
-    if (mode != 1 && !f2d) return sd3d_set_error(SD3D_ERR_ARG, "voxel_mean: 2D features missing");
-    hipLaunchKernelGGL(voxel_mean_kernel, dim3((unsigned)cdiv(n_vox, 4)), dim3(256), 0, st, pts, ld_pts, f2d, F, mode, stats,
-                       1.0f / (float)n_points, sidx, seg_start, n_vox, out, ld_out);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
 }
 
 extern "C" int sd3d_voxel_mean_batch(const sd3d_scene_src* scenes, int n_scenes, int F, int mode, const uint64_t* ukeys, const uint32_t* sidx,
@@ -961,6 +882,7 @@ extern "C" int sd3d_voxel_mean_batch(const sd3d_scene_src* scenes, int n_scenes,
     hipStream_t st = (hipStream_t)stream;
     if (n_vox <= 0) return SD3D_OK;
     if (n_scenes <= 0 || n_scenes > SD3D_MAX_BATCH) return sd3d_set_error(SD3D_ERR_ARG, "voxel_mean_batch: 1..16 scenes per call");
+    if (n_scenes > 1 && !ukeys) return sd3d_set_error(SD3D_ERR_ARG, "voxel_mean_batch: several scenes need the voxel keys");
     VMBatch b;
     b.n = n_scenes;
     for (int i = 0; i < n_scenes; ++i) {
@@ -981,16 +903,6 @@ extern "C" int sd3d_voxel_mean_batch(const sd3d_scene_src* scenes, int n_scenes,
 // members (C/4 lanes x float4 each, 3 more lanes for xyz) and are combined with one cross-half
 // shuffle, so the summation order is fixed.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void segment_starts_kernel(const uint64_t* __restrict__ sorted_ids, int64_t n, int64_t S,
-                                                             int32_t* __restrict__ start /*[S+1]*/) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j > n) return;
-    const int64_t prev = (j == 0) ? -1 : (int64_t)sorted_ids[j - 1];
-    int64_t cur = (j == n) ? S : (int64_t)sorted_ids[j];
-    if (cur > S) cur = S;
-    for (int64_t s = prev + 1; s <= cur; ++s) start[s] = (int32_t)j;
-}
-
 // Round 5: one WORKGROUP (four waves) per superpoint, the rows staged through LDS.  With one wave per superpoint the launch lasted as
 // long as its largest superpoint (176 points on the benchmark scene against a mean of 50): three rounds of {sidx -> inverse -> two
 // batches of feature rows}, twelve dependent memory latencies, 36 us for 58 MB.  Now the 256 threads resolve the sidx -> inverse chain
@@ -1094,13 +1006,6 @@ extern "C" int sd3d_segment_starts_batch(const uint64_t* sorted_ids, int64_t n, 
     so.n = n_scenes;
     for (int i = 0; i < n_scenes; ++i) so.off[i] = off_host[i];
     hipLaunchKernelGGL(segment_starts_batch_kernel, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, st, sorted_ids, n, S, so, start);
-    SD3D_CHECK_LAUNCH();
-    return SD3D_OK;
-}
-
-extern "C" int sd3d_segment_starts(const uint64_t* sorted_ids, int64_t n, int64_t S, int32_t* start, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(segment_starts_kernel, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, st, sorted_ids, n, S, start);
     SD3D_CHECK_LAUNCH();
     return SD3D_OK;
 }

@@ -257,7 +257,6 @@ _WS = _PerThread()
 _WS2 = _PerThread()       # split-K partial sums of gather_gemm
 _WS3 = _PerThread()       # partial products of pair_conv
 _WS4 = _PerThread()       # pair_lists scratch
-_WS5 = _PerThread()       # expand_masks bit table
 _WS6 = _PerThread()       # attention key-split partial states
 
 
@@ -373,25 +372,9 @@ def unique_sorted(keys, src_idx, n_cap, n_dev=None, shift=0, want_seg_start=Fals
     return ukeys, seg, mp, nuniq
 
 
-def unique_levels(keys0: torch.Tensor, n_cap: int, n0_dev: torch.Tensor, n_extra: int, counts_out=None):
-    """All coarser levels from the sorted level-0 unique keys in four launches (`sd3d_unique_levels`): ([ukeys_1..], [parent_1..],
-    counts int32 [n_extra]) - what `unique_sorted(keys_l, None, n_cap, n_l, 3, want_map=True)` gives level after level (no extent clip)."""
-    lib = _lib.load()
-    dev = keys0.device
-    uk = torch.empty(n_extra, n_cap, dtype=torch.int64, device=dev)
-    par = torch.empty(n_extra, n_cap, dtype=torch.int32, device=dev)
-    counts = torch.empty(n_extra, dtype=torch.int32, device=dev) if counts_out is None else counts_out
-    ws = _WS.get(lib.sd3d_unique_levels_ws_bytes(n_cap, n_extra), dev)
-    up = (ctypes.c_void_p * n_extra)(*[uk.data_ptr() + 8 * n_cap * l for l in range(n_extra)])
-    pp = (ctypes.c_void_p * n_extra)(*[par.data_ptr() + 4 * n_cap * l for l in range(n_extra)])
-    _lib.check(lib.sd3d_unique_levels(_ptr(keys0, torch.int64, "keys0"), n_cap, _ptr(n0_dev, torch.int32, "n0"), n_extra,
-                                      ctypes.addressof(up), ctypes.addressof(pp), _ptr(counts), ws.data_ptr(), ws.numel(), _stream()), "unique_levels")
-    return [uk[l] for l in range(n_extra)], [par[l] for l in range(n_extra)], counts
-
-
 def voxel_levels_all(skeys, sidx, n_levels: int, counts_out):
     """Every level of a (batch of) scene(s) from its sorted point keys in four launches (`sd3d_voxel_levels_all`): what
-    `unique_sorted(skeys, sidx, N, None, 0, want_seg_start=True, want_map=True)` followed by `unique_levels` returns -
+    `unique_sorted(skeys, sidx, N, None, 0, want_seg_start=True, want_map=True)` followed by `unique_sorted(shift=3)` level after level returns -
     (ukeys [L x [N]], seg_start [N + 1], inverse [N], parents [(L - 1) x [N]]); counts_out int32 [L] receives the voxels per level."""
     lib = _lib.load()
     N, dev, L = skeys.numel(), skeys.device, int(n_levels)
@@ -399,7 +382,7 @@ def voxel_levels_all(skeys, sidx, n_levels: int, counts_out):
     par = torch.empty(max(1, L - 1), N, dtype=torch.int32, device=dev)
     seg = torch.empty(N + 1, dtype=torch.int32, device=dev)
     inv = torch.empty(N, dtype=torch.int32, device=dev)
-    ws = _WS.get(lib.sd3d_unique_levels_ws_bytes(N, L), dev)
+    ws = _WS.get(lib.sd3d_voxel_levels_all_ws_bytes(N, L), dev)
     up = (ctypes.c_void_p * L)(*[uk.data_ptr() + 8 * N * l for l in range(L)])
     pp = (ctypes.c_void_p * max(1, L - 1))(*[par.data_ptr() + 4 * N * l for l in range(L - 1)])
     _lib.check(lib.sd3d_voxel_levels_all(_ptr(skeys, torch.int64, "skeys"), _ptr(sidx, torch.int32, "sidx"), N, L, ctypes.addressof(up), _ptr(seg),
@@ -418,7 +401,7 @@ assert _VOX_DESC_DT.itemsize == 176, _VOX_DESC_DT.itemsize
 
 def voxelise_scene(points, inv_voxel: float, shift_to_min: bool, key_bits: int, n_levels: int, superpoints=None, sp_bits: int = 64):
     """One scene's voxelisation chain from ONE C call (`sd3d_voxelise_scene`): what scene_stats + voxel_keys + sort_pairs + unique_sorted
-    (segment starts, point -> voxel map) + unique_levels + keys_from_i64(max_out) give when called one after the other - the same kernels
+    (segment starts, point -> voxel map, then the coarser levels) + keys_from_i64(max_out) give when called one after the other - the same kernels
     in the same order, issued from C instead of from ~10 Python calls in front of everything else the scene needs.
     -> dict(stats, origin, icoords, skeys, sidx, ukeys [L x [N]], seg_start, inverse, parents [L-1 x [N]], readback int32 [L + 2], sp_keys | None)"""
     lib = _lib.load()
@@ -528,18 +511,6 @@ def stride_maps(fine_keys, parent, n_fine, n_coarse, perm8, want_down=True, want
     return down, up
 
 
-def voxel_mean(points, feats2d, mode, stats, sorted_idx, seg_start, n_vox, ld_out):
-    lib = _lib.load()
-    p, ld = _rows(points, "points")
-    F = 0 if feats2d is None else feats2d.shape[1]
-    out = torch.empty(n_vox, ld_out, dtype=torch.float32, device=points.device)
-    _lib.check(lib.sd3d_voxel_mean(p, ld, _ptr(feats2d, torch.float32, "feats2d"), F, mode,
-                                   _ptr(stats, torch.float32, "stats"), points.shape[0],
-                                   _ptr(sorted_idx, torch.int32, "sorted_idx"), _ptr(seg_start, torch.int32, "seg_start"),
-                                   n_vox, _ptr(out), ld_out, _stream()), "voxel_mean")
-    return out
-
-
 _SCENE_SRC_DT = np.dtype([("points", "<u8"), ("feats2d", "<u8"), ("stats", "<u8"), ("point_off", "<i8"), ("n_points", "<i8"),
                           ("ld_points", "<i4"), ("pad_", "<i4")], align=True)                                              # sd3d_scene_src
 assert _SCENE_SRC_DT.itemsize == 48
@@ -567,6 +538,11 @@ def voxel_mean_batch(scenes, mode, ukeys, sorted_idx, seg_start, n_vox, ld_out):
     return out
 
 
+def voxel_mean(points, feats2d, mode, stats, sorted_idx, seg_start, n_vox, ld_out):
+    """One scene: a batch of one, whose voxel keys are not needed."""
+    return voxel_mean_batch([(points, feats2d, stats, 0)], mode, None, sorted_idx, seg_start, n_vox, ld_out)
+
+
 def segment_starts_batch(sorted_ids, n, S, id_off):
     """sorted (scene << 32 | id) keys -> start[S + 1] over the dense ids id_off[scene] + id."""
     import ctypes as C
@@ -579,11 +555,8 @@ def segment_starts_batch(sorted_ids, n, S, id_off):
 
 
 def segment_starts(sorted_ids, n, S):
-    lib = _lib.load()
-    start = torch.empty(S + 1, dtype=torch.int32, device=sorted_ids.device)
-    _lib.check(lib.sd3d_segment_starts(_ptr(sorted_ids, torch.int64, "sorted_ids"), n, S, _ptr(start), _stream()),
-               "segment_starts")
-    return start
+    """One scene: plain sorted ids (below 2^32) -> start[S + 1]."""
+    return segment_starts_batch(sorted_ids, n, S, [0])
 
 
 def pool_superpoints(feat, C, inverse, icoords, voxel_size, sorted_idx, start, S):
@@ -1264,13 +1237,8 @@ def dinox_mask_bits_batch(blocked_list, near_list):
 
 
 def mask_bits(logits, S, thr):
-    lib = _lib.load()
-    pl, ld = _rows(logits, "logits")
-    Q = logits.shape[0]
-    nw = (S + 31) // 32
-    bits = torch.empty(Q, nw, dtype=torch.int32, device=logits.device)
-    _lib.check(lib.sd3d_mask_bits(pl, ld, Q, S, float(thr), _ptr(bits), nw, _stream()), "mask_bits")
-    return bits
+    """One scene: a batch of one."""
+    return mask_bits_batch([logits], [S], thr)[0]
 
 
 def near_bits(sp_pos, centers, thr):
@@ -1284,14 +1252,8 @@ def near_bits(sp_pos, centers, thr):
 
 
 def dinox_mask_bits(blocked, near):
-    lib = _lib.load()
-    Q, nw = blocked.shape
-    M = near.shape[0]
-    nwo = (M + 1 + 31) // 32
-    out = torch.empty(Q, nwo, dtype=torch.int32, device=blocked.device)
-    _lib.check(lib.sd3d_dinox_mask_bits(_ptr(blocked, torch.int32, "blocked"), _ptr(near, torch.int32, "near"), nw, Q, M,
-                                        _ptr(out), nwo, _stream()), "dinox_mask_bits")
-    return out
+    """One scene: a batch of one."""
+    return dinox_mask_bits_batch([blocked], [near])[0]
 
 
 def box_refine(ref_points, d_center, size_prev, d_size, rng, normalize, row_scene=None):
@@ -1471,20 +1433,6 @@ class MaskBits:
                                             _ptr(self.superpoints, torch.int64, "superpoints"), pp, ldp, self.N,
                                             _ptr(self.boxes, torch.float32, "boxes"), self.loose, _ptr(out), _stream()), "expand_rows")
         return out
-
-
-def expand_masks(sig, src_row, superpoints, points, sp_thr, boxes=None, loose_ratio=1.5):
-    lib = _lib.load()
-    ps, lds = _rows(sig, "sig")
-    pp, ldp = _rows(points, "points")
-    n, N = src_row.numel(), superpoints.numel()
-    out = torch.empty(n, N, dtype=torch.uint8, device=sig.device)
-    count = torch.empty(n, dtype=torch.int32, device=sig.device)
-    ws = _WS5.get(lib.sd3d_expand_masks_ws_bytes(n, lds), sig.device)
-    _lib.check(lib.sd3d_expand_masks(ps, lds, _ptr(src_row, torch.int32, "src_row"), n, _ptr(superpoints, torch.int64, "superpoints"),
-                                     pp, ldp, N, float(sp_thr), _ptr(boxes, torch.float32, "boxes"), float(loose_ratio),
-                                     _ptr(out), _ptr(count), ws.data_ptr(), ws.numel(), _stream()), "expand_masks")
-    return out, count
 
 
 def pack_mask_rows(masks_u8, rows=None):

@@ -108,7 +108,7 @@ def exact_pair_capacity(n_vox0: int, device=None) -> bool:
 
 # SD3D_HIER_MAPS=0: kernel maps by hash-table probes (rounds 1-4: one table + one probe launch per level).  Default: every 3^3 map of a
 # scene and the stem's 5^3 map from ONE call through the level hierarchy of the sorted keys (csrc/voxel.hip kmap_hier_kernel: two
-# cache-friendly loads per probe, no hash tables, no memsets) whenever the levels came from `sd3d_unique_levels` (MinkowskiEngine
+# cache-friendly loads per probe, no hash tables, no memsets) whenever the levels came without the extent clip (MinkowskiEngine
 # semantics: every parent exists).  Entry for entry the same tables.
 HIER_MAPS = os.environ.get("SD3D_HIER_MAPS", "1") != "0"
 _INV27 = {}
@@ -138,8 +138,8 @@ def inv27_table(order: str) -> np.ndarray:
 PAIR_CHAIN_LEVELS = (0, 1, 2)
 # SD3D_OPTIMISTIC_SORT=0: a scene's voxel keys / superpoint ids are always sorted over all their bits (7 + 4 radix passes instead of 4 + 2)
 OPTIMISTIC_SORT = os.environ.get("SD3D_OPTIMISTIC_SORT", "1") != "0"
-# SD3D_LEVELS_AT_ONCE=0: the coarser levels of a scene by one run-length unique per level (four launches each) instead of all of them
-# from the level-0 keys in four launches (`sd3d_unique_levels`; MinkowskiEngine semantics only - spconv's extent clip keeps the per-level path)
+# SD3D_LEVELS_AT_ONCE=0: the levels of a scene by one run-length unique per level (four launches each) instead of all of them from
+# the sorted point keys in four launches (`sd3d_voxel_levels_all`; MinkowskiEngine semantics only - spconv's extent clip keeps the per-level path)
 LEVELS_AT_ONCE = os.environ.get("SD3D_LEVELS_AT_ONCE", "1") != "0"
 # SD3D_VOXELISE_ONE_CALL=0: the voxelisation chain of a scene as ~10 Python calls (the round 1 - 4 path; the clipped / per-level variants keep it)
 VOXELISE_ONE_CALL = os.environ.get("SD3D_VOXELISE_ONE_CALL", "1") != "0"
@@ -154,16 +154,12 @@ def _levels_from_sorted(skeys, sidx, n_levels: int, rb, clip=None):
     """Sorted point keys -> (keys_l, seg_start, inverse, parents) of every level; the voxel counts land in the read-back slots
     rb[0:n_levels].  clip = (stats, inv_voxel, clip_min_shape): spconv's output-extent rule for the strided levels."""
     N = skeys.shape[0]
-    at_once = _levels_at_once(n_levels, clip[2] if clip else 0)
-    if at_once and VOXELISE_ONE_CALL:
-        # every level from the sorted point keys in four launches (level 0 and the coarser levels were four each).  Batches only:
-        # one scene with these settings never gets here, its whole chain is `ops.voxelise_scene`
+    if _levels_at_once(n_levels, clip[2] if clip else 0):
+        # every level from the sorted point keys in four launches instead of four per level (a batch, or one scene as the Python chain:
+        # with SD3D_VOXELISE_ONE_CALL one scene never gets here, its whole chain is `ops.voxelise_scene`)
         return ops.voxel_levels_all(skeys, sidx, n_levels, rb[0:n_levels])
     ukeys, seg_start, inverse, n_prev = ops.unique_sorted(
         skeys, sidx, N, None, 0, want_seg_start=True, want_map=True, map_size=N, nuniq_out=rb[0:1])
-    if at_once:
-        uks, parents, _ = ops.unique_levels(ukeys, N, n_prev, n_levels - 1, counts_out=rb[1:n_levels])   # every coarser level in four launches
-        return [ukeys] + uks, seg_start, inverse, parents
     keys_l, parents = [ukeys], []
     for lvl in range(1, n_levels):
         uk, _, parent, n_prev = ops.unique_sorted(keys_l[-1], None, N, n_prev, 3, want_seg_start=False, want_map=True,

@@ -142,6 +142,16 @@ def test_dinox_mask_bits_sizes(Q, S, M):
     assert torch.equal(torch.cat(two), got)
 
 
+def test_dinox_mask_bits_batch_refuses_more_lds_than_a_workgroup_has():
+    """Two queries per workgroup x 8193 superpoint words = 65 544 bytes of LDS, eight past the 64 KiB a launch may ask for: refused before
+    any launch, with the same words whether one scene or a batch is given."""
+    from segdino3d_amd import ops
+    d = dev()
+    blocked, near = torch.zeros(1, 8193, dtype=torch.int32, device=d), torch.zeros(1, 8193, dtype=torch.int32, device=d)
+    with pytest.raises(RuntimeError, match="65536 superpoints"):
+        ops.dinox_mask_bits_batch([blocked], [near])
+
+
 def _build_decoder(kw_over=None, sd_kw=None):
     from segdino3d_amd.decoder import ScanNetQueryDecoder
     kw = dict(DEC_KW); kw.update(kw_over or {})

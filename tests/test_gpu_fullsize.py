@@ -184,10 +184,11 @@ def test_full_forward_is_deterministic_and_counts_add_up():
     assert torch.equal(r1.instance_scores, r2.instance_scores)
     # semantic / panoptic maps label every point
     assert r1.pts_semantic_mask[0].shape == (N_POINTS,) and r1.pts_semantic_mask[1].shape == (N_POINTS,)
-    # expand_masks: point counts = row sums when the box filter is off
+    # the whole mask table: point counts = row sums when the box filter is off
     sig = torch.rand(600, 3008, device=d)
     src = torch.arange(600, dtype=torch.int32, device=d)
     sp = tgt.extra_features["super_point_masks"].contiguous()
-    masks, count = ops.expand_masks(sig, src, sp, pts, 0.4, None)
+    mb = ops.MaskBits(sig, src, sp, pts, 0.4, None)
+    masks, count = mb.rows(torch.arange(600, dtype=torch.int32, device=d)), mb.count
     assert torch.equal(masks.sum(dim=1, dtype=torch.int64), count.long())
     assert torch.equal(masks.view(torch.bool), (sig[:, :3000] > 0.4)[:, sp])

@@ -305,7 +305,7 @@ def test_gather_i64(N):
     assert torch.equal(ops.gather_i64(table.to(d), idx.to(d), False).cpu(), table[torch.zeros_like(idx)])
 
 
-# ---- expand_masks, MaskBits.rows ------------------------------------------------------------------------------------------------------------
+# ---- MaskBits, MaskBits.rows ----------------------------------------------------------------------------------------------------------------
 def _expand_case(N, n, with_boxes):
     g = torch.Generator().manual_seed(1000 * N + n)
     W, S_real, thr = 96, 90, np.float32(0.4)
@@ -344,8 +344,8 @@ def _expand_case(N, n, with_boxes):
 
 @pytest.mark.parametrize("with_boxes", [False, True])
 @pytest.mark.parametrize("N", [1, 3, 4, 5, 1023, 1024, 1025, 4099])
-def test_expand_masks_and_mask_bits(N, with_boxes):
-    """`expand_masks` and `MaskBits(...).rows` each against `expand_masks_ref` (not against each other): bytes and counts exact."""
+def test_mask_bits_rows_and_counts(N, with_boxes):
+    """`MaskBits(...).count` and `MaskBits(...).rows` (the whole table among the lists) against `expand_masks_ref`: bytes and counts exact."""
     from segdino3d_amd import ops
     d = _dev()
     for n in (1, 31, 32, 33, 127, 128, 129):
@@ -356,9 +356,6 @@ def test_expand_masks_and_mask_bits(N, with_boxes):
             assert 0 < ref.sum() < plain.sum() and ref[0].sum() >= 1       # the filter cuts, the zero-size box keeps its centre
         dsig, dsrc, dsp, dpts = sig.to(d), src.to(d), sp.to(d), pts.to(d)
         dbox = None if boxes is None else boxes.to(d)
-        full, count = ops.expand_masks(dsig, dsrc, dsp, dpts, thr, dbox)
-        assert np.array_equal(full.cpu().numpy(), ref), (N, n, "expand_masks")
-        assert np.array_equal(count.cpu().numpy().astype(np.int64), ref_count), (N, n, "expand_masks count")
         mb = ops.MaskBits(dsig, dsrc, dsp, dpts, thr, dbox)
         assert np.array_equal(mb.count.cpu().numpy().astype(np.int64), ref_count), (N, n, "MaskBits count")
         lists = ([], [0], [n - 1, 0, 0, n // 2], list(range(n)), list(range(n))[::-1], [n // 2, n // 3, n - 1, 31 % n, 32 % n, 33 % n, 96 % n])

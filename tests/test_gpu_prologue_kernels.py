@@ -115,7 +115,7 @@ def test_voxel_keys_error_flags_at_their_limits(rel, axis, want):
     assert err == ref["flag"] == want and np.array_equal(keys, ref["keys"])
 
 
-# ---- 3. unique_sorted, unique_levels, voxel_levels_all, voxelise_scene -------------------------------------------------------------------
+# ---- 3. unique_sorted, voxel_levels_all, voxelise_scene ---------------- -------------------------------------------------------------------
 def _route_per_level(skeys, sidx, L, n_cap=None, n_dev=None):
     """Level 0 and every coarser level by one `unique_sorted` each (the route the clipped levels take)."""
     ops = _ops()
@@ -128,15 +128,6 @@ def _route_per_level(skeys, sidx, L, n_cap=None, n_dev=None):
         parents.append(par)
         counts.append(n_prev)
     return dict(ukeys=keys_l, seg_start=seg, inverse=inv, parents=parents, counts=[int(c.item()) for c in counts])
-
-
-def _route_levels(skeys, sidx, L, n_cap=None, n_dev=None):
-    """Level 0 by `unique_sorted`, the coarser levels by one `unique_levels`."""
-    ops = _ops()
-    N = skeys.numel() if n_cap is None else n_cap
-    uk, seg, inv, n0 = ops.unique_sorted(skeys, sidx, N, n_dev, 0, want_seg_start=True, want_map=True, map_size=N)
-    uks, parents, counts = ops.unique_levels(uk, N, n0, L - 1)
-    return dict(ukeys=[uk] + uks, seg_start=seg, inverse=inv, parents=parents, counts=[int(n0.item())] + counts.tolist())
 
 
 def _route_all(skeys, sidx, L):
@@ -163,8 +154,6 @@ def test_unique_routes_on_built_keys(kind, L):
     ref = K.levels_ref(keys, src, L)
     skeys, sidx = up(keys), up(src)
     routes = {"per level": _route_per_level(skeys, sidx, L), "all levels": _route_all(skeys, sidx, L)}
-    if L > 1:
-        routes["unique_levels"] = _route_levels(skeys, sidx, L)
     for what, got in routes.items():
         _assert_levels(got, ref, L, len(keys), (kind, L, what))
     assert torch.equal(skeys, up(keys)) and torch.equal(sidx, up(src)), "the inputs are read only"
@@ -176,8 +165,7 @@ def test_unique_capacity_tail_is_not_data(n_dev, n_cap):
     keys = K.sorted_keys_case("runs")[0][2000:2000 + n_cap]
     ref = K.levels_ref(keys[:n_dev], None, 5)
     n = torch.tensor([n_dev], dtype=torch.int32, device=_dev())
-    for what, route in (("per level", _route_per_level), ("unique_levels", _route_levels)):
-        _assert_levels(route(up(keys), None, 5, n_cap=n_cap, n_dev=n), ref, 5, n_dev, (what, n_dev, n_cap))
+    _assert_levels(_route_per_level(up(keys), None, 5, n_cap=n_cap, n_dev=n), ref, 5, n_dev, ("per level", n_dev, n_cap))
     # a count above the capacity is clamped to it
     big = torch.tensor([n_cap + 77], dtype=torch.int32, device=_dev())
     _assert_levels(_route_per_level(up(keys), None, 2, n_cap=n_cap, n_dev=big), K.levels_ref(keys, None, 2), 2, n_cap, "clamped")
@@ -186,7 +174,7 @@ def test_unique_capacity_tail_is_not_data(n_dev, n_cap):
 @pytest.mark.parametrize("L", [1, 2, 5])
 @pytest.mark.parametrize("shift,pad", [(False, 0), (True, 3)])
 def test_voxelise_scene_equals_the_chain_and_the_reference(L, shift, pad):
-    """Points -> every level: `voxelise_scene` (one C call), the op-by-op chain with each of the three level routes, and numpy."""
+    """Points -> every level: `voxelise_scene` (one C call), the op-by-op chain with each of the two level routes, and numpy."""
     ops = _ops()
     pts = K.level_scene()
     pd = strided(pts, pad)
@@ -207,8 +195,6 @@ def test_voxelise_scene_equals_the_chain_and_the_reference(L, shift, pad):
     skeys, sidx = ops.sort_pairs(keys, None, 0, 32)
     assert torch.equal(skeys, v["skeys"]) and torch.equal(sidx, v["sidx"]) and int(err.item()) == 0
     routes = {"per level": _route_per_level(skeys, sidx, L), "all levels": _route_all(skeys, sidx, L)}
-    if L > 1:
-        routes["unique_levels"] = _route_levels(skeys, sidx, L)
     for what, got in routes.items():
         _assert_levels(got, ref, L, len(pts), what)
 
@@ -551,6 +537,8 @@ def test_refusals_on_the_device():
         with pytest.raises(RuntimeError, match="2D features missing"):
             ops.voxel_mean_batch([(up(sc["pts"]), None, torch.zeros(9, device=d), 0)], mode, torch.zeros(sc["n_vox"], dtype=torch.int64, device=d),
                                  up(sc["sidx"]), up(sc["seg_start"]), sc["n_vox"], 32)
+    with pytest.raises(RuntimeError, match="need the voxel keys"):     # only one scene may come without them
+        ops.voxel_mean_batch([(up(sc["pts"]), None, torch.zeros(9, device=d), 0)] * 2, 1, None, up(sc["sidx"]), up(sc["seg_start"]), sc["n_vox"], 32)
     c = K.pool_case(96)
     args = (up(c["inverse"]), up(c["icoords"]), K.VS, up(c["sidx"]), up(c["start"]), c["S"])
     wide104 = torch.zeros(K.POOL_VOX, 104, device=d)
@@ -560,10 +548,9 @@ def test_refusals_on_the_device():
     with pytest.raises(RuntimeError, match="multiple of 4"):
         ops.pool_superpoints(torch.zeros(K.POOL_VOX, 98, device=d)[:, :96], 96, *args)
     keys = up(K.sorted_keys_case("distinct")[0])
-    n0 = torch.tensor([keys.numel()], dtype=torch.int32, device=d)
-    for n_extra in (0, 8):
-        with pytest.raises(RuntimeError, match="1..7 coarser levels"):
-            ops.unique_levels(keys, keys.numel(), n0, n_extra)
+    for n_levels in (0, 9):
+        with pytest.raises(RuntimeError, match="1..8 levels"):
+            ops.voxel_levels_all(keys, None, n_levels, torch.zeros(9, dtype=torch.int32, device=d))
     with pytest.raises(RuntimeError, match="1..16 scenes"):
         ops.segment_starts_batch(torch.zeros(4, dtype=torch.int64, device=d), 4, 17, list(range(17)))
     torch.cuda.synchronize()
@@ -576,13 +563,11 @@ def test_cpu_tensors_are_refused():
     sc, c = K.vm_scene(), K.pool_case(4)
     pts, keys = sc["pts"], torch.from_numpy(K.sorted_keys_case("distinct")[0])
     i32 = torch.zeros(700, dtype=torch.int32)
-    n0 = torch.tensor([700], dtype=torch.int32, device=d)
     calls = [lambda: ops.scene_stats(pts),
              lambda: ops.voxel_keys(pts, 50.0, torch.zeros(9, device=d)),
              lambda: ops.voxel_keys(up(pts), 50.0, torch.zeros(9)),
              lambda: ops.unique_sorted(keys, None, 700),
              lambda: ops.unique_sorted(up(keys), i32, 700),
-             lambda: ops.unique_levels(keys, 700, n0, 2),
              lambda: ops.voxel_levels_all(keys, None, 2, torch.zeros(2, dtype=torch.int32, device=d)),
              lambda: ops.voxelise_scene(pts, 50.0, False, 32, 2),
              lambda: ops.stride_maps(keys, up(i32), 700, 700, up(np.arange(8, dtype=np.int32))),

@@ -683,7 +683,7 @@ def test_batch_optimistic_radix_passes_fall_back_to_the_full_sort(extent_m, sp_b
 @pytest.mark.parametrize("n,ext,with_sp", [(30_000, 5.0, True), (12_345, 3.0, True), (1, 1.0, True), (150_001, 9.0, False), (4097, 30.0, True)])
 def test_voxelisation_from_one_call_equals_the_separate_calls(n, ext, with_sp, monkeypatch):
     """`sd3d_voxelise_scene` (round 5: the voxelisation chain of a scene issued by ONE C call) against the chain of separate calls
-    (scene_stats, voxel_keys, sort_pairs, unique_sorted, unique_levels, keys_from_i64): every array and every count, bit for bit -
+    (scene_stats, voxel_keys, sort_pairs, voxel_levels_all, keys_from_i64): every array and every count, bit for bit -
     odd sizes (row padding of the shared buffers), one point, a scene that needs the full key sort, no superpoints."""
     from segdino3d_amd import sparse
     from segdino3d_amd.sparse import SceneMaps
@@ -713,7 +713,7 @@ def test_voxelisation_from_one_call_equals_the_separate_calls(n, ext, with_sp, m
 @pytest.mark.gpu
 @pytest.mark.parametrize("batched", [False, True])
 def test_all_levels_at_once_equal_the_level_by_level_unique(batched, monkeypatch):
-    """`sparse.LEVELS_AT_ONCE` (`sd3d_unique_levels`: every coarser level from the sorted level-0 keys in four launches): the keys, the
+    """`sparse.LEVELS_AT_ONCE` (`sd3d_voxel_levels_all`: every level from the sorted point keys in four launches): the keys, the
     parent maps and the voxel counts of the level-by-level run-length unique, bit for bit - one scene and a batch (scene bits in the keys)."""
     from segdino3d_amd import sparse
     from segdino3d_amd.sparse import BatchSceneMaps, SceneMaps
@@ -772,16 +772,3 @@ def test_hierarchical_kernel_maps_equal_the_hash_probed_maps(batched, order, mon
             assert torch.equal(pa.in_idx, pb.in_idx) and torch.equal(pa.tile_k, pb.tile_k), key
         for l in range(4):                                     # the stride-2 maps came out of the same launches
             assert torch.equal(a.down(l), b.down(l)) and torch.equal(a.up(l), b.up(l)), l
-
-
-def test_unique_levels_of_an_empty_scene_report_zero_voxels():
-    """`sd3d_unique_levels` with a device-side row count of 0 (an empty or fully filtered scene): every coarser level reports 0
-    voxels - the counts are written by the kernels, never left as allocated."""
-    from segdino3d_amd import ops
-    d = torch.device("cuda:0")
-    keys = torch.arange(1000, dtype=torch.int64, device=d)
-    for n0 in (0, 1000):
-        for _ in range(3):                                      # (fresh `torch.empty` counts each call: garbage would show)
-            _, _, counts = ops.unique_levels(keys, 1000, torch.tensor([n0], dtype=torch.int32, device=d), 4)
-            ref = [0] * 4 if n0 == 0 else [len(torch.unique(keys >> (3 * l))) for l in range(1, 5)]
-            assert counts.tolist() == ref, (n0, counts.tolist())
