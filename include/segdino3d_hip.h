@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 23
+#define SD3D_ABI_VERSION 24
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1457,6 +1457,50 @@ int sd3d_track_iterate(const void* depth, int depth_u16, float depth_scale, cons
                        int min_samples, float damping, float max_rot, float max_trans, void* state, size_t state_bytes, void* ws,
                        size_t ws_bytes, int64_t capacity, void* stream);
 int sd3d_track_end(void* state, size_t state_bytes, double* pose, float* cam_to_world, float* world_to_cam, int64_t* info, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh rasteriser (csrc/raster.hip, csrc/raster_rule.h): a triangle mesh drawn into posed views - per pixel the depth of the nearest
+ * face, that face, the face's corner nearest the pixel, and label channels read through either.  The depth image is what the RGB-D
+ * stages above take as float metres, for frames that have no depth of their own.  The reference has no counterpart;
+ * tests/raster_ref.py restates the rule below in numpy and the kernels EQUAL it, bit for bit.  segdino3d_amd/raster.py has the rule
+ * in full.  The call only enqueues work.  The images are a minimum over a set of keys, so they are a pure function of mesh, cameras
+ * and rule: the same bits whatever the order of the faces in flight, the cut of the views into calls or passes, and the stream.  The
+ * only global atomics are 64-bit integer minima and integer sums.
+ *
+ *   vertices float [Nv, 3], faces int32 [F, 3], Nv, F < 2^31; per view world_to_cam float [12] ([R | t], row-major) and intrinsics
+ *   float [4] = (fx, fy, cx, cy); one image size 1 <= H, W <= 16384, pixel centres at integer coordinates; 0 < near <= far.
+ *   Every float operation is rounded on its own, no fused multiply-add.  Per (view, face):
+ *   1. Bad face: an index outside [0, Nv), or a corner coordinate that fails |c| < 2^14 as floats (NaN and infinity fail).
+ *   2. Camera space: x_c = ((r00 x + r01 y) + r02 z) + t0, y_c and z_c alike; any corner with z_c < near drops the face ("near": there
+ *      is no near-plane clipping).
+ *   3. u = (fx x_c) / z_c + cx, v alike; any corner that fails |u| < 2^14 && |v| < 2^14 drops the face ("guard"); X = (int)rint(u 256),
+ *      Y alike.
+ *   4. int64 edge functions E(a, b, P) = (bx - ax)(Py - ay) - (by - ay)(Px - ax), P = (256 ui, 256 vi); A = E(v0, v1, v2); A == 0 or a
+ *      clamped bounding box without a pixel centre drops the face ("empty"); s = sign(A), w0 = s E(v1, v2, P), w1 = s E(v2, v0, P),
+ *      w2 = s E(v0, v1, P); covered iff all three >= 0 (edges inclusive, both windings, no culling).
+ *   5. double: q_i = 1 / z_c,i, num = (w0 q0 + w1 q1) + w2 q2, d = (float)(|A| / num); the sample is kept iff near <= d <= far.
+ *   6. The pixel keeps the minimum key (bits of d << 32) | face: the nearest face, ties to the lower face index.
+ *   7. depth float (0 where nothing was hit), face int32 (-1), vertex int32 = faces[face][i] for the largest w_i, ties to the lowest i
+ *      (-1); face_labels int32 [Lf, F] read at `face`, vertex_labels int32 [Lv, Nv] read at `vertex`, `fill` where nothing was hit;
+ *      Lf + Lv <= SD3D_RASTER_MAX_LABELS.
+ *   8. info int64 [SD3D_RASTER_INFO_WORDS] = drawn, near, guard, empty, bad (each (view, face) pair exactly once, precedence bad, near,
+ *      guard, empty, drawn), pixels hit.  The call clears it first.
+ *
+ *   sd3d_raster_views: the V views in passes of at most views_per_pass that share one key buffer; the result does not depend on it.
+ *     Records of drawn pairs split by clamped bounding-box area: up to SD3D_RASTER_SMALL_MAX_PIXELS one lane draws the face, above it
+ *     one wave.  depth_out float [V, H, W], face_out, vertex_out int32 [V, H, W], face_labels_out int32 [Lf, V, H, W],
+ *     vertex_labels_out int32 [Lv, V, H, W]: each optional, the label outputs required when their labels are given.  A pass must keep
+ *     views * F below 2^31.  ws: sd3d_raster_ws_bytes(F, min(views_per_pass, V), H, W) bytes (0 for bad arguments), 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_RASTER_MAX_LABELS 8
+#define SD3D_RASTER_INFO_WORDS 6
+#define SD3D_RASTER_SMALL_MAX_PIXELS 64
+size_t sd3d_raster_ws_bytes(int64_t n_faces, int views_per_pass, int H, int W);
+int sd3d_raster_views(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const float* world_to_cam,
+                      const float* intrinsics, int V, int H, int W, float near, float far, int views_per_pass, const int32_t* face_labels,
+                      int n_face_labels, const int32_t* vertex_labels, int n_vertex_labels, int fill, float* depth_out, int32_t* face_out,
+                      int32_t* vertex_out, int32_t* face_labels_out, int32_t* vertex_labels_out, int64_t* info, void* ws, size_t ws_bytes,
+                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -3001,3 +3001,72 @@ def instance_map(masks, scores, score_thr: float = 0.0):
     if N:
         _lib.check(lib.sd3d_instance_map(mp if I else None, sp if I else None, I, N, float(score_thr), _ptr(out), _stream()), who)
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# mesh rasteriser: a triangle mesh drawn into posed views (csrc/raster.hip; the rule: include/segdino3d_hip.h, segdino3d_amd/raster.py)
+# --------------------------------------------------------------------------------------------
+RASTER_MAX_LABELS = 8
+RASTER_SMALL_MAX_PIXELS = 64     # SD3D_RASTER_SMALL_MAX_PIXELS: up to this clamped bounding-box area one lane draws a face, above it one wave
+RASTER_MAX_DIM = 16384
+RASTER_INFO = ("drawn", "near", "guard", "empty", "bad", "pixels")
+_WS_RASTER = _PerThread()        # raster_views: the key buffer of one pass, its records and their counts
+
+
+def raster_views(vertices, faces, world_to_cam, intrinsics, height: int, width: int, near=0.1, far=6.0, views_per_pass: int = 32,
+                 face_labels=None, vertex_labels=None, fill: int = -1, return_depth: bool = True, return_face: bool = True,
+                 return_vertex: bool = False):
+    """A mesh drawn into V posed views (`sd3d_raster_views`): vertices fp32 [Nv, 3], faces int32 [F, 3], world_to_cam fp32 [V, 3, 4],
+    intrinsics fp32 [V, 4], face_labels int32 [Lf, F] or None, vertex_labels int32 [Lv, Nv] or None -> (depth fp32 [V, H, W] or None,
+    face int32 [V, H, W] or None, vertex int32 [V, H, W] or None, face label images int32 [Lf, V, H, W] or None, vertex label images
+    int32 [Lv, V, H, W] or None, info int64 [len(RASTER_INFO)]).  Enqueues only."""
+    lib = _lib.load()
+    who = "raster_views"
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise ValueError(f"{who}: vertices must be fp32 [Nv, 3], got {vertices.dtype} {list(vertices.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{who}: faces must be int32 [F, 3], got {faces.dtype} {list(faces.shape)}")
+    Nv, F, V, H, W = vertices.shape[0], faces.shape[0], world_to_cam.shape[0], int(height), int(width)
+    if Nv >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"{who}: need Nv, F < 2^31, got {Nv}, {F}")
+    if not (1 <= H <= RASTER_MAX_DIM and 1 <= W <= RASTER_MAX_DIM):
+        raise ValueError(f"{who}: images must be 1 .. {RASTER_MAX_DIM} a side, got {H} x {W}")
+    _want_shape(world_to_cam, [(V, 3, 4)], f"{who}: world_to_cam")
+    _want_shape(intrinsics, [(V, 4)], f"{who}: intrinsics")
+    if not (float(near) > 0.0 and float(far) >= float(near)):
+        raise ValueError(f"{who}: need 0 < near <= far, got near = {near}, far = {far}")
+    if int(views_per_pass) != views_per_pass or views_per_pass < 1:
+        raise ValueError(f"{who}: views_per_pass must be an integer >= 1, got {views_per_pass}")
+    if int(fill) != fill or not -(1 << 31) <= fill < 1 << 31:
+        raise ValueError(f"{who}: fill must be an int32, got {fill}")
+    Lf = Lv = 0
+    if face_labels is not None:
+        _want_shape(face_labels, [(face_labels.shape[0], F)], f"{who}: face_labels")
+        Lf = face_labels.shape[0]
+    if vertex_labels is not None:
+        _want_shape(vertex_labels, [(vertex_labels.shape[0], Nv)], f"{who}: vertex_labels")
+        Lv = vertex_labels.shape[0]
+    if Lf + Lv > RASTER_MAX_LABELS:
+        raise ValueError(f"{who}: at most {RASTER_MAX_LABELS} label channels in one call, got {Lf} + {Lv}")
+    dev = vertices.device
+    vp, fp = _ptr(vertices, torch.float32, f"{who}: vertices"), _ptr(faces, torch.int32, f"{who}: faces")
+    cp, ip = _ptr(world_to_cam, torch.float32, f"{who}: world_to_cam"), _ptr(intrinsics, torch.float32, f"{who}: intrinsics")
+    flp = _ptr(face_labels, torch.int32, f"{who}: face_labels") if Lf else None
+    vlp = _ptr(vertex_labels, torch.int32, f"{who}: vertex_labels") if Lv else None
+    shape = (V, H, W)
+    depth = torch.empty(shape, dtype=torch.float32, device=dev) if return_depth else None
+    face = torch.empty(shape, dtype=torch.int32, device=dev) if return_face else None
+    vertex = torch.empty(shape, dtype=torch.int32, device=dev) if return_vertex else None
+    fout = torch.empty((Lf,) + shape, dtype=torch.int32, device=dev) if Lf else None
+    vout = torch.empty((Lv,) + shape, dtype=torch.int32, device=dev) if Lv else None
+    info = torch.zeros(len(RASTER_INFO), dtype=torch.int64, device=dev)
+    if V:
+        per_pass = min(int(views_per_pass), V)
+        need = lib.sd3d_raster_ws_bytes(F, per_pass, H, W)
+        if need == 0:
+            raise ValueError(f"{who}: views_per_pass * F must stay below 2^31, got {per_pass} * {F}; lower views_per_pass")
+        ws = _WS_RASTER.get(need, dev)
+        _lib.check(lib.sd3d_raster_views(vp if Nv else None, Nv, fp if F else None, F, cp, ip, V, H, W, float(near), float(far), per_pass,
+                                         flp if F else None, Lf, vlp if Nv else None, Lv, int(fill), _ptr(depth), _ptr(face), _ptr(vertex),
+                                         _ptr(fout), _ptr(vout), _ptr(info), ws.data_ptr(), ws.numel(), _stream()), who)
+    return depth, face, vertex, fout, vout, info

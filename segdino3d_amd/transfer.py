@@ -31,8 +31,11 @@ The answer is a minimum over a set, so it is a pure function of the source cloud
 views are cut into calls and on whatever stream.  The grid behind the search (the one `knn_graph` builds) only chooses which pairs are
 evaluated and cannot change the answer.  Nothing in this module reads the device.
 
-Out of scope: `k > 1` and interpolated (soft) transfer, batches of scenes in one launch, z-buffered rendering for frames without
-depth, writing image files, the edge test of `fuse_views` step 3."""
+Frames without depth are served by `raster.py`: it z-buffers a mesh into posed views, and `raster.render_prediction_mesh` paints the
+same five images onto them.
+
+Out of scope: `k > 1` and interpolated (soft) transfer, batches of scenes in one launch, writing image files, the edge test of
+`fuse_views` step 3."""
 from __future__ import annotations
 
 import numbers
@@ -197,21 +200,35 @@ def _field(pred, key):
     return pred[key] if isinstance(pred, dict) else getattr(pred, key)
 
 
-def _device_field(pred, key):
+def _device_field(pred, key, who="render_prediction"):
     t = _field(pred, key)
     if isinstance(t, (list, tuple)):
-        return [_device_tensor(x, key) for x in t]
-    return _device_tensor(t, key)
+        return [_device_tensor(x, key, who) for x in t]
+    return _device_tensor(t, key, who)
 
 
-def _device_tensor(t, key):
+def _device_tensor(t, key, who="render_prediction"):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"render_prediction: {key}: expected tensors on the HIP device (run the model with `model.to_host = False`; "
+        raise RuntimeError(f"{who}: {key}: expected tensors on the HIP device (run the model with `model.to_host = False`; "
                            "no CPU fallback)")
     return t
 
 
 PREDICTION_IMAGES = ("semantic", "panoptic_semantic", "panoptic_instance", "instance", "instance_label")
+
+
+def prediction_channels(pred, score_thr, fill, who):
+    """The five per-point channels of `PREDICTION_IMAGES`, int32 [5, N] on the device, of a model output or its `pred_pts_seg`: what
+    `render_prediction` paints through the nearest point and `raster.render_prediction_mesh` through the nearest vertex of a face."""
+    pred = getattr(pred, "pred_pts_seg", pred)
+    sem, inst = _device_field(pred, "pts_semantic_mask", who), _device_field(pred, "pts_instance_mask", who)
+    labels, scores = _device_field(pred, "instance_labels", who), _device_field(pred, "instance_scores", who)
+    if len(sem) < 2 or len(inst) < 2:
+        raise ValueError(f"{who}: pts_semantic_mask and pts_instance_mask must hold the plain and the panoptic result")
+    imap = instance_map(inst[0], scores.to(torch.float32), score_thr)
+    ilab = labels.reshape(-1).to(torch.int32)
+    ilabel = torch.cat([ilab, ilab.new_full((1,), fill)])[imap.long()]                # -1 reads the appended `fill`
+    return torch.stack([sem[0].to(torch.int32), sem[1].to(torch.int32), inst[1].to(torch.int32), imap, ilabel])
 
 
 def render_prediction(views: Views, points, pred, radius: float, score_thr: float = 0.0, fill: int = -1, **rule):
@@ -226,14 +243,6 @@ def render_prediction(views: Views, points, pred, radius: float, score_thr: floa
 
     `fill` where a pixel has no depth or no point within `radius`.  One index build, one pixel launch with the five channels."""
     rule, fill = _rule(rule), _fill(fill, "render_prediction")
-    pred = getattr(pred, "pred_pts_seg", pred)
-    sem, inst = _device_field(pred, "pts_semantic_mask"), _device_field(pred, "pts_instance_mask")
-    labels, scores = _device_field(pred, "instance_labels"), _device_field(pred, "instance_scores")
-    if len(sem) < 2 or len(inst) < 2:
-        raise ValueError("render_prediction: pts_semantic_mask and pts_instance_mask must hold the plain and the panoptic result")
-    imap = instance_map(inst[0], scores.to(torch.float32), score_thr)
-    ilab = labels.reshape(-1).to(torch.int32)
-    ilabel = torch.cat([ilab, ilab.new_full((1,), fill)])[imap.long()]                # -1 reads the appended `fill`
-    chans = torch.stack([sem[0].to(torch.int32), sem[1].to(torch.int32), inst[1].to(torch.int32), imap, ilabel])
+    chans = prediction_channels(pred, score_thr, fill, "render_prediction")
     out = PointIndex(points, radius).nearest_pixels(views, labels=chans, fill=fill, return_index=False, **rule)
     return {name: out[i] for i, name in enumerate(PREDICTION_IMAGES)}
