@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SD3D_ABI_VERSION 24
+#define SD3D_ABI_VERSION 25
 
 int sd3d_abi_version(void);
 const char* sd3d_last_error(void);
@@ -1501,6 +1501,42 @@ int sd3d_raster_views(const float* vertices, int64_t n_vertices, const int32_t* 
                       int n_face_labels, const int32_t* vertex_labels, int n_vertex_labels, int fill, float* depth_out, int32_t* face_out,
                       int32_t* vertex_out, int32_t* face_labels_out, int32_t* vertex_labels_out, int64_t* info, void* ws, size_t ws_bytes,
                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh decimation (csrc/simplify.hip): vertex clustering on a grid - the vertices of one cell become one vertex, faces follow their
+ * corners, collapsed and duplicate faces go - with the maps that carry per-vertex results back to the full mesh and face labels
+ * forward.  The reference has no counterpart (it loads meshes decimated offline); tests/simplify_ref.py restates the rule below in
+ * numpy and the kernels EQUAL it, bit for bit.  segdino3d_amd/simplify.py has the rule in full.  The call only enqueues work.  Every
+ * sum is a 64-bit integer sum and every choice a minimum over a set, so the result is a pure function of the mesh and the rule: the
+ * same bits whatever the schedule and the stream.  The only global atomics are 64-bit integer sums and minima.
+ *
+ *   vertices float [V, C], 3 <= C <= SD3D_SIMPLIFY_MAX_CHANNELS (x, y, z, then attributes), faces int32 [F, 3], V, F < 2^31;
+ *   inv_cell = (float)(1 / cell) with cell >= 2^-6, so 0 < inv_cell <= 64.  Every float operation is rounded on its own, no fused
+ *   multiply-add.
+ *   1. A vertex is bad unless all C channels satisfy |c| < 2^14 as floats (NaN and infinity fail): vertex_map = -1.
+ *   2. k_i = floorf(x_i inv_cell); key ((k_x + 2^20) << 42) | ((k_y + 2^20) << 21) | (k_z + 2^20).
+ *   3. Per cell: n members, S_j = sum of (int64) rintf(c_j 65536.0f) per channel.
+ *   4. One output vertex per occupied cell, in ascending key.  nearest == 0: channel j = (float)((double) S_j / ((double) n 65536.0)).
+ *      nearest != 0: the row of the member with the smallest (bits of d2 << 32) | vertex index, copied bit for bit, d2 = (dx dx + dy dy)
+ *      + dz dz against the float mean of x, y, z.
+ *   5. A face with an index outside [0, V) or a bad corner is bad.  Otherwise its corners go through vertex_map; two equal corners:
+ *      collapsed.  Otherwise it is rotated so that its smallest index comes first; of the faces with one oriented triple the lowest
+ *      original index survives (the others: duplicates); survivors come out in ascending original index, as the rotated triple.
+ *   6. keep_unreferenced == 0: output vertices that no surviving face references are dropped (their members' vertex_map = -1), the rest
+ *      renumbered in key order.  The counter is filled either way.
+ *   7. info int64 [SD3D_SIMPLIFY_INFO_WORDS] = vertices, faces, bad_vertices, bad_faces, collapsed, duplicates, unreferenced.  More than
+ *      2^21 occupied cells (vertices + unreferenced) do not fit the 63-bit face key: the caller must refuse the result.
+ *
+ *   sd3d_simplify_mesh: vertices_out float [V, C] and faces_out int32 [F, 3], face_source int32 [F] at capacity (the first info[0] /
+ *     info[1] rows are written), vertex_map int32 [V].  V == 0 and F == 0 are ordinary inputs.  ws: sd3d_simplify_ws_bytes(V, F, C)
+ *     bytes (0 when the sizes do not fit), 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_SIMPLIFY_INFO_WORDS 7
+#define SD3D_SIMPLIFY_MAX_CHANNELS 11
+size_t sd3d_simplify_ws_bytes(int64_t n_vertices, int64_t n_faces, int n_channels);
+int sd3d_simplify_mesh(const float* vertices, int64_t n_vertices, int n_channels, const int32_t* faces, int64_t n_faces, float inv_cell,
+                       int nearest, int keep_unreferenced, float* vertices_out, int32_t* faces_out, int32_t* vertex_map,
+                       int32_t* face_source, int64_t* info, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SD3D_LIB: another build of the same library (same-box A/B of kernel variants; tools/ab_lib.sh)
 LIB_PATH = os.environ.get("SD3D_LIB") or os.path.join(_HERE, "libsegdino3d_hip.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _lib = None
 
@@ -206,6 +206,8 @@ SIGNATURES = {
     "sd3d_track_end": (_i, [_p, _z, _p, _p, _p, _p, _p]),
     "sd3d_raster_ws_bytes": (_z, [_l, _i, _i, _i]),
     "sd3d_raster_views": (_i, [_p, _l, _p, _l, _p, _p, _i, _i, _i, _f, _f, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "sd3d_simplify_ws_bytes": (_z, [_l, _l, _i]),
+    "sd3d_simplify_mesh": (_i, [_p, _l, _i, _p, _l, _f, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
 }
 
 

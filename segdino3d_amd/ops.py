@@ -3070,3 +3070,46 @@ def raster_views(vertices, faces, world_to_cam, intrinsics, height: int, width: 
                                          flp if F else None, Lf, vlp if Nv else None, Lv, int(fill), _ptr(depth), _ptr(face), _ptr(vertex),
                                          _ptr(fout), _ptr(vout), _ptr(info), ws.data_ptr(), ws.numel(), _stream()), who)
     return depth, face, vertex, fout, vout, info
+
+
+# --------------------------------------------------------------------------------------------
+# mesh decimation: vertex clustering on a grid (csrc/simplify.hip; the rule: include/segdino3d_hip.h, segdino3d_amd/simplify.py)
+# --------------------------------------------------------------------------------------------
+SIMPLIFY_MAX_CHANNELS = 11
+SIMPLIFY_MAX_INV_CELL = 64.0     # cell >= 2^-6: with |x| < 2^14 every cell index fits 21 bits
+SIMPLIFY_MAX_CELLS = 1 << 21     # the oriented triple of a face packs into one 63-bit sort key
+SIMPLIFY_INFO = ("vertices", "faces", "bad_vertices", "bad_faces", "collapsed", "duplicates", "unreferenced")
+_WS_SIMPLIFY = _PerThread()      # simplify_mesh: the sort buffers, the per-cell sums and the flags of one call
+
+
+def simplify_mesh(vertices, faces, inv_cell: float, nearest: bool = False, keep_unreferenced: bool = True):
+    """A mesh clustered on a grid (`sd3d_simplify_mesh`): vertices fp32 [V, C] with 3 <= C <= 11, faces int32 [F, 3], `inv_cell` =
+    1 / cell -> (vertices fp32 [V, C], faces int32 [F, 3] and face_source int32 [F] at capacity, vertex_map int32 [V], info int64
+    [len(SIMPLIFY_INFO)] on the device): the first info[0] vertices and the first info[1] faces are written.  Enqueues only."""
+    lib = _lib.load()
+    who = "simplify_mesh"
+    if vertices.dim() != 2 or vertices.dtype != torch.float32 or not 3 <= vertices.shape[1] <= SIMPLIFY_MAX_CHANNELS:
+        raise ValueError(f"{who}: vertices must be fp32 [V, C] with 3 <= C <= {SIMPLIFY_MAX_CHANNELS}, got {vertices.dtype} {list(vertices.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{who}: faces must be int32 [F, 3], got {faces.dtype} {list(faces.shape)}")
+    V, C, F = vertices.shape[0], vertices.shape[1], faces.shape[0]
+    if V >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"{who}: need V, F < 2^31, got {V}, {F}")
+    inv32 = _positive_f32(inv_cell, "inv_cell", who)
+    if inv32 > SIMPLIFY_MAX_INV_CELL:
+        raise ValueError(f"{who}: inv_cell must be at most {SIMPLIFY_MAX_INV_CELL} (cell >= 2^-6), got {inv_cell}")
+    dev = vertices.device
+    vp, fp = _ptr(vertices, torch.float32, f"{who}: vertices"), _ptr(faces, torch.int32, f"{who}: faces")
+    vout = torch.empty(V, C, dtype=torch.float32, device=dev)
+    fout = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    vmap = torch.empty(V, dtype=torch.int32, device=dev)
+    fsrc = torch.empty(F, dtype=torch.int32, device=dev)
+    info = torch.zeros(len(SIMPLIFY_INFO), dtype=torch.int64, device=dev)
+    need = lib.sd3d_simplify_ws_bytes(V, F, C)
+    if need == 0:
+        raise ValueError(f"{who}: a mesh of {V} vertices and {F} faces does not fit the workspace sizes")
+    ws = _WS_SIMPLIFY.get(need, dev)
+    _lib.check(lib.sd3d_simplify_mesh(vp if V else None, V, C, fp if F else None, F, inv32, int(bool(nearest)), int(bool(keep_unreferenced)),
+                                      _ptr(vout) if V else None, _ptr(fout) if F else None, _ptr(vmap) if V else None,
+                                      _ptr(fsrc) if F else None, _ptr(info), ws.data_ptr(), ws.numel(), _stream()), who)
+    return vout, fout, vmap, fsrc, info

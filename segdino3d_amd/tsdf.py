@@ -56,7 +56,7 @@ and `mesh()` then raises: a scene that does not fit is an error, not a thinner m
 (default 16 per block of capacity) and raises when the volume holds more.
 
 Not built: reading image files, marching cubes proper (it needs a case table; the surface nets here put one vertex in a cell and so
-round sharp edges), mesh decimation, growing the table, free-space carving outside the touched blocks (a voxel in front of a surface
+round sharp edges), growing the table, free-space carving outside the touched blocks (a voxel in front of a surface
 is only updated within the band, so an object that was removed between frames leaves its surface behind)."""
 from __future__ import annotations
 
