@@ -1538,6 +1538,54 @@ int sd3d_simplify_mesh(const float* vertices, int64_t n_vertices, int n_channels
                        int nearest, int keep_unreferenced, float* vertices_out, int32_t* faces_out, int32_t* vertex_map,
                        int32_t* face_source, int64_t* info, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Connected components (csrc/components.hip): the components of a mesh, an edge list or a neighbour table, their sizes and boxes, and
+ * the clean that keeps only the components that pass - the stage that throws away the floating shells and specks of a fused TSDF or
+ * cloud before simplify_mesh / the superpoints.  The reference has no counterpart (its meshes were cleaned offline);
+ * tests/components_ref.py restates the rule below in numpy and the kernels EQUAL it, bit for bit.  segdino3d_amd/components.py has the
+ * rule in full.  The call only enqueues work.  Components are a function of the SET of links, every decision is an integer one and
+ * every statistic a sum or a minimum over a set: the same bits whatever the schedule and the stream.
+ *
+ *   n_nodes nodes; links int32, one of three sources:  SD3D_COMPONENTS_FACES [n_links, 3] (a link joins its three corners),
+ *   SD3D_COMPONENTS_EDGES [n_links, 2], SD3D_COMPONENTS_TABLE [n_nodes, link_width] (entry j of row i joins i and j; -1 is an empty
+ *   slot, skipped and not counted; n_links = n_nodes * link_width, the entries).  coords float [n_nodes, n_channels], 3 <= n_channels <=
+ *   SD3D_COMPONENTS_MAX_CHANNELS (x, y, z first), or NULL with n_channels = 0: the pure graph form.  n_nodes, n_links < 2^31.
+ *   1. A node is good iff all channels satisfy |c| < 2^14 as floats (a NaN fails; step 1 of the decimation); without coords every node
+ *      is good.  A bad node has label -1, is never written out and counts in bad_nodes.
+ *   2. A link is good iff every index lies in [0, n_nodes) and every end is good; otherwise it counts in bad_links and joins nothing.
+ *      A link with repeated ends is good: it joins its distinct ends and is kept or dropped with its component.
+ *   3. Components: the classes of the good nodes under "joined by a good link", closed transitively; a good node in no good link is a
+ *      component of one node and counts in isolated.  They are numbered 0 .. K-1 in ascending order of their smallest node.
+ *   4. Per component: comp_nodes, comp_links (good links, table entries one each), box float [K, 6] = x lo, x hi, y lo, y hi, z lo, z hi:
+ *      the member coordinate that is smallest / largest under the integer key of its bits (b ^ 0x80000000 for b >= 0, ~b otherwise: -0
+ *      sorts below +0), bit for bit; extent = max over the axes of (hi - lo), one float subtraction each.  Graph form: zeros.
+ *   5. A component passes iff comp_nodes >= min_nodes, comp_links >= min_links and extent >= min_extent.  keep_largest = m > 0: only
+ *      the first m passing components in the order (comp_links descending, label ascending) stay.  keep uint8 [K].
+ *   6. The clean (every output optional): kept nodes in ascending original index, rows copied bit for bit (nodes_out [., n_channels]);
+ *      node_map int32 [n_nodes] old -> new or -1; kept links in ascending original index with renumbered ends (links_out) and their
+ *      original rows (link_source); labels_out = the component of each output node, renumbered densely over the kept components.  The
+ *      table form writes the cleaned table of the same width at the nodes' new rows: an entry that is not a good link becomes -1, in
+ *      place; link_source is not written.
+ *   7. info int64 [SD3D_COMPONENTS_INFO_WORDS] = components, kept, nodes (written), links (written), bad_nodes, bad_links, isolated,
+ *      unsettled: good links whose ends ended in different components - always 0; the caller must refuse the result otherwise.
+ *
+ *   sd3d_components: labels, comp_nodes, comp_links int32 [n_nodes] (the first info[0] of the latter two are written; required when
+ *     n_nodes > 0); box float [n_nodes, 6], keep uint8 [n_nodes], nodes_out, node_map, links_out (the shape of links), link_source
+ *     int32 [n_links], labels_out int32 [n_nodes]: at capacity, NULL = not wanted.  n_nodes == 0 and n_links == 0 are ordinary
+ *     inputs.  ws: sd3d_components_ws_bytes(n_nodes, n_links, link_width, n_channels) bytes (0 when the sizes do not fit), 256-byte
+ *     aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define SD3D_COMPONENTS_INFO_WORDS 8
+#define SD3D_COMPONENTS_MAX_CHANNELS 11
+#define SD3D_COMPONENTS_FACES 0
+#define SD3D_COMPONENTS_EDGES 1
+#define SD3D_COMPONENTS_TABLE 2
+size_t sd3d_components_ws_bytes(int64_t n_nodes, int64_t n_links, int link_width, int n_channels);
+int sd3d_components(int source, const int32_t* links, int64_t n_links, int link_width, const float* coords, int64_t n_nodes, int n_channels,
+                    int min_nodes, int min_links, float min_extent, int keep_largest, int32_t* labels, int32_t* comp_nodes,
+                    int32_t* comp_links, float* box, uint8_t* keep, float* nodes_out, int32_t* node_map, int32_t* links_out,
+                    int32_t* link_source, int32_t* labels_out, int64_t* info, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,8 @@ SIGNATURES = {
     "sd3d_raster_views": (_i, [_p, _l, _p, _l, _p, _p, _i, _i, _i, _f, _f, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "sd3d_simplify_ws_bytes": (_z, [_l, _l, _i]),
     "sd3d_simplify_mesh": (_i, [_p, _l, _i, _p, _l, _f, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "sd3d_components_ws_bytes": (_z, [_l, _l, _i, _i]),
+    "sd3d_components": (_i, [_i, _p, _l, _i, _p, _l, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
 }
 
 

@@ -3113,3 +3113,62 @@ def simplify_mesh(vertices, faces, inv_cell: float, nearest: bool = False, keep_
                                       _ptr(vout) if V else None, _ptr(fout) if F else None, _ptr(vmap) if V else None,
                                       _ptr(fsrc) if F else None, _ptr(info), ws.data_ptr(), ws.numel(), _stream()), who)
     return vout, fout, vmap, fsrc, info
+
+
+# --------------------------------------------------------------------------------------------
+# connected components and the clean (csrc/components.hip; the rule: include/segdino3d_hip.h, segdino3d_amd/components.py)
+# --------------------------------------------------------------------------------------------
+COMPONENTS_MAX_CHANNELS = 11
+COMPONENTS_SOURCES = ("faces", "edges", "table")        # SD3D_COMPONENTS_FACES, _EDGES, _TABLE
+COMPONENTS_INFO = ("components", "kept", "nodes", "links", "bad_nodes", "bad_links", "isolated", "unsettled")
+_WS_COMPONENTS = _PerThread()    # components: the sort buffers, the union-find and the flags of one call
+
+
+def components(source: str, links, n: int, coords=None, min_nodes: int = 0, min_links: int = 0, min_extent: float = 0.0, keep_largest: int = 0,
+               clean: bool = False):
+    """The components of `n` nodes under `links` (`sd3d_components`): source "faces" int32 [F, 3], "edges" int32 [E, 2] or "table" int32
+    [n, k]; `coords` fp32 [n, C] with 3 <= C <= 11 or None (the graph form) -> a dict of device tensors at capacity: labels int32 [n],
+    n_nodes and n_links int32 [n], box fp32 [n, 6], keep uint8 [n], info int64 [len(COMPONENTS_INFO)] (the first info[0] components are
+    written), and with `clean` nodes fp32 [n, C] (None without coords), node_map int32 [n], links (the shape of `links`), link_source
+    int32 [rows] (None for a table), labels_out int32 [n]: the first info[2] nodes and info[3] links are written (a table: info[2]
+    rows).  Enqueues only."""
+    lib = _lib.load()
+    who = "components"
+    if source not in COMPONENTS_SOURCES:
+        raise ValueError(f"{who}: source must be one of {COMPONENTS_SOURCES}, got {source!r}")
+    src = COMPONENTS_SOURCES.index(source)
+    if links.dim() != 2 or links.dtype != torch.int32 or (src == 0 and links.shape[1] != 3) or (src == 1 and links.shape[1] != 2) or \
+            (src == 2 and (links.shape[0] != n or links.shape[1] < 1)):
+        raise ValueError(f"{who}: links must be int32 [F, 3] (faces), [E, 2] (edges) or [n, k] (table), got {links.dtype} {list(links.shape)} as {source} with n = {n}")
+    if coords is not None and (coords.dim() != 2 or coords.dtype != torch.float32 or coords.shape[0] != n or not 3 <= coords.shape[1] <= COMPONENTS_MAX_CHANNELS):
+        raise ValueError(f"{who}: coords must be fp32 [n, C] with 3 <= C <= {COMPONENTS_MAX_CHANNELS}, got {coords.dtype} {list(coords.shape)}")
+    rows, width = links.shape
+    L = rows * width if src == 2 else rows
+    if n < 0 or n >= 1 << 31 or L >= 1 << 31:
+        raise ValueError(f"{who}: need 0 <= n < 2^31 and fewer than 2^31 links, got {n} nodes, {L} links")
+    min_extent32 = float(np.float32(min_extent))
+    if min_nodes < 0 or min_links < 0 or keep_largest < 0 or not (min_extent32 >= 0.0 and np.isfinite(min_extent32)):
+        raise ValueError(f"{who}: min_nodes, min_links, keep_largest must be >= 0 and min_extent finite and >= 0, got {min_nodes}, {min_links}, "
+                         f"{keep_largest}, {min_extent}")
+    dev = links.device
+    lp = _ptr(links, torch.int32, f"{who}: links")
+    cp = _ptr(coords, torch.float32, f"{who}: coords")
+    C = coords.shape[1] if coords is not None else 0
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    out = dict(labels=new((n,), torch.int32), n_nodes=new((n,), torch.int32), n_links=new((n,), torch.int32), box=new((n, 6), torch.float32),
+               keep=new((n,), torch.uint8), info=torch.zeros(len(COMPONENTS_INFO), dtype=torch.int64, device=dev),
+               nodes=None, node_map=None, links=None, link_source=None, labels_out=None)
+    if clean:
+        out.update(nodes=new((n, C), torch.float32) if coords is not None else None, node_map=new((n,), torch.int32),
+                   links=new((rows, width), torch.int32), link_source=new((rows,), torch.int32) if src != 2 else None,
+                   labels_out=new((n,), torch.int32))
+    need = lib.sd3d_components_ws_bytes(n, L, width, C)
+    if need == 0:
+        raise ValueError(f"{who}: {n} nodes and {L} links do not fit the workspace sizes")
+    ws = _WS_COMPONENTS.get(need, dev)
+    opt = lambda t, live: _ptr(t) if (t is not None and live) else None
+    _lib.check(lib.sd3d_components(src, lp if L else None, L, width, cp if n else None, n, C if n else 0, int(min_nodes), int(min_links), min_extent32,
+                                   int(keep_largest), opt(out["labels"], n), opt(out["n_nodes"], n), opt(out["n_links"], n), opt(out["box"], n),
+                                   opt(out["keep"], n), opt(out["nodes"], n), opt(out["node_map"], n), opt(out["links"], L),
+                                   opt(out["link_source"], L), opt(out["labels_out"], n), _ptr(out["info"]), ws.data_ptr(), ws.numel(), _stream()), who)
+    return out
